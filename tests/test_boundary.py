@@ -3,6 +3,7 @@
 loaders, and train/losses.py + LossLog.backwards_loss.  No GPU, no compute through the library."""
 import json
 import os
+import re
 
 import pytest
 import torch
@@ -88,16 +89,34 @@ def _flatten(d, prefix=""):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/config/config.yml"),
-                    reason="the reference tree only exists in the build container")
-def test_config_loaders_agree_with_the_reference_loaders_on_the_reference_files():
+def _yaml_from_values(flat):
+    """YAML text of a nested mapping rebuilt from dotted keys (None = a field the reference's models default: left out).
+    Learning rates are written as the reference's config/config.yml writes them (`lr: 1e-4`, which YAML 1.1 reads as a
+    string), so the loader's coercion stays under test."""
+    d = {}
+    for k, v in flat.items():
+        if v is None:
+            continue
+        *path, leaf = k.split(".")
+        node = d
+        for p in path:
+            node = node.setdefault(p, {})
+        node[leaf] = f"{v:.0e}".replace("e-0", "e-") if leaf == "lr" else v
+    text = yaml.safe_dump(d, allow_unicode=True, sort_keys=False)
+    return re.sub(r"(\blr: )'([0-9.e+-]+)'", r"\1\2", text)
+
+
+def test_config_loaders_agree_with_the_reference_loaders_on_the_reference_files(tmp_path):
     """config/config.yml and train/config/model.yml parsed by stylish_tts_amd.config carry the values the reference's
-    own pydantic loaders returned (tests/golden/config_values.json, written by tools/gen_golden_boundary.py)."""
+    own pydantic loaders returned (tests/golden/config_values.json, written by tools/gen_golden_boundary.py).  The two
+    files are rebuilt from those values, so the test needs nothing outside the repository."""
     from stylish_tts_amd.config import load_config_yaml, load_model_config_yaml
     want = json.load(open(os.path.join(G, "config_values.json")))
-    cfg = _flatten(load_config_yaml("/root/reference/config/config.yml"))
-    with open("/root/reference/src/stylish_tts/train/config/model.yml", encoding="utf-8") as f:
-        mc = _flatten(load_model_config_yaml(f))
+    cfg_text = _yaml_from_values(want["config"])
+    assert re.search(r"^\s+lr: 1e-5$", cfg_text, re.M), cfg_text
+    (tmp_path / "config.yml").write_text(cfg_text, encoding="utf-8")
+    cfg = _flatten(load_config_yaml(str(tmp_path / "config.yml")))
+    mc = _flatten(load_model_config_yaml(_yaml_from_values(want["model"])))
     for name, got, ref in (("config", cfg, want["config"]), ("model", mc, want["model"])):
         for k, v in ref.items():
             if v is None and k not in got:
@@ -179,6 +198,28 @@ def test_bench_line_fits_the_drivers_record():
         assert "kernels" not in back and "single_stream_kernels" not in back
         for e in back.get("extra", {}).values():
             assert set(e) <= {"ms_per_step", "value", "roofline", "hbm_counter_GBps", "hbm_counter_source"}
+
+
+def test_bench_dump_outputs_writes_float32_within_the_size_cap(tmp_path):
+    """bench.dump_outputs (behind --dump-outputs): the step's output as <name>.npy, shape kept while under the cap, a fixed
+    seeded flat sample above it; the trained modules' parameters as a seeded sample; float32 whatever came in."""
+    import numpy as np
+    import bench
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    mod = torch.nn.Linear(1500, 1000)  # 1.5 M parameters: more than the sample holds
+    bench.dump_outputs(str(tmp_path / "a"), "losses", small, [mod])
+    a = np.load(tmp_path / "a" / "losses.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 4) and np.array_equal(a, small.float().numpy())
+    p = np.load(tmp_path / "a" / "params_sample.npy")
+    assert p.dtype == np.float32 and p.shape == (bench.DUMP_PARAM_ELEMS,)
+    big = torch.randn(bench.DUMP_OUT_ELEMS + 5, dtype=torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "b"), "audio", big, [])
+    bench.dump_outputs(str(tmp_path / "c"), "audio", big, [])
+    b, c = np.load(tmp_path / "b" / "audio.npy"), np.load(tmp_path / "c" / "audio.npy")
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_OUT_ELEMS,) and np.array_equal(b, c)
+    assert not (tmp_path / "b" / "params_sample.npy").exists()
+    total = sum(f.stat().st_size for f in tmp_path.rglob("*.npy") if f.parent.name == "a")
+    assert (bench.DUMP_OUT_ELEMS + bench.DUMP_PARAM_ELEMS) * 4 <= 64 << 20 and total < 64 << 20
 
 
 def test_bench_roofline_joins_the_committed_profiles_by_instantiation():

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 for Q in ${@:-2 4 8}; do
   export GPU_MAX_HW_QUEUES=$Q
   rm -rf /tmp/prof_q
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_q -- python $R/bench.py --no-cpu-baseline --no-extra --steps 6 --warmup 2 > /tmp/prof_q.json 2> /tmp/prof_q.log
+  rocprofv3 --kernel-trace --stats -d /tmp/prof_q -- python $R/bench.py --full --no-cpu-baseline --no-extra --steps 6 --warmup 2 > /tmp/prof_q.json 2> /tmp/prof_q.log
   DB=$(find /tmp/prof_q -name "*_results.db" | head -1)
   python $R/tools/step_gaps.py $DB 6 150 > $R/gpurun_out/c3_gaps_q$Q.txt
   python $R/tools/stream_busy.py $DB 6 > $R/gpurun_out/c3_streams_q$Q.txt
