@@ -450,7 +450,8 @@ int sty_acoustic_gan_loss_fwd_bwd(int B, int N, const float *audio_gt, const flo
  * train/train.py:208-211: bucketed gradient all-reduce over NCCL): one communicator per process (one process per GPU) over
  * RCCL, on a HIP stream the LIBRARY owns.  The rank that calls sty_comm_unique_id hands the 128 bytes to the others by any
  * side channel (stylish_tts_amd/dist.py: one broadcast through torch.distributed), every rank then calls sty_comm_init
- * (collective: it returns when all `world` ranks have called it).  stream_priority: < 0 lowest, 0 default, > 0 highest.
+ * (collective: it returns when all `world` ranks have called it).  stream_priority: < 0 the runtime's greatest priority, 0
+ * priority 0, > 0 its least priority (hipDeviceGetStreamPriorityRange; -1 / 1 on MI355X).
  * sty_comm_allreduce_bucket(buf, n): buf[0..n) := sum over ranks, in place, asynchronously on the communicator's stream, ordered
  * BEHIND everything `producer_stream` holds at the time of the call; as ncclReduceScatter + ncclAllGather when n is a multiple
  * of 4 * world, ncclAllReduce otherwise.  sty_comm_wait makes `consumer_stream` wait for every bucket handed over so far (no

@@ -947,7 +947,7 @@ struct Run {
     // persistent 32-channel kernel does not take the conv; where it does (round 5), a LayerNorm pass + the persistent kernel are
     // faster than the fused tiled launch (c5-bf16: 121 us against ~35 + 40; the real / imag pair shares one pass)
     ConvArgs head_probe = base(v.amp_output_conv, trunk, Tu, logamp);
-    const bool head32p = takes32p(head_probe) && getenv("STY_NO_HEAD32P") == nullptr;
+    const bool head32p = takes32p(head_probe);
     float* lnbuf = head32p ? ws.take<float>((size_t)B * 32 * Tu) : nullptr;
     if (live()) {
       ConvArgs a = base(v.amp_output_conv, trunk, Tu, logamp);

@@ -532,16 +532,12 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(AttnArgs a, const f
 size_t attention_bwd_ws_floats(int B, int H, int T) { return (size_t)2 * B * H * T; }
 
 // the fp32 matrix-core backward: head dims that are multiples of 32, the forward's row log-sum-exp kept (AttnArgs::lse)
-bool attention_bwd_mfma_dh(int DH) {
-  static const bool off = getenv("STY_NO_ATTN_BWD_MFMA") != nullptr;
-  return !off && (DH == 64 || DH == 96 || DH == 160);
-}
+bool attention_bwd_mfma_dh(int DH) { return DH == 64 || DH == 96 || DH == 160; }
 static bool attn_bwd_mfma_path(const AttnArgs& a, int DH) { return a.lse && attention_bwd_mfma_dh(DH); }
 static bool attn_bwd_small_path(const AttnArgs& a, int DH) {
-  static const bool no_small = getenv("STY_NO_ATTN_BWD_SMALL") != nullptr;
   if (attention16_eligible(a, DH) && a.lse) return false;
   if (attn_bwd_mfma_path(a, DH)) return false;
-  return DH == 16 && a.T <= 128 && !no_small;
+  return DH == 16 && a.T <= 128;
 }
 // true: launch_attention_bwd can take `overwrite` bits for this problem (the one-workgroup-per-(batch, head) kernel writes every
 // element of dQ / dK / dV exactly once) -- the caller may then hand it buffers nobody zero-filled
@@ -595,35 +591,22 @@ int launch_attention_bwd(const AttnArgs& a, const float* dO, float* dQ, float* d
     STY_LAUNCH_CHECK();
     return STY_OK;
   }
-  dim3 grid(cdiv(a.T, 64), a.H, B);
-#define STY_ABWD(DHV, DR)                                                                                            \
-  hipLaunchKernelGGL(attn_bwd_a_kernel<DHV>, grid, dim3(64), 0, st, a, dO, dobs, lse, delta);                        \
-  if ((DHV) > 96) {                                                                                                  \
-    static bool raised_ = false;                                                                                     \
-    if (!raised_) {                                                                                                  \
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_b_kernel<DHV, DR>),                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (DHV) * 65 * 4));                  \
-      raised_ = true;                                                                                                \
-    }                                                                                                                \
-  }                                                                                                                  \
-  hipLaunchKernelGGL((attn_bwd_b_kernel<DHV, DR>), grid, dim3(256), 2 * (DHV) * 65 * sizeof(float), st, a, dO, dobs, lse, delta, \
-                     dK, dkbs, dV, dvbs);                                                                            \
-  hipLaunchKernelGGL((attn_bwd_c_kernel<DHV, DR>), grid, dim3(64), 0, st, a, dO, dobs, lse, delta, dQ, dqbs)
-  if (DH == 64 && !drop) {
-    STY_ABWD(64, false);
-  } else if (DH == 16 && !drop) {
-    STY_ABWD(16, false);
-  } else if (DH == 16) {
-    STY_ABWD(16, true);
-  } else if (DH == 96 && !drop) {  // the same encoder at inter_dim 128
-    STY_ABWD(96, false);
-  } else if (DH == 160 && !drop) {  // prosody encoder of the pitch / energy predictor: 2 heads x (256 + 64) / 2
-    STY_ABWD(160, false);
-  } else if (DH == 160) {
-    STY_ABWD(160, true);
-  } else {
+  // the rest (every caller keeps the forward's lse, so the head dims of the matrix-core path never get here): DH = 16 past
+  // 128 positions
+  if (DH != 16) {
     set_error("attention_bwd: head dim %d%s not built", DH, drop ? " with dropout" : "");
     return STY_EINVAL;
+  }
+  dim3 grid(cdiv(a.T, 64), a.H, B);
+#define STY_ABWD(DR)                                                                                                         \
+  hipLaunchKernelGGL(attn_bwd_a_kernel<16>, grid, dim3(64), 0, st, a, dO, dobs, lse, delta);                                 \
+  hipLaunchKernelGGL((attn_bwd_b_kernel<16, DR>), grid, dim3(256), 2 * 16 * 65 * sizeof(float), st, a, dO, dobs, lse, delta, \
+                     dK, dkbs, dV, dvbs);                                                                                    \
+  hipLaunchKernelGGL((attn_bwd_c_kernel<16, DR>), grid, dim3(64), 0, st, a, dO, dobs, lse, delta, dQ, dqbs)
+  if (drop) {
+    STY_ABWD(true);
+  } else {
+    STY_ABWD(false);
   }
 #undef STY_ABWD
   STY_LAUNCH_CHECK();

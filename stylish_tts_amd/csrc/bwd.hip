@@ -703,8 +703,6 @@ bool chan_ln32_eligible(int B, int C, int T, int relu) {
 int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, int C, int T, float eps, int ada,
                        const float* w, const float* gb, int relu, const float* out_mask, float* dx, int accumulate,
                        float* mu_tmp, float* r_tmp, float* dgb, float* dw, float* db, hipStream_t st, int h16) {
-  static const bool noreg = getenv("STY_NO_LN_BWD_REG") != nullptr;
-  static const bool regall = getenv("STY_LN_BWD_REG_ALL") != nullptr;  // experiment: the register form for the long rows too
   const bool no32 = getenv("STY_NO_LN32_BWD") != nullptr;  // (read per call: the A/B test toggles it)
   if (C == 32 && !relu && (size_t)B * T >= 65536 && !no32) {  // the 75T-rate LayerNorms: one thread per column (above)
     const int nblk = cdiv(T, 256);                           // partial rows live in mu_tmp (B T floats >= 64 B nblk)
@@ -722,7 +720,7 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
     set_error("chan_ln_bwd: two-byte tensors only on the C = 32 long-row kernel (chan_ln32_eligible)");
     return STY_EINVAL;
   }
-  if (((size_t)B * T < 65536 || regall) && C <= 256 && !noreg)
+  if ((size_t)B * T < 65536 && C <= 256)
     hipLaunchKernelGGL((chan_ln_bwd_dx_reg_kernel<16, 16>), dim3(cdiv(T, 16), B), dim3(256), 0, st, x, dy, y, C, T, eps, ada, w,
                        gb, relu, out_mask, dx, accumulate, mu_tmp, r_tmp);
   else if ((size_t)B * T >= 65536)
@@ -1059,13 +1057,12 @@ __global__ __launch_bounds__(256) void dwconv7_fwd_kernel(const float* __restric
 int launch_dwconv_fwd(const float* x, const float* w, const float* bias, int B, int C, int T, int K, int pad, float* y,
                       hipStream_t st) {
   const size_t ng = (size_t)B * C * (T / 4);
-  if (K == 7 && pad == 3 && T % 4 == 0 && ((((size_t)x | (size_t)y) & 15) == 0) && ng < ((size_t)1 << 31) &&
-      getenv("STY_NO_DWCONV7_FWD") == nullptr) {
+  if (K == 7 && pad == 3 && T % 4 == 0 && ((((size_t)x | (size_t)y) & 15) == 0) && ng < ((size_t)1 << 31)) {
     hipLaunchKernelGGL(dwconv7_fwd_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, x, w, bias, C, T / 4, (unsigned)ng, y);
     STY_LAUNCH_CHECK();
     return STY_OK;
   }
-  if (K <= 31 && getenv("STY_NO_DWCONV7_FWD") == nullptr) {  // any other K (the conformer's k = 31): four outputs per thread, taps unrolled
+  if (K <= 31) {  // any other K (the conformer's k = 31): four outputs per thread, taps unrolled
     if (K <= 7)
       hipLaunchKernelGGL(dwconv_fwd4_kernel<7>, dim3(cdiv(T, 1024), C, B), dim3(256), 0, st, x, w, bias, C, T, K, pad, y);
     else

@@ -137,7 +137,7 @@ int sty_comm_init(const void* id128, int rank, int world, int stream_priority, s
   int lo = 0, hi = 0;  // (numerically lower = higher priority)
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
   int pr = stream_priority < 0 ? hi : (stream_priority > 0 ? lo : 0);
-  hipError_t he = hipStreamCreateWithPriority(&c->stream, getenv("STY_COMM_BLOCKING_STREAM") ? hipStreamDefault : hipStreamNonBlocking, pr);
+  hipError_t he = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, pr);
   if (he == hipSuccess) he = hipEventCreateWithFlags(&c->handed, hipEventDisableTiming);
   if (he == hipSuccess) he = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
   if (he != hipSuccess) {
@@ -158,7 +158,7 @@ int sty_comm_allreduce_bucket(sty_comm* c, float* buf, size_t n, void* producer_
   STY_HIP(hipEventRecord(c->handed, static_cast<hipStream_t>(producer_stream)));
   STY_HIP(hipStreamWaitEvent(c->stream, c->handed, 0));
   const size_t w = (size_t)c->world;
-  if (n % (4 * w) == 0 && !getenv("STY_COMM_ALLREDUCE")) {
+  if (n % (4 * w) == 0) {
     const size_t per = n / w;
     float* mine = buf + (size_t)c->rank * per;  // in place: recvbuff = sendbuff + rank * recvcount (rccl.h:655-681)
     STY_NCCL(g_rccl.ReduceScatter(buf, mine, per, kNcclFloat, kNcclSum, c->comm, c->stream));

@@ -35,9 +35,7 @@ __device__ __forceinline__ float act_apply(float x, float alpha) {
   return x;
 }
 
-#ifndef STY_MINW
-#define STY_MINW 2
-#endif
+constexpr int STY_MINW = 2;  // workgroups per CU asked of the register allocator for the tile shapes with fewer than 8 waves
 // KS > 1: split-K INSIDE the workgroup.  KS groups of WM*WN waves work on the same output tile, group g takes the
 // reduction chunks g, g+KS, ... into its own LDS tile and accumulators; the partial tiles are summed through LDS in a
 // fixed order before the epilogue.  For the small-grid GEMMs (stage A at T = 160, the text encoder, the deep layers of
@@ -453,28 +451,15 @@ static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st) {
   }
   if (convk1_eligible(a)) return launch_convk1(a, st);
   if (convp16_eligible(a)) return launch_convp16(a, st);
-  // tuning aid: STY_CONV_CFG=0..5 forces one tile configuration (when the shape allows it)
-  static const int forced = getenv("STY_CONV_CFG") ? atoi(getenv("STY_CONV_CFG")) : -1;
-  if (forced >= 0 && a.act != ACT_GLU) {
-    if (forced == 0 && a.w.CoutP % 128 == 0) return launch_cfg<2, 2, 2, 2>(a, st);
-    if (forced == 1 && a.w.CoutP % 64 == 0) return launch_cfg<1, 4, 2, 2>(a, st);
-    if (forced == 2 && a.w.CoutP % 64 == 0) return launch_cfg<2, 2, 1, 1>(a, st);
-    if (forced == 3) return launch_cfg<1, 8, 1, 2>(a, st);
-    if (forced == 4) return launch_cfg<1, 4, 1, 2>(a, st);
-    if (forced == 5 && a.w.CoutP % 64 == 0 && a.w.CinP >= 2 * CI_CHUNK) return launch_cfg<2, 2, 1, 1, 2>(a, st);
-    if (forced == 6 && a.w.CoutP % 64 == 0 && a.w.CinP >= 4 * CI_CHUNK) return launch_cfg<2, 2, 1, 1, 4>(a, st);
-  }
   // Tile choice: the biggest output tile that still gives the chip >= ~2 workgroups per CU; the 256-channel stage
   // runs at T <= 800 frames, where 128x128 tiles would launch ~100 workgroups on 256 CUs.
   const long tiles128 = (long)cdiv(a.T, 128) * (a.w.CoutP / 128) * a.B;
   // (round 5, bf16 mode: 256 -- what is left on this kernel there are a dozen launches of 300-600 tiles, the pixel-shuffle
   //  up-convs and their input gradients, and they run faster on the larger tiles: c3 45.48 -> 45.19 ms, c5-bf16 4.42 -> 4.35;
   //  fp32 (c2): neutral in the step, +0.5 ms in the serial step: stays at 512.  profiles/r05_ab_env.txt block 20)
-  static const long t128_env = getenv("STY_T128_TILES") ? atol(getenv("STY_T128_TILES")) : 0;
-  static const long t64_env = getenv("STY_T64_TILES") ? atol(getenv("STY_T64_TILES")) : 0;
-  const long t128_min = t128_env ? t128_env : (a.bf16 ? 256 : 512);
-  const long t64_min = t64_env ? t64_env : (a.bf16 ? 256 : 512);
-  static const long t32_min = getenv("STY_T32_TILES") ? atol(getenv("STY_T32_TILES")) : 512;
+  const long t128_min = a.bf16 ? 256 : 512;
+  const long t64_min = a.bf16 ? 256 : 512;
+  constexpr long t32_min = 512;
   if (a.act == ACT_GLU) {
     if (a.w.CoutP % 128 == 0 && tiles128 >= t128_min) return launch_cfg<2, 2, 2, 2>(a, st);
     return launch_cfg<1, 4, 2, 1>(a, st);  // 64 packed couts (value+gate) x 128 time
@@ -485,24 +470,23 @@ static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st) {
     if (tiles64 >= t64_min) return launch_cfg<1, 4, 2, 2>(a, st);
     // 64 couts x 64 time; with few workgroups (<= one per CU) and a long reduction two wave groups split the reduction,
     // with very few (<= 64) and from 8 chunks up, four
-    static const bool ks_on = getenv("STY_NO_KSPLIT") == nullptr;
     const long wgs = (long)cdiv(a.T, 64) * (a.w.CoutP / 64) * a.B;
     // thresholds re-tuned at the end of round 3 with both workloads in one call (ms per step, c3 / c2): KS2 <= 768 and
     // KS4 <= 256 (round 2): 60.95 / 33.0; 384 / 64: 60.9 / 33.1; 256 / 64: 60.6-61.1 / 31.5-31.7; 256 / 32: 60.8 / 32.1;
     // 256 / 0: 61.0 / 33.1; 192 / 64: 60.5-60.7 / 31.9-32.1; no split at all: 60.9-61.1 / 34.3
-    static const int ks4_wgs = getenv("STY_KS4_WGS") ? atoi(getenv("STY_KS4_WGS")) : 64;
+    constexpr int ks4_wgs = 64;
     // (not for the DFT GEMMs of the front end / losses, ksplit_max = 2: their phase outputs are pinned at a wrapped
     // tolerance that a different summation order moves at the magnitude gate -- n_fft 2048: 7e-3 vs 5e-3)
-    if (ks_on && wgs <= ks4_wgs && a.ksplit_max >= 4 && a.w.CinP >= 8 * CI_CHUNK && a.pro != PRO_LN_AFFINE)
+    if (wgs <= ks4_wgs && a.ksplit_max >= 4 && a.w.CinP >= 8 * CI_CHUNK && a.pro != PRO_LN_AFFINE)
       return launch_cfg<2, 2, 1, 1, 4>(a, st);
-    static const int ks2_wgs = getenv("STY_KS2_WGS") ? atoi(getenv("STY_KS2_WGS")) : 256;
-    if (ks_on && wgs <= ks2_wgs && a.w.CinP >= 4 * CI_CHUNK && a.pro != PRO_LN_AFFINE) return launch_cfg<2, 2, 1, 1, 2>(a, st);
+    constexpr int ks2_wgs = 256;
+    if (wgs <= ks2_wgs && a.w.CinP >= 4 * CI_CHUNK && a.pro != PRO_LN_AFFINE) return launch_cfg<2, 2, 1, 1, 2>(a, st);
     return launch_cfg<2, 2, 1, 1>(a, st);
   }
   // 32-cout blocks: at the 75T frame rate use 8 waves on a 512-sample tile (2 workgroups = 16 waves per CU, halo
   // overhead halved); short sequences keep the 4-wave 256-sample tile for grid size.
-  static const bool w8 = getenv("STY_CO32_W4") == nullptr;  // A/B switch; 8 waves measured 73 vs 69 TF on config c5
-  if (w8 && (long)cdiv(a.T, 512) * (a.w.CoutP / 32) * a.B >= t32_min) return launch_cfg<1, 8, 1, 2>(a, st);
+  // (8 waves measured 73 vs 69 TF on config c5)
+  if ((long)cdiv(a.T, 512) * (a.w.CoutP / 32) * a.B >= t32_min) return launch_cfg<1, 8, 1, 2>(a, st);
   return launch_cfg<1, 4, 1, 2>(a, st);
 }
 

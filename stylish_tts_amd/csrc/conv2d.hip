@@ -229,8 +229,7 @@ __global__ __launch_bounds__(256) void stem2d_kernel(const float* __restrict__ x
   }
 }
 bool stem2d_eligible(const ConvArgs& a) {
-  static const bool off = getenv("STY_NO_STEM2D") != nullptr;
-  return !off && a.flatW > 0 && a.Cin2d == 1 && a.w.Cin == 3 && a.w.K == 3 && a.hpad == 1 && a.pad == 1 && a.dil == 1 &&
+  return a.flatW > 0 && a.Cin2d == 1 && a.w.Cin == 3 && a.w.K == 3 && a.hpad == 1 && a.pad == 1 && a.dil == 1 &&
          a.nsrc == 1 && a.pro == PRO_NONE && a.act == ACT_NONE && !a.residual && a.shuffle == 1 && a.in_shuffle <= 1 &&
          !a.ln_out && !a.Tin && !a.y_split && !a.stat_part && a.T % 4 == 0 && (!a.out_mask || a.out_mask_post) &&
          a.w.Cout <= 1024 && ((((size_t)a.y | (size_t)a.out_mask) & 15) == 0);

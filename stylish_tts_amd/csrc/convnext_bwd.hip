@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256, 2) void convnext32_bwd_kernel(Cnx32BwdArgs a) 
       // library-sine path in it -- that path is a function call per element, and merely having it in the loop body cost the
       // fast path its schedule (registers saved around the calls, a wait in front of every branch) -- and the rare block with it.
       auto elem_loop = [&](auto slow_c) {
-        const bool SLOWP = slow_c;  // (a compile-time constant after inlining, except in the STY_CNX_BWD_OLD build variant)
+        const bool SLOWP = slow_c;  // (a compile-time constant after inlining)
         float g0e = 0.f;
   #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -313,14 +313,9 @@ __global__ __launch_bounds__(256, 2) void convnext32_bwd_kernel(Cnx32BwdArgs a) 
             rsum = ok ? uu[r] * hv : 0.f;
           } else {
             const float cf = prm[384 + ch];
-            
-#ifdef STY_CNX_BWD_OLD
-          const float gH = ok ? fmaf(uu[r], sc, cf * hv) : 0.f;
-#else
-          const float gH = okf * fmaf(uu[r], sc, cf * hv);  // (a multiply, not a select: hipcc turned `ok ? ... : 0` into an
+            const float gH = okf * fmaf(uu[r], sc, cf * hv);  // (a multiply, not a select: hipcc turned `ok ? ... : 0` into an
               // exec-mask branch around the parameter reads of EVERY element, and the basic-block boundary kept the LDS reads of the next
               // rows from being requested early: three exposed LDS round trips per element; columns past the end hold finite values)
-#endif
             const float g0 = gH * (1.f + s2a);
             if constexpr (!LEAN) rsum = ownf * gH * (z * s2a - s2 * ral) * ral;  // (d alpha: owned columns only)
             if (LEAN) {
@@ -361,14 +356,10 @@ __global__ __launch_bounds__(256, 2) void convnext32_bwd_kernel(Cnx32BwdArgs a) 
                                                                 // rows from being hoisted (that cost 106 spilled VGPRs)
         }
       };
-#ifdef STY_CNX_BWD_OLD
-      elem_loop(slow);
-#else
       if (slow)
         elem_loop(std::true_type{});
       else
         elem_loop(std::false_type{});
-#endif
       if (PASS == 2) {  // gXn[ci][t] += sum_ch W1[ch][ci] gH0[ch][t]: the gH0 fragment is the B operand
         if constexpr (BF) {
 #pragma unroll

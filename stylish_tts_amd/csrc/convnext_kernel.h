@@ -2,7 +2,7 @@
 // the two modes are compiled with different flags: convnext.hip holds the fp32 instantiations (SLP vectoriser on: 135 vs 138 us
 // for pass 2, 90.6 vs 94.2 for pass 1 at c5), convnext16.hip the bf16 ones (-fno-slp-vectorize: the vectoriser pairs the
 // depthwise taps / AdaLN into v_pk_fma_f32, whose operands cannot be the SGPR weights -- 135 extra v_mov + 176 s_mov per wave,
-// 16 more registers; pass 2 62.7 vs 65.4 us at c5-bf16; stylish_tts_amd/build.py FILE_FLAGS, measured with tools/ab_slp.sh).
+// 16 more registers; pass 2 62.7 vs 65.4 us at c5-bf16; stylish_tts_amd/build.py FILE_FLAGS).
 #pragma once
 #include <type_traits>
 
@@ -11,15 +11,8 @@
 namespace sty {
 
 constexpr int CNX_TT = 256;  // time positions per block (4 waves x 2 MFMA column tiles)
-#ifndef CNX_P1_XN16
-#define CNX_P1_XN16 0  // pass 1 keeps the fp32 tile (measured: 49.5 us against 54.0 with the bf16 tile at c5; tools/ab_slp.sh)
-#endif
-#ifndef CNX_F32_XN32
-#define CNX_F32_XN32 1
-#endif
-#ifndef CNX_PAD
-#define CNX_PAD 0  // tuning aid: extra LDS bytes per workgroup (occupancy experiments)
-#endif
+constexpr bool CNX_P1_XN16 = false;  // pass 1 keeps the fp32 tile (measured: 49.5 us against 54.0 with the bf16 tile at c5)
+constexpr bool CNX_F32_XN32 = true;
 
 
 // BF: bf16 compute mode -- the two GEMMs take bf16-rounded operands, eight reduction elements per lane and MFMA (for the
@@ -47,10 +40,6 @@ __global__ __launch_bounds__(256, 2) void convnext32_kernel(Cnx32Args a) {
   constexpr bool RED_IN_XS = XN16 && !PASS2;
   __shared__ float red_s[RED_IN_XS ? 1 : 4 * 128];
   float (*red)[128] = reinterpret_cast<float (*)[128]>(RED_IN_XS ? xs : red_s);
-#if CNX_PAD
-  __shared__ char cnx_pad[CNX_PAD];
-  if (a.T < 0) cnx_pad[threadIdx.x] = 1;
-#endif
   __shared__ float prm[3][128];  // b1, alpha, GRN scale of this batch row: LDS broadcasts instead of global loads in
                                  // the element loops
   __shared__ float gbs[64];      // 1 + gamma | beta of the AdaLN

@@ -325,9 +325,7 @@ __device__ __forceinline__ void q_drain(const ConvArgs& a, const float* ost, con
 }
 
 template <int MTW, int PRO, int RELU, bool FLAT, bool X16 = false>
-__global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles, int dbg_) {
-  constexpr int dbg = 0;  // (the STY_Q_DBG phase switches of round 2 cost scalar instructions in every wave and step)
-  (void)dbg_;
+__global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int CO32 = 2 * MTW;
   constexpr int NFRAG = 2;  // A fragments per producer wave and chunk: K 2 CO32 <= 24 over 12 waves
@@ -406,11 +404,11 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
     }
     int ncommit = 0;  // chunk step number of the next commit
 #define STY_Q_ISSUE(R)                                                          \
-  if (pi.n < nchunks && !(dbg & 1)) q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R); \
+  if (pi.n < nchunks) q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R);       \
   q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);
 #define STY_Q_STEP(R) /* commit chunk `ncommit` from its register set, then request the chunk two ahead into the same set */ \
   {                                                                                                             \
-    if (!(dbg & 4)) q_commit<PRO, NFRAG, X16>(kc, R, bring + (ncommit & 1) * bsz, aring + (ncommit & 1) * asz, lane); \
+    q_commit<PRO, NFRAG, X16>(kc, R, bring + (ncommit & 1) * bsz, aring + (ncommit & 1) * asz, lane);           \
     ++ncommit;                                                                                                  \
     STY_Q_ISSUE(R)                                                                                              \
   }
@@ -457,7 +455,7 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
 #define STY_Q_FAST(R)                                                                                  \
   {                                                                                                    \
     if (ti > 0 && c < ndr) q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, c, ndr); \
-    q_commit<PRO, NFRAG, X16>(kc, R, bring + (ncommit & 1) * bsz, aring + (ncommit & 1) * asz, lane);       \
+    q_commit<PRO, NFRAG, X16>(kc, R, bring + (ncommit & 1) * bsz, aring + (ncommit & 1) * asz, lane);  \
     ++ncommit;                                                                                         \
     q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R);                                                     \
     q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);                       \
@@ -478,7 +476,7 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
 #undef STY_Q_FAST
 #undef STY_Q_NEXT
 #undef STY_Q_BODY
-    if (!(dbg & 8)) q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, 0, 1);  // the last tile
+    q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, 0, 1);  // the last tile
 #undef STY_Q_STEP
 #undef STY_Q_ISSUE
     return;
@@ -490,19 +488,18 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
   int g = 0, c = 0;
 #define STY_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
   for (int step = 0; step < nsteps; ++step) {
-    if (!(dbg & 16)) {
-      // one 32-channel chunk
-      if (c == 0) {
+    // one 32-channel chunk
+    if (c == 0) {
 #pragma unroll
-        for (int m = 0; m < MTW; ++m)
+      for (int m = 0; m < MTW; ++m)
 #pragma unroll
-          for (int n = 0; n < 2; ++n)
+        for (int n = 0; n < 2; ++n)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
-      }
-      const __bf16* xb = bring + (g & 1) * bsz + (size_t)(wn * 64 + l31) * Q_PITCH + 8 * hi;
-      const bf16x8* wb = aring + (g & 1) * asz + (wm * MTW) * 64 + lane;
-      bf16x8 avA[MTW], bvA[2], avB[MTW], bvB[2];
+          for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+    }
+    const __bf16* xb = bring + (g & 1) * bsz + (size_t)(wn * 64 + l31) * Q_PITCH + 8 * hi;
+    const bf16x8* wb = aring + (g & 1) * asz + (wm * MTW) * 64 + lane;
+    bf16x8 avA[MTW], bvA[2], avB[MTW], bvB[2];
 #define STY_QLD(AV, BV, j)                                                                          \
   {                                                                                                 \
     const int k_ = (j) >> 1, s_ = (j) & 1;                                                          \
@@ -513,36 +510,35 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
 #define STY_QMM(AV, BV)                                 \
   _Pragma("unroll") for (int m = 0; m < MTW; ++m)       \
   _Pragma("unroll") for (int n = 0; n < 2; ++n) acc[m][n] = \
-      __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[m], BV[n], acc[m][n], 0, 0, 0);
+    __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[m], BV[n], acc[m][n], 0, 0, 0);
 #define STY_QSCHED                                           \
   _Pragma("unroll") for (int q_ = 0; q_ < 2 * MTW; ++q_) {   \
     STY_SGB(0x008, 1);                                       \
     STY_SGB(0x100, 1);                                       \
   }                                                          \
   __builtin_amdgcn_sched_barrier(0);
-      const int J = 2 * K;
-      STY_QLD(avA, bvA, 0)
-      __builtin_amdgcn_sched_barrier(0);
-      int j = 0;
-      for (; j + 2 < J; j += 2) {
-        STY_QLD(avB, bvB, j + 1)
-        STY_QMM(avA, bvA)
-        STY_QSCHED
-        STY_QLD(avA, bvA, j + 2)
-        STY_QMM(avB, bvB)
-        STY_QSCHED
-      }
-      // J is even: two steps left
+    const int J = 2 * K;
+    STY_QLD(avA, bvA, 0)
+    __builtin_amdgcn_sched_barrier(0);
+    int j = 0;
+    for (; j + 2 < J; j += 2) {
       STY_QLD(avB, bvB, j + 1)
       STY_QMM(avA, bvA)
       STY_QSCHED
+      STY_QLD(avA, bvA, j + 2)
       STY_QMM(avB, bvB)
+      STY_QSCHED
+    }
+    // J is even: two steps left
+    STY_QLD(avB, bvB, j + 1)
+    STY_QMM(avA, bvA)
+    STY_QSCHED
+    STY_QMM(avB, bvB)
 #undef STY_QSCHED
 #undef STY_QMM
 #undef STY_QLD
-      ++g;
-    }
-    if (c == nch - 1 && !(dbg & 32)) {
+    ++g;
+    if (c == nch - 1) {
       // accumulators -> output stage [64 MTW][128]
 #pragma unroll
       for (int m = 0; m < MTW; ++m)
@@ -767,11 +763,8 @@ static int q_num_cus() {
 // leave some CUs alone: a persistent launch holds one workgroup on every CU it was given until it ends, and a kernel of
 // another stream that becomes ready in the meantime waits for the whole launch.  Measured on c3 with time stamps on the
 // streams (STY_STEP_PROBE): 0 / 8 / 16 / 32 / 64 free CUs -> predictor forward done at 17.8 / 17.8 / 18.0 / 17.2 / 17.2 ms,
-// step 56.9 / 57.0 / 57.2 / 56.5 / 56.3 ms.  STY_CONVP16_FREE_CUS overrides (0 = the whole chip).
-static int q_style_free_cus() {
-  static const int v = getenv("STY_CONVP16_FREE_CUS") ? atoi(getenv("STY_CONVP16_FREE_CUS")) : 32;
-  return v;
-}
+// step 56.9 / 57.0 / 57.2 / 56.5 / 56.3 ms.
+constexpr int Q_STYLE_FREE_CUS = 32;
 
 static int q_mtw(const ConvArgs& a) { return a.w.CoutP <= 64 || a.w.K > 3 ? 1 : 2; }
 static size_t q_lds_bytes(const ConvArgs& a) {
@@ -816,7 +809,7 @@ static int launch_q(const ConvArgs& a, hipStream_t st) {
   const int tiles_per_row = cdiv(a.T, Q_TT), ncot = cdiv(a.w.CoutP, 64 * MTW);
   const int ntiles = tiles_per_row * a.B * ncot;
   int cus = q_num_cus();
-  if (a.flatW && q_style_free_cus() > 0 && q_style_free_cus() < cus / 2) cus -= q_style_free_cus();
+  if (a.flatW && Q_STYLE_FREE_CUS < cus / 2) cus -= Q_STYLE_FREE_CUS;
   const int grid = ntiles < cus ? ntiles : cus;
   const double outs = (double)a.B * a.w.Cout * a.T;
   const double flops = 2.0 * a.w.Cin * a.w.K * outs;
@@ -830,14 +823,12 @@ static int launch_q(const ConvArgs& a, hipStream_t st) {
   // the 1-D convs (decoder, text encoder: launches of 50-500 tiles since round 5)
   snprintf(fam, sizeof(fam), a.flatW ? "convp16_kernel<%d,true>" : "convp16_kernel<%d,true,1d>", MTW);
   ProfScope prof(fam, flops, bytes, st, detail);
-  const char* de = getenv("STY_Q_DBG");  // timing experiments only (wrong results): 1 no input loads, 2 no weight path,
-                                         // 4 no input commit, 8 no drain, 16 no MFMA loop, 32 no accumulator spill
   if (a.flatW)
     hipLaunchKernelGGL((convp16_kernel<MTW, PRO, RELU, true, X16>), dim3(grid), dim3(Q_THREADS), lds, st, a, tiles_per_row, ncot,
-                       ntiles, de ? atoi(de) : 0);
+                       ntiles);
   else
     hipLaunchKernelGGL((convp16_kernel<MTW, PRO, RELU, false, X16>), dim3(grid), dim3(Q_THREADS), lds, st, a, tiles_per_row, ncot,
-                       ntiles, de ? atoi(de) : 0);
+                       ntiles);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -855,11 +846,11 @@ static int launch_q_pro(const ConvArgs& a, hipStream_t st) {
 int convp16_frags(const ConvArgs& a, hipStream_t st, const void** out) { return q_frags(a, st, out); }  // (convk1.hip)
 
 int launch_convp16(const ConvArgs& a0, hipStream_t st) {
-  if (a0.x16 && getenv("STY_NO_CONVP16_X16") == nullptr && convq_eligible(a0)) return launch_convq(a0, st);  // round 6: convq.hip
+  if (a0.x16 && convq_eligible(a0)) return launch_convq(a0, st);  // round 6: convq.hip
   ConvArgs a = a0;
   int rc = q_frags(a0, st, &a.w.wf);
   if (rc) return rc;
-  if (a.x16 && a.act != ACT_LRELU01 && getenv("STY_NO_CONVP16_X16") == nullptr) {
+  if (a.x16 && a.act != ACT_LRELU01) {
     // source 0 comes as its bf16 operand twin: the prologue (LeakyReLU / the [B][T] mask) is already in it
     a.pro = PRO_NONE;
     a.mask = nullptr;

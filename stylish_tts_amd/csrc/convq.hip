@@ -48,12 +48,9 @@ constexpr int CQ_XB = CQ_LW * 64;  // bytes per X buffer
 
 __device__ __forceinline__ int cq_xaddr(int L, int g) { return L * 64 + ((g ^ ((L >> 2) & 3)) << 4); }
 
-// DBG (STY_CQ_DBG=mask, timing experiments only -- wrong results): 1 no tile loads, 2 no weight loads, 4 no commits (LDS writes),
-// 8 no fragment reads + MFMAs, 16 no epilogue, 32 fragment reads but no MFMAs
-// (compile-time: a run-time switch around the MFMAs makes the allocator keep two copies of the accumulators)
-template <int MB, int K, int RELU, int DBG = 0>
+// (the fourth parameter is always 0: it keeps the instantiation names that profiles/r06_* record, convq_kernel<3, 3, 0, 0>)
+template <int MB, int K, int RELU, int = 0>
 __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles, int per_xcd) {
-  constexpr int dbg = DBG;
   extern __shared__ __attribute__((aligned(16))) unsigned char cq_lds[];
   constexpr int J = 2 * K;             // k-steps of 16 channels per chunk
   constexpr int NFR = J * MB;          // A fragments per chunk
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
     fok[i] = f < NFR;
   }
   auto issue_a = [&](ASet& A) {
-    const bool live = achunk < nch && !(dbg & 2);
+    const bool live = achunk < nch;
     const int cbase = live ? achunk * (J * NMB * 1024) : 0;
 #pragma unroll
     for (int i = 0; i < NFW; ++i) {
@@ -135,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
     ++achunk;
   };
   auto issue_x = [&](XSet& S) {
-    const bool live = xchunk < nch && !(dbg & 1);
+    const bool live = xchunk < nch;
     const int pos0 = t0 - a.pad + (flat ? (kh - a.hpad) * a.flatW : 0);
     S.pos0 = pos0;
     const int e = pos0 - (pos0 & 1) + 4 * q;  // even: dword-aligned loads (T is even)
@@ -172,7 +169,6 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
     }
   };
   auto commit = [&](XSet& S, const ASet& A, int buf) {
-    if constexpr ((dbg & 4) != 0) return;
     unsigned char* xb = xbuf + buf * CQ_XB;
     unsigned char* ab = abuf + buf * ABYTES;
     const int pos0 = S.pos0, d = pos0 & 1;
@@ -229,7 +225,6 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
 
   auto compute = [&](int buf) {
-    if constexpr ((dbg & 8) != 0) return;
     const unsigned char* xw = xbuf + buf * CQ_XB + wave * (64 * 64);
     const bf16x8* aw = reinterpret_cast<const bf16x8*>(abuf + buf * ABYTES) + lane;
     bf16x8 A0[MB], B0[2], A1[MB], B1[2];
@@ -239,10 +234,6 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
     _Pragma("unroll") for (int n = 0; n < 2; ++n) BV[n] = *reinterpret_cast<const bf16x8*>(xw + n * 2048 + boff[j]); \
   }
 #define CQ_MM(AV, BV)                                   \
-  if constexpr ((dbg & 32) != 0) {                        \
-    _Pragma("unroll") for (int m = 0; m < MB; ++m)        \
-    _Pragma("unroll") for (int n = 0; n < 2; ++n) acc[m][n][0] += (float)AV[m][0] + (float)BV[n][0]; \
-  } else                                                  \
   _Pragma("unroll") for (int m = 0; m < MB; ++m)        \
   _Pragma("unroll") for (int n = 0; n < 2; ++n) acc[m][n] = \
       __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[m], BV[n], acc[m][n], 0, 0, 0);
@@ -291,17 +282,6 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
 
   // ---- epilogue: q_drain's arithmetic.  A row block's accumulators (lane = column) go through a 32 x 64 stage of this wave's
   // own (the X / A rings are free behind the last barrier) and leave as rows: 16-byte stores, 8-byte stores of the bf16 twin ----
-  if constexpr ((dbg & 16) != 0) {
-    float sum = 0.f;
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += acc[m][n][r];
-    if (sum == 12345.f) a.y[0] = 1.f;
-    return;
-  }
   float* const stg = reinterpret_cast<float*>(cq_lds + wave * (32 * 68 * 4));
   const __amdgpu_buffer_rsrc_t yrs =
       __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)b * Cout * T, 0, Cout * T * 4, 0x00020000);
@@ -377,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
 static size_t cq_lds_bytes(int MB, int K) { return (size_t)2 * CQ_XB + (size_t)2 * 2 * K * MB * 1024 + (size_t)MB * 32 * 4; }
 
 bool convq_eligible(const ConvArgs& a) {
-  if (!a.bf16 || !a.x16 || getenv("STY_NO_CONVQ")) return false;  // (read per call: the A/B parity tests toggle it)
+  if (!a.bf16 || !a.x16) return false;
   if (a.nsrc != 1 || a.in_shuffle > 1 || a.shuffle != 1 || a.ln_out || a.Tin || a.dil != 1 || a.y_split || a.stat_part ||
       a.xh || a.yh || a.rh)
     return false;
@@ -417,23 +397,7 @@ static int launch_cq(const ConvArgs& a, hipStream_t st) {
   char detail[40];
   snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", a.w.Cin, a.w.Cout, a.w.K, a.T, a.flatW);
   ProfScope prof(a.flatW ? "convq_kernel<3,true>" : "convq_kernel<3,true,1d>", flops, bytes, st, detail);
-  const char* de = getenv("STY_CQ_DBG");
-  const int dm = de ? atoi(de) : 0;
-  bool done = false;
-  if constexpr (K == 3 && RELU == 0) {  // the phase switches exist for this instantiation only
-#define CQ_DBG_CASE(M)                                                                                                     \
-  if (dm == (M)) {                                                                                                         \
-    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&convq_kernel<MB, K, RELU, (M)>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                  \
-    hipLaunchKernelGGL((convq_kernel<MB, K, RELU, (M)>), dim3(8 * per_xcd), dim3(256), lds, st, a, tiles_per_row, ncot, ntiles, \
-                       per_xcd);                                                                                           \
-    done = true;                                                                                                           \
-  }
-    CQ_DBG_CASE(3) CQ_DBG_CASE(4) CQ_DBG_CASE(7) CQ_DBG_CASE(8) CQ_DBG_CASE(16) CQ_DBG_CASE(24) CQ_DBG_CASE(32) CQ_DBG_CASE(48)
-#undef CQ_DBG_CASE
-  }
-  if (!done)
-    hipLaunchKernelGGL((convq_kernel<MB, K, RELU, 0>), dim3(8 * per_xcd), dim3(256), lds, st, a, tiles_per_row, ncot, ntiles, per_xcd);
+  hipLaunchKernelGGL((convq_kernel<MB, K, RELU, 0>), dim3(8 * per_xcd), dim3(256), lds, st, a, tiles_per_row, ncot, ntiles, per_xcd);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

@@ -312,40 +312,8 @@ __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ au
 //   e[n] = xt[n] + xt[N-n], o[n] = xt[n] - xt[N-n]  (e[0] = xt[0], e[H] = xt[H])
 //   ee[n] = e[n] + e[H-n] (n < Q), ee[Q] = e[Q];  eo[n] = e[n] - e[H-n] (n < Q)
 //   oo[n] = o[n] + o[H-n] (1 <= n < Q), oo[Q] = o[Q];  oe[n] = o[n] - o[H-n] (1 <= n < Q)
-// rows: ee at 0..Q, eo at Q+1 + n, oo at 2Q+1 + (n-1), oe at 3Q+1 + (n-1).  One thread per (n <= Q, frame).
-__global__ __launch_bounds__(256) void frame_fold_kernel(const float* __restrict__ audio, const float* __restrict__ w, int N,
-                                                         int n_fft, int hop, int frames, size_t sb, size_t sc,
-                                                         float* __restrict__ xt) {
-  const int fr = blockIdx.x * 256 + threadIdx.x;
-  const int n = blockIdx.y, b = blockIdx.z;
-  if (fr >= frames) return;
-  const int H = n_fft / 2, Q = n_fft / 4;
-  auto at = [&](int k) {
-    int i = fr * hop + k - H;
-    if (i < 0) i = -i;
-    if (i >= N) i = 2 * (N - 1) - i;
-    return w[k] * audio[(size_t)b * N + i];
-  };
-  float* o_ = xt + b * sb + fr;
-  if (n == 0) {
-    const float e0 = at(0), eH = at(H);
-    o_[0] = e0 + eH;
-    o_[(size_t)(Q + 1) * sc] = e0 - eH;
-  } else if (n == Q) {
-    const float u = at(Q), v = at(n_fft - Q);
-    o_[(size_t)Q * sc] = u + v;              // ee[Q] = e[Q]
-    o_[(size_t)(2 * Q + Q) * sc] = u - v;    // oo[Q] = o[Q]   (row 2Q+1 + Q-1)
-  } else {
-    const float a0 = at(n), a1 = at(n_fft - n), b0 = at(H - n), b1 = at(H + n);
-    const float en = a0 + a1, on = a0 - a1, eh = b0 + b1, oh = b0 - b1;
-    o_[(size_t)n * sc] = en + eh;
-    o_[(size_t)(Q + 1 + n) * sc] = en - eh;
-    o_[(size_t)(2 * Q + n) * sc] = on + oh;
-    o_[(size_t)(3 * Q + n) * sc] = on - oh;
-  }
-}
-
-// The same values through a 32 (n) x 32 (frames) tile: in the kernel above a wave's 64 lanes are 64 frames, i.e. 64 reads
+// rows: ee at 0..Q, eo at Q+1 + n, oo at 2Q+1 + (n-1), oe at 3Q+1 + (n-1).
+// Through a 32 (n) x 32 (frames) tile: with one thread per (n <= Q, frame) a wave's 64 lanes are 64 frames, i.e. 64 reads
 // `hop` samples apart for each of the four taps (one cache line per lane).  Here the lanes of a half-wave run over n -- the
 // four taps of a frame are four contiguous 128-byte runs of the signal (two ascending, two descending) -- and the results
 // go through LDS so that the stores still run along the frame axis (128 bytes per row of the tile).
@@ -402,13 +370,8 @@ __global__ __launch_bounds__(256) void frame_fold_tiled_kernel(const float* __re
 }
 static void launch_frame_fold(const float* audio, const float* w, int B, int N, int n_fft, int hop, int frames, size_t sb,
                               size_t sc, float* xt, hipStream_t st) {
-  static const bool off = getenv("STY_NO_FRAME_FOLD_TILED") != nullptr;
-  if (off)
-    hipLaunchKernelGGL(frame_fold_kernel, dim3(cdiv(frames, 256), n_fft / 4 + 1, B), dim3(256), 0, st, audio, w, N, n_fft, hop,
-                       frames, sb, sc, xt);
-  else
-    hipLaunchKernelGGL(frame_fold_tiled_kernel, dim3(cdiv(frames, 32), cdiv(n_fft / 4 + 1, 32), B), dim3(256), 0, st, audio, w, N,
-                       n_fft, hop, frames, sb, sc, xt);
+  hipLaunchKernelGGL(frame_fold_tiled_kernel, dim3(cdiv(frames, 32), cdiv(n_fft / 4 + 1, 32), B), dim3(256), 0, st, audio, w, N,
+                     n_fft, hop, frames, sb, sc, xt);
 }
 
 
@@ -426,8 +389,9 @@ static void launch_frame_fold(const float* audio, const float* w, int B, int N, 
 // The adjoint (backward of the loss features): d xt[n] = Re sum_{f=0..M} (dRe_f + i dIm_f) e^(+2 pi i f n / n_fft) is half the
 // un-normalised inverse transform of the Hermitian extension Y (Y_0 = 2 dRe_0, Y_M = 2 dRe_M, Y_f = dRe_f + i dIm_f):
 //   Z_k = (Y_k + conj Y_{M-k}) + i e^(+2 pi i k / n_fft) (Y_k - conj Y_{M-k}),  z = IFFT_M(Z),  d xt[2m] = Re z[m] / 2,
-//   d xt[2m+1] = Im z[m] / 2 -- the same passes with conjugated twiddles.  It writes the UNFOLDED frame gradient; the
-// overlap-add (frame_bwd, folded = 0) is unchanged.
+//   d xt[2m+1] = Im z[m] / 2 -- the same passes with conjugated twiddles.  Every launch takes the span mode (the tile's frames
+// overlap-added in the kernel, span_gather_kernel below); the kernel's older output, the UNFOLDED frame gradient for
+// frame_bwd (span == nullptr), is no longer launched.
 // tw[f] = (cos, -sin)(2 pi f / n_fft), f = 0..M, computed in double precision; the pass with span h uses tw[pos * n_fft / (2h)].
 constexpr int FFT_NT = 1024;
 // which (utterance, first frame) a workgroup works on.  xcd != 0 (= the number of utterances): the hardware deals consecutive workgroup ids to the eight
@@ -436,7 +400,7 @@ constexpr int FFT_NT = 1024;
 __device__ __forceinline__ bool fft_tile(int frames, int TF, int xcd, int& b, int& f0) {
   const int ntx = (frames + TF - 1) / TF;
   int tile = blockIdx.x;
-  if (xcd) {
+  if (xcd) {  // (always: every launch passes the number of utterances; xcd == 0, the hardware order, is no longer launched)
     const int total = ntx * xcd, per = (total + 7) / 8;
     const int id = blockIdx.y * gridDim.x + blockIdx.x;
     tile = (id & 7) * per + (id >> 3);
@@ -628,6 +592,7 @@ __global__ __launch_bounds__(FFT_NT) void stft_fft_adj_kernel(const float* __res
     }
     return;
   }
+  // (no longer launched -- span is never null, see launch_stft_fft_adj -- and kept so that the kernel's code is the measured one)
   float* xb = dxt + (size_t)b * sb;
 #pragma unroll 4
   for (int idx = threadIdx.x; idx < TF * M; idx += FFT_NT) {
@@ -671,17 +636,12 @@ static bool fft_enabled(int n_fft) {
   static const bool off = getenv("STY_DFT_GEMM") != nullptr;
   return !off && (n_fft == 512 || n_fft == 1024 || n_fft == 2048);
 }
-// (measured alone on the chip, B = 32 x 6.5 s, tools/probes/fft_variants.sh: 2048 points 102 -> 93 us with the XCD map, -> 72 with
+// (measured alone on the chip, B = 32 x 6.5 s, profiles/r04_fft_variants.txt: 2048 points 102 -> 93 us with the XCD map, -> 72 with
 // 8-frame tiles on top of it (two workgroups per CU); 1024 points 62 -> 51, 512 points 47 -> 41; adjoint 123 / 80 / 73 ->
 // 78 / 67 / 64; 32-frame tiles gain nothing)
-static int fft_xcd() {
-  static const int v = getenv("STY_FFT_XCD") ? atoi(getenv("STY_FFT_XCD")) : 1;
-  return v;
-}
-// (xcd mode: the id -> tile map needs a multiple of eight workgroups; one extra row of the grid covers the remainder)
+// (the XCD map: the id -> tile map needs a multiple of eight workgroups; one extra row of the grid covers the remainder)
 static dim3 fft_grid(int frames, int TF, int B) {
   const int ntx = cdiv(frames, TF);
-  if (!fft_xcd()) return dim3(ntx, B);
   const int total = ntx * B, per = cdiv(total, 8);
   return dim3(ntx, cdiv(per * 8, ntx));
 }
@@ -701,13 +661,13 @@ static int launch_stft_fft_t(const float* audio, const FrontTables& t, int B, in
   ProfScope prof("stft_fft_kernel", (double)B * frames * (5.0 * (N / 2) * (LN - 1) + 10.0 * (N / 2 + 1)),
                  4.0 * ((double)B * Ns + (double)B * frames * (N + 2)), st);
   hipLaunchKernelGGL((stft_fft_kernel<LN, TF>), fft_grid(frames, TF, B), dim3(FFT_NT), lds, st, audio, t.window, t.tw, Ns, hop,
-                     frames, sb, sc, y, 1, fft_xcd() ? B : 0);
+                     frames, sb, sc, y, 1, B);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
 template <int LN, int TF>
 static int launch_stft_fft_adj_t(const float* dy, const FrontTables& t, int B, int frames, size_t sb, size_t sc, float* dxt,
-                                 hipStream_t st, int hop, float* span) {
+                                 hipStream_t st, int hop) {  // span mode: the per-tile spans go to dxt
   constexpr int N = 1 << LN;
   const size_t lds = (size_t)TF * (N + 4) * 4 + (size_t)(N / 2 + 1) * 8;
   static bool attr = false;
@@ -719,78 +679,45 @@ static int launch_stft_fft_adj_t(const float* dy, const FrontTables& t, int B, i
   ProfScope prof("stft_fft_adj_kernel", (double)B * frames * (5.0 * (N / 2) * (LN - 1) + 10.0 * (N / 2 + 1)),
                  4.0 * ((double)B * frames * (N + 2) + (double)B * frames * N), st);
   hipLaunchKernelGGL((stft_fft_adj_kernel<LN, TF>), fft_grid(frames, TF, B), dim3(FFT_NT), lds, st, dy, t.tw, frames, sb, sc,
-                     dxt, 1, fft_xcd() ? B : 0, t.window, hop, span);
+                     dxt, 1, B, t.window, hop, dxt);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
 // frames per workgroup: 16 (64-byte runs per spectrum row), 8 for the 2048-point transform (70 instead of 139 KB of LDS: two
-// workgroups per CU overlap their load / butterfly / store phases); STY_FFT_TF = 8 / 16 / 32 overrides (32 does not fit at
-// 2048 points)
-static int fft_tf(int n_fft) {
-  static const int v = getenv("STY_FFT_TF") ? atoi(getenv("STY_FFT_TF")) : 0;
-  return v ? v : (n_fft >= 2048 ? 8 : 16);
-}
+// workgroups per CU overlap their load / butterfly / store phases)
+static int fft_tf(int n_fft) { return n_fft >= 2048 ? 8 : 16; }
 // windowed frames of `audio` -> spectrum y [2F][B * frames] in dft_row order (what launch_frame_fold + dft_fold_fwd produce)
 static int launch_stft_fft(const float* audio, const FrontTables& t, int B, int Ns, int hop, int frames, size_t sb, size_t sc,
                            float* y, hipStream_t st) {
-  const int tf = fft_tf(t.n_fft);
 #define STY_FFT_FWD(LN_, TF_) return launch_stft_fft_t<LN_, TF_>(audio, t, B, Ns, hop, frames, sb, sc, y, st)
-  switch (t.n_fft) {
-    case 512:
-      if (tf == 8) STY_FFT_FWD(9, 8);
-      if (tf == 32) STY_FFT_FWD(9, 32);
-      STY_FFT_FWD(9, 16);
-    case 1024:
-      if (tf == 8) STY_FFT_FWD(10, 8);
-      if (tf == 32) STY_FFT_FWD(10, 32);
-      STY_FFT_FWD(10, 16);
-    case 2048:
-      if (tf == 8) STY_FFT_FWD(11, 8);
-      STY_FFT_FWD(11, 16);
+  switch (t.n_fft) {  // (TF_: fft_tf)
+    case 512: STY_FFT_FWD(9, 16);
+    case 1024: STY_FFT_FWD(10, 16);
+    case 2048: STY_FFT_FWD(11, 8);
   }
 #undef STY_FFT_FWD
   set_error("front end: no FFT for this n_fft");
   return STY_EINVAL;
 }
-// d spectrum (dft_row order) -> d windowed frames, UNFOLDED rows [n_fft][B * frames]
-static int launch_stft_fft_adj_sel(const float* dy, const FrontTables& t, int B, int frames, size_t sb, size_t sc, float* dxt,
-                                   hipStream_t st, int hop, float* span, int tf);
-// span_out != nullptr (with hop and the signal length Ns): the windowed overlap-add straight into d audio (+=) through per-tile
-// spans kept in `dxt` -- stft_fft_adj_kernel's span mode + span_gather_kernel -- instead of the frame gradient
+// d spectrum (dft_row order) -> the windowed overlap-add straight into d audio (+=, signal length Ns) through per-tile spans
+// kept in `dxt` -- stft_fft_adj_kernel's span mode + span_gather_kernel -- instead of the frame gradient
 static int launch_stft_fft_adj(const float* dy, const FrontTables& t, int B, int frames, size_t sb, size_t sc, float* dxt,
-                               hipStream_t st, int hop = 0, int Ns = 0, float* daudio = nullptr) {
-  const int tf = fft_tf(t.n_fft);
-  if (daudio) {
-    int tfe = (t.n_fft == 2048 && tf > 16) ? 16 : tf;
-    if (tfe != 8 && tfe != 16 && tfe != 32) tfe = 16;
-    int rc = launch_stft_fft_adj_sel(dy, t, B, frames, sb, sc, dxt, st, hop, dxt, tfe);
-    if (rc) return rc;
-    hipLaunchKernelGGL(span_gather_kernel, dim3(cdiv(Ns, 256), B), dim3(256), 0, st, dxt, Ns, t.n_fft, hop, tfe, cdiv(frames, tfe),
-                       daudio);
-    STY_LAUNCH_CHECK();
-    return STY_OK;
-  }
-  return launch_stft_fft_adj_sel(dy, t, B, frames, sb, sc, dxt, st, 0, nullptr, tf);
-}
-static int launch_stft_fft_adj_sel(const float* dy, const FrontTables& t, int B, int frames, size_t sb, size_t sc, float* dxt,
-                                   hipStream_t st, int hop, float* span, int tf) {
-#define STY_FFT_ADJ(LN_, TF_) return launch_stft_fft_adj_t<LN_, TF_>(dy, t, B, frames, sb, sc, dxt, st, hop, span)
-  switch (t.n_fft) {
-    case 512:
-      if (tf == 8) STY_FFT_ADJ(9, 8);
-      if (tf == 32) STY_FFT_ADJ(9, 32);
-      STY_FFT_ADJ(9, 16);
-    case 1024:
-      if (tf == 8) STY_FFT_ADJ(10, 8);
-      if (tf == 32) STY_FFT_ADJ(10, 32);
-      STY_FFT_ADJ(10, 16);
-    case 2048:
-      if (tf == 8) STY_FFT_ADJ(11, 8);
-      STY_FFT_ADJ(11, 16);
+                               hipStream_t st, int hop, int Ns, float* daudio) {
+  int rc;
+#define STY_FFT_ADJ(LN_, TF_) rc = launch_stft_fft_adj_t<LN_, TF_>(dy, t, B, frames, sb, sc, dxt, st, hop)
+  switch (t.n_fft) {  // (TF_: fft_tf)
+    case 512: STY_FFT_ADJ(9, 16); break;
+    case 1024: STY_FFT_ADJ(10, 16); break;
+    case 2048: STY_FFT_ADJ(11, 8); break;
+    default: set_error("front end: no FFT for this n_fft"); return STY_EINVAL;
   }
 #undef STY_FFT_ADJ
-  set_error("front end: no FFT for this n_fft");
-  return STY_EINVAL;
+  if (rc) return rc;
+  const int tf = fft_tf(t.n_fft);
+  hipLaunchKernelGGL(span_gather_kernel, dim3(cdiv(Ns, 256), B), dim3(256), 0, st, dxt, Ns, t.n_fft, hop, tf, cdiv(frames, tf),
+                     daudio);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
 }
 
 // y [B][2F][frames] -> power [B][F][frames]
@@ -1112,7 +1039,9 @@ __global__ void magphase_bwd_kernel(const float* __restrict__ y, const float* __
 }
 
 // d audio[b][i] += sum over frames / reflections of w[n] * dxt[b][n][fr]   (gather, no atomics)
-// folded != 0: dxt holds d ee | d eo | d oo | d oe in frame_fold_kernel's row layout
+// folded != 0: dxt holds d ee | d eo | d oo | d oe in frame_fold_tiled_kernel's row layout.  (Every launch passes folded = 1
+// -- launch_frame_bwd, behind dft_fold_bwd; the unfolded branches of both kernels are no longer reached and are kept so that
+// the kernels' code is the measured one.)
 __global__ void frame_bwd_kernel(const float* __restrict__ dxt, const float* __restrict__ w, int N, int n_fft, int hop,
                                  int frames, size_t sb, size_t sc, float* __restrict__ daudio, int folded) {
   const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
@@ -1139,7 +1068,7 @@ __global__ void frame_bwd_kernel(const float* __restrict__ dxt, const float* __r
         if (!folded) {
           g = dxt[b * sb + n * sc + fr];
         } else {
-          // un-fold both levels (frame_fold_kernel): xt[n] feeds e[n'] and +-o[n'], n' = min(n, N - n); e[n'] feeds
+          // un-fold both levels (frame_fold_tiled_kernel): xt[n] feeds e[n'] and +-o[n'], n' = min(n, N - n); e[n'] feeds
           // ee / eo at j = min(n', H - n') with sign +- for eo, o[n'] feeds oo / oe likewise
           const int Q = half / 2;
           const float* d_ = dxt + b * sb + fr;
@@ -1232,19 +1161,17 @@ __global__ __launch_bounds__(256) void frame_bwd_tiled_kernel(const float* __res
     daudio[(size_t)b * N + i] += acc;
   }
 }
+// dxt: the frame gradient in frame_fold_tiled_kernel's folded row layout (what dft_fold_bwd leaves)
 static int launch_frame_bwd(const float* dxt, const float* w, int B, int N, int n_fft, int hop, int frames, size_t sb, size_t sc,
-                            float* daudio, int folded, hipStream_t st) {
+                            float* daudio, hipStream_t st) {
   int pitch = (FB_S - 1 + n_fft - hop) / hop + 2;
   pitch |= 1;  // odd: consecutive threads read consecutive rows
-  const int rows = folded ? n_fft + 1 : n_fft;
-  const size_t lds = (size_t)rows * pitch * sizeof(float);
-  static const bool off = getenv("STY_NO_FRAME_BWD_TILED") != nullptr;
-  if (off || lds > 64 * 1024) {
-    hipLaunchKernelGGL(frame_bwd_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, st, dxt, w, N, n_fft, hop, frames, sb, sc, daudio,
-                       folded);
+  const size_t lds = (size_t)(n_fft + 1) * pitch * sizeof(float);
+  if (lds > 64 * 1024) {
+    hipLaunchKernelGGL(frame_bwd_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, st, dxt, w, N, n_fft, hop, frames, sb, sc, daudio, 1);
   } else {
     hipLaunchKernelGGL(frame_bwd_tiled_kernel, dim3(cdiv(N, FB_S), B), dim3(256), lds, st, dxt, w, N, n_fft, hop, frames, sb, sc,
-                       daudio, folded, pitch);
+                       daudio, 1, pitch);
   }
   STY_LAUNCH_CHECK();
   return STY_OK;
@@ -1412,17 +1339,14 @@ int launch_acoustic_loss_gan(int B, int N, const float* audio_gt, const float* a
     hipLaunchKernelGGL(magphase_bwd_kernel, dim3(cdiv(frames, 256), F, B), dim3(256), 0, st, rb[r].p_y, dabs,
                        rb[r].d_phase, F, frames, (size_t)frames, (size_t)frames, (size_t)B * frames, dy, n_fft / 4);
     const size_t cols = (size_t)B * frames;
-    const bool fft = fft_enabled(n_fft);
-    static const bool no_span = getenv("STY_FFT_NO_SPAN") != nullptr;
-    if (fft && !no_span) {  // inverse transform + windowed overlap-add into d_pred (two launches, no frame-gradient tensor)
+    if (fft_enabled(n_fft)) {  // inverse transform + windowed overlap-add into d_pred (two launches, no frame-gradient tensor)
       rc = launch_stft_fft_adj(dy, *t, B, frames, (size_t)frames, cols, dxt, st, rb[r].hop, N, d_pred);
       if (rc) return rc;
       continue;
     }
-    rc = fft ? launch_stft_fft_adj(dy, *t, B, frames, (size_t)frames, cols, dxt, st) : dft_fold_bwd(*t, dy, cols, dxt, st);
+    rc = dft_fold_bwd(*t, dy, cols, dxt, st);
     if (rc) return rc;
-    rc = launch_frame_bwd(dxt, t->window, B, N, n_fft, rb[r].hop, frames, (size_t)frames, (size_t)B * frames, d_pred,
-                          fft ? 0 : 1, st);
+    rc = launch_frame_bwd(dxt, t->window, B, N, n_fft, rb[r].hop, frames, (size_t)frames, (size_t)B * frames, d_pred, st);
     if (rc) return rc;
   }
   STY_LAUNCH_CHECK();

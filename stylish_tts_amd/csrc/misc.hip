@@ -109,8 +109,7 @@ __global__ __launch_bounds__(256) void bmm_ct_mfma_kernel(const float* __restric
   }
 }
 int launch_bmm_ct(const float* enc, const float* ali, int B, int C, int L, int T, float* y, hipStream_t st) {
-  static const bool no_mfma = getenv("STY_NO_BMM_MFMA") != nullptr;
-  if (!no_mfma && L % 4 == 0 && T % 4 == 0)
+  if (L % 4 == 0 && T % 4 == 0)
     hipLaunchKernelGGL(bmm_ct_mfma_kernel, dim3(cdiv(T, 128), cdiv(C, 32), B), dim3(256), 0, st, enc, ali, C, L, T, y);
   else
     hipLaunchKernelGGL(bmm_ct_kernel, dim3(cdiv(T, 64), cdiv(C, 4), B), dim3(256), 4 * L * sizeof(float), st, enc, ali,
@@ -337,8 +336,7 @@ __global__ __launch_bounds__(256) void bmm_ct_bwd_mfma_kernel(const float* __res
   }
 }
 int launch_bmm_ct_bwd(const float* g, const float* ali, int B, int C, int L, int T, float* denc, hipStream_t st) {
-  static const bool no_mfma = getenv("STY_NO_BMM_MFMA") != nullptr;
-  if (L <= 128 && !no_mfma)
+  if (L <= 128)
     hipLaunchKernelGGL(bmm_ct_bwd_mfma_kernel, dim3(cdiv(C, 32), B), dim3(256), 0, st, g, ali, C, L, T, denc);
   else
     hipLaunchKernelGGL(bmm_ct_bwd_kernel, dim3(L, C, B), dim3(64), 0, st, g, ali, C, L, T, denc);

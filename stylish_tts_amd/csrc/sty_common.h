@@ -113,7 +113,7 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // of a 2-D conv -- is fetched into two L2s: wgradp32_kernel fetched 1.8x (k = 11) / 2.8x (k = 21) its algorithmic bytes, wgrad_cnx
 // 1.5-1.7x (profiles/r06_c3_pmc_traffic.json).  Mode 1: a CONSECUTIVE range [first, end) per workgroup (returns the stride, 1).
 // Mode 2: the strided front, with the workgroups of one XCD (blockIdx % 8) on neighbouring chunks -- eight fronts, one per L2.
-// Measured per kernel, alone on the chip (tools/ab_serial.sh; modes 1 / 2 / 0) and on the block workload of tools/cnx_traffic.sh:
+// Measured per kernel, alone on the chip (modes 1 / 2 / 0, one build per mode) and on the block workload of tools/cnx_traffic.sh:
 // wgradb16_kernel<3,128,..> 273 / 317 / 316 us, wgradb_kernel<3,3,..> 48.8 / 50.7 / 50.9; wgradp32_kernel<3,..> 144 / 141 / 142 us and
 // 68 / 65 / 119 MB fetched; wgrad_cnx_kernel<false,..> 143 / 128 / 132 us and 134 / 101 / 144 MB; stem_wgrad_kernel 198 / 188 / 185,
 // conv1d_wgrad_kernel<6> 243 / 240 / 235 (mode 1 turns a streaming kernel's one front into 1 024 scattered streams).  Each kernel

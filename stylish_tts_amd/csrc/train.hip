@@ -48,22 +48,20 @@ struct Trainer {
   // A weight gradient is a leaf of the backward graph: it reads (x, gY) and nothing reads it before the optimizer.
   // On the sample_dataset shapes the input-gradient chain is a sequence of kernels too small to fill 256 CUs, so the
   // weight-gradient kernels (512-1024 workgroups each) run on a second, lower-priority stream and take the idle CUs.
-  // Launches can be queued and handed over SIDE_BATCH at a time (one event on the main stream per batch); measured,
-  // handing each launch over at once is best (c2 step 46.9 ms at 1, 47.5 at 4, 49.0 at 16: the weight gradient then
+  // Each launch is handed over at once (one event on the main stream per launch; measured against batches of launches:
+  // c2 step 46.9 ms at 1, 47.5 at 4, 49.0 at 16: the weight gradient then
   // overlaps the input gradient of its own layer, a kernel of the same size class).  The side stream only ever waits for the main
   // stream; the main stream never waits for the side stream before the join at the end of the tape, because a
   // gradient buffer with a side-stream reader is never written again: when G / Gw find such a buffer (it can only
   // be written again through the residual aliasing below) they hand out a copy instead (copy on write).
   // The side stream has its own partial-sum buffer (side_partial, sized in the forward for the largest conv): the
-  // main stream recycles its temporaries while the queued launches are still pending.
-  size_t SIDE_BATCH = getenv("STY_SIDE_BATCH") ? atoi(getenv("STY_SIDE_BATCH")) : 1;
+  // main stream recycles its temporaries while the side-stream launches are still pending.
   std::vector<char> fcs_bwd_sent;  // last fc-backward table uploaded to m->fcs_bwd_dev
   hipStream_t st2 = nullptr;
   bool side_on = getenv("STY_NO_SIDE_STREAM") == nullptr;
   std::vector<hipEvent_t> evs;
   size_t ev_used = 0;
-  std::unordered_set<const float*> side_reads;  // buffers read by a queued or running side-stream launch
-  std::vector<std::function<void(hipStream_t)>> side_q;
+  std::unordered_set<const float*> side_reads;  // buffers read by a side-stream launch
   bool side_dirty = false;
   size_t side_need = 0;  // floats
   float* side_partial = nullptr;
@@ -150,7 +148,6 @@ struct Trainer {
   void side_begin() {
     ev_used = 0;
     side_reads.clear();
-    side_q.clear();
     side_dirty = false;
     const bool on = side_on && !single_stream_mode();
     side_partial = on && side_need ? take<float>(side_need) : nullptr;
@@ -169,15 +166,11 @@ struct Trainer {
     }
   }
   bool side_ready() const { return side_partial != nullptr; }  // also in the sizing pass (same allocations)
-  // queue a launch that reads gbuf (complete on the main stream at this point) and nothing the main stream writes later
-  void side_push(const float* gbuf, std::function<void(hipStream_t)> fn) {
+  // launch on the side stream, behind the main stream's work so far, what reads gbuf (complete on the main stream at this
+  // point) and nothing the main stream writes later
+  void side_push(const float* gbuf, const std::function<void(hipStream_t)>& fn) {
     side_reads.insert(gbuf);
     if (!live() || !st2) return;
-    side_q.push_back(std::move(fn));
-    if (side_q.size() >= SIDE_BATCH) side_flush();
-  }
-  void side_flush() {
-    if (side_q.empty()) return;
     hipEvent_t e = next_event();
     if (rc == STY_OK) {
       hipError_t r = hipEventRecord(e, st);
@@ -186,17 +179,14 @@ struct Trainer {
     }
     if (rc == STY_OK) {
       DeferScope ds(this);
-      for (auto& fn : side_q) fn(st2);
+      fn(st2);
     }
-    side_q.clear();
     side_dirty = true;
   }
   void side_reduce_nowait() {
-    side_flush();
     if (side_dirty && st2) reduce_flush(st2);
   }
   void side_join() {
-    side_flush();
     reduce_flush(side_dirty && st2 ? st2 : st);
     if (side_dirty && st2) {
       hipEvent_t e = next_event();
@@ -396,7 +386,7 @@ struct Trainer {
     // aliasing of the resblock: G(x) IS the next conv's output gradient, which that conv's weight gradient reads): the kernel
     // reads the old values from there and writes a new buffer -- no copy-on-write pass over 160 MB in front of it
     const float* gX_src = nullptr;
-    if (f.nsrc == 1 && f.pro == PRO_AFFINE_SNAKE && pro_fuse_on && Tt % 8 == 0 && wants(f.x[0]) && !side_reads.empty()) {
+    if (f.nsrc == 1 && f.pro == PRO_AFFINE_SNAKE && Tt % 8 == 0 && wants(f.x[0]) && !side_reads.empty()) {
       auto ia = adain_of.find(f.pa);
       auto ig = gmap.find(f.x[0]);
       if (ia != adain_of.end() && ia->second.x == f.x[0] && ia->second.s == f.ps && !*ia->second.done && ig != gmap.end() &&
@@ -426,7 +416,7 @@ struct Trainer {
     // the fold and the instance-norm statistics term run as ONE launch (launch_pro_bwd_adain); adain()'s tape entry then has
     // nothing left to do
     AdainInfo* fuse = nullptr;
-    if (any && f.pro == PRO_AFFINE_SNAKE && f.nsrc == 1 && pro_fuse_on && Tt % 8 == 0) {
+    if (any && f.pro == PRO_AFFINE_SNAKE && f.nsrc == 1 && Tt % 8 == 0) {
       auto it = adain_of.find(f.pa);
       if (it != adain_of.end() && it->second.x == f.x[0] && it->second.s == f.ps && !*it->second.done) fuse = &it->second;
     }
@@ -650,7 +640,6 @@ struct Trainer {
     std::shared_ptr<bool> done;
   };
   std::unordered_map<const float*, AdainInfo> adain_of;  // folded scale a -> the instance norm it came from
-  bool pro_fuse_on = getenv("STY_NO_PRO_FUSE") == nullptr;
   void adain(const float* x, int C, int Tt, const AdaFc& fc, float*& a, float*& s, const double* have_part = nullptr,
              int have_nseg = 0) {
     a = take<float>((size_t)B * C);
@@ -957,8 +946,7 @@ struct Trainer {
   // GeneratorConvNeXtBlock (conv_next.py:80-93), any channel count
   float* convnext(const ConvNeXt& c, const float* x, int Tt, bool branch_only = false) {
     const int C = c.C;
-    static const bool fuse32 = getenv("STY_NO_CNX_FUSED") == nullptr;
-    if (C == 32 && fuse32 && c.w2a && c.w1_raw && c.w2_raw) return convnext32_fused(c, x, Tt);
+    if (C == 32 && c.w2a && c.w1_raw && c.w2_raw) return convnext32_fused(c, x, Tt);
     float* u = dwconv(x, c.dw_w, c.dw_b, C, Tt, 7, 3);
     float* xn = layernorm(u, C, Tt, 1e-6f, &c.norm, nullptr, nullptr);
     float* h0 = take<float>((size_t)B * 4 * C * Tt);
@@ -1098,7 +1086,7 @@ struct Trainer {
   bool resblock16(const ResBlock32& r, int Tt) const {
     // two-byte storage of the block's internal tensors: every conv of the block has to run on the persistent kernel (the only
     // one with the two-byte input / residual / output stages) and the fused prologue backward needs T % 8 == 0
-    if (!act16_on() || !pro_fuse_on || Tt % 8 != 0) return false;
+    if (!act16_on() || Tt % 8 != 0) return false;
     const int dil[3] = {1, 3, 5};
     for (int i = 0; i < 3; ++i) {
       ConvArgs c1, c2;

@@ -15,41 +15,36 @@
 
 #include "conv_stage.h"
 
-#ifndef WG_MODE
-#define WG_MODE 0  // chunk order (sty_common.h: wg_chunks)
-#endif
-
 namespace sty {
 
+constexpr int WG_MODE = 0;      // chunk order (sty_common.h: wg_chunks)
 constexpr int WG_TW = 128;      // time samples per chunk
 // workgroups per launch aimed at: the (batch, time) list is split to get there.  4 per CU in the fp32 modes; 3 per CU in the
 // bf16 mode, whose weight-gradient kernels share the chip with a main stream of much shorter kernels (c3, one A/B run:
 // 61.3-61.6 ms at 1024, 61.05-61.2 at 768, 61.0-61.4 at 640, 61.5 at 896, 62.2 at 1536; c2 (fp32): 32.7 at 1024, 32.8 at 768).
 // The scratch for the partial planes is sized for the larger count (wgrad_partial_floats).
-static const int WG_TARGET_ENV = getenv("STY_WG_TARGET") ? atoi(getenv("STY_WG_TARGET")) : 0;
-static const int WG_TARGET = WG_TARGET_ENV ? WG_TARGET_ENV : 1024;
-static inline int wg_target(bool bf16) { return WG_TARGET_ENV ? WG_TARGET_ENV : (bf16 ? 768 : 1024); }
+constexpr int WG_TARGET = 1024;
+static inline int wg_target(bool bf16) { return bf16 ? 768 : WG_TARGET; }
 // The partial planes are traffic too: nsplit planes written by the weight-gradient kernel and read back by the reduction.
 // On the layers with few positions and many weights (the 256 <-> 1024 pointwise convs at T = 520: 16 640 positions, planes
 // of 0.25-1 M elements) a split aimed at ~3 workgroups per CU moved 50 MB of partial sums for 85 MB of operands -- 3 GB
-// per c3 step in all.  STY_WG_PARTIAL_FRAC = f caps the split so that the partial planes stay below f x the operand bytes
-// (0 = no cap).  Default 0.25 since round 5 (A/B on the c3 step, one gpurun call, profiles/r05_ab_env.txt: no cap 54.06 ms,
+// per c3 step in all.  WG_PARTIAL_FRAC = f caps the split so that the partial planes stay below f x the operand bytes.
+// 0.25 since round 5 (A/B on the c3 step, profiles/r05_ab_env.txt: no cap 54.06 ms,
 // f = 1.0 53.71, 0.5 53.45, 0.25 51.71 [the grouped reduction 1.43 -> 0.81 ms], 0.125 52.94, 0.06 58.37: below 0.25 the
 // weight-gradient launches of those layers no longer fill the chip).  Round 4 had it off: with a reduction launch per
 // weight gradient the cap bought nothing; with the grouped reduction the partial planes are its whole cost.
-static const float WG_PARTIAL_FRAC = getenv("STY_WG_PARTIAL_FRAC") ? (float)atof(getenv("STY_WG_PARTIAL_FRAC")) : 0.25f;
-// bf16 mode only (or wherever the variable is set explicitly): on c2 -- fp32 MFMAs, 16x longer matrix phases -- the same cap
+constexpr float WG_PARTIAL_FRAC = 0.25f;
+// bf16 mode only: on c2 -- fp32 MFMAs, 16x longer matrix phases -- the same cap
 // COSTS 1.4 ms (30.92 ms without, 31.53 at f = 0.5, 32.31 at 0.25): there the splits are what fills the chip.
-static const bool WG_PARTIAL_FRAC_SET = getenv("STY_WG_PARTIAL_FRAC") != nullptr;
 // ... but never below the split that puts WG_MIN_WGS workgroups on the chip (`tiles` workgroups per split): on the text encoder's
 // k = 3 FFN layers (3 200 positions, planes of 0.2 M elements) the bare cap left 32 workgroups per launch -- 108 us alone for
-// 1.3 GFLOP (STY_WG_MIN_WGS, default 128; 0 = no floor; A/B in profiles/r05_ab_env.txt block 11: 256 and 512 buy the serial step 3 ms but cost the overlapped step 0.4 ms -- these launches run on the side stream).
-static const int WG_MIN_WGS = getenv("STY_WG_MIN_WGS") ? atoi(getenv("STY_WG_MIN_WGS")) : 128;
+// 1.3 GFLOP (A/B in profiles/r05_ab_env.txt block 11: 256 and 512 buy the serial step 3 ms but cost the overlapped step 0.4 ms -- these launches run on the side stream).
+constexpr int WG_MIN_WGS = 128;
 static inline int wg_cap_partial(int nsplit, const PackedConv& w, int B, int T, bool bf16, int tiles = 0) {
-  if (WG_PARTIAL_FRAC <= 0.f || !(bf16 || WG_PARTIAL_FRAC_SET)) return nsplit;
+  if (!bf16) return nsplit;
   const double operands = (double)B * T * (w.Cin + w.Cout), plane = (double)w.K * w.CinP * w.CoutP;
   int cap = (int)(WG_PARTIAL_FRAC * operands / plane);
-  if (tiles > 0 && WG_MIN_WGS > 0 && cap < cdiv(WG_MIN_WGS, tiles)) cap = cdiv(WG_MIN_WGS, tiles);
+  if (tiles > 0 && cap < cdiv(WG_MIN_WGS, tiles)) cap = cdiv(WG_MIN_WGS, tiles);
   if (cap < 1) cap = 1;
   if (cap >= 8) cap &= ~7;
   return nsplit < cap ? nsplit : cap;
@@ -441,8 +436,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_wgrad64_kernel(ConvArgs ax, Con
   }
 }
 static bool wgrad64_ok(const PackedConv& w, int dil) {
-  static const bool on = getenv("STY_NO_WGRAD64") == nullptr;
-  return on && w.K >= 2 && w.K <= 5 && w.CinP >= 64 && w.CoutP >= 64 && (w.K - 1) * dil <= 63;
+  return w.K >= 2 && w.K <= 5 && w.CinP >= 64 && w.CoutP >= 64 && (w.K - 1) * dil <= 63;
 }
 // the blocked kernel stages plain / flat-2-D operands only (one descriptor per batch slab)
 static bool wgrad64_operands_ok(const ConvArgs& fwd) {
@@ -827,15 +821,6 @@ int wgrad_defer_flush(WgReduceDefer* d, int site, hipStream_t st) {
   if (!d || d->jobs.empty()) return STY_OK;
   std::vector<WgReduceJob> all;
   all.swap(d->jobs);
-  if (getenv("STY_WG_DUMP")) {  // tuning aid: the partial volume of every recorded reduction
-    double tot = 0.0;
-    for (const WgReduceJob& j : all) {
-      fprintf(stderr, "wg_reduce site %d: plane %llu nb %d nslices %d -> %.2f MB\n", site, j.plane, j.nb, j.nslices,
-              4e-6 * (double)(j.plane + j.nb) * j.nslices);
-      tot += 4e-6 * (double)(j.plane + j.nb) * j.nslices;
-    }
-    fprintf(stderr, "wg_reduce site %d: %zu jobs, %.1f MB of partial sums\n", site, all.size(), tot);
-  }
   // split into rounds without overlapping destinations (stable: a job goes to the first round after every job it overlaps)
   std::vector<int> round(all.size(), 0);
   int nrounds = 1;

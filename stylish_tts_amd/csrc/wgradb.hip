@@ -24,15 +24,9 @@ namespace sty {
 
 // chunk order per kernel (sty_common.h: wg_chunks has the measurements): the tiled kernels take consecutive ranges, the two
 // streaming ones keep the strided front but with an XCD's workgroups on neighbouring chunks
-#ifndef WB_MODE
-#define WB_MODE 1   // wgradb_kernel, wgradb16_kernel
-#endif
-#ifndef WP32_MODE
-#define WP32_MODE 2  // wgradp32_kernel: 144 (1) / 141 (2) / 142 us (0) alone on the chip; 68 / 65 / 119 MB fetched on the block workload
-#endif
-#ifndef CNX_MODE
-#define CNX_MODE 2   // wgrad_cnx_kernel: 143 (1) / 128 (2) / 132 us (0); 134 / 101 / 144 MB
-#endif
+constexpr int WB_MODE = 1;    // wgradb_kernel, wgradb16_kernel
+constexpr int WP32_MODE = 2;  // wgradp32_kernel: 144 (1) / 141 (2) / 142 us (0) alone on the chip; 68 / 65 / 119 MB fetched on the block workload
+constexpr int CNX_MODE = 2;   // wgrad_cnx_kernel: 143 (1) / 128 (2) / 132 us (0); 134 / 101 / 144 MB
 constexpr int WB_PITCH = 136;  // bf16 elements between LDS rows
 constexpr int WB_TW_MASKED = 64;
 constexpr int WB_OOB = 0x7fffff00;
@@ -742,7 +736,7 @@ __global__ __launch_bounds__(256, 2) void wgradb16_kernel(ConvArgs ax, int nspli
 static bool wb_wide(const ConvArgs& ax);
 bool wgradb16_eligible(const ConvArgs& fwd) {
   const PackedConv& w = fwd.w;
-  if (!fwd.x16 || !fwd.g16 || !fwd.bf16 || getenv("STY_NO_WGRADB16")) return false;
+  if (!fwd.x16 || !fwd.g16 || !fwd.bf16) return false;
   if (!(w.K == 1 || w.K == 3 || w.K == 5) || w.CinP < 64 || w.CoutP < 64) return false;
   if (!(fwd.flatW || fwd.nsrc == 1) || fwd.in_shuffle > 1 || fwd.shuffle > 1 || fwd.Tin) return false;
   if (fwd.flatW && w.K == 1) return false;
@@ -764,10 +758,8 @@ static void wb16_launch(const ConvArgs& ax, dim3 grid, size_t lds, int nsplit, i
 // block shape of a launch: 0 = 64 x 64, 1 = 128 x 128 (K = 1 wide), 2 = 128 ci x 64 co, 3 = 128 ci x 96 co (K = 3)
 static int wb16_shape(const ConvArgs& ax) {
   const PackedConv& w = ax.w;
-  const char* fs = getenv("STY_WGRADB16_SHAPE");  // tuning aid, read per call (the A/B test toggles it): 0 = 64 x 64 everywhere
   if (w.K == 1) return wb_wide(ax) ? 1 : 0;
   if (w.K != 3) return 0;
-  if (fs) return atoi(fs) == 1 ? 0 : atoi(fs);
   if (w.CoutP <= 96 && w.CinP >= 128) return 3;
   if (w.CinP >= 128) return 2;
   return 0;

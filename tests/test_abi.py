@@ -39,6 +39,25 @@ def test_every_exported_symbol_is_declared(lib):
     assert exported == set(L.SYMBOLS), exported ^ set(L.SYMBOLS)
 
 
+def test_environment_switches_are_the_documented_ones():
+    """every STY_* variable the library (getenv under csrc/) or the package (os.environ) reads is in INTEGRATION.md's
+    switch table, and every name in the table is read: a tuning override that outlived its A/B shows up here"""
+    pkg = os.path.join(ROOT, "stylish_tts_amd")
+    read = set()
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            text = open(os.path.join(d, f), errors="replace").read() if f.endswith((".hip", ".h", ".py")) else ""
+            if f.endswith((".hip", ".h")):
+                read |= set(re.findall(r'getenv\(\s*"(STY_[A-Z0-9_]+)"', text))
+            elif f.endswith(".py"):
+                read |= set(re.findall(r'os\.(?:environ(?:\.get)?\s*[\[(]|getenv\s*\()\s*["\'](STY_[A-Z0-9_]+)', text))
+                read |= set(re.findall(r'["\'](STY_[A-Z0-9_]+)["\']\s+(?:not\s+)?in\s+os\.environ', text))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc.split("### Environment switches", 1)[1].split("\n### ", 1)[0]
+    table = {n for ln in section.splitlines() if ln.startswith("|") for n in re.findall(r"`(STY_[A-Z0-9_]+)", ln)}
+    assert read == table, {"read, not in the table": sorted(read - table), "in the table, not read": sorted(table - read)}
+
+
 def test_default_stft_bases_are_the_reference_buffers(lib):
     """sty_stft64_bases_host (host only: no device needed) against the buffers the reference's STFT module registers
     (tests/golden/stft_buffers.safetensors, dumped by tools/gen_golden.py): within 2 ulp of fp32 (the library's host

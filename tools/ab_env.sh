@@ -1,6 +1,6 @@
 #!/bin/bash
-# A/B of environment switches / library variants on one GPU box:
-#   WL=c3 tools/ab_env.sh "TAG1:VAR=1 VAR2=x" "TAG2:" "TAG3:STY_LIB_VARIANT=name" ...   (TAG: with nothing = product defaults)
+# A/B of environment switches on one GPU box:
+#   WL=c3 tools/ab_env.sh "TAG1:VAR=1 VAR2=x" "TAG2:" ...   (TAG: with nothing = product defaults)
 wl=${WL:-c3}
 steps=${STEPS:-20}
 O=${OUT:-tool_out}   # where the records go

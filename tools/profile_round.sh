@@ -70,13 +70,10 @@ done
 ( cd /tmp && STY_NO_SIDE_STREAM=1 STY_NO_SE_STREAM=1 rocprofv3 --kernel-trace --stats -d $O/serial_trace -- $B --steps 6 --warmup 2 > /dev/null 2> $O/serial_trace.log )
 python tools/rocpd_summary.py $O/serial_trace/*/*_results.db > $O/${tag}_c3_serial_kernel_stats.txt
 rm -rf $O/serial_trace
-bash tools/probes/fft_variants.sh > $O/${tag}_fft_variants.txt 2>&1
 # matrix-pipe utilisation counters (SQ_VALU_MFMA_BUSY_CYCLES) of the serialised c3 step -> gpurun_out/pmc_mfma/${tag}_c3_pmc_mfma.txt
 bash tools/pmc_mfma.sh $tag; cp $R/gpurun_out/pmc_mfma/${tag}_c3_pmc_mfma.txt $O/ 2>/dev/null
 python tools/convp16_bench.py 10 2>/dev/null | grep conv > $O/${tag}_convp16_microbench.txt
-# round 6: the twin-operand conv against convp16_kernel<.., X16> (A/B, bit-equality), its phases, the per-shape table of the serial step
-python tools/convq_bench.py 10 > $O/${tag}_convq_microbench.txt 2>/dev/null
-python tools/convq_phases.py 10 > $O/${tag}_convq_phases.txt 2>/dev/null
+# the per-shape table of the serial step
 bash tools/shapes_c3.sh $tag > /dev/null 2>&1; cp $R/gpurun_out/shapes_$tag.txt $O/${tag}_c3_shapes.txt 2>/dev/null
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/probes/overlap_probe.hip -o /tmp/overlap_probe 2>/dev/null && /tmp/overlap_probe > $O/${tag}_overlap_probe.txt
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/probes/buffer_offset_probe.hip -o /tmp/buffer_offset_probe 2>/dev/null && /tmp/buffer_offset_probe > $O/${tag}_buffer_offset_probe.txt
