@@ -409,6 +409,10 @@ static int launch_cfg(const ConvArgs& a, hipStream_t st) {
 
 static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st);
 int launch_conv1d(const ConvArgs& a, hipStream_t st) {
+  if (a.up_g && !conv1d_has_up_stage(a)) {
+    set_error("conv1d: up-sample + gate output stage asked of a conv that does not run on convq_kernel");
+    return STY_EINVAL;
+  }
   // ConvArgs::y16 (the bf16 operand twin of the output): convp16_kernel writes it from its output stage; for every other
   // kernel the cast pass makes it behind the conv -- the caller gets the twin either way
   const bool native16 = a.y16 && (stem2d_eligible(a) || (!conv32p_eligible(a) && !convk1_eligible(a) && convp16_eligible(a)));
@@ -421,6 +425,19 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
     rc = launch_twin_cast(a.y, nullptr, a.y16_act, a.B, a.w.Cout, a.T, a.y16, st);
   }
   return rc;
+}
+// (follows launch_conv1d_dispatch: the kernels in front of convp16 / convq in the chain read the fp32 tensor)
+bool conv1d_reads_twin_only(const ConvArgs& a) {
+  if (!a.x16 || a.nsrc != 1 || a.act == ACT_LRELU01) return false;
+  if (stem2d_eligible(a) || conv32p_eligible(a) || a.xh || a.yh || a.rh || a.stat_part || convk1_eligible(a)) return false;
+  return convp16_eligible(a);
+}
+// the stage lives in convq_kernel, for 2-D convs without an output mask, a residual or an activation of their own
+bool conv1d_has_up_stage(const ConvArgs& a) {
+  if (!conv1d_reads_twin_only(a) || !convq_eligible(a)) return false;
+  if (!a.flatW || a.act != ACT_NONE || a.out_mask || a.residual) return false;
+  if (a.up_g && (!a.up_gate16 || !a.up_mask || a.up_H <= 0 || a.up_H * a.flatW != a.T)) return false;
+  return (long)a.w.Cout * a.T < (1l << 26);  // (31-bit byte offsets into the pooled gradient with room for the marker)
 }
 static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st) {
   int cin = 0;

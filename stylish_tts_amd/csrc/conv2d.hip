@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256) void dwconv2d_s2_bwd_kernel(const float* __res
   const int nq = Ho * Wo;
   auto put = [&](int o, float v) {  // one element of dx (and of its twin)
     if (ACC) v += d[o];
-    d[o] = v;
+    if (ACC || dx) d[o] = v;  // (dx == nullptr: every reader of dx takes the twin, the caller says)
     if (!ACC && d16) d16[o] = (__bf16)(v * mk[o]);
   };
 #pragma unroll 1
@@ -501,6 +501,10 @@ int launch_dwconv2d_s2_bwd(const float* x, const float* gy, const float* gate, c
   const int nblk = cdiv(Ho * Wo, 256 * DW2_R);  // <= the cdiv(H (W + 1), 1024) dwconv2d_s2_bwd_scratch_floats sizes for
   if (dx16 && (accumulate || !mask16)) {
     set_error("dwconv2d_s2_bwd: the operand twin of dx needs the overwriting form and the mask");
+    return STY_EINVAL;
+  }
+  if (!dx && !dx16) {
+    set_error("dwconv2d_s2_bwd: neither dx nor its operand twin to write");
     return STY_EINVAL;
   }
   if (accumulate)
@@ -614,6 +618,9 @@ int launch_avgpool2_bwd(const float* gy, int BC, int H, int W, float scale, floa
     set_error("avgpool2_bwd: the operand twin of dx needs the mask and the channel count");
     return STY_EINVAL;
   }
+  // (in the kernel table: the parity tests look for the launches the input-gradient conv's output stage replaces)
+  const double ne = (double)BC * H * (W + 1);
+  ProfScope prof("avgpool2_bwd_kernel", 0.0, ne * (4.0 * (gate ? 3.0 : 2.0) + 1.0 + (dx16 ? 2.0 : 0.0)), st);
   hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(cdiv(H * (W + 1), 1024), BC), dim3(256), 0, st, gy, H, W, Ho, Wo, scale, dx,
                      gate, dx16, mask16, C > 0 ? C : 1);
   STY_LAUNCH_CHECK();

@@ -48,8 +48,9 @@ constexpr int CQ_XB = CQ_LW * 64;  // bytes per X buffer
 
 __device__ __forceinline__ int cq_xaddr(int L, int g) { return L * 64 + ((g ^ ((L >> 2) & 3)) << 4); }
 
-// (the fourth parameter is always 0: it keeps the instantiation names that profiles/r06_* record, convq_kernel<3, 3, 0, 0>)
-template <int MB, int K, int RELU, int = 0>
+// UP = 1: the up-sample + gate + twin output stage (ConvArgs::up_g ...) of the style encoder's input-gradient convs; only those
+// instantiations carry its registers.  (UP = 0 keeps the names that profiles/r06_* record, convq_kernel<3, 3, 0, 0>.)
+template <int MB, int K, int RELU, int UP = 0>
 __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles, int per_xcd) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cq_lds[];
   constexpr int J = 2 * K;             // k-steps of 16 channels per chunk
@@ -304,6 +305,40 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
     om[3] = o4.w;
   }
   const bool lrelu16 = a.y16_act == PRO_LRELU;
+  // UP: a lane's four columns as image positions (h, w) -> their element of the pooled plane [up_H / 2][Wo + 1] and the
+  // factor of the replicated last column; positions that take nothing (pad column, a last odd row, columns >= T) get an offset
+  // outside the descriptor, which loads as zero: v += 0, as avgpool2_bwd_kernel adds it
+  constexpr int UP_NONE = 1 << 28;
+  [[maybe_unused]] int upo[UP ? 4 : 1];
+  [[maybe_unused]] float upm[UP ? 4 : 1], um[UP ? 4 : 1];
+  [[maybe_unused]] int up_plane = 0;
+  __amdgpu_buffer_rsrc_t grs = yrs, prs = yrs;
+  if constexpr (UP) {
+    const int ldi = a.flatW, W = ldi - 1, Ho = a.up_H >> 1, Wo = (W + 1) >> 1;
+    up_plane = Ho * (Wo + 1);
+    int h = t / ldi, w = t - h * ldi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool ok = tin && w < W && (h >> 1) < Ho;
+      upo[e] = ok ? (h >> 1) * (Wo + 1) + (w >> 1) : UP_NONE;
+      upm[e] = ((W & 1) && w == W - 1) ? 2.f : 1.f;
+      um[e] = 0.f;
+      if (++w == ldi) {
+        w = 0;
+        ++h;
+      }
+    }
+    if (tin) {
+      const float4 m4 = *reinterpret_cast<const float4*>(a.up_mask + (size_t)b * T + t);
+      um[0] = m4.x;
+      um[1] = m4.y;
+      um[2] = m4.z;
+      um[3] = m4.w;
+    }
+    grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.up_gate16 + (size_t)b * Cout * T), 0, Cout * T * 2, 0x00020000);
+    prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.up_g + (size_t)b * Cout * up_plane), 0, Cout * up_plane * 4,
+                                            0x00020000);
+  }
 #pragma unroll
   for (int m = 0; m < MB; ++m) {
     const int cob = cot * MB * 32 + m * 32;
@@ -314,10 +349,9 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
       for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * hi) * 68 + n * 32 + l31] = acc[m][n][r];
     __builtin_amdgcn_wave_barrier();  // (the LDS queue of a wave is in order; this only keeps the compiler from moving the reads up)
     __builtin_amdgcn_sched_barrier(0);
-    // (rolled, two rows per trip: fully unrolled the scheduler hoists the 24 residual loads and stage reads of a tile to the top --
-    // 190 registers of temporaries -- and the allocator then spills inside the MAIN loop)
-#pragma unroll 2
-    for (int i = 0; i < 8; ++i) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    // one output row of the block: four columns per lane.  gq / gp (UP): the gate twin and the pooled gradient of the row
+    auto emit = [&](int i, [[maybe_unused]] u32x2 gq, [[maybe_unused]] const float* gp) {
       const int row = 4 * i + rr4, co = cob + row;
       const float4 sv = *reinterpret_cast<const float4*>(stg + row * 68 + 4 * c4);
       const float bi = bias_lds[m * 32 + row];
@@ -335,19 +369,53 @@ __global__ __launch_bounds__(256, 2) void convq_kernel(ConvArgs a, int tiles_per
         v[e] += rs4[e];  // (also without a residual, as q_drain does: -0 + 0 = +0)
         if (post) v[e] *= om[e];
       }
+      if constexpr (UP) {
+        // the sign of the conv's forward input, read off its operand twin bf16(lrelu(x)): LeakyReLU and the rounding keep it
+        const short qs[4] = {(short)(gq[0] & 0xFFFFu), (short)(gq[0] >> 16), (short)(gq[1] & 0xFFFFu), (short)(gq[1] >> 16)};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[e] = qs[e] > 0 ? v[e] : 0.2f * v[e];
+          v[e] += gp[e] * 0.25f * a.up_scale * upm[e];
+        }
+      }
       const float4 o4 = make_float4(v[0], v[1], v[2], v[3]);
       __builtin_amdgcn_raw_buffer_store_b128(
           __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o4), yrs, off * 4, 0, 0);
       if (a.y16) {
         float u[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = (lrelu16 && v[e] < 0.f) ? 0.2f * v[e] : v[e];
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        for (int e = 0; e < 4; ++e) u[e] = UP ? v[e] * um[UP ? e : 0] : ((lrelu16 && v[e] < 0.f) ? 0.2f * v[e] : v[e]);
         u32x2 dd;
         dd[0] = sty_pack2_bf16(u[0], u[1]);
         dd[1] = sty_pack2_bf16(u[2], u[3]);
         __builtin_amdgcn_raw_buffer_store_b64(dd, trs, off * 2, 0, 0);
       }
+    };
+    if constexpr (UP) {
+      // The eight rows' gate and pooled-gradient loads are requested together, in the registers the block's accumulators have
+      // just left (48 per lane), and consumed row by row: three round trips to memory per tile.  (Loaded where they are
+      // used -- two rows per trip -- the epilogue waited for twelve, each longer than a small layer's whole main loop.)
+      u32x2 gq[8];
+      float gp[8][4];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int co = cob + 4 * i + rr4;
+        gq[i] = __builtin_amdgcn_raw_buffer_load_b64(grs, tin ? (co * T + t) * 2 : 0x7FFFFF00, 0, 0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          gp[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, (co * up_plane + upo[e]) * 4, 0, 0));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        emit(i, gq[i], gp[i]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      // (rolled, two rows per trip: fully unrolled the scheduler hoists the 24 residual loads and stage reads of a tile to the top --
+      // 190 registers of temporaries -- and the allocator then spills inside the MAIN loop)
+#pragma unroll 2
+      for (int i = 0; i < 8; ++i) emit(i, u32x2{0u, 0u}, nullptr);
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -376,13 +444,13 @@ bool convq_eligible(const ConvArgs& a) {
   return (long)cdiv(a.T, CQ_TT) * a.B * cdiv(a.w.CoutP, 96) >= min_tiles;
 }
 
-template <int K, int RELU>
+template <int K, int RELU, int UP = 0>
 static int launch_cq(const ConvArgs& a, hipStream_t st) {
   constexpr int MB = 3;
   const size_t lds = cq_lds_bytes(MB, K);
   static bool raised = false;
   if (!raised) {
-    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&convq_kernel<MB, K, RELU, 0>),
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&convq_kernel<MB, K, RELU, UP>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     raised = true;
   }
@@ -393,11 +461,12 @@ static int launch_cq(const ConvArgs& a, hipStream_t st) {
   const double flops = 2.0 * a.w.Cin * a.w.K * outs;
   const double in_elems = (double)a.B * (a.flatW ? a.Cin2d : a.w.Cin) * a.T;
   const double bytes = 2.0 * in_elems + 4.0 * (outs * (a.residual ? 2.0 : 1.0) + (double)a.w.Cout * a.w.Cin * a.w.K) +
-                       (a.y16 ? 2.0 * outs : 0.0);
+                       (a.y16 ? 2.0 * outs : 0.0) + (UP ? 5.0 * outs : 0.0);  // (UP: the gate, a quarter-size pooled gradient)
   char detail[40];
   snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", a.w.Cin, a.w.Cout, a.w.K, a.T, a.flatW);
-  ProfScope prof(a.flatW ? "convq_kernel<3,true>" : "convq_kernel<3,true,1d>", flops, bytes, st, detail);
-  hipLaunchKernelGGL((convq_kernel<MB, K, RELU, 0>), dim3(8 * per_xcd), dim3(256), lds, st, a, tiles_per_row, ncot, ntiles, per_xcd);
+  ProfScope prof(UP ? "convq_kernel<3,true,up>" : (a.flatW ? "convq_kernel<3,true>" : "convq_kernel<3,true,1d>"), flops, bytes, st,
+                 detail);
+  hipLaunchKernelGGL((convq_kernel<MB, K, RELU, UP>), dim3(8 * per_xcd), dim3(256), lds, st, a, tiles_per_row, ncot, ntiles, per_xcd);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -409,6 +478,7 @@ int launch_convq(const ConvArgs& a0, hipStream_t st) {
   a.pro = PRO_NONE;  // the prologue (LeakyReLU / the [B][T] mask) is in the twin
   a.mask = nullptr;
   const bool relu = a.act == ACT_RELU;
+  if (a.up_g) return a.w.K == 1 ? launch_cq<1, 0, 1>(a, st) : launch_cq<3, 0, 1>(a, st);  // (conv1d_has_up_stage: no activation)
   if (a.w.K == 1) return relu ? launch_cq<1, 1>(a, st) : launch_cq<1, 0>(a, st);
   return relu ? launch_cq<3, 1>(a, st) : launch_cq<3, 0>(a, st);
 }

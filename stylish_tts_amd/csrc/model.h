@@ -325,6 +325,9 @@ int wgrad_defer_flush(WgReduceDefer* d, int site, hipStream_t st);
 inline bool wgrad_fuses_bias(const PackedConv& w) { return w.K <= 12; }
 int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask, float scale, float* gwp,
                         float* partial, float* gbias, bool* bias_done, hipStream_t st);
+// whether that launch reads both operands as their bf16 twins alone (fwd.x16 / fwd.g16 set; wgradb16_kernel, bias gradient
+// fused): the fp32 output gradient `g` then has no reader in it and need not exist
+bool conv1d_wgrad_reads_twins_only(const ConvArgs& fwd, bool gmask);
 int launch_pack_dgrad(const float* wp, int K, int CinP, int CoutP, float* wd, hipStream_t st);
 int launch_b2eff_bwd(const float* g, const float* w2, const float* beta, int C, float* db2, float* dbeta, float* dW2,
                      hipStream_t st);
@@ -350,6 +353,7 @@ int launch_pack_dgrad2d(const float* wp, int KW, int KH, int Cin, int Cout, int 
                         float* wd, hipStream_t st);
 size_t dwconv2d_s2_bwd_scratch_floats(int B, int C, int H, int W);
 // dx16 / mask16 (optional; overwriting form only): also write bf16(dx * mask16[b][n]), the operand twin of dx
+// dx == nullptr (with dx16): the twin alone -- the caller knows that every reader of dx takes the twin
 int launch_dwconv2d_s2_bwd(const float* x, const float* gy, const float* gate, const float* w9, int B, int C, int H, int W, float* dx,
                            int accumulate, float* dw9, float* db, float* scratch, hipStream_t st, __bf16* dx16 = nullptr,
                            const float* mask16 = nullptr);

@@ -224,6 +224,19 @@ struct ConvArgs {
   // y16 (producers): also store act16(y) as bf16 [B][Cout][T] -- the twin the next conv reads; y16_act = PRO_NONE or PRO_LRELU
   __bf16* y16 = nullptr;
   int y16_act = PRO_NONE;
+  // up-sample + gate + twin output stage of an input-gradient conv on the padded-flat layout (convq_kernel<.., 1>; the style
+  // encoder's ResBlk, train.hip): with the pooled gradient up_g [B][Cout][up_H / 2][(W + 1) / 2 + 1] of the block's shortcut
+  // branch (W = flatW - 1), the operand twin up_gate16 = bf16(lrelu(x)) [B][Cout][T] of the conv's forward input x (LeakyReLU and
+  // the rounding keep the sign of x) and the [B][T] mask of that input,
+  //   y = (up_gate16 > 0 ? y : 0.2 y) + up_g[c][h / 2][w / 2] * 0.25 * up_scale * (2 on the replicated last column of an odd W)
+  //   y16 = bf16(y * up_mask)   (where y16 is set)
+  // -- the operations of avgpool2_bwd_kernel behind a deferred LeakyReLU gate, in its order.  conv1d_has_up_stage(a) says
+  // whether the kernel launch_conv1d picks has the stage; every other kernel refuses the operands.
+  const float* up_g = nullptr;
+  const __bf16* up_gate16 = nullptr;
+  const float* up_mask = nullptr;
+  float up_scale = 1.f;
+  int up_H = 0;
   // ---- bf16 STORAGE of the 75T-rate activations (bf16 compute mode) ----
   // What autocast stores (config/config.yml:9-12, train/train_context.py:97-103: conv outputs live in HBM as bf16): the
   // tensor itself is two bytes per element, there is no fp32 copy.  xh: source 0 is a bf16 tensor [B][Cin][T] (x[0] is an
@@ -245,6 +258,9 @@ bool wgradb16_eligible(const ConvArgs& fwd);
 int launch_wgradb16(const ConvArgs& fwd, int nsplit, float* partial, int want_bias, hipStream_t st);
 
 int launch_conv1d(const ConvArgs& a, hipStream_t st);
+// whether that launch reads source 0 as its bf16 twin a.x16 alone (the fp32 tensor a.x[0] then has no reader in it)
+bool conv1d_reads_twin_only(const ConvArgs& a);
+bool conv1d_has_up_stage(const ConvArgs& a);  // (asked with or without the up_* operands set)
 // conv32p.hip: persistent, wave-specialised kernel for the 32 -> 32 channel convs at the 75T rate
 bool conv32p_eligible(const ConvArgs& a);
 int conv32p_stat_nseg(int T);

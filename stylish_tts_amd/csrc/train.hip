@@ -130,6 +130,66 @@ struct Trainer {
     mp[x] = t;
     return t;
   }
+  // Gradient stores nobody loads (style encoder, twins on).  g_twin_only = conv outputs y whose conv reads G(y) through the
+  // bf16 twin alone (conv2d decides with bwd_reads_twin_only when it records the conv); the element-wise backward that is the
+  // one writer of such a gradient then stores the twin and leaves the fp32 tensor out (dwconv2d_s2_bwd: conv1 of a
+  // down-sampling ResBlk).  g_no_fp32 = the buffers left that way: conv2d_bwd refuses one it would have to load.
+  // lazy_mask = activation -> the copy `G(act) = src * mask` its gradient is owed: the shortcut branch's gradient is the
+  // block's output gradient times the output mask, which the twin g16 already holds value for value.  The copy is made by
+  // whoever asks for the fp32 buffer (G / Gw), and never when the one reader takes the twin.
+  std::unordered_set<const float*> g_twin_only, g_no_fp32;
+  struct LazyMask {
+    const float* src;
+    const float* mask;
+    int C, n;
+    float* dst;
+  };
+  std::unordered_map<const float*, LazyMask> lazy_mask;
+  bool mask_pending(const float* act) const { return !lazy_mask.empty() && lazy_mask.count(act) != 0; }
+  void mask_flush(const float* act) {
+    auto it = lazy_mask.find(act);
+    if (it == lazy_mask.end()) return;
+    const LazyMask z = it->second;
+    lazy_mask.erase(it);
+    if (live())
+      chk(launch_pro_bwd(PRO_MASK, z.src, z.C, 0, z.src, B, z.C, z.n, nullptr, nullptr, z.C, 0, nullptr, z.mask, z.dst, 0,
+                         nullptr, nullptr, nullptr, st));
+  }
+  // pend_up = activation x -> the pooled gradient of the shortcut branch that has still to be up-sampled into G(x) (the
+  // backward of pool(x)).  The branch's backward runs BEFORE the main branch's first conv (style_forward records them in that
+  // order); that conv's input-gradient conv then takes the pooled gradient as an output-stage operand (ConvArgs::up_g: gate,
+  // up-sample and twin in its epilogue) where the kernel has the stage, and the element-wise pass (up_apply: what the tape
+  // entry of pool() used to launch) runs behind it otherwise -- or for whoever else asks for G(x) first.
+  struct PendUp {
+    const float* g;     // [BC][H / 2][(W + 1) / 2 + 1]
+    const float* mask;  // [B][n]: the mask of x's producer
+    float scale;
+    int BC, C, H, W, n;
+  };
+  std::unordered_map<const float*, PendUp> pend_up;
+  void up_apply(const float* src, const PendUp& u) {
+    // gs = gs * lrelu'(src) + up(g) in the one pass that accumulates into gs anyway
+    const bool gated = gate_pending(src);
+    if (gated) ungated.erase(src);
+    float* gs = G(src, (size_t)u.BC * u.n);
+    // this pass is the last writer of d loss / d src: it also leaves the bf16 operand twin for src's producer
+    __bf16* g16 = twins_on() && tw_want.count(src) && u.n % 4 == 0 ? take<__bf16>((size_t)u.BC * u.n) : nullptr;
+    if (g16) tw_g[gs] = std::make_pair(g16, u.mask);
+    if (live()) chk(launch_avgpool2_bwd(u.g, u.BC, u.H, u.W, u.scale, gs, gated ? src : nullptr, st, g16, u.mask, u.C));
+  }
+  void up_flush(const float* act) {
+    auto it = pend_up.find(act);
+    if (it == pend_up.end()) return;
+    const PendUp u = it->second;
+    pend_up.erase(it);
+    up_apply(act, u);
+  }
+  void grad_sets_clear() {
+    g_twin_only.clear();
+    g_no_fp32.clear();
+    lazy_mask.clear();
+    pend_up.clear();
+  }
   ~Trainer() {
     wgrad_defer_destroy(defer);
     for (hipEvent_t e : evs) (void)hipEventDestroy(e);
@@ -284,8 +344,11 @@ struct Trainer {
     chk(launch_pro_bwd(PRO_LRELU, g, C, 0, act, B, C, n, nullptr, nullptr, C, 0, nullptr, nullptr, g, 0, nullptr, nullptr,
                        nullptr, st));
   }
-  float* G(const float* act, size_t n, bool raw = false) {  // raw: the caller deals with a deferred gate itself
+  // raw: the caller deals with a deferred gate itself; keep_lazy: ... and with a pending masked copy (lazy_mask)
+  float* G(const float* act, size_t n, bool raw = false, bool keep_lazy = false) {
+    if (!pend_up.empty()) up_flush(act);
     if (!raw && !ungated.empty()) gate_flush(act);
+    if (!keep_lazy && !lazy_mask.empty()) mask_flush(act);
     auto it = gmap.find(act);
     if (it != gmap.end() && is16(it->second)) {
       set_error("a two-byte gradient buffer reached a consumer without a two-byte form");
@@ -303,7 +366,12 @@ struct Trainer {
   // same, for a producer that can either overwrite or accumulate: the first writer of a buffer overwrites it
   // (acc = 0) and no zero-fill is issued; later writers accumulate
   float* Gw(const float* act, size_t n, int& acc) {
+    if (!pend_up.empty()) up_flush(act);
     if (!ungated.empty()) gate_flush(act);
+    if (mask_pending(act)) {  // a second writer: the buffer gets its values now, and the shared twin is no longer its twin
+      tw_g.erase(lazy_mask[act].dst);
+      mask_flush(act);
+    }
     auto it = gmap.find(act);
     if (it != gmap.end() && is16(it->second)) {
       set_error("a two-byte gradient buffer reached a second writer");
@@ -1901,35 +1969,130 @@ struct Trainer {
     side_need = pn > side_need ? pn : side_need;
     wg_need(pn);
     if (live()) chk(launch_conv1d(a, st));
+    if (a.x16 && bwd_reads_twin_only(a)) g_twin_only.insert(y);
     tape.push_back([this, a]() { conv2d_bwd(a); });
   }
+  // the input-gradient conv of f: the conv of gY (as the twin g16 where there is one) with the transposed weights
+  bool dgrad_args(const ConvArgs& f, const float* gY, ConvArgs& d) const {
+    const PackedConv& w = f.w;
+    auto it = m->dgrad.find(w.wp);
+    if (it == m->dgrad.end()) return false;
+    const int KH = w.Cin / f.Cin2d;
+    d.x[0] = gY;
+    d.xc[0] = it->second.Cin;
+    d.nsrc = 1;
+    d.B = B;
+    d.T = f.T;
+    d.pad = (w.K - 1) - f.pad;
+    d.bf16 = f.bf16;
+    d.w = it->second;
+    d.flatW = f.flatW;
+    d.hpad = (KH - 1) - f.hpad;
+    d.Cin2d = w.Cout;
+    d.pro = PRO_MASK;
+    d.mask = f.out_mask;
+    d.x16 = f.g16;  // (the mask is in the twin)
+    d.out_scale = f.out_scale;
+    return true;
+  }
+  // whether conv2d_bwd(f) loads the output gradient through its bf16 twin alone: both GEMMs take the twin, the bias gradient
+  // comes out of the weight-gradient kernel and no shortcut branch wants a masked fp32 copy.  (Eligibility tests that a
+  // twin is there, not which: the forward asks with a stand-in.)
+  bool bwd_reads_twin_only(const ConvArgs& f0) const {
+    if (!f0.x16) return false;  // (conv2d_bwd takes g16 for convs that read their input as a twin)
+    ConvArgs f = f0;
+    if (!f.g16) f.g16 = f.x16;
+    if (f.residual && wants(f.residual)) return false;
+    if (!m->topts.frozen && !conv1d_wgrad_reads_twins_only(f, f.out_mask != nullptr)) return false;
+    if (wants(f.x[0])) {
+      ConvArgs d;
+      if (!dgrad_args(f, nullptr, d) || !conv1d_reads_twin_only(d)) return false;
+    }
+    return true;
+  }
   void conv2d_bwd(const ConvArgs& f0) {
+    // a pooled shortcut gradient waiting for the input's gradient buffer: taken along, as an operand of the input-gradient
+    // conv or as the pass behind it
+    PendUp up;
+    bool has_up = false;
+    auto pu = pend_up.find(f0.x[0]);
+    if (pu != pend_up.end()) {
+      up = pu->second;
+      has_up = true;
+      pend_up.erase(pu);
+    }
+    conv2d_bwd_run(f0, has_up ? &up : nullptr, has_up);
+    if (has_up && rc == STY_OK) up_apply(f0.x[0], up);
+  }
+  // up != nullptr: has_up is cleared when the input-gradient conv took the pooled gradient into its output stage
+  void conv2d_bwd_run(const ConvArgs& f0, const PendUp* up, bool& has_up) {
     ConvArgs f = f0;
     const PackedConv& w = f.w;
-    const int KH = w.Cin / f.Cin2d, n = f.T;
+    const int n = f.T;
     const size_t ny = (size_t)B * w.Cout * n, nx = (size_t)B * f.Cin2d * n;
-    float* gY = G(f.y, ny);
+    float* gY = G(f.y, ny, false, true);
+    bool own_twin = false;
     if (f.x16) {  // the weight gradient and the input gradient read gY * mask as a bf16 twin, rounded once
       auto tg = tw_g.find(gY);
       if (tg != tw_g.end() && tg->second.second == f.out_mask) {
-        f.g16 = tg->second.first;  // written by gY's last writer
-      } else {
-        __bf16* g16 = take<__bf16>(ny);  // (kept to the end of the step: a side-stream launch reads it)
-        if (live()) chk(launch_twin_cast(gY, f.out_mask, PRO_NONE, B, w.Cout, n, g16, st));
-        f.g16 = g16;
+        f.g16 = tg->second.first;  // written by gY's last writer (or, for a shortcut conv, the twin conv2 of the block read)
+        own_twin = true;
       }
+    }
+    // the fp32 values of gY: owed as a masked copy (lazy_mask) or left out by the writer (g_no_fp32) -- made now, or refused,
+    // unless every load below goes through the twin
+    const bool twin_only = own_twin && bwd_reads_twin_only(f);
+    if (twin_only && mask_pending(f.y)) {
+      lazy_mask.erase(f.y);
+      g_no_fp32.insert(gY);
+    }
+    mask_flush(f.y);
+    if (!twin_only && g_no_fp32.count(gY)) {
+      set_error("training: a 2-D conv's backward loads an fp32 output gradient its writer left out");
+      rc = STY_ESTATE;
+      return;
+    }
+    if (f.x16 && !own_twin) {
+      __bf16* g16 = take<__bf16>(ny);  // (kept to the end of the step: a side-stream launch reads it)
+      if (live()) chk(launch_twin_cast(gY, f.out_mask, PRO_NONE, B, w.Cout, n, g16, st));
+      f.g16 = g16;
     }
     int accR = 1;  // (the first writer of the residual's gradient overwrites: no zero-fill, no read)
     float* gR = (f.residual && wants(f.residual)) ? Gw(f.residual, ny, accR) : nullptr;
     int accX = 1;
     float* gX = wants(f.x[0]) ? Gw(f.x[0], nx, accX) : nullptr;
     if (side_ready() && gX && gX == gY) gX = fresh_copy(f.x[0], gY, nx);
+    const bool defer_gate = getenv("STY_NO_DEFERRED_GATE") == nullptr;  // A/B switch, read per call (the parity test toggles it)
+    // Output stage of the input-gradient conv instead of two element-wise passes: this conv is the first writer of d x, its
+    // prologue is the LeakyReLU whose factor would be deferred anyway, the pooled gradient of the shortcut branch is waiting
+    // -- gate, up-sample, fp32 store and (where x's producer reads one) the twin leave the conv's epilogue (convq_kernel<.., 1>)
+    ConvArgs dup;
+    bool staged = false;
+    if (up && gX && gX != gY && !accX && f.pro == PRO_LRELU && defer_gate && twins_on() && f.g16 &&
+        n % 4 == 0 && up->n == n && up->C == f.Cin2d && up->BC == B * f.Cin2d && dgrad_args(f, gY, dup)) {
+      dup.y = gX;
+      dup.up_g = up->g;
+      dup.up_gate16 = f.x16;  // (bf16(lrelu(x)): the sign of x)
+      dup.up_mask = up->mask;
+      dup.up_scale = up->scale;
+      dup.up_H = up->H;
+      if (conv1d_has_up_stage(dup)) {
+        if (tw_want.count(f.x[0])) dup.y16 = take<__bf16>(nx);  // (in front of `mark`: kept for x's producer)
+        staged = true;
+      }
+    }
     const size_t mark = ws.off;
     // gY may carry values in the pad columns (written by element-wise backward steps): everything below sees
     // gY * mask, exactly as the forward stored y * mask
-    if (gR && live())
+    if (gR && !accR && f.g16) {
+      // first writer of the shortcut's gradient: gR = gY * mask is what g16 holds already.  The twin is registered for the
+      // shortcut's producer and the fp32 copy waits for a reader (lazy_mask)
+      tw_g[gR] = std::make_pair(const_cast<__bf16*>(f.g16), f.out_mask);
+      lazy_mask[f.residual] = LazyMask{gY, f.out_mask, w.Cout, n, gR};
+    } else if (gR && live()) {
       chk(launch_pro_bwd(PRO_MASK, gY, w.Cout, 0, gY, B, w.Cout, n, nullptr, nullptr, w.Cout, 0, nullptr, f.out_mask,
                          gR, accR, nullptr, nullptr, nullptr, st));
+    }
     bool bias_done = false;
     float* gbias = w.bias ? PGpacked(w.bias) : nullptr;
     if (m->topts.frozen) {
@@ -1953,31 +2116,21 @@ struct Trainer {
       if (live()) chk(launch_bias_grad(gY, f.out_mask, B, w.Cout, n, 0, f.out_scale, PGpacked(w.bias), bs, st));
     }
     if (gX) {
-      auto it = m->dgrad.find(w.wp);
-      if (it == m->dgrad.end()) {
+      ConvArgs d;
+      if (!dgrad_args(f, gY, d)) {
         set_error("training: no input-gradient weights for a 2-D conv");
         rc = STY_ESTATE;
         return;
       }
+      if (staged) {
+        if (dup.y16) tw_g[gX] = std::make_pair(dup.y16, up->mask);
+        if (live()) chk(launch_conv1d(dup, st));
+        has_up = false;
+        ws.off = mark;
+        return;
+      }
       float* U = take<float>(nx);
-      ConvArgs d;
-      d.x[0] = gY;
-      d.xc[0] = it->second.Cin;
-      d.nsrc = 1;
-      d.B = B;
-      d.T = n;
-      d.pad = (w.K - 1) - f.pad;
-      d.bf16 = f.bf16;
-      d.w = it->second;
-      d.flatW = f.flatW;
-      d.hpad = (KH - 1) - f.hpad;
-      d.Cin2d = w.Cout;
-      d.pro = PRO_MASK;
-      d.mask = f.out_mask;
-      d.x16 = f.g16;  // (the mask is in the twin)
-      d.out_scale = f.out_scale;
       d.y = U;
-      const bool defer_gate = getenv("STY_NO_DEFERRED_GATE") == nullptr;  // A/B switch, read per call (the parity test toggles it)
       if (gX != gY && (f.pro == PRO_NONE || (f.pro == PRO_LRELU && !accX && defer_gate))) {
         // no pass of its own for the prologue's derivative: the input-gradient conv writes (or, without a prologue,
         // accumulates through its residual operand) the gradient buffer.  LeakyReLU prologue, first writer of the buffer:
@@ -2019,6 +2172,7 @@ struct Trainer {
     tw_x[1].clear();
     tw_want.clear();
     tw_g.clear();
+    grad_sets_clear();
     nograd.clear();
     ungated.clear();
     scratch_param_n = 1 << 16;
@@ -2092,32 +2246,42 @@ struct Trainer {
         const int BC = B * Cc;
         const float* mk_in = mk;  // the mask of the activation being pooled (its producer's output mask)
         tape.push_back([=]() {
-          float* g = G(out, (size_t)BC * no);
-          // gs = gs * lrelu'(src) + up(g) in the one pass that accumulates into gs anyway
-          const bool gated = gate_pending(src);
-          if (gated) ungated.erase(src);
-          float* gs = G(src, (size_t)BC * n);
-          // this pass is the last writer of d loss / d src: it also leaves the bf16 operand twin for src's producer
-          __bf16* g16 = twins_on() && tw_want.count(src) && n % 4 == 0 ? take<__bf16>((size_t)BC * n) : nullptr;
-          if (g16) tw_g[gs] = std::make_pair(g16, mk_in);
-          if (live()) chk(launch_avgpool2_bwd(g, BC, Hc, Wc, scale, gs, gated ? src : nullptr, st, g16, mk_in, Cc));
+          const float* g = nullptr;
+          auto lz = lazy_mask.find(out);
+          if (lz != lazy_mask.end() && lz->second.mask == mko) {
+            // the pooled tensor is the block's shortcut: its gradient is conv2's output gradient times the mask of the pad
+            // column, which the pass below never indexes -- it reads conv2's buffer and the masked copy is not made
+            g = lz->second.src;
+            lazy_mask.erase(lz);
+          } else {
+            g = G(out, (size_t)BC * no);
+          }
+          // up-sampled into G(src) by the backward of the conv that reads src (conv2d_bwd), or by up_apply
+          up_flush(src);  // (a second pooling of the same tensor: one at a time)
+          pend_up[src] = PendUp{g, mk_in, scale, BC, Cc, Hc, Wc, n};
         });
         return out;
       };
-      if (k.down && k.has_sc) {
-        const float* pooled = pool(xin, k.Cin, 1.f, true);
-        float* sc = take<float>((size_t)B * k.Cout * no);
-        conv2d(k.sc, pooled, k.Cin, no, Wo + 1, sc, 0, 0, PRO_NONE, r2, nullptr, mko);
-        res = sc;
-      } else if (k.down) {
-        res = pool(xin, k.Cout, r2);
-      } else if (k.has_sc) {
-        float* sc_full = take<float>((size_t)B * k.Cout * n);
-        conv2d(k.sc, xin, k.Cin, n, W + 1, sc_full, 0, 0, PRO_NONE, r2, nullptr, mk);
-        res = sc_full;
-      }
+      auto shortcut = [&]() {
+        if (k.down && k.has_sc) {
+          const float* pooled = pool(xin, k.Cin, 1.f, true);
+          float* sc = take<float>((size_t)B * k.Cout * no);
+          conv2d(k.sc, pooled, k.Cin, no, Wo + 1, sc, 0, 0, PRO_NONE, r2, nullptr, mko);
+          res = sc;
+        } else if (k.down) {
+          res = pool(xin, k.Cout, r2);
+        } else if (k.has_sc) {
+          float* sc_full = take<float>((size_t)B * k.Cout * n);
+          conv2d(k.sc, xin, k.Cin, n, W + 1, sc_full, 0, 0, PRO_NONE, r2, nullptr, mk);
+          res = sc_full;
+        }
+      };
+      // A pooled shortcut is recorded BEHIND conv1, so that the backward has the branch's pooled gradient before conv1's
+      // input-gradient conv runs and can hand it to that conv's output stage (pend_up); the two branches are independent
+      if (!k.down) shortcut();
       float* h1 = take<float>((size_t)B * k.Cin * n);
       conv2d(k.c1, xin, k.Cin, n, W + 1, h1, 1, 1, PRO_LRELU, 1.f, nullptr, mk, k.down ? -1 : PRO_LRELU);
+      if (k.down) shortcut();
       const float* h = h1;
       if (k.down) {
         float* h2 = take<float>((size_t)B * k.Cin * no);
@@ -2137,11 +2301,16 @@ struct Trainer {
           // ... and the last: the bf16 operand twin of d loss / d h1 (times conv1's output mask) for conv1's backward
           __bf16* g16 = twins_on() && !acc && tw_want.count(h1) && n % 4 == 0 ? take<__bf16>((size_t)B * Cc * n) : nullptr;
           if (g16) tw_g[gx] = std::make_pair(g16, mk1);
+          // ... and where conv1's backward loads the twin alone (and h1 is no parity tap) the fp32 tensor is not stored
+          bool tap = false;
+          for (const SeTap& tp : se_taps) tap = tap || tp.act == h1;
+          const bool no32 = g16 && !tap && g_twin_only.count(h1) != 0;
+          if (no32) g_no_fp32.insert(gx);
           const size_t mark = ws.off;
           float* sc = take<float>(dwconv2d_s2_bwd_scratch_floats(B, Cc, Hc, Wc));
           if (live())
-            chk(launch_dwconv2d_s2_bwd(h1, g, gated ? h2 : nullptr, w9, B, Cc, Hc, Wc, gx, acc, PGpacked(w9), PG(dwb, Cc), sc,
-                                       st, g16, mk1));
+            chk(launch_dwconv2d_s2_bwd(h1, g, gated ? h2 : nullptr, w9, B, Cc, Hc, Wc, no32 ? nullptr : gx, acc, PGpacked(w9),
+                                       PG(dwb, Cc), sc, st, g16, mk1));
           ws.off = mark;
         });
         h = h2;
@@ -2203,6 +2372,7 @@ struct Trainer {
       (*it)();
       if (rc != STY_OK) break;
     }
+    while (rc == STY_OK && !pend_up.empty()) up_flush(pend_up.begin()->first);
     side_join();
   }
 
@@ -2217,6 +2387,7 @@ struct Trainer {
     tw_x[1].clear();
     tw_want.clear();
     tw_g.clear();
+    grad_sets_clear();
     nograd.clear();
     half_.clear();
     g16_ok.clear();

@@ -1030,6 +1030,18 @@ static bool stem_wgrad_eligible(const ConvArgs& f, const float* g, const float* 
          ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(gmask)) & 15) == 0;
 }
 
+// (follows the two branches of launch_conv1d_wgrad that end in launch_wgradb16; both produce the bias gradient)
+bool conv1d_wgrad_reads_twins_only(const ConvArgs& fwd, bool gmask) {
+  const PackedConv& w = fwd.w;
+  if (fwd.xh || fwd.gh) return false;
+  if (w.K == 1) {
+    ConvArgs ax1 = fwd;
+    ax1.flatW = 0;
+    return wgradb_eligible(ax1, gmask) && wgradb16_eligible(ax1);
+  }
+  return wgrad64_ok(w, fwd.dil) && wgrad64_operands_ok(fwd) && wgradb_eligible(fwd, gmask) && wgradb16_eligible(fwd);
+}
+
 // ax: forward ConvArgs (sources, prologue, dil, pad, w); g: output gradient [B][Cout][T] (shuffled when ax.shuffle > 1);
 // gmask: optional [B][T] multiplier of g; scale: constant factor (the forward out_scale); gwp += result.
 // gbias: packed bias gradient (+=) or nullptr; *bias_done tells the caller whether this launch produced it (K == 1 and
