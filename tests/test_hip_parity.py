@@ -554,12 +554,23 @@ def test_attention_backward_vs_float64(DH, T, masked):
     """sty_attention_fwd_bwd: the text encoder's masked attention (DH = 16, VALU backward kernels attn_bwd_{a,b,c}), the
     conformer's (DH = 64, MFMA backward attn_bwd_{kv,q}_mfma) and the prosody encoder's (2 heads x 160 / 96 with the length
     mask, the same MFMA backward since round 6) vs float64 softmax attention: o, dq, dk, dv."""
+    _attention_backward_vs_float64(DH, T, torch.tensor([T, max(1, T - 7), max(1, T // 2)]) if masked else None)
+
+
+@pytest.mark.parametrize("DH,T", [(16, 100), (160, 200), (160, 520), (96, 77), (64, 160)])
+def test_attention_backward_vs_float64_row_of_one_and_tile_edge_lengths(DH, T):
+    """the masked rows of the test above (T >= 65) on a second length table: a row of length 1 (one key carries the whole
+    softmax, every other query row is padding) and lengths on and one above the 64-key edge of two 32-key tiles; same gates."""
+    _attention_backward_vs_float64(DH, T, torch.tensor([1, 64, 65]))
+
+
+def _attention_backward_vs_float64(DH, T, lengths):
     from stylish_tts_amd import lib as L
     lib = L.load()
+    masked = lengths is not None
     B, H = 3, (8 if DH <= 64 else 2)
     g = torch.Generator().manual_seed(DH + T)
     q, k, v, do = (torch.randn(B, H * DH, T, generator=g) for _ in range(4))
-    lengths = torch.tensor([T, max(1, T - 7), max(1, T // 2)]) if masked else None
     valid = torch.ones(B, 1, T)
     if masked:
         # padded QUERY rows: the reference adds -1e4 to every score of the row, which in fp32 rounds the scores to 1e-3 --
