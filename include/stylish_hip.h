@@ -466,6 +466,21 @@ int sty_comm_set_stream(sty_comm *c, void *stream);
 int sty_comm_stats(sty_comm *c, uint64_t *buckets, uint64_t *reduce_scatter_all_gather, double *bytes);
 int sty_comm_destroy(sty_comm *c);
 
+/* ---- the static voicepack's table (train/voicepack.py:116-136 `make_static`) -----------------------------------------
+ * sty_pack_accumulate replaces `styles[length.item() - 1].append(combined)` (voicepack.py:118-122) for a whole batch:
+ * row i of styles [n][D] is added to bucket text_lengths[i] - 1 of sums [rows][D] (float64) and counts [rows] is
+ * incremented; all buffers on the device, the caller zeroes sums / counts before the first call.  The rows of one bucket
+ * are added in row order by one thread per column, with no float atomics: the same calls give the same bits.  A length
+ * outside 1..rows is the caller's to refuse on the host (before upload); such a row is not added.
+ * sty_pack_finalize replaces `torch.stack(sum(styles[lower:upper], []), 0).mean(0)` per row of the pack
+ * (voicepack.py:131-135): pack[i] = (sum of sums[b] for b in [lo[i], hi[i]) ascending) / (sum of counts[b]), one division
+ * and one rounding to fp32.  lo / hi [rows] (device): the windows as a Python slice normalises them, resolved on the host
+ * from `counts` (stylish_tts_amd/voicepack.py resolve_windows, voicepack.py:124-130).  A window without rows gives NaN. */
+int sty_pack_accumulate(int n, int D, int rows, const float *styles, const int64_t *text_lengths, double *sums,
+                        int64_t *counts, void *stream);
+int sty_pack_finalize(int rows, int D, const double *sums, const int64_t *counts, const int32_t *lo, const int32_t *hi,
+                      float *pack, void *stream);
+
 /* ---- in-situ kernel timing (used by bench.py for the roofline object) --------------------------------
  * When enabled, every launch of the instrumented kernel families is bracketed by HIP events on the launch
  * stream.  sty_prof_report synchronises the device, sums the event times per family and writes up to `cap`

@@ -161,6 +161,8 @@ SYMBOLS = {
     "sty_comm_set_stream": (C.c_int, [_P, _P]),
     "sty_comm_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "sty_comm_destroy": (C.c_int, [_P]),
+    "sty_pack_accumulate": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    "sty_pack_finalize": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, _P]),
     "sty_prof_enable": (C.c_int, [_I]),
     "sty_prof_only": (C.c_int, [C.c_char_p]),
     "sty_set_single_stream": (C.c_int, [_I]),

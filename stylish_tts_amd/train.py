@@ -7,6 +7,8 @@ the HIP path -> accelerate-layout checkpoints, stage after stage (acoustic -> te
 or `stylish_tts_amd.train.train(config_path, model_config_path, out, stage, checkpoint, reset_stage)` -- the reference
 command's arguments in the reference command's order.  What is joined here exists piece by piece elsewhere in this package
 (config.py, data.py, acoustic.py / textual.py / duration.py, optim.py, stage_io.py); this file holds no arithmetic.
+The reference's other two commands on the same files: `convert` is below (--convert), `voicepack` is
+stylish_tts_amd/voicepack.py (its consumer, `speak`, is stylish_tts_amd/speak.py); both take the last stage's checkpoint.
 
 What the reference's loop does and this one does NOT (out of scope): the alignment stage (its model is
 not on this path), validation audio / tensorboard, the WavLM loss term (third-party weights), the batch-size PROBE
