@@ -650,6 +650,21 @@ struct Run {
   float* gb = nullptr;  // style fc outputs
   int rc = STY_OK;
 
+  // workspace == nullptr: a sizing call (allocations are tracked, nothing is launched)
+  Run(sty_model* model, int batch, void* workspace, size_t ws_bytes, void* stream) : m(model), st(S(stream)), B(batch) {
+    ws.base = (char*)workspace;
+    ws.cap = ws_bytes;
+  }
+  // the end of an entry point: the size a sizing call asked for, or an overflow of the caller's workspace
+  int finish(size_t* need, const void* workspace, size_t ws_bytes) {
+    if (need) *need = align_up(peak > ws.off ? peak : ws.off, 256) + 256;
+    if (workspace && (ws.overflow || peak > ws_bytes)) {
+      set_error("workspace too small: need %zu bytes, have %zu", peak, ws_bytes);
+      return STY_ENOMEM;
+    }
+    return rc;
+  }
+
   const float* gbp(const AdaFc& a) const { return gb ? gb + a.off * B : nullptr; }
   void chk(int r) {
     if (rc == STY_OK && r != STY_OK) rc = r;
@@ -1687,14 +1702,33 @@ static int unpack_grads(sty_model* m, hipStream_t st, int seg = -1) {
   return STY_OK;
 }
 
-int sty_speech_train_workspace_bytes(sty_model* m, int B, int L, int T, size_t* bytes) {
-  int rc = model_ready(m, "speech_predictor");
+// ready for a training forward or its sizing call: the model is finalized and of the right kind, training is enabled
+// (not_enabled: the status when it is not) and the trainer exists
+static int train_ready(sty_model* m, int not_enabled, const char* kind_a, const char* kind_b = nullptr) {
+  int rc = model_ready(m, kind_a, kind_b);
   if (rc) return rc;
-  if (!m->train_enabled || !bytes || B <= 0 || L <= 0 || T <= 1) {
-    set_error("sty_speech_train_workspace_bytes: bad argument or training not enabled");
-    return STY_EINVAL;
+  if (!m->train_enabled) {
+    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
+    return not_enabled;
   }
   if (!m->trainer) m->trainer = trainer_create(m);
+  return STY_OK;
+}
+// the end of a backward: the packed gradients of a segment (-1: all) go to the caller's buffers, then the gradient hook
+static int finish_bwd(sty_model* m, hipStream_t st, int seg = -1) {
+  int rc = unpack_grads(m, st, seg);
+  if (rc) return rc;
+  if (m->grad_hook) m->grad_hook(m->grad_hook_user, seg < 0 ? 0 : seg);
+  return STY_OK;
+}
+
+int sty_speech_train_workspace_bytes(sty_model* m, int B, int L, int T, size_t* bytes) {
+  int rc = train_ready(m, STY_EINVAL, "speech_predictor");
+  if (rc) return rc;
+  if (!bytes || B <= 0 || L <= 0 || T <= 1) {
+    set_error("sty_speech_train_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
   sty_speech_io io;
   memset(&io, 0, sizeof(io));
   io.B = B;
@@ -1717,12 +1751,8 @@ static int prepared_consume(sty_model* m, void* stream) {
   return STY_OK;
 }
 int sty_speech_fwd_train(sty_model* m, const sty_speech_io* io, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor");
+  int rc = train_ready(m, STY_ESTATE, "speech_predictor");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!io || !workspace || !io->texts || !io->text_lengths || !io->alignment || !io->pitch || !io->energy ||
       !io->voiced || !io->style || !io->denormal_pitch || !io->audio || io->B <= 0 || io->L <= 0 || io->T <= 1) {
     set_error("sty_speech_fwd_train: bad argument");
@@ -1734,19 +1764,14 @@ int sty_speech_fwd_train(sty_model* m, const sty_speech_io* io, void* workspace,
     return rc;
   }
   m->prepared = false;  // a training step mutates buffers and is followed by an optimizer step: inference re-prepares
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_speech_forward(m->trainer, io, workspace, ws_bytes, S(stream), nullptr);
 }
 // The weight-side half of the next sty_speech_fwd_train (packs, input-gradient packs, bf16 fragments: ~20 launches that depend
 // on the parameters only) ahead of time: AcousticTrainer issues it right after the predictor's AdamW step, while the style
 // encoder's backward still runs on its streams, so the next step's forward starts with the text encoder.
 int sty_speech_prepare_train(sty_model* m, void* stream) {
-  int rc = model_ready(m, "speech_predictor");
+  int rc = train_ready(m, STY_ESTATE, "speech_predictor");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   m->train_prepared = false;
   if ((rc = sty_model_prepare(m, stream))) return rc;
   if ((rc = prepared_mark(m, stream))) return rc;
@@ -1775,21 +1800,15 @@ int sty_speech_bwd_pe(sty_model* m, const float* d_audio, float* d_style, float*
   // not stop for the weight-gradient stream in the middle of the backward, and both segments are un-packed at the end.)
   if (m->grad_hook)
     trainer_set_segment_hook(m->trainer, [&](int) {
-      hook_rc = unpack_grads(m, st, 0);
-      if (hook_rc == STY_OK && m->grad_hook) m->grad_hook(m->grad_hook_user, 0);
+      hook_rc = finish_bwd(m, st, 0);
       seg0_done = true;
     });
   rc = trainer_speech_backward(m->trainer, d_audio, d_style, d_energy, st, d_pitch);
   trainer_set_segment_hook(m->trainer, nullptr);
   if (rc) return rc;
   if (hook_rc) return hook_rc;
-  if (!seg0_done) {
-    if ((rc = unpack_grads(m, st, 0))) return rc;
-    if (m->grad_hook) m->grad_hook(m->grad_hook_user, 0);
-  }
-  if ((rc = unpack_grads(m, st, 1))) return rc;
-  if (m->grad_hook) m->grad_hook(m->grad_hook_user, 1);
-  return STY_OK;
+  if (!seg0_done && (rc = finish_bwd(m, st, 0))) return rc;
+  return finish_bwd(m, st, 1);
 }
 
 int sty_speech_d_style_ready(sty_model* m, void* stream) {
@@ -1802,13 +1821,12 @@ int sty_speech_d_style_ready(sty_model* m, void* stream) {
   return trainer_wait_d_style(m->trainer, S(stream));
 }
 int sty_vocoder_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  int rc = train_ready(m, STY_EINVAL, "speech_predictor", "vocoder");
   if (rc) return rc;
-  if (!m->train_enabled || !bytes || B <= 0 || T <= 1) {
-    set_error("sty_vocoder_train_workspace_bytes: bad argument or training not enabled");
+  if (!bytes || B <= 0 || T <= 1) {
+    set_error("sty_vocoder_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  if (!m->trainer) m->trainer = trainer_create(m);
   sty_vocoder_io io;
   memset(&io, 0, sizeof(io));
   io.B = B;
@@ -1817,12 +1835,8 @@ int sty_vocoder_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes)
 }
 
 int sty_vocoder_fwd_train(sty_model* m, const sty_vocoder_io* io, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  int rc = train_ready(m, STY_ESTATE, "speech_predictor", "vocoder");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!io || !workspace || !io->mel || !io->style || !io->audio || io->B <= 0 || io->T <= 1 ||
       (!io->prior_override && (!io->pitch || !io->voiced))) {
     set_error("sty_vocoder_fwd_train: bad argument");
@@ -1830,7 +1844,6 @@ int sty_vocoder_fwd_train(sty_model* m, const sty_vocoder_io* io, void* workspac
   }
   if ((rc = sty_model_prepare(m, stream))) return rc;  // parameters change every step
   m->prepared = false;
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_vocoder_forward(m->trainer, io, workspace, ws_bytes, S(stream), nullptr);
 }
 
@@ -1843,9 +1856,7 @@ int sty_vocoder_bwd(sty_model* m, const float* d_audio, float* d_mel, float* d_s
   }
   rc = trainer_vocoder_backward(m->trainer, d_audio, d_mel, d_style, S(stream));
   if (rc) return rc;
-  if ((rc = unpack_grads(m, S(stream)))) return rc;
-  if (m->grad_hook) m->grad_hook(m->grad_hook_user, 0);
-  return STY_OK;
+  return finish_bwd(m, S(stream));
 }
 
 int sty_model_num_keys(const sty_model* m) { return m ? (int)m->requested.size() : 0; }
@@ -2076,20 +2087,10 @@ int sty_model_prepare(sty_model* m, void* stream) {
 }
 
 static int vocoder_run(sty_model* m, const sty_vocoder_io* io, void* ws, size_t ws_bytes, void* stream, size_t* need) {
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = io->B;
-  r.ws.base = (char*)ws;
-  r.ws.cap = ws_bytes;
+  Run r(m, io->B, ws, ws_bytes, stream);
   run_style_fc(r, io->style);
   r.vocoder(*io);
-  if (need) *need = align_up(r.peak > r.ws.off ? r.peak : r.ws.off, 256) + 256;
-  if (ws && (r.ws.overflow || r.peak > ws_bytes)) {
-    set_error("workspace too small: need %zu bytes, have %zu", r.peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(need, ws, ws_bytes);
 }
 
 int sty_vocoder_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
@@ -2122,12 +2123,7 @@ int sty_vocoder_fwd(sty_model* m, const sty_vocoder_io* io, void* workspace, siz
 }
 
 static int speech_run(sty_model* m, const sty_speech_io* io, void* ws, size_t ws_bytes, void* stream, size_t* need) {
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = io->B;
-  r.ws.base = (char*)ws;
-  r.ws.cap = ws_bytes;
+  Run r(m, io->B, ws, ws_bytes, stream);
   run_style_fc(r, io->style);
   const int B = io->B, L = io->L, T = io->T;
   const int inter = m->te.proj_m.Cout ? m->te.proj_m.Cout : 128;
@@ -2141,24 +2137,10 @@ static int speech_run(sty_model* m, const sty_speech_io* io, void* ws, size_t ws
   }
   r.decoder(asr, io->pitch, io->energy, io->voiced, T, mel);
   if (r.live()) r.tap(io->tap_decoder_out, mel, (size_t)B * m->dec.encode.Cout * T);
-  sty_vocoder_io v = io->voc_taps;
-  v.B = B;
-  v.T = T;
+  sty_vocoder_io v = vocoder_io_of(*io);
   v.mel = mel;
-  v.style = io->style;
-  v.pitch = io->denormal_pitch;
-  v.voiced = io->voiced;
-  v.noise = io->noise;
-  v.prior_override = io->prior_override;
-  v.seed = io->seed;
-  v.audio = io->audio;
   r.vocoder(v);
-  if (need) *need = align_up(r.peak > r.ws.off ? r.peak : r.ws.off, 256) + 256;
-  if (ws && (r.ws.overflow || r.peak > ws_bytes)) {
-    set_error("workspace too small: need %zu bytes, have %zu", r.peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(need, ws, ws_bytes);
 }
 
 int sty_speech_workspace_bytes(const sty_model* m, int B, int L, int T, size_t* bytes) {
@@ -2194,20 +2176,10 @@ int sty_speech_fwd(sty_model* m, const sty_speech_io* io, void* workspace, size_
 // ---- second-stage predictors (inference) ----
 static int duration_run(sty_model* m, int B, int L, const int64_t* texts, const int64_t* lengths, const float* style,
                         float* out, void* ws, size_t ws_bytes, void* stream, size_t* need) {
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = B;
-  r.ws.base = (char*)ws;
-  r.ws.cap = ws_bytes;
+  Run r(m, B, ws, ws_bytes, stream);
   run_style_fc(r, style);
   duration_forward(r, texts, lengths, L, out);
-  if (need) *need = align_up(r.peak > r.ws.off ? r.peak : r.ws.off, 256) + 256;
-  if (ws && (r.ws.overflow || r.peak > ws_bytes)) {
-    set_error("workspace too small: need %zu bytes, have %zu", r.peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(need, ws, ws_bytes);
 }
 int sty_duration_workspace_bytes(const sty_model* m, int B, int L, size_t* bytes) {
   int rc = model_ready(m, "duration_predictor");
@@ -2232,47 +2204,31 @@ int sty_duration_fwd(sty_model* m, int B, int L, const int64_t* texts, const int
 static int pitch_energy_run(sty_model* m, int B, int L, int T, const int64_t* texts, const int64_t* lengths,
                             const float* alignment, const float* style, float* f0, float* energy, void* ws,
                             size_t ws_bytes, void* stream, size_t* need) {
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = B;
-  r.ws.base = (char*)ws;
-  r.ws.cap = ws_bytes;
+  Run r(m, B, ws, ws_bytes, stream);
   run_style_fc(r, style);
   pitch_energy_forward(r, texts, lengths, alignment, style, L, T, f0, energy);
-  if (need) *need = align_up(r.peak > r.ws.off ? r.peak : r.ws.off, 256) + 256;
-  if (ws && (r.ws.overflow || r.peak > ws_bytes)) {
-    set_error("workspace too small: need %zu bytes, have %zu", r.peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(need, ws, ws_bytes);
 }
 // DurationPredictor in the training graph (train_duration, stage_type.py:495-556): forward, then sty_duration_bwd
 int sty_duration_train_workspace_bytes(sty_model* m, int B, int L, size_t* bytes) {
-  int rc = model_ready(m, "duration_predictor");
+  int rc = train_ready(m, STY_EINVAL, "duration_predictor");
   if (rc) return rc;
-  if (!m->train_enabled || !bytes || B <= 0 || L <= 0) {
-    set_error("sty_duration_train_workspace_bytes: bad argument or training not enabled");
+  if (!bytes || B <= 0 || L <= 0) {
+    set_error("sty_duration_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_duration_forward(m->trainer, B, L, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, bytes);
 }
 int sty_duration_fwd_train(sty_model* m, int B, int L, const int64_t* texts, const int64_t* text_lengths, const float* style,
                            float* out, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "duration_predictor");
+  int rc = train_ready(m, STY_ESTATE, "duration_predictor");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!texts || !text_lengths || !style || !out || !workspace || B <= 0 || L <= 0) {
     set_error("sty_duration_fwd_train: bad argument");
     return STY_EINVAL;
   }
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_duration_forward(m->trainer, B, L, texts, text_lengths, style, out, workspace, ws_bytes, S(stream), nullptr);
 }
 int sty_duration_bwd(sty_model* m, const float* d_out, float* d_style, void* stream) {
@@ -2284,38 +2240,30 @@ int sty_duration_bwd(sty_model* m, const float* d_out, float* d_style, void* str
   }
   rc = trainer_duration_backward(m->trainer, d_out, d_style, S(stream));
   if (rc) return rc;
-  if ((rc = unpack_grads(m, S(stream)))) return rc;
-  if (m->grad_hook) m->grad_hook(m->grad_hook_user, 0);
-  return STY_OK;
+  return finish_bwd(m, S(stream));
 }
 // PitchEnergyPredictor in the training graph (train_textual, stage_type.py:119-127): forward, then sty_pitch_energy_bwd
 int sty_pitch_energy_train_workspace_bytes(sty_model* m, int B, int L, int T, size_t* bytes) {
-  int rc = model_ready(m, "pitch_energy_predictor");
+  int rc = train_ready(m, STY_EINVAL, "pitch_energy_predictor");
   if (rc) return rc;
-  if (!m->train_enabled || !bytes || B <= 0 || L <= 0 || T <= 0) {
-    set_error("sty_pitch_energy_train_workspace_bytes: bad argument or training not enabled");
+  if (!bytes || B <= 0 || L <= 0 || T <= 0) {
+    set_error("sty_pitch_energy_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_pitch_energy_forward(m->trainer, B, L, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                                       nullptr, bytes);
 }
 int sty_pitch_energy_fwd_train(sty_model* m, int B, int L, int T, const int64_t* texts, const int64_t* text_lengths,
                                const float* alignment, const float* style, float* pitch, float* energy, void* workspace,
                                size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "pitch_energy_predictor");
+  int rc = train_ready(m, STY_ESTATE, "pitch_energy_predictor");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!texts || !text_lengths || !alignment || !style || !pitch || !energy || !workspace || B <= 0 || L <= 0 || T <= 0) {
     set_error("sty_pitch_energy_fwd_train: bad argument");
     return STY_EINVAL;
   }
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_pitch_energy_forward(m->trainer, B, L, T, texts, text_lengths, alignment, style, pitch, energy, workspace,
                                       ws_bytes, S(stream), nullptr);
 }
@@ -2328,9 +2276,7 @@ int sty_pitch_energy_bwd(sty_model* m, const float* d_pitch, const float* d_ener
   }
   rc = trainer_pitch_energy_backward(m->trainer, d_pitch, d_energy, d_style, S(stream));
   if (rc) return rc;
-  if ((rc = unpack_grads(m, S(stream)))) return rc;
-  if (m->grad_hook) m->grad_hook(m->grad_hook_user, 0);
-  return STY_OK;
+  return finish_bwd(m, S(stream));
 }
 int sty_pitch_energy_workspace_bytes(const sty_model* m, int B, int L, int T, size_t* bytes) {
   int rc = model_ready(m, "pitch_energy_predictor");
@@ -2386,23 +2332,14 @@ int sty_convnext_fwd(sty_model* m, const char* prefix, int B, int C, int T, cons
     set_error("block %s not found or channel mismatch", prefix);
     return STY_EINVAL;
   }
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = B;
-  r.ws.base = (char*)workspace;
-  r.ws.cap = ws_bytes;
+  Run r(m, B, workspace, ws_bytes, stream);
   run_style_fc(r, style);
   if (x == y && C == 32) {
     set_error("sty_convnext_fwd: C == 32 runs out of place, y must differ from x");
     return STY_EINVAL;
   }
   r.convnext(*blk, x, y, T);
-  if (r.ws.overflow || r.peak > ws_bytes) {
-    set_error("workspace too small: need %zu bytes", r.peak);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(nullptr, workspace, ws_bytes);
 }
 
 int sty_resblock_fwd(sty_model* m, const char* prefix, int B, int T, const float* x, const float* style, float* y,
@@ -2422,20 +2359,11 @@ int sty_resblock_fwd(sty_model* m, const char* prefix, int B, int T, const float
     set_error("no such resblock: %s", prefix);
     return STY_EINVAL;
   }
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = B;
-  r.ws.base = (char*)workspace;
-  r.ws.cap = ws_bytes;
+  Run r(m, B, workspace, ws_bytes, stream);
   run_style_fc(r, style);
   if (y != x) STY_HIP(hipMemcpyAsync(y, x, (size_t)B * 32 * T * sizeof(float), hipMemcpyDeviceToDevice, r.st));
   r.resblock(*blk, y, T);
-  if (r.ws.overflow || r.peak > ws_bytes) {
-    set_error("workspace too small: need %zu bytes", r.peak);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(nullptr, workspace, ws_bytes);
 }
 
 // ---- unit backward entry points: one sub-module in the training graph, forward + backward ----
@@ -2481,16 +2409,15 @@ static int find_block(sty_model* m, const char* kind, const char* prefix, int C,
 
 int sty_block_train_workspace_bytes(sty_model* m, const char* kind, const char* prefix, int B, int C, int T,
                                     size_t* bytes) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  int rc = train_ready(m, STY_EINVAL, "speech_predictor", "vocoder");
   if (rc) return rc;
-  if (!m->train_enabled || !kind || !prefix || !bytes || B <= 0 || C <= 0 || T <= 0) {
-    set_error("sty_block_train_workspace_bytes: bad argument or training not enabled");
+  if (!kind || !prefix || !bytes || B <= 0 || C <= 0 || T <= 0) {
+    set_error("sty_block_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
   int k = 0;
   const void* blk = nullptr;
   if ((rc = find_block(m, kind, prefix, C, &k, &blk))) return rc;
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_block_fwd_bwd(m->trainer, k, blk, B, C, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                                nullptr, bytes);
 }
@@ -2498,12 +2425,8 @@ int sty_block_train_workspace_bytes(sty_model* m, const char* kind, const char* 
 int sty_block_fwd_bwd(sty_model* m, const char* kind, const char* prefix, int B, int C, int T, const float* x,
                       const float* style, const float* gy, float* y, float* gx, float* d_style, void* workspace,
                       size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  int rc = train_ready(m, STY_ESTATE, "speech_predictor", "vocoder");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!kind || !prefix || !x || !style || !gy || !workspace || B <= 0 || C <= 0 || T <= 0) {
     set_error("sty_block_fwd_bwd: bad argument");
     return STY_EINVAL;
@@ -2513,7 +2436,6 @@ int sty_block_fwd_bwd(sty_model* m, const char* kind, const char* prefix, int B,
   if ((rc = find_block(m, kind, prefix, C, &k, &blk))) return rc;
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
-  if (!m->trainer) m->trainer = trainer_create(m);
   rc = trainer_block_fwd_bwd(m->trainer, k, blk, B, C, T, x, style, gy, y, gx, d_style, workspace, ws_bytes, S(stream),
                              nullptr);
   if (rc) return rc;
@@ -2631,29 +2553,14 @@ int sty_alignment_fwd(int B, int L, int T, const float* durations, float* alignm
 
 static int style_entry(sty_model* m, int B, int T, const float* mel, float* style, void* ws, size_t ws_bytes,
                        void* stream, size_t* need) {
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = B;
-  r.ws.base = (char*)ws;
-  r.ws.cap = ws_bytes;
+  Run r(m, B, ws, ws_bytes, stream);
   style_run(r, mel, T, style);
-  if (need) *need = align_up(r.peak > r.ws.off ? r.peak : r.ws.off, 256) + 256;
-  if (ws && (r.ws.overflow || r.peak > ws_bytes)) {
-    set_error("workspace too small: need %zu bytes, have %zu", r.peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(need, ws, ws_bytes);
 }
 // PitchStyleEncoder.forward at coarse_multiplier 1 (mel_style_encoder.py:188-205)
 static int pitch_style_entry(sty_model* m, int B, int T, const float* mel, const float* pitch, const float* energy,
                              float* style, void* ws, size_t ws_bytes, void* stream, size_t* need) {
-  Run r;
-  r.m = m;
-  r.st = S(stream);
-  r.B = B;
-  r.ws.base = (char*)ws;
-  r.ws.cap = ws_bytes;
+  Run r(m, B, ws, ws_bytes, stream);
   const int C = m->pse_pre.Cin, D = m->pse_pre.Cout, Tp = T + 2;
   float* cat = r.ws.take<float>((size_t)B * C * T);
   float* padded = r.ws.take<float>((size_t)B * C * Tp);
@@ -2666,12 +2573,7 @@ static int pitch_style_entry(sty_model* m, int B, int T, const float* mel, const
     r.conv(r.base(m->pse_pre, padded, Tp, pre));
   }
   style_run(r, pre, Tp, style);
-  if (need) *need = align_up(r.peak > r.ws.off ? r.peak : r.ws.off, 256) + 256;
-  if (ws && (r.ws.overflow || r.peak > ws_bytes)) {
-    set_error("workspace too small: need %zu bytes, have %zu", r.peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return r.rc;
+  return r.finish(need, ws, ws_bytes);
 }
 int sty_pitch_style_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
   int rc = model_ready(m, "pitch_style_encoder");
@@ -2733,12 +2635,8 @@ static int style_train_prepare(sty_model* m, void* stream) {
   return STY_OK;
 }
 int sty_style_prepare_train(sty_model* m, void* stream) {
-  int rc = model_ready(m, "mel_style_encoder", "pitch_style_encoder");
+  int rc = train_ready(m, STY_ESTATE, "mel_style_encoder", "pitch_style_encoder");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   m->train_prepared = false;
   if ((rc = style_train_prepare(m, stream))) return rc;
   if ((rc = prepared_mark(m, stream))) return rc;
@@ -2746,56 +2644,44 @@ int sty_style_prepare_train(sty_model* m, void* stream) {
   return STY_OK;
 }
 int sty_style_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "mel_style_encoder");
+  int rc = train_ready(m, STY_EINVAL, "mel_style_encoder");
   if (rc) return rc;
-  if (!m->train_enabled || !bytes || B <= 0 || T < 40) {
-    set_error("sty_style_train_workspace_bytes: bad argument or training not enabled");
+  if (!bytes || B <= 0 || T < 40) {
+    set_error("sty_style_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_style_forward(m->trainer, B, T, nullptr, nullptr, nullptr, 0, nullptr, bytes);
 }
 int sty_style_fwd_train(sty_model* m, int B, int T, const float* mel, float* style, void* workspace, size_t ws_bytes,
                         void* stream) {
-  int rc = model_ready(m, "mel_style_encoder");
+  int rc = train_ready(m, STY_ESTATE, "mel_style_encoder");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!mel || !style || !workspace || B <= 0 || T < 40) {
     set_error("sty_style_fwd_train: bad argument (T >= 40 frames)");
     return STY_EINVAL;
   }
   if ((rc = style_train_prepare(m, stream))) return rc;
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_style_forward(m->trainer, B, T, mel, style, workspace, ws_bytes, S(stream), nullptr);
 }
 // PitchStyleEncoder in the training graph (the second-stage `pe_style_encoder`): forward, then sty_style_bwd
 int sty_pitch_style_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "pitch_style_encoder");
+  int rc = train_ready(m, STY_EINVAL, "pitch_style_encoder");
   if (rc) return rc;
-  if (!m->train_enabled || !bytes || B <= 0 || T < 40) {
-    set_error("sty_pitch_style_train_workspace_bytes: bad argument or training not enabled");
+  if (!bytes || B <= 0 || T < 40) {
+    set_error("sty_pitch_style_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_style_forward(m->trainer, B, T, nullptr, nullptr, nullptr, 0, nullptr, bytes);
 }
 int sty_pitch_style_fwd_train(sty_model* m, int B, int T, const float* mel, const float* pitch, const float* energy,
                               float* style, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "pitch_style_encoder");
+  int rc = train_ready(m, STY_ESTATE, "pitch_style_encoder");
   if (rc) return rc;
-  if (!m->train_enabled) {
-    set_error("training not enabled: call sty_model_enable_training / sty_model_bind_grad before finalize");
-    return STY_ESTATE;
-  }
   if (!mel || !pitch || !energy || !style || !workspace || B <= 0 || T < 40) {
     set_error("sty_pitch_style_fwd_train: bad argument (T >= 40 frames)");
     return STY_EINVAL;
   }
   if ((rc = style_train_prepare(m, stream))) return rc;
-  if (!m->trainer) m->trainer = trainer_create(m);
   return trainer_style_forward(m->trainer, B, T, mel, style, workspace, ws_bytes, S(stream), nullptr, pitch, energy);
 }
 int sty_style_bwd(sty_model* m, const float* d_style, void* stream) {
@@ -2807,9 +2693,7 @@ int sty_style_bwd(sty_model* m, const float* d_style, void* stream) {
   }
   rc = trainer_style_backward(m->trainer, d_style, S(stream));
   if (rc) return rc;
-  if ((rc = unpack_grads(m, S(stream)))) return rc;
-  if (m->grad_hook) m->grad_hook(m->grad_hook_user, 0);
-  return STY_OK;
+  return finish_bwd(m, S(stream));
 }
 // parity taps of the style encoder's training graph: activation (grad = 0) or its gradient (grad = 1, after sty_style_bwd)
 int sty_style_tap(sty_model* m, int index, int grad, float* dst, int* C, int* H, int* W, void* stream) {

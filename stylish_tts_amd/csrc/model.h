@@ -377,6 +377,20 @@ int trainer_style_forward(struct Trainer* t, int B, int T, const float* mel, flo
                           hipStream_t st, size_t* need, const float* pitch = nullptr, const float* energy = nullptr);
 int trainer_style_backward(struct Trainer* t, const float* d_style, hipStream_t st);
 int trainer_style_tap(struct Trainer* t, int i, int grad, float* dst, int* C, int* H, int* W, hipStream_t st);
+// the vocoder's half of a speech predictor call (taps included); the caller adds mel, the decoder's output
+inline sty_vocoder_io vocoder_io_of(const sty_speech_io& io) {
+  sty_vocoder_io v = io.voc_taps;
+  v.B = io.B;
+  v.T = io.T;
+  v.style = io.style;
+  v.pitch = io.denormal_pitch;
+  v.voiced = io.voiced;
+  v.noise = io.noise;
+  v.prior_override = io.prior_override;
+  v.seed = io.seed;
+  v.audio = io.audio;
+  return v;
+}
 struct Trainer;
 Trainer* trainer_create(sty_model* m);
 int trainer_speech_forward(Trainer* t, const sty_speech_io* io, void* ws, size_t ws_bytes, hipStream_t st,

@@ -9,6 +9,12 @@
 // sty_train_opts selects module.train() behaviour (BatchNorm batch statistics, smoothing, power iteration, dropout,
 // bf16 operands); all zero = the eval-mode graph of the golden gradient fixtures.  Weight gradients run on a second
 // stream (see "side stream" below).
+//
+// Every entry point (trainer_*_forward / _backward, trainer_block_fwd_bwd) follows one protocol.  Forward: open() binds
+// stream, shape and workspace (or the fake base of a sizing pass), the graph's method records ops and tape, the outputs
+// are copied out, and close_forward() reports the size (after a dry backward) or an overflow.  Backward: run_tape()
+// seeds the output gradients, walks the tape in reverse, joins the weight-gradient stream and runs fc(style)'s backward;
+// what a graph does differently is an argument of it.  close_backward() reports an overflow.
 #include <stdlib.h>
 #include <string.h>
 
@@ -42,6 +48,98 @@ struct Trainer {
   bool live() const { return !dry && ws.base != nullptr && rc == STY_OK; }
   void chk(int r) {
     if (rc == STY_OK && r != STY_OK) rc = r;
+  }
+  // ---- the entry-point protocol: open, record the graph, close; backward = seed, tape, join, fc (run_tape) ----
+  // the sizing pass bumps from a fake base that is never dereferenced, under a cap no graph reaches
+  static constexpr size_t kDryBase = size_t(1) << 30, kDryCap = size_t(1) << 46;
+  // what a sizing pass adds to the measured peak
+  static constexpr size_t kSlack = 64 << 20, kSlackStyle = 16 << 20;
+  // the style encoders' sizing pass has no tensors of the caller: these stand in as distinct non-null map keys
+  static inline float kDryMel = 0.f, kDryStyle = 0.f;
+  void open(int B_, int T_, void* ws_, size_t ws_bytes, hipStream_t st_, bool dry_) {
+    st = st_;
+    B = B_;
+    T = T_;
+    rc = STY_OK;
+    ws = Bump();
+    dry = dry_;
+    ws.base = dry ? reinterpret_cast<char*>(kDryBase) : (char*)ws_;
+    ws.cap = dry ? kDryCap : ws_bytes;
+    peak = 0;
+  }
+  // every per-step container and counter; begin() and style_forward() start from here.  ungated is only ever filled by the
+  // 2-D convs of the style encoders, half_ / g16_ok / adain_of / drop_site only by the 1-D graphs: each is empty (zero) on
+  // the path that used to leave it alone.  (se_taps is cleared where it is rebuilt.)
+  void reset_step() {
+    tape.clear();
+    gmap.clear();
+    tw_x[0].clear();
+    tw_x[1].clear();
+    tw_want.clear();
+    tw_g.clear();
+    g_twin_only.clear();
+    g_no_fp32.clear();
+    lazy_mask.clear();
+    pend_up.clear();
+    nograd.clear();
+    half_.clear();
+    g16_ok.clear();
+    adain_of.clear();
+    ungated.clear();
+    side_need = 0;
+    wg_sum = 0;
+    drop_site = 0;
+  }
+  // the sizing pass (the entry has run its backward dry by now) reports the peak and drops the tape; the live pass reports
+  // an overflow of the caller's workspace
+  int close_forward(size_t* need, size_t ws_bytes, size_t slack, const char* what) {
+    if (need) {
+      *need = align_up(peak, 256) + slack;
+      tape.clear();
+      return rc;
+    }
+    if (ws.overflow) {
+      set_error("%s workspace too small: need %zu bytes, have %zu", what, peak, ws_bytes);
+      return STY_ENOMEM;
+    }
+    return rc;
+  }
+  int close_backward() {
+    if (ws.overflow) {
+      set_error("training workspace too small in backward: need %zu bytes", peak);
+      return STY_ENOMEM;
+    }
+    return rc;
+  }
+  void copy_f32(float* dst, const float* src, size_t n, const char* what) {  // device to device, on the main stream
+    if (!live()) return;
+    hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) rc = hip_fail(e, what);
+  }
+  // the gradient buffer of a graph output, holding the caller's gradient d (sizing pass: d == nullptr, the buffer alone)
+  float* seed(const float* act, const float* d, size_t n) {
+    float* g = G(act, n);
+    if (d) copy_f32(g, d, n, "seed copy");
+    return g;
+  }
+  // The backward of every graph.  `seeds` calls seed() for each output; the tape runs in reverse and stops at the first
+  // error.  flush_up (the style encoders): pooled shortcut gradients nobody has asked for are up-sampled before the join.
+  // fc (every graph with AdaIN / AdaLN layers): d_style is armed before the tape and fc(style)'s backward runs behind the
+  // join, unless a tape hook has run it (the speech graph); the style encoders have neither.
+  void run_tape(const std::function<void()>& seeds, bool flush_up, bool fc, float* d_style) {
+    side_begin();
+    if (fc) {
+      d_style_out = d_style;
+      fc_bwd_done = false;
+    }
+    seeds();
+    for (auto it = tape.rbegin(); it != tape.rend(); ++it) {
+      (*it)();
+      if (rc != STY_OK) break;
+    }
+    while (flush_up && rc == STY_OK && !pend_up.empty()) up_flush(pend_up.begin()->first);
+    side_join();
+    if (fc && rc == STY_OK) style_fc_backward();
   }
 
   // ---- side stream for the weight gradients ----
@@ -184,12 +282,6 @@ struct Trainer {
     pend_up.erase(it);
     up_apply(act, u);
   }
-  void grad_sets_clear() {
-    g_twin_only.clear();
-    g_no_fp32.clear();
-    lazy_mask.clear();
-    pend_up.clear();
-  }
   ~Trainer() {
     wgrad_defer_destroy(defer);
     for (hipEvent_t e : evs) (void)hipEventDestroy(e);
@@ -264,10 +356,7 @@ struct Trainer {
   }
   float* fresh_copy(const float* act, float* g, size_t n) {
     float* g2 = take<float>(n);
-    if (live()) {
-      hipError_t e = hipMemcpyAsync(g2, g, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "grad copy");
-    }
+    copy_f32(g2, g, n, "grad copy");
     gmap[act] = g2;
     return g2;
   }
@@ -1575,11 +1664,8 @@ struct Trainer {
   float* mask_mul(const float* x, const float* mask, int C, int Tt) {
     const size_t n = (size_t)B * C * Tt;
     float* y = take<float>(n);
-    if (live()) {
-      hipError_t e = hipMemcpyAsync(y, x, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "mask copy");
-      chk(launch_mask_mul(y, mask, B, C, Tt, st));
-    }
+    copy_f32(y, x, n, "mask copy");
+    if (live()) chk(launch_mask_mul(y, mask, B, C, Tt, st));
     tape.push_back([=]() {
       if (!wants(x)) return;
       float* gY = G(y, n);
@@ -1626,12 +1712,9 @@ struct Trainer {
       conv(base(l.v, xm, L, v));
       float* qr = take<float>(nh);
       float* kr = take<float>(nh);
-      if (live()) {
-        hipError_t e = hipMemcpyAsync(qr, q, nh * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(kr, k, nh * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) rc = hip_fail(e, "rope copy");
-        chk(launch_rope_n(qr, kr, B, H, DH, L, DH / 2, st));
-      }
+      copy_f32(qr, q, nh, "rope copy");
+      copy_f32(kr, k, nh, "rope copy");
+      if (live()) chk(launch_rope_n(qr, kr, B, H, DH, L, DH / 2, st));
       tape.push_back([=]() {
         float* gqr = G(qr, nh);
         float* gkr = G(kr, nh);
@@ -1696,23 +1779,14 @@ struct Trainer {
   }
   void pitch_energy_backward(const float* d_pitch, const float* d_energy, float* d_style) {
     const size_t n = (size_t)B * T;
-    side_begin();
-    d_style_out = d_style;
-    fc_bwd_done = false;
-    float* g0 = G(pe_f0, n);
-    float* g1 = G(pe_n, n);
-    if (live() && d_pitch) {
-      hipError_t e = hipMemcpyAsync(g0, d_pitch, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(g1, d_energy, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "seed copy");
-    }
-    for (auto it = tape.rbegin(); it != tape.rend(); ++it) {
-      (*it)();
-      if (rc != STY_OK) break;
-    }
-    side_join();
-    if (rc != STY_OK) return;
-    style_fc_backward();
+    run_tape(
+        [&]() {
+          G(pe_f0, n);  // (both zero-fills are issued before the first copy)
+          G(pe_n, n);
+          seed(pe_f0, d_pitch, n);
+          seed(pe_n, d_energy, n);
+        },
+        /*flush_up=*/false, /*fc=*/true, d_style);
     if (live() && d_style && pe_sx) {  // the style channels concatenated to every prosody layer's input
       float* gs = G(pe_sx, (size_t)B * m->style_dim * pe_L);
       chk(launch_row_sum_add(gs, B * m->style_dim, pe_L, d_style, st));
@@ -1742,12 +1816,9 @@ struct Trainer {
     float* qr = take<float>(n);
     float* kr = take<float>(n);
     const float* th = m->te.theta;
-    if (live()) {
-      hipError_t e = hipMemcpyAsync(qr, q, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(kr, k, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "rope copy");
-      chk(launch_rope(qr, kr, B, H, C / H, L, 8, th, st));
-    }
+    copy_f32(qr, q, n, "rope copy");
+    copy_f32(kr, k, n, "rope copy");
+    if (live()) chk(launch_rope(qr, kr, B, H, C / H, L, 8, th, st));
     tape.push_back([=]() {
       float* gqr = G(qr, n);
       float* gkr = G(kr, n);
@@ -1821,21 +1892,7 @@ struct Trainer {
   }
   void duration_backward(const float* d_out, float* d_style) {
     const size_t n = (size_t)B * du_L * m->dur.classes;
-    side_begin();
-    d_style_out = d_style;
-    fc_bwd_done = false;
-    float* g = G(du_out, n);
-    if (live() && d_out) {
-      hipError_t e = hipMemcpyAsync(g, d_out, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "seed copy");
-    }
-    for (auto it = tape.rbegin(); it != tape.rend(); ++it) {
-      (*it)();
-      if (rc != STY_OK) break;
-    }
-    side_join();
-    if (rc != STY_OK) return;
-    style_fc_backward();
+    run_tape([&]() { seed(du_out, d_out, n); }, /*flush_up=*/false, /*fc=*/true, d_style);
   }
 
   // text_encoding @ alignment (speech_predictor.py:60)
@@ -2160,21 +2217,12 @@ struct Trainer {
   };
   std::vector<SeTap> se_taps;
   SeTap se_pre2[4] = {};
-  // pitch / energy != nullptr: PitchStyleEncoder (mel_style_encoder.py:155-205, coarse_multiplier 1): the trunk runs on
+  // pse: PitchStyleEncoder (mel_style_encoder.py:155-205, coarse_multiplier 1): the trunk runs on
   // preconv(cat(mel, pitch, energy)) -- a weight-normed Conv1d(k = 1, padding = 1), so T + 2 frames -- and the backward
   // reaches the preconv's parameters (the three inputs are data: no gradient)
-  void style_forward(const float* mel, int Tt, float* style_dst, const float* pitch = nullptr,
-                     const float* energy = nullptr) {
+  void style_forward(const float* mel, int Tt, float* style_dst, bool pse, const float* pitch, const float* energy) {
     const StylePlan& sp = m->sty_enc;
-    tape.clear();
-    gmap.clear();
-    tw_x[0].clear();
-    tw_x[1].clear();
-    tw_want.clear();
-    tw_g.clear();
-    grad_sets_clear();
-    nograd.clear();
-    ungated.clear();
+    reset_step();
     scratch_param_n = 1 << 16;
     scratch_param = take<float>(scratch_param_n);
     if (live() && m->garena) {
@@ -2182,7 +2230,6 @@ struct Trainer {
       if (e != hipSuccess) rc = hip_fail(e, "grad arena memset");
     }
     const float r2 = 0.70710678118654752f;
-    const bool pse = pitch != nullptr;
     float* pre = nullptr;
     if (pse) {
       const int Cc = m->pse_pre.Cin, D = m->pse_pre.Cout, Tp = Tt + 2;
@@ -2362,36 +2409,12 @@ struct Trainer {
   }
   void style_backward(const float* d_style) {
     const size_t n = (size_t)B * m->sty_enc.style_dim;
-    side_begin();
-    float* g = G(style_out, n);
-    if (live() && d_style) {
-      hipError_t e = hipMemcpyAsync(g, d_style, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "seed copy");
-    }
-    for (auto it = tape.rbegin(); it != tape.rend(); ++it) {
-      (*it)();
-      if (rc != STY_OK) break;
-    }
-    while (rc == STY_OK && !pend_up.empty()) up_flush(pend_up.begin()->first);
-    side_join();
+    run_tape([&]() { seed(style_out, d_style, n); }, /*flush_up=*/true, /*fc=*/false, nullptr);
   }
 
   void begin(const float* style_in) {
     style = style_in;
-    side_need = 0;
-    wg_sum = 0;
-    drop_site = 0;
-    tape.clear();
-    gmap.clear();
-    tw_x[0].clear();
-    tw_x[1].clear();
-    tw_want.clear();
-    tw_g.clear();
-    grad_sets_clear();
-    nograd.clear();
-    half_.clear();
-    g16_ok.clear();
-    adain_of.clear();
+    reset_step();
     scratch_param_n = 1 << 20;
     scratch_param = take<float>(scratch_param_n);
     gb = take<float>(m->gb_floats_per_batch * B);
@@ -2424,7 +2447,6 @@ struct Trainer {
 
   void forward(const sty_vocoder_io& io, bool fresh = true) {
     const VocoderPlan& v = m->voc;
-    T = io.T;
     const int Tt = io.T, Tu = 75 * Tt, N = 300 * Tt, C = v.hidden;
     if (fresh) {
       begin(io.style);
@@ -2582,45 +2604,22 @@ struct Trainer {
     }
   }
 
-  void backward(const float* d_audio, float* d_mel, float* d_style) {
-    // seed: gradient of the audio
-    const size_t na = (size_t)B * 300 * T;
-    side_begin();
-    d_style_out = d_style;
-    fc_bwd_done = false;
-    float* gA = G(audio, na);
-    if (live() && d_audio) {
-      hipError_t e = hipMemcpyAsync(gA, d_audio, na * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "seed copy");
-    }
-    if (!d_mel) nograd.insert(mel_in);
-    if (d_mel == reinterpret_cast<float*>(2)) d_mel = nullptr;  // speech graph: mel is an internal activation
-    for (auto it = tape.rbegin(); it != tape.rend(); ++it) {
-      (*it)();
-      if (rc != STY_OK) break;
-    }
-    side_join();
-    if (rc != STY_OK) return;
-    style_fc_backward();
-    if (live() && d_mel) {
-      float* gm = G(mel_in, (size_t)B * m->voc.amp_input_conv.Cin * T);
-      hipError_t e = hipMemcpyAsync(d_mel, gm, (size_t)B * m->voc.amp_input_conv.Cin * T * sizeof(float),
-                                    hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "d_mel copy");
+  // what becomes of d loss / d mel: nobody wants it (the vocoder alone, no d_mel asked for), it flows on into the graph that
+  // produced mel (the speech predictor's decoder), or it is copied out to the caller (d_mel; nullptr in the sizing pass)
+  enum MelGrad { MEL_GRAD_NONE, MEL_GRAD_INTERNAL, MEL_GRAD_COPY };
+  void backward(const float* d_audio, MelGrad mel_grad, float* d_mel, float* d_style) {
+    if (mel_grad == MEL_GRAD_NONE) nograd.insert(mel_in);
+    run_tape([&]() { seed(audio, d_audio, (size_t)B * 300 * T); }, /*flush_up=*/false, /*fc=*/true, d_style);
+    if (live() && mel_grad == MEL_GRAD_COPY && d_mel) {
+      const size_t n = (size_t)B * m->voc.amp_input_conv.Cin * T;
+      copy_f32(d_mel, G(mel_in, n), n, "d_mel copy");
     }
   }
 };
 
 int trainer_speech_forward(Trainer* t, const sty_speech_io* io, void* ws, size_t ws_bytes, hipStream_t st,
                            size_t* need) {
-  t->st = st;
-  t->B = io->B;
-  t->rc = STY_OK;
-  t->ws = Bump();
-  t->dry = need != nullptr;
-  t->ws.base = need ? reinterpret_cast<char*>(size_t(1) << 30) : (char*)ws;
-  t->ws.cap = need ? (size_t(1) << 46) : ws_bytes;
-  t->peak = 0;
+  t->open(io->B, io->T, ws, ws_bytes, st, need != nullptr);
   t->begin(io->style);
   const int inter = t->m->te.proj_m.Cout ? t->m->te.proj_m.Cout : 128;
   float* mu = t->text_encoder(io->texts, io->text_lengths, io->L);
@@ -2642,30 +2641,12 @@ int trainer_speech_forward(Trainer* t, const sty_speech_io* io, void* ws, size_t
   float* asr = t->expand(mu, io->alignment, inter, io->L, io->T);
   float* mel = t->decoder(asr, io->pitch, io->energy, io->voiced, io->T);
   if (mel) {
-    sty_vocoder_io v = io->voc_taps;
-    v.B = io->B;
-    v.T = io->T;
+    sty_vocoder_io v = vocoder_io_of(*io);
     v.mel = mel;
-    v.style = io->style;
-    v.pitch = io->denormal_pitch;
-    v.voiced = io->voiced;
-    v.noise = io->noise;
-    v.prior_override = io->prior_override;
-    v.seed = io->seed;
-    v.audio = io->audio;
     t->forward(v, false);
   }
-  if (need) {
-    t->backward(nullptr, reinterpret_cast<float*>(2), nullptr);
-    *need = align_up(t->peak, 256) + (64 << 20);
-    t->tape.clear();
-    return t->rc;
-  }
-  if (t->ws.overflow) {
-    set_error("training workspace too small: need %zu bytes, have %zu", t->peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  if (need) t->backward(nullptr, Trainer::MEL_GRAD_INTERNAL, nullptr, nullptr);
+  return t->close_forward(need, ws_bytes, Trainer::kSlack, "training");
 }
 
 int trainer_speech_backward(Trainer* t, const float* d_audio, float* d_style, float* d_energy, hipStream_t st,
@@ -2673,106 +2654,49 @@ int trainer_speech_backward(Trainer* t, const float* d_audio, float* d_style, fl
   t->st = st;
   if (!d_energy && t->in_energy) t->nograd.insert(t->in_energy);
   if (!d_pitch && t->in_pitch) t->nograd.insert(t->in_pitch);
-  t->backward(d_audio, reinterpret_cast<float*>(2), d_style);
-  if (t->rc == STY_OK && d_pitch && t->in_pitch && t->live()) {
-    float* g = t->G(t->in_pitch, (size_t)t->B * t->T);
-    hipError_t e = hipMemcpyAsync(d_pitch, g, (size_t)t->B * t->T * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) t->rc = hip_fail(e, "d_pitch copy");
-  }
-  if (t->rc == STY_OK && d_energy && t->in_energy && t->live()) {
-    float* g = t->G(t->in_energy, (size_t)t->B * t->T);
-    hipError_t e = hipMemcpyAsync(d_energy, g, (size_t)t->B * t->T * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) t->rc = hip_fail(e, "d_energy copy");
-  }
-  if (t->ws.overflow) {
-    set_error("training workspace too small in backward: need %zu bytes", t->peak);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  t->backward(d_audio, Trainer::MEL_GRAD_INTERNAL, nullptr, d_style);
+  const size_t n = (size_t)t->B * t->T;
+  if (d_pitch && t->in_pitch && t->live()) t->copy_f32(d_pitch, t->G(t->in_pitch, n), n, "d_pitch copy");
+  if (d_energy && t->in_energy && t->live()) t->copy_f32(d_energy, t->G(t->in_energy, n), n, "d_energy copy");
+  return t->close_backward();
 }
 
 int trainer_pitch_energy_forward(Trainer* t, int B, int L, int T, const int64_t* texts, const int64_t* lengths,
                                  const float* alignment, const float* style, float* pitch, float* energy, void* ws,
                                  size_t ws_bytes, hipStream_t st, size_t* need) {
-  t->st = st;
-  t->B = B;
-  t->T = T;
-  t->rc = STY_OK;
-  t->ws = Bump();
-  t->dry = need != nullptr;
-  t->ws.base = need ? reinterpret_cast<char*>(size_t(1) << 30) : (char*)ws;
-  t->ws.cap = need ? (size_t(1) << 46) : ws_bytes;
-  t->peak = 0;
+  t->open(B, T, ws, ws_bytes, st, need != nullptr);
   t->begin(style);
   t->style_fc(nullptr);
   t->pitch_energy(texts, lengths, alignment, L, T);
-  if (need) {
-    if (t->rc == STY_OK) t->pitch_energy_backward(nullptr, nullptr, reinterpret_cast<float*>(0));
-    *need = align_up(t->peak, 256) + (64 << 20);
-    t->tape.clear();
-    return t->rc;
+  if (need && t->rc == STY_OK) t->pitch_energy_backward(nullptr, nullptr, nullptr);
+  if (!need && t->pe_f0 && t->pe_n) {
+    t->copy_f32(pitch, t->pe_f0, (size_t)B * T, "output copy");
+    t->copy_f32(energy, t->pe_n, (size_t)B * T, "output copy");
   }
-  if (t->rc == STY_OK && t->live() && t->pe_f0 && t->pe_n) {
-    hipError_t e = hipMemcpyAsync(pitch, t->pe_f0, (size_t)B * T * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(energy, t->pe_n, (size_t)B * T * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) t->rc = hip_fail(e, "output copy");
-  }
-  if (t->ws.overflow) {
-    set_error("training workspace too small: need %zu bytes, have %zu", t->peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  return t->close_forward(need, ws_bytes, Trainer::kSlack, "training");
 }
 
 int trainer_pitch_energy_backward(Trainer* t, const float* d_pitch, const float* d_energy, float* d_style, hipStream_t st) {
   t->st = st;
   t->pitch_energy_backward(d_pitch, d_energy, d_style);
-  if (t->ws.overflow) {
-    set_error("training workspace too small in backward: need %zu bytes", t->peak);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  return t->close_backward();
 }
 
 int trainer_duration_forward(Trainer* t, int B, int L, const int64_t* texts, const int64_t* lengths, const float* style,
                              float* out, void* ws, size_t ws_bytes, hipStream_t st, size_t* need) {
-  t->st = st;
-  t->B = B;
-  t->T = L;
-  t->rc = STY_OK;
-  t->ws = Bump();
-  t->dry = need != nullptr;
-  t->ws.base = need ? reinterpret_cast<char*>(size_t(1) << 30) : (char*)ws;
-  t->ws.cap = need ? (size_t(1) << 46) : ws_bytes;
-  t->peak = 0;
+  t->open(B, L, ws, ws_bytes, st, need != nullptr);
   t->begin(style);
   t->style_fc(nullptr);
   t->duration(texts, lengths, L);
-  if (need) {
-    if (t->rc == STY_OK) t->duration_backward(nullptr, nullptr);
-    *need = align_up(t->peak, 256) + (64 << 20);
-    t->tape.clear();
-    return t->rc;
-  }
-  if (t->rc == STY_OK && t->live() && t->du_out) {
-    hipError_t e = hipMemcpyAsync(out, t->du_out, (size_t)B * L * t->m->dur.classes * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) t->rc = hip_fail(e, "output copy");
-  }
-  if (t->ws.overflow) {
-    set_error("training workspace too small: need %zu bytes, have %zu", t->peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  if (need && t->rc == STY_OK) t->duration_backward(nullptr, nullptr);
+  if (!need && t->du_out) t->copy_f32(out, t->du_out, (size_t)B * L * t->m->dur.classes, "output copy");
+  return t->close_forward(need, ws_bytes, Trainer::kSlack, "training");
 }
 
 int trainer_duration_backward(Trainer* t, const float* d_out, float* d_style, hipStream_t st) {
   t->st = st;
   t->duration_backward(d_out, d_style);
-  if (t->ws.overflow) {
-    set_error("training workspace too small in backward: need %zu bytes", t->peak);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  return t->close_backward();
 }
 
 int trainer_wait_d_style(Trainer* t, hipStream_t stream) {
@@ -2787,32 +2711,11 @@ int trainer_wait_d_style(Trainer* t, hipStream_t stream) {
 
 int trainer_style_forward(Trainer* t, int B, int T, const float* mel, float* style, void* ws, size_t ws_bytes,
                           hipStream_t st, size_t* need, const float* pitch, const float* energy) {
-  t->st = st;
-  t->B = B;
-  t->T = T;
-  t->rc = STY_OK;
-  t->ws = Bump();
-  t->dry = need != nullptr;
-  t->ws.base = need ? reinterpret_cast<char*>(size_t(1) << 30) : (char*)ws;
-  t->ws.cap = need ? (size_t(1) << 46) : ws_bytes;
-  t->peak = 0;
-  t->side_need = 0;
-  t->wg_sum = 0;
+  t->open(B, T, ws, ws_bytes, st, need != nullptr);
   const bool pse = t->m->kind == "pitch_style_encoder";
-  t->style_forward(need ? reinterpret_cast<const float*>(8) : mel, T, need ? reinterpret_cast<float*>(16) : style,
-                   pse ? (need ? reinterpret_cast<const float*>(24) : pitch) : nullptr,
-                   pse ? (need ? reinterpret_cast<const float*>(32) : energy) : nullptr);
-  if (need) {
-    if (t->rc == STY_OK) t->style_backward(nullptr);
-    *need = align_up(t->peak, 256) + (16 << 20);
-    t->tape.clear();
-    return t->rc;
-  }
-  if (t->ws.overflow) {
-    set_error("training workspace too small: need %zu bytes, have %zu", t->peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  t->style_forward(need ? &Trainer::kDryMel : mel, T, need ? &Trainer::kDryStyle : style, pse, pitch, energy);
+  if (need && t->rc == STY_OK) t->style_backward(nullptr);
+  return t->close_forward(need, ws_bytes, Trainer::kSlackStyle, "training");
 }
 
 int trainer_style_tap(Trainer* t, int i, int grad, float* dst, int* C, int* H, int* W, hipStream_t st) {
@@ -2846,11 +2749,7 @@ int trainer_style_tap(Trainer* t, int i, int grad, float* dst, int* C, int* H, i
 int trainer_style_backward(Trainer* t, const float* d_style, hipStream_t st) {
   t->st = st;
   t->style_backward(d_style);
-  if (t->ws.overflow) {
-    set_error("training workspace too small in backward: need %zu bytes", t->peak);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  return t->close_backward();
 }
 
 // One sub-module in the training graph, forward and backward (unit parity of the fused backward kernels):
@@ -2858,73 +2757,39 @@ int trainer_style_backward(Trainer* t, const float* d_style, hipStream_t st) {
 int trainer_block_fwd_bwd(Trainer* t, int kind, const void* blk, int B, int C, int T, const float* x, const float* style,
                           const float* gy, float* y, float* gx, float* d_style, void* ws, size_t ws_bytes, hipStream_t st,
                           size_t* need) {
-  t->st = st;
-  t->B = B;
-  t->T = T;
-  t->rc = STY_OK;
-  t->ws = Bump();
-  t->dry = need != nullptr;
-  t->ws.base = need ? reinterpret_cast<char*>(size_t(1) << 30) : (char*)ws;
-  t->ws.cap = need ? (size_t(1) << 46) : ws_bytes;
-  t->peak = 0;
+  t->open(B, T, ws, ws_bytes, st, need != nullptr);
   t->begin(style);
   t->style_fc(nullptr);
   const size_t n = (size_t)B * C * T;
   float* xin = t->take<float>(n);  // the graph's own copy of the input (a resblock aliases its residual stream)
-  if (t->live()) {
-    hipError_t e = hipMemcpyAsync(xin, x, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) t->rc = hip_fail(e, "block input copy");
-  }
+  t->copy_f32(xin, x, n, "block input copy");
   float* out = kind == 0 ? t->convnext(*static_cast<const ConvNeXt*>(blk), xin, T)
                          : t->resblock(*static_cast<const ResBlock32*>(blk), xin, T);
-  if (t->live() && out && y) {
-    hipError_t e = hipMemcpyAsync(y, out, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) t->rc = hip_fail(e, "block output copy");
-  }
+  if (out && y) t->copy_f32(y, out, n, "block output copy");
   // backward from gy
-  t->side_begin();
-  t->d_style_out = d_style;
-  t->fc_bwd_done = false;
   // STY_BLOCK_G16=1 (test aid): the block sits inside a two-byte gradient chain -- its output gradient arrives as bf16 (gy
   // rounded here) and its input's producer takes a bf16 gradient back (converted to fp32 for the caller below)
   const bool g16 = kind == 0 && getenv("STY_BLOCK_G16") != nullptr && t->grad16_on() && t->g16_ok.count(out) != 0;
-  if (g16) {
-    float* gO16 = t->take_act(n, true);
-    t->gmap[out] = gO16;
-    t->g16_ok.insert(xin);
-    if (t->live() && gy) t->chk(launch_cast_f32_to_16(gy, n, gO16, st));
-  } else {
-    float* gO = t->G(out, n);
-    if (t->live() && gy) {
-      hipError_t e = hipMemcpyAsync(gO, gy, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) t->rc = hip_fail(e, "block seed copy");
-    }
-  }
-  for (auto it = t->tape.rbegin(); it != t->tape.rend(); ++it) {
-    (*it)();
-    if (t->rc != STY_OK) break;
-  }
-  t->side_join();
-  if (t->rc == STY_OK) t->style_fc_backward();
+  t->run_tape(
+      [&]() {
+        if (!g16) {
+          t->seed(out, gy, n);
+          return;
+        }
+        float* gO16 = t->take_act(n, true);
+        t->gmap[out] = gO16;
+        t->g16_ok.insert(xin);
+        if (t->live() && gy) t->chk(launch_cast_f32_to_16(gy, n, gO16, st));
+      },
+      /*flush_up=*/false, /*fc=*/true, d_style);
   if (t->live() && gx) {
     float* g = g16 ? t->G16(xin, n) : t->G(xin, n);
-    if (t->is16(g)) {
+    if (t->is16(g))
       t->chk(launch_cast_16_to_f32(g, n, gx, st));
-    } else {
-      hipError_t e = hipMemcpyAsync(gx, g, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) t->rc = hip_fail(e, "block input-gradient copy");
-    }
+    else
+      t->copy_f32(gx, g, n, "block input-gradient copy");
   }
-  if (need) {
-    *need = align_up(t->peak, 256) + (64 << 20);
-    t->tape.clear();
-    return t->rc;
-  }
-  if (t->ws.overflow) {
-    set_error("block workspace too small: need %zu bytes, have %zu", t->peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  return t->close_forward(need, ws_bytes, Trainer::kSlack, "block");
 }
 
 void trainer_set_segment_hook(Trainer* t, std::function<void(int)> fn) {
@@ -2940,37 +2805,17 @@ void trainer_destroy(Trainer* t) { delete t; }
 
 int trainer_vocoder_forward(Trainer* t, const sty_vocoder_io* io, void* ws, size_t ws_bytes, hipStream_t st,
                             size_t* need) {
-  t->st = st;
-  t->B = io->B;
-  t->rc = STY_OK;
-  t->ws = Bump();
-  t->dry = need != nullptr;
-  t->ws.base = need ? reinterpret_cast<char*>(size_t(1) << 30) : (char*)ws;  // dry: fake base, never dereferenced
-  t->ws.cap = need ? (size_t(1) << 46) : ws_bytes;
-  t->peak = 0;
+  t->open(io->B, io->T, ws, ws_bytes, st, need != nullptr);
   t->forward(*io);
-  if (need) {
-    // dry run: also run the backward allocations to size the workspace
-    t->backward(nullptr, reinterpret_cast<float*>(1), nullptr);
-    *need = align_up(t->peak, 256) + (64 << 20);
-    t->tape.clear();
-    return t->rc;
-  }
-  if (t->ws.overflow) {
-    set_error("training workspace too small: need %zu bytes, have %zu", t->peak, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  // the sizing pass also sizes the path of d loss / d mel to the caller
+  if (need) t->backward(nullptr, Trainer::MEL_GRAD_COPY, nullptr, nullptr);
+  return t->close_forward(need, ws_bytes, Trainer::kSlack, "training");
 }
 
 int trainer_vocoder_backward(Trainer* t, const float* d_audio, float* d_mel, float* d_style, hipStream_t st) {
   t->st = st;
-  t->backward(d_audio, d_mel, d_style);
-  if (t->ws.overflow) {
-    set_error("training workspace too small in backward: need %zu bytes", t->peak);
-    return STY_ENOMEM;
-  }
-  return t->rc;
+  t->backward(d_audio, d_mel ? Trainer::MEL_GRAD_COPY : Trainer::MEL_GRAD_NONE, d_mel, d_style);
+  return t->close_backward();
 }
 
 }  // namespace sty
