@@ -769,10 +769,6 @@ struct Run {
   // AdaptiveGeneratorBlock in place on x [B][32][T].  When the convs run on the persistent 32-channel kernel, each one
   // leaves the (sum, sum of squares) partials of its OUTPUT behind (ConvArgs::stat_part), so only the first AdaIN of
   // the block needs a statistics pass of its own.
-  bool takes32p(ConvArgs a) const {
-    a.bf16 = m->topts.compute_bf16;
-    return conv32p_eligible(a);
-  }
   void resblock(const ResBlock32& r, float* x, int T) {
     Scope sc_(*this);
     float* xt = ws.take<float>((size_t)B * 32 * T);
@@ -796,7 +792,7 @@ struct Run {
       c1.pa = a;
       c1.ps = s;
       c1.palpha = r.a1[i];
-      const bool f1 = takes32p(c1);
+      const bool f1 = plan_route(m, c1).stats();
       if (f1) c1.stat_part = part_t;
       conv(c1);
       if (f1)
@@ -809,7 +805,7 @@ struct Run {
       c2.ps = s;
       c2.palpha = r.a2[i];
       c2.residual = x;
-      have_x = takes32p(c2) && i + 1 < 3;
+      have_x = plan_route(m, c2).stats() && i + 1 < 3;
       if (have_x) c2.stat_part = part_x;
       conv(c2);
     }
@@ -962,7 +958,7 @@ struct Run {
     // persistent 32-channel kernel does not take the conv; where it does (round 5), a LayerNorm pass + the persistent kernel are
     // faster than the fused tiled launch (c5-bf16: 121 us against ~35 + 40; the real / imag pair shares one pass)
     ConvArgs head_probe = base(v.amp_output_conv, trunk, Tu, logamp);
-    const bool head32p = takes32p(head_probe);
+    const bool head32p = plan_route(m, head_probe).kernel == CONV_32P;
     float* lnbuf = head32p ? ws.take<float>((size_t)B * 32 * Tu) : nullptr;
     if (live()) {
       ConvArgs a = base(v.amp_output_conv, trunk, Tu, logamp);

@@ -407,67 +407,8 @@ static int launch_cfg(const ConvArgs& a, hipStream_t st) {
   return STY_OK;
 }
 
-static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st);
-int launch_conv1d(const ConvArgs& a, hipStream_t st) {
-  if (a.up_g && !conv1d_has_up_stage(a)) {
-    set_error("conv1d: up-sample + gate output stage asked of a conv that does not run on convq_kernel");
-    return STY_EINVAL;
-  }
-  // ConvArgs::y16 (the bf16 operand twin of the output): convp16_kernel writes it from its output stage; for every other
-  // kernel the cast pass makes it behind the conv -- the caller gets the twin either way
-  const bool native16 = a.y16 && (stem2d_eligible(a) || (!conv32p_eligible(a) && !convk1_eligible(a) && convp16_eligible(a)));
-  int rc = launch_conv1d_dispatch(a, st);
-  if (rc == STY_OK && a.y16 && !native16) {
-    if (a.shuffle > 1) {
-      set_error("conv1d: no output twin for a pixel-shuffled store");
-      return STY_EINVAL;
-    }
-    rc = launch_twin_cast(a.y, nullptr, a.y16_act, a.B, a.w.Cout, a.T, a.y16, st);
-  }
-  return rc;
-}
-// (follows launch_conv1d_dispatch: the kernels in front of convp16 / convq in the chain read the fp32 tensor)
-bool conv1d_reads_twin_only(const ConvArgs& a) {
-  if (!a.x16 || a.nsrc != 1 || a.act == ACT_LRELU01) return false;
-  if (stem2d_eligible(a) || conv32p_eligible(a) || a.xh || a.yh || a.rh || a.stat_part || convk1_eligible(a)) return false;
-  return convp16_eligible(a);
-}
-// the stage lives in convq_kernel, for 2-D convs without an output mask, a residual or an activation of their own
-bool conv1d_has_up_stage(const ConvArgs& a) {
-  if (!conv1d_reads_twin_only(a) || !convq_eligible(a)) return false;
-  if (!a.flatW || a.act != ACT_NONE || a.out_mask || a.residual) return false;
-  if (a.up_g && (!a.up_gate16 || !a.up_mask || a.up_H <= 0 || a.up_H * a.flatW != a.T)) return false;
-  return (long)a.w.Cout * a.T < (1l << 26);  // (31-bit byte offsets into the pooled gradient with room for the marker)
-}
-static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st) {
-  int cin = 0;
-  for (int i = 0; i < a.nsrc; ++i) cin += a.xc[i];
-  if (a.flatW) cin = a.w.Cin;  // 2-D mode: Cin of the packed weight = kh * Cin2d, checked by the caller
-  if (cin != a.w.Cin) {
-    set_error("conv1d: input channels %d != weight Cin %d", cin, a.w.Cin);
-    return STY_ESHAPE;
-  }
-  if (a.pro == PRO_LN_AFFINE && a.w.CinP != CI_CHUNK) {
-    set_error("conv1d: LN prologue needs Cin <= %d", CI_CHUNK);
-    return STY_EINVAL;
-  }
-  if (a.ln_out && a.w.Cout != 32) {
-    set_error("conv1d: LN epilogue needs Cout == 32");
-    return STY_EINVAL;
-  }
-  if (stem2d_eligible(a)) return launch_stem2d(a, st);
-  if (conv32p_eligible(a)) return launch_conv32p(a, st);
-  if (a.xh || a.yh || a.rh) {
-    set_error("conv1d: bf16-stored operand (xh %d yh %d rh %d) on a conv the persistent 32-channel kernel does not take", a.xh,
-              a.yh, a.rh);
-    return STY_EINVAL;
-  }
-  if (a.stat_part) {
-    set_error("conv1d: output statistics requested for a conv the persistent 32-channel kernel does not take");
-    return STY_EINVAL;
-  }
-  if (convk1_eligible(a)) return launch_convk1(a, st);
-  if (convp16_eligible(a)) return launch_convp16(a, st);
+// the tiled kernel: every conv no other family takes
+static int launch_tiled(const ConvArgs& a, hipStream_t st) {
   // Tile choice: the biggest output tile that still gives the chip >= ~2 workgroups per CU; the 256-channel stage
   // runs at T <= 800 frames, where 128x128 tiles would launch ~100 workgroups on 256 CUs.
   const long tiles128 = (long)cdiv(a.T, 128) * (a.w.CoutP / 128) * a.B;
@@ -505,6 +446,94 @@ static int launch_conv1d_dispatch(const ConvArgs& a, hipStream_t st) {
   // (8 waves measured 73 vs 69 TF on config c5)
   if ((long)cdiv(a.T, 512) * (a.w.CoutP / 32) * a.B >= t32_min) return launch_cfg<1, 8, 1, 2>(a, st);
   return launch_cfg<1, 4, 1, 2>(a, st);
+}
+
+// The families' shape predicates and launchers, each beside its kernel (LDS size, halo and offset limits belong there; every
+// family reads its switches and thresholds in its predicate).  conv1d_route is their only caller and the only statement of the order.
+bool stem2d_eligible(const ConvArgs& a);   // conv2d.hip
+bool conv32p_eligible(const ConvArgs& a);  // conv32p.hip
+bool convk1_eligible(const ConvArgs& a);   // convk1.hip
+bool convp16_eligible(const ConvArgs& a);  // convp16.hip
+bool convq_eligible(const ConvArgs& a);    // convq.hip
+int launch_stem2d(const ConvArgs& a, hipStream_t st);
+int launch_conv32p(const ConvArgs& a, hipStream_t st);
+int launch_convk1(const ConvArgs& a, hipStream_t st);
+int launch_convq(const ConvArgs& a, hipStream_t st);
+int launch_convp16(const ConvArgs& a, hipStream_t st);
+
+ConvRoute conv1d_route(const ConvArgs& a) {
+  ConvRoute r;
+  if (stem2d_eligible(a))
+    r.kernel = CONV_STEM2D;
+  else if (conv32p_eligible(a))
+    r.kernel = CONV_32P;
+  else if (a.xh || a.yh || a.rh)  // (the persistent 32-channel kernel alone has the two-byte stages and the statistics)
+    r.refusal = CONV_NO_TWO_BYTE;
+  else if (a.stat_part)
+    r.refusal = CONV_NO_STATS;
+  else if (convk1_eligible(a))
+    r.kernel = CONV_K1;
+  else if (convp16_eligible(a))
+    r.kernel = a.x16 && convq_eligible(a) ? CONV_Q : CONV_P16;
+  // (the kernels in front of convq / convp16 in the order read the fp32 tensor)
+  r.x16_only = (r.kernel == CONV_Q || r.kernel == CONV_P16) && a.x16 && a.act != ACT_LRELU01;
+  // the stage lives in convq_kernel, for 2-D convs without an output mask, a residual or an activation of their own
+  r.up_stage = r.kernel == CONV_Q && a.flatW && a.act == ACT_NONE && !a.out_mask && !a.residual &&
+               !(a.up_g && (!a.up_gate16 || !a.up_mask || a.up_H <= 0 || a.up_H * a.flatW != a.T)) &&
+               (long)a.w.Cout * a.T < (1l << 26);  // (31-bit byte offsets into the pooled gradient with room for the marker)
+  if (a.up_g && !r.up_stage) r.refusal = CONV_NO_UP_STAGE;
+  return r;
+}
+
+int launch_conv1d(const ConvArgs& a, hipStream_t st) {
+  const ConvRoute r = conv1d_route(a);
+  if (r.refusal == CONV_NO_UP_STAGE) {
+    set_error("conv1d: up-sample + gate output stage asked of a conv that does not run on convq_kernel");
+    return STY_EINVAL;
+  }
+  int cin = 0;
+  for (int i = 0; i < a.nsrc; ++i) cin += a.xc[i];
+  if (a.flatW) cin = a.w.Cin;  // 2-D mode: Cin of the packed weight = kh * Cin2d, checked by the caller
+  if (cin != a.w.Cin) {
+    set_error("conv1d: input channels %d != weight Cin %d", cin, a.w.Cin);
+    return STY_ESHAPE;
+  }
+  if (a.pro == PRO_LN_AFFINE && a.w.CinP != CI_CHUNK) {
+    set_error("conv1d: LN prologue needs Cin <= %d", CI_CHUNK);
+    return STY_EINVAL;
+  }
+  if (a.ln_out && a.w.Cout != 32) {
+    set_error("conv1d: LN epilogue needs Cout == 32");
+    return STY_EINVAL;
+  }
+  if (r.refusal == CONV_NO_TWO_BYTE) {
+    set_error("conv1d: bf16-stored operand (xh %d yh %d rh %d) on a conv the persistent 32-channel kernel does not take", a.xh,
+              a.yh, a.rh);
+    return STY_EINVAL;
+  }
+  if (r.refusal == CONV_NO_STATS) {
+    set_error("conv1d: output statistics requested for a conv the persistent 32-channel kernel does not take");
+    return STY_EINVAL;
+  }
+  int rc = STY_OK;
+  switch (r.kernel) {
+    case CONV_STEM2D: rc = launch_stem2d(a, st); break;
+    case CONV_32P: rc = launch_conv32p(a, st); break;
+    case CONV_K1: rc = launch_convk1(a, st); break;
+    case CONV_Q: rc = launch_convq(a, st); break;
+    case CONV_P16: rc = launch_convp16(a, st); break;
+    case CONV_TILED: rc = launch_tiled(a, st); break;
+  }
+  // ConvArgs::y16 (the bf16 operand twin of the output): the caller gets the twin from every kernel, from the cast pass behind
+  // the conv where the kernel does not write it in its output stage
+  if (rc == STY_OK && a.y16 && !r.writes_y16()) {
+    if (a.shuffle > 1) {
+      set_error("conv1d: no output twin for a pixel-shuffled store");
+      return STY_EINVAL;
+    }
+    rc = launch_twin_cast(a.y, nullptr, a.y16_act, a.B, a.w.Cout, a.T, a.y16, st);
+  }
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------

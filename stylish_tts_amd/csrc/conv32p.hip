@@ -560,16 +560,6 @@ __global__ __launch_bounds__(64 * (4 + p_npw<BF>()), 1) void conv32p_kernel(Conv
 
 int conv32p_stat_nseg(int T) { return cdiv(T, P_TT); }
 
-static int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 static size_t p_lds_bytes(const ConvArgs& a) {
   const int LW = P_TT + (a.w.K - 1) * a.dil + (a.bf16 && a.xh ? (a.pad & 1) : 0);
   const size_t in = a.bf16 ? (size_t)2 * LW * P_PITCH * 2 : (size_t)2 * CI_CHUNK * LW * 4;
@@ -600,7 +590,7 @@ static int launch_p(const ConvArgs& a, hipStream_t st) {
   return STY_OK;
 }
 
-// Whether the persistent kernel takes this conv (launch_conv1d asks before its own tile choice).
+// Whether the persistent kernel takes this conv (conv1d_route asks; second in its order).
 bool conv32p_eligible(const ConvArgs& a) {
   if (getenv("STY_NO_CONV32P")) return false;  // (read per call: the A/B parity test toggles it)
   // one reduction chunk, <= 32 couts, one plain source, linear output (an activation switch with the erf / exp bodies

@@ -750,15 +750,6 @@ int convp16_repack_range(const void* lo, const void* hi, hipStream_t st) {
   return STY_OK;
 }
 
-static int q_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
 // The style encoder's launches (flat 2-D convs, on a stream of their own beside the text encoder's chain of ~20 us kernels)
 // leave some CUs alone: a persistent launch holds one workgroup on every CU it was given until it ends, and a kernel of
 // another stream that becomes ready in the meantime waits for the whole launch.  Measured on c3 with time stamps on the
@@ -808,7 +799,7 @@ static int launch_q(const ConvArgs& a, hipStream_t st) {
   }
   const int tiles_per_row = cdiv(a.T, Q_TT), ncot = cdiv(a.w.CoutP, 64 * MTW);
   const int ntiles = tiles_per_row * a.B * ncot;
-  int cus = q_num_cus();
+  int cus = num_cus();
   if (a.flatW && Q_STYLE_FREE_CUS < cus / 2) cus -= Q_STYLE_FREE_CUS;
   const int grid = ntiles < cus ? ntiles : cus;
   const double outs = (double)a.B * a.w.Cout * a.T;
@@ -846,7 +837,6 @@ static int launch_q_pro(const ConvArgs& a, hipStream_t st) {
 int convp16_frags(const ConvArgs& a, hipStream_t st, const void** out) { return q_frags(a, st, out); }  // (convk1.hip)
 
 int launch_convp16(const ConvArgs& a0, hipStream_t st) {
-  if (a0.x16 && convq_eligible(a0)) return launch_convq(a0, st);  // round 6: convq.hip
   ConvArgs a = a0;
   int rc = q_frags(a0, st, &a.w.wf);
   if (rc) return rc;

@@ -438,8 +438,8 @@ bool convq_eligible(const ConvArgs& a) {
   if ((long)(a.flatW ? a.Cin2d : a.w.Cin) * a.T >= (1l << 29) || (long)a.w.Cout * a.T >= (1l << 28)) return false;
   // 256-column tiles per row: a row of 520 columns would run three tiles for the work of two (the 1-D convs of the decoder stay
   // on convp16_kernel's 128-column tiles); STY_CONVQ_MIN_TILES set: the parity tests run every shape
-  if (!getenv("STY_CONVQ_MIN_TILES") && (double)a.T < 0.85 * CQ_TT * cdiv(a.T, CQ_TT)) return false;
   const char* mt = getenv("STY_CONVQ_MIN_TILES");
+  if (!mt && (double)a.T < 0.85 * CQ_TT * cdiv(a.T, CQ_TT)) return false;
   const int min_tiles = mt ? atoi(mt) : 48;
   return (long)cdiv(a.T, CQ_TT) * a.B * cdiv(a.w.CoutP, 96) >= min_tiles;
 }
@@ -478,7 +478,7 @@ int launch_convq(const ConvArgs& a0, hipStream_t st) {
   a.pro = PRO_NONE;  // the prologue (LeakyReLU / the [B][T] mask) is in the twin
   a.mask = nullptr;
   const bool relu = a.act == ACT_RELU;
-  if (a.up_g) return a.w.K == 1 ? launch_cq<1, 0, 1>(a, st) : launch_cq<3, 0, 1>(a, st);  // (conv1d_has_up_stage: no activation)
+  if (a.up_g) return a.w.K == 1 ? launch_cq<1, 0, 1>(a, st) : launch_cq<3, 0, 1>(a, st);  // (ConvRoute::up_stage: no activation)
   if (a.w.K == 1) return relu ? launch_cq<1, 1>(a, st) : launch_cq<1, 0>(a, st);
   return relu ? launch_cq<3, 1>(a, st) : launch_cq<3, 0>(a, st);
 }

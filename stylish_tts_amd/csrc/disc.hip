@@ -471,7 +471,7 @@ struct SdRun : DiscBase {
           ConvArgs a = conv_args(i, i < 4 ? ac.as[i - 1] : ac.a[3], ac.a[i]);
           a.act = ACT_LRELU01;  // bf16 mode: LeakyReLU and the column split happen in convp16's output stage
           a.y_split = i < 3 ? ac.as[i] : nullptr;
-          if (convp16_eligible(a)) {
+          if (conv1d_route(a).kernel == CONV_P16) {  // (the one kernel with that output stage)
             chk(launch_conv1d(a, st));
           } else {
             a.act = ACT_NONE;

@@ -267,6 +267,13 @@ struct sty_model {
 #include <functional>
 #include <unordered_set>
 namespace sty {
+// The route launch_conv1d takes for `a` in the model's compute mode.  The plans (Run, Trainer) ask ahead of the launch: who
+// leaves AdaIN statistics behind, whether a resblock stores two-byte tensors (ask with xh / yh / rh set), whether the head
+// LayerNorm is a pass in front of the persistent kernel or a prologue of the tiled one.
+inline ConvRoute plan_route(const sty_model* m, ConvArgs a) {
+  a.bf16 = m->topts.compute_bf16;
+  return conv1d_route(a);
+}
 int launch_pro_bwd(int mode, const float* u, int Cu, int cu0, const float* x, int B, int C, int T, const float* pa,
                    const float* ps, int pC, int pc0, const float* alpha, const float* mask, float* dx, int accumulate,
                    float* dpa, float* dps, float* dalpha, hipStream_t st);
@@ -321,13 +328,6 @@ void wgrad_defer_destroy(WgReduceDefer* d);
 WgReduceDefer* wgrad_defer_set(WgReduceDefer* d);  // returns the previous one (nullptr = immediate reductions)
 size_t wgrad_defer_pending(const WgReduceDefer* d);
 int wgrad_defer_flush(WgReduceDefer* d, int site, hipStream_t st);
-// whether launch_conv1d_wgrad produces the bias gradient as a by-product (every kernel for K <= 12 does)
-inline bool wgrad_fuses_bias(const PackedConv& w) { return w.K <= 12; }
-int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask, float scale, float* gwp,
-                        float* partial, float* gbias, bool* bias_done, hipStream_t st);
-// whether that launch reads both operands as their bf16 twins alone (fwd.x16 / fwd.g16 set; wgradb16_kernel, bias gradient
-// fused): the fp32 output gradient `g` then has no reader in it and need not exist
-bool conv1d_wgrad_reads_twins_only(const ConvArgs& fwd, bool gmask);
 int launch_pack_dgrad(const float* wp, int K, int CinP, int CoutP, float* wd, hipStream_t st);
 int launch_b2eff_bwd(const float* g, const float* w2, const float* beta, int C, float* db2, float* dbeta, float* dW2,
                      hipStream_t st);

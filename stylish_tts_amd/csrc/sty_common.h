@@ -208,7 +208,7 @@ struct ConvArgs {
   // convp16_kernel with ACT_LRELU01 only: second copy of the output split into even / odd time samples,
   // [B][2 Cout][T/2] with the even samples in channels [0, Cout) (the input layout of a stride-2 conv, disc.hip); T % 4 == 0
   float* y_split = nullptr;
-  // conv32p_kernel only (conv32p_eligible(a) must hold): per-(b, cout, 256-column tile) partial (sum, sum of squares)
+  // conv32p_kernel only (conv1d_route(a).stats() must hold): per-(b, cout, 256-column tile) partial (sum, sum of squares)
   // of the OUTPUT, laid out as launch_row_stats lays out its segments: [B * Cout][conv32p_stat_nseg(T)][2] doubles.
   // The AdaIN fold of the next layer then needs no pass of its own over the tensor.
   double* stat_part = nullptr;
@@ -230,7 +230,7 @@ struct ConvArgs {
   // the rounding keep the sign of x) and the [B][T] mask of that input,
   //   y = (up_gate16 > 0 ? y : 0.2 y) + up_g[c][h / 2][w / 2] * 0.25 * up_scale * (2 on the replicated last column of an odd W)
   //   y16 = bf16(y * up_mask)   (where y16 is set)
-  // -- the operations of avgpool2_bwd_kernel behind a deferred LeakyReLU gate, in its order.  conv1d_has_up_stage(a) says
+  // -- the operations of avgpool2_bwd_kernel behind a deferred LeakyReLU gate, in its order.  conv1d_route(a).up_stage says
   // whether the kernel launch_conv1d picks has the stage; every other kernel refuses the operands.
   const float* up_g = nullptr;
   const __bf16* up_gate16 = nullptr;
@@ -254,23 +254,75 @@ struct ConvArgs {
 // misc.hip: y16 = bf16(pro(x) * mask[b][t]) for [B*C][T] rows; pro = PRO_NONE or PRO_LRELU; mask optional
 int launch_twin_cast(const float* x, const float* mask, int pro, int B, int C, int T, __bf16* y16, hipStream_t st);
 // wgradb.hip: the K = 1 / 3 / 5 weight gradient on two bf16 twins (fwd.x16, fwd.g16)
-bool wgradb16_eligible(const ConvArgs& fwd);
 int launch_wgradb16(const ConvArgs& fwd, int nsplit, float* partial, int want_bias, hipStream_t st);
 
+// ---- which kernel runs a conv ----
+// conv1d_route (conv1d.hip) is the one ordered list of the kernel families.  launch_conv1d launches from it; a caller that
+// needs a property of the kernel ahead of the launch asks it with the same ConvArgs.  (Each family's shape predicate lives
+// beside its kernel and is declared in conv1d.hip alone.)
+enum ConvKernel : int {
+  CONV_STEM2D,  // conv2d.hip: Conv2d(1 -> C, 3 x 3) of the style encoder's stem, VALU, store-bound
+  CONV_32P,     // conv32p.hip: persistent, wave-specialised kernel for the 32 -> 32 channel convs at the 75T rate
+  CONV_K1,      // convk1.hip: K = 1 as a plain GEMM (transposing LDS reads)
+  CONV_Q,       // convq.hip: convp16's job on bf16 operand twins (ConvArgs::x16), K = 1 / 3: 96 x 256 tiles, wide loads
+  CONV_P16,     // convp16.hip: persistent producer / consumer kernel of the bf16 compute mode for Cin >= 64
+  CONV_TILED,   // conv1d.hip: conv1d_mfma_kernel, tile configuration chosen by its launcher
+};
+// what the args ask for and the chosen kernel cannot do (launch_conv1d turns it into the error)
+enum ConvRefusal : int { CONV_OK = 0, CONV_NO_UP_STAGE, CONV_NO_TWO_BYTE, CONV_NO_STATS };
+struct ConvRoute {
+  ConvKernel kernel = CONV_TILED;
+  ConvRefusal refusal = CONV_OK;
+  bool x16_only = false;  // reads source 0 as its bf16 twin a.x16 alone (the fp32 tensor a.x[0] then has no reader in the launch)
+  bool up_stage = false;  // has the up-sample + gate output stage (ConvArgs::up_g; asked with or without the up_* operands set)
+  // writes the a.y16 twin from its own output stage (behind every other kernel launch_conv1d runs the cast pass)
+  bool writes_y16() const { return kernel == CONV_STEM2D || kernel == CONV_Q || kernel == CONV_P16; }
+  bool stats() const { return kernel == CONV_32P; }     // leaves the output statistics (ConvArgs::stat_part)
+  bool two_byte() const { return kernel == CONV_32P; }  // takes two-byte tensors (the xh / yh / rh of these args)
+};
+ConvRoute conv1d_route(const ConvArgs& a);
 int launch_conv1d(const ConvArgs& a, hipStream_t st);
-// whether that launch reads source 0 as its bf16 twin a.x16 alone (the fp32 tensor a.x[0] then has no reader in it)
-bool conv1d_reads_twin_only(const ConvArgs& a);
-bool conv1d_has_up_stage(const ConvArgs& a);  // (asked with or without the up_* operands set)
-// conv32p.hip: persistent, wave-specialised kernel for the 32 -> 32 channel convs at the 75T rate
-bool conv32p_eligible(const ConvArgs& a);
 int conv32p_stat_nseg(int T);
-// convp16.hip: persistent producer / consumer kernel of the bf16 compute mode for Cin >= 64
-// wgradb.hip: bf16-mode weight gradient, K = 1 / 3, 64 x 64 blocks, operands converted once on their way into LDS
-bool wgradb_eligible(const ConvArgs& fwd, bool gmask);
+// compute units of the current device: the grid size of the persistent kernels (conv32p.hip, convp16.hip)
+inline int num_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+  }
+  return n;
+}
+// Which kernel runs a conv's weight gradient, and what callers ask about it ahead of the launch (wgrad.hip: conv1d_wgrad_route
+// is the one ordered list, launch_conv1d_wgrad launches from it)
+enum WgradKernel : int {
+  WGRAD_B,       // wgradb.hip: bf16 mode, K = 1 / 3 / 5, 64 x 64 blocks, operands converted once on their way into LDS
+  WGRAD_B16,     // ... on the two bf16 twins fwd.x16 / fwd.g16
+  WGRAD_K1,      // K = 1: a workgroup owns a block of dW
+  WGRAD_64,      // K = 2 .. 5, 64 x 64 blocks
+  WGRAD_ROWS32,  // flat 2-D, 32 output channels: one many-tap 32 x 32 launch per image row of the window
+  WGRAD_STEM,    // the style encoder's stem (3 x 3 conv of a one-channel image)
+  WGRAD_P32,     // wgradb.hip: the many-tap 32 x 32 form
+  WGRAD_TILED,   // one 32 x 32 tile per workgroup
+};
+struct WgradRoute {
+  WgradKernel kernel = WGRAD_TILED;
+  int nsplit = 1;          // partial planes the kernel writes (<= what wgrad_partial_floats sized the buffer for)
+  size_t plane = 0;        // floats of one plane, without its bias row
+  bool fuses_bias = true;  // produces the bias gradient as a by-product
+  bool twins_only = false; // reads both operands as their bf16 twins alone (fwd.x16 / fwd.g16, bias gradient fused): the fp32
+                           // output gradient `g` then has no reader in the launch and need not exist
+  bool refused = false;    // bf16-stored operands (fwd.xh / fwd.gh) the kernel does not take
+};
+WgradRoute conv1d_wgrad_route(const ConvArgs& fwd, const float* g, const float* gmask);
+// fuses_bias of every route, for callers that hand the launch to another stream and do not see *bias_done (every kernel for
+// K <= 12 produces the bias gradient; launch_conv1d_wgrad refuses a route that disagrees)
+inline bool wgrad_fuses_bias(const PackedConv& w) { return w.K <= 12; }
+int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask, float scale, float* gwp,
+                        float* partial, float* gbias, bool* bias_done, hipStream_t st);
 int launch_wgradb(const ConvArgs& ax, const ConvArgs& ag, int nsplit, float* partial, int want_bias, hipStream_t st);
 int wgradb_chunks(const PackedConv& w, int B, int T, int dil);
 // ... and the 32 x 32 many-tap form (eight phase-shifted copies of G in LDS)
-bool wgradp32_eligible(const ConvArgs& fwd);
 int wgradp32_chunks(const ConvArgs& fwd);
 int launch_wgradp32(const ConvArgs& ax, const ConvArgs& ag, int nsplit, float* partial, int want_bias, hipStream_t st);
 // ... and the two pointwise weight gradients of a fused ConvNeXt32 block from its bf16 outputs
@@ -280,18 +332,8 @@ int launch_conv_wgrad_cnx(int x_wide, const void* wide, const float* narrow, int
 int wgrad_cnx_per_b(int B, int T);
 int launch_wgrad_cnx(int x_wide, const void* wide, const float* narrow, int B, int T, float* partial, int want_bias,
                      hipStream_t st, int per_b = 0, int narrow16 = 0);
-bool stem2d_eligible(const ConvArgs& a);  // conv2d.hip: Conv2d(1 -> C, 3 x 3) of the style encoder's stem, VALU, store-bound
-int launch_stem2d(const ConvArgs& a, hipStream_t st);
-bool convk1_eligible(const ConvArgs& a);  // convk1.hip: K = 1 as a plain GEMM (transposing LDS reads)
-int launch_convk1(const ConvArgs& a, hipStream_t st);
-bool convp16_eligible(const ConvArgs& a);
-// convq.hip: the same job on bf16 operand twins (ConvArgs::x16), K = 1 / 3: 96 x 256 tiles, wide loads, register transposes
-bool convq_eligible(const ConvArgs& a);
-int launch_convq(const ConvArgs& a, hipStream_t st);
 int convp16_repack_range(const void* lo, const void* hi, hipStream_t st);
 void convp16_forget_range(const void* lo, const void* hi);  // before the arena is freed or re-laid out  // bf16 weight fragments of a model's packed weights, one launch
-int launch_convp16(const ConvArgs& a, hipStream_t st);
-int launch_conv32p(const ConvArgs& a, hipStream_t st);
 
 // one entry of a batched weight-side launch (wgrad.hip: pack / input-gradient pack / gradient un-pack)
 struct MultiJob {

@@ -521,6 +521,32 @@ struct Trainer {
     ConvArgs f = a;
     tape.push_back([this, f]() { conv_bwd(f); });
   }
+  // Weight gradient of conv f from its output gradient gY (times gmask), on the side stream where there is one.  The bias gradient
+  // is a by-product of the same pass over gY where the kernel fuses it (every route for K <= 12), a pass of its own otherwise.
+  void conv_wgrad(const ConvArgs& f, float* gY, const float* gmask, int shuffle) {
+    const PackedConv& w = f.w;
+    const int Tt = f.T;
+    bool bias_done = false;
+    float* gbias = w.bias ? PGpacked(w.bias) : nullptr;
+    if (m->topts.frozen) {  // eval_models of a stage (e.g. the speech predictor in train_textual): input gradients only
+      bias_done = true;
+    } else if (side_ready()) {
+      float* sp = deferring() ? wg_take(wgrad_partial_floats(w, B, Tt)) : side_partial;
+      float* gwp = PGpacked(w.wp);
+      const float osc = f.out_scale;
+      side_push(gY, [=](hipStream_t s) { chk(launch_conv1d_wgrad(f, gY, gmask, osc, gwp, sp, gbias, nullptr, s)); });
+      bias_done = wgrad_fuses_bias(w);  // (the launch is not made yet: launch_conv1d_wgrad holds every route to this)
+    } else {
+      const size_t pn = wgrad_partial_floats(w, B, Tt);
+      float* partial = deferring() ? wg_take(pn) : take<float>(pn);
+      DeferScope ds(this);
+      if (live()) chk(launch_conv1d_wgrad(f, gY, gmask, f.out_scale, PGpacked(w.wp), partial, gbias, &bias_done, st));
+    }
+    if (w.bias && !bias_done) {
+      float* bs = take<float>(bias_grad_scratch_floats(B, w.Cout, Tt));
+      if (live()) chk(launch_bias_grad(gY, gmask, B, w.Cout, Tt, shuffle, f.out_scale, PGpacked(w.bias), bs, st));
+    }
+  }
   void conv_bwd(const ConvArgs& f) {
     const PackedConv& w = f.w;
     const int Tt = f.T;
@@ -600,27 +626,7 @@ struct Trainer {
       else
         chk(launch_row_scale_add(gY, nullptr, 1.0f, B * w.Cout, Tt, gR, st));
     }
-    // weight gradient; the bias gradient is a by-product of the same pass over gY for K <= 12
-    bool bias_done = false;
-    float* gbias = w.bias ? PGpacked(w.bias) : nullptr;
-    if (m->topts.frozen) {  // eval_models of a stage (e.g. the speech predictor in train_textual): input gradients only
-      bias_done = true;
-    } else if (side_ready()) {
-      float* sp = deferring() ? wg_take(wgrad_partial_floats(w, B, Tt)) : side_partial;
-      float* gwp = PGpacked(w.wp);
-      const float osc = f.out_scale;
-      side_push(gY, [=](hipStream_t s) { chk(launch_conv1d_wgrad(f, gY, gmask, osc, gwp, sp, gbias, nullptr, s)); });
-      bias_done = wgrad_fuses_bias(w);
-    } else {
-      const size_t pn = wgrad_partial_floats(w, B, Tt);
-      float* partial = deferring() ? wg_take(pn) : take<float>(pn);
-      DeferScope ds(this);
-      if (live()) chk(launch_conv1d_wgrad(f, gY, gmask, f.out_scale, PGpacked(w.wp), partial, gbias, &bias_done, st));
-    }
-    if (w.bias && !bias_done) {
-      float* bs = take<float>(bias_grad_scratch_floats(B, w.Cout, Tt));
-      if (live()) chk(launch_bias_grad(gY, gmask, B, w.Cout, Tt, f.shuffle, f.out_scale, PGpacked(w.bias), bs, st));
-    }
+    conv_wgrad(f, gY, gmask, f.shuffle);
     if (any) {
       auto it = m->dgrad.find(w.wp);
       if (it == m->dgrad.end()) {
@@ -1141,10 +1147,6 @@ struct Trainer {
 
   // AdaptiveGeneratorBlock (ada_norm.py:109-120).  Convs that run on the persistent 32-channel kernel leave the
   // statistics of their output behind for the next AdaIN (see Run::resblock in api.hip).
-  bool takes32p(ConvArgs a) const {
-    a.bf16 = m->topts.compute_bf16;
-    return conv32p_eligible(a);
-  }
   // A conv over THREE concatenated 32-channel sources with a 32-channel output (phase_input_conv, generator.py:760-768: k = 21
   // over [trunk | logamp prior | phase prior]) on the persistent kernel, bf16 mode: three accumulating launches forward -- one per
   // source, each with the source's 32 x 32 block of every tap (ConvArgs::w_row / w_tap), the second and third through the
@@ -1179,7 +1181,7 @@ struct Trainer {
     if (it == m->dgrad.end()) return false;
     ConvArgs f = cat3_slice(a3, a3.w, 0, false), d = cat3_slice(a3, it->second, 0, true);
     d.pad = (a3.w.K - 1) * a3.dil - a3.pad;
-    return takes32p(f) && takes32p(d);
+    return plan_route(m, f).kernel == CONV_32P && plan_route(m, d).kernel == CONV_32P;
   }
   void conv_cat3(const ConvArgs& a0) {
     ConvArgs a3 = a0;
@@ -1205,26 +1207,7 @@ struct Trainer {
       int accX[3] = {1, 1, 1};
       for (int i = 0; i < 3; ++i) gX[i] = wants(a3.x[i]) ? Gw(a3.x[i], ny, accX[i]) : nullptr;
       const size_t mark = ws.off;
-      // weight / bias gradient: as conv_bwd (the multi-source weight-gradient kernel reads the three sources itself)
-      bool bias_done = false;
-      float* gbias = w.bias ? PGpacked(w.bias) : nullptr;
-      if (m->topts.frozen) {
-        bias_done = true;
-      } else if (side_ready()) {
-        float* sp = deferring() ? wg_take(wgrad_partial_floats(w, B, Tt)) : side_partial;
-        float* gwp = PGpacked(w.wp);
-        side_push(gY, [=](hipStream_t s) { chk(launch_conv1d_wgrad(a3, gY, nullptr, a3.out_scale, gwp, sp, gbias, nullptr, s)); });
-        bias_done = wgrad_fuses_bias(w);
-      } else {
-        const size_t pn_ = wgrad_partial_floats(w, B, Tt);
-        float* partial = deferring() ? wg_take(pn_) : take<float>(pn_);
-        DeferScope ds(this);
-        if (live()) chk(launch_conv1d_wgrad(a3, gY, nullptr, a3.out_scale, PGpacked(w.wp), partial, gbias, &bias_done, st));
-      }
-      if (w.bias && !bias_done) {
-        float* bs = take<float>(bias_grad_scratch_floats(B, w.Cout, Tt));
-        if (live()) chk(launch_bias_grad(gY, nullptr, B, w.Cout, Tt, 1, a3.out_scale, PGpacked(w.bias), bs, st));
-      }
+      conv_wgrad(a3, gY, nullptr, 1);  // (the multi-source weight-gradient kernel reads the three sources itself)
       const PackedConv& wd = m->dgrad.find(w.wp)->second;
       for (int i = 0; i < 3; ++i) {
         if (!gX[i] || !live()) continue;
@@ -1252,7 +1235,7 @@ struct Trainer {
       c1.dil = dil[i], c1.pad = 5 * dil[i], c2.pad = 5;
       c1.pro = c2.pro = PRO_AFFINE_SNAKE;
       c1.xh = c1.yh = c2.xh = c2.yh = c2.rh = 1;
-      if (!takes32p(c1) || !takes32p(c2)) return false;
+      if (!plan_route(m, c1).two_byte() || !plan_route(m, c2).two_byte()) return false;
     }
     return true;
   }
@@ -1277,7 +1260,7 @@ struct Trainer {
       c1.ps = s;
       c1.palpha = r.a1[i];
       double* part_t = nullptr;
-      if (takes32p(c1)) c1.stat_part = part_t = take<double>((size_t)B * 32 * nseg_p * 2);
+      if (plan_route(m, c1).stats()) c1.stat_part = part_t = take<double>((size_t)B * 32 * nseg_p * 2);
       conv(c1);
       adain(xt, 32, Tt, r.n2[i], a, s, part_t, nseg_p);
       float* xn = take_act((size_t)B * 32 * Tt, h16 && i + 1 < 3);  // (the block's output feeds kernels without a two-byte form)
@@ -1288,7 +1271,7 @@ struct Trainer {
       c2.palpha = r.a2[i];
       c2.residual = x;
       part_x = nullptr;
-      if (takes32p(c2) && i + 1 < 3) {
+      if (plan_route(m, c2).stats() && i + 1 < 3) {
         double* p = take<double>((size_t)B * 32 * nseg_p * 2);
         c2.stat_part = p;
         part_x = p;
@@ -2060,10 +2043,10 @@ struct Trainer {
     ConvArgs f = f0;
     if (!f.g16) f.g16 = f.x16;
     if (f.residual && wants(f.residual)) return false;
-    if (!m->topts.frozen && !conv1d_wgrad_reads_twins_only(f, f.out_mask != nullptr)) return false;
+    if (!m->topts.frozen && !conv1d_wgrad_route(f, nullptr, f.out_mask).twins_only) return false;
     if (wants(f.x[0])) {
       ConvArgs d;
-      if (!dgrad_args(f, nullptr, d) || !conv1d_reads_twin_only(d)) return false;
+      if (!dgrad_args(f, nullptr, d) || !conv1d_route(d).x16_only) return false;
     }
     return true;
   }
@@ -2133,7 +2116,7 @@ struct Trainer {
       dup.up_mask = up->mask;
       dup.up_scale = up->scale;
       dup.up_H = up->H;
-      if (conv1d_has_up_stage(dup)) {
+      if (conv1d_route(dup).up_stage) {
         if (tw_want.count(f.x[0])) dup.y16 = take<__bf16>(nx);  // (in front of `mark`: kept for x's producer)
         staged = true;
       }
@@ -2150,28 +2133,7 @@ struct Trainer {
       chk(launch_pro_bwd(PRO_MASK, gY, w.Cout, 0, gY, B, w.Cout, n, nullptr, nullptr, w.Cout, 0, nullptr, f.out_mask,
                          gR, accR, nullptr, nullptr, nullptr, st));
     }
-    bool bias_done = false;
-    float* gbias = w.bias ? PGpacked(w.bias) : nullptr;
-    if (m->topts.frozen) {
-      bias_done = true;
-    } else if (side_ready()) {
-      float* sp = deferring() ? wg_take(wgrad_partial_floats(w, B, n)) : side_partial;
-      float* gwp = PGpacked(w.wp);
-      side_push(gY, [=](hipStream_t s) {
-        chk(launch_conv1d_wgrad(f, gY, f.out_mask, f.out_scale, gwp, sp, gbias, nullptr, s));
-      });
-      bias_done = wgrad_fuses_bias(w);
-    } else {
-      const size_t pn = wgrad_partial_floats(w, B, n);
-      float* partial = deferring() ? wg_take(pn) : take<float>(pn);
-      DeferScope ds(this);
-      if (live())
-        chk(launch_conv1d_wgrad(f, gY, f.out_mask, f.out_scale, PGpacked(w.wp), partial, gbias, &bias_done, st));
-    }
-    if (w.bias && !bias_done) {
-      float* bs = take<float>(bias_grad_scratch_floats(B, w.Cout, n));
-      if (live()) chk(launch_bias_grad(gY, f.out_mask, B, w.Cout, n, 0, f.out_scale, PGpacked(w.bias), bs, st));
-    }
+    conv_wgrad(f, gY, f.out_mask, 0);
     if (gX) {
       ConvArgs d;
       if (!dgrad_args(f, gY, d)) {
@@ -2475,7 +2437,7 @@ struct Trainer {
       ConvArgs ca = base(pc, i ? hp : hs, Tu, nullptr);
       ConvArgs probe = ca;
       probe.yh = 1;
-      const bool h16 = resblock16(i ? v.phase_prior_block : v.amp_prior_block, Tu) && takes32p(probe);
+      const bool h16 = resblock16(i ? v.phase_prior_block : v.amp_prior_block, Tu) && plan_route(m, probe).two_byte();
       prior_out[i] = ca.y = take_act((size_t)B * 32 * Tu, h16);
       if (h16) {
         double* p = take<double>((size_t)B * 32 * conv32p_stat_nseg(Tu) * 2);

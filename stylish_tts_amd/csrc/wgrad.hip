@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <optional>
 #include <vector>
 
 #include "conv_stage.h"
@@ -1030,84 +1031,111 @@ static bool stem_wgrad_eligible(const ConvArgs& f, const float* g, const float* 
          ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(gmask)) & 15) == 0;
 }
 
-// (follows the two branches of launch_conv1d_wgrad that end in launch_wgradb16; both produce the bias gradient)
-bool conv1d_wgrad_reads_twins_only(const ConvArgs& fwd, bool gmask) {
+// ---- which kernel runs a conv's weight gradient ----
+// wgradb.hip's shape predicates (conv1d_wgrad_route is their only caller)
+bool wgradb_eligible(const ConvArgs& fwd, bool gmask);
+bool wgradb16_eligible(const ConvArgs& fwd);
+bool wgradp32_eligible(const ConvArgs& fwd);
+
+// the forward args as the kernels stage them (KH == KW == 1: the flat image is a plain [B][C][T] tensor)
+static ConvArgs wgrad_x_args(const ConvArgs& fwd) {
+  ConvArgs ax = fwd;
+  if (fwd.w.K == 1) ax.flatW = 0;
+  return ax;
+}
+// flat 2-D conv with 32 output channels (the spectrogram discriminators' 3x5 / 3x3 layers): one many-tap 32x32 launch
+// per image row of the window -- row kh is the plain 1-D weight gradient against x shifted by (kh - hpad) rows -- summed
+// straight into rows [kh*Cin2d, (kh+1)*Cin2d) of the packed gradient.  The args of one such launch (pad: set per row):
+static bool wgrad_rows32_args(const ConvArgs& fwd, ConvArgs& a1) {
   const PackedConv& w = fwd.w;
-  if (fwd.xh || fwd.gh) return false;
-  if (w.K == 1) {
-    ConvArgs ax1 = fwd;
-    ax1.flatW = 0;
-    return wgradb_eligible(ax1, gmask) && wgradb16_eligible(ax1);
-  }
-  return wgrad64_ok(w, fwd.dil) && wgrad64_operands_ok(fwd) && wgradb_eligible(fwd, gmask) && wgradb16_eligible(fwd);
+  if (!(fwd.flatW && w.CoutP == 32 && fwd.Cin2d % 32 == 0 && fwd.Cin2d <= 96 && w.Cin % fwd.Cin2d == 0 && w.CinP == w.Cin &&
+        fwd.nsrc == 1))
+    return false;
+  a1 = fwd;
+  a1.flatW = 0;
+  a1.hpad = 0;
+  a1.Cin2d = 0;
+  a1.xc[0] = fwd.Cin2d;
+  a1.w.Cin = a1.w.CinP = fwd.Cin2d;
+  return wgradp32_eligible(a1);
 }
 
-// ax: forward ConvArgs (sources, prologue, dil, pad, w); g: output gradient [B][Cout][T] (shuffled when ax.shuffle > 1);
-// gmask: optional [B][T] multiplier of g; scale: constant factor (the forward out_scale); gwp += result.
-// gbias: packed bias gradient (+=) or nullptr; *bias_done tells the caller whether this launch produced it (K == 1 and
-// K <= 12 do; the others need launch_bias_grad)
-int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask, float scale, float* gwp,
-                        float* partial, float* gbias, bool* bias_done, hipStream_t st) {
-  if (bias_done) *bias_done = false;
+// The one ordered list of the weight-gradient kernels (g / gmask as launch_conv1d_wgrad gets them; a caller that asks ahead
+// of the launch may pass g = nullptr).  The partial planes were sized by wgrad_partial_floats for the largest count.
+WgradRoute conv1d_wgrad_route(const ConvArgs& fwd, const float* g, const float* gmask) {
   const PackedConv& w = fwd.w;
-  ConvArgs ax = fwd;
-  ax.pad = fwd.pad;  // staging start t0 - pad
-  ConvArgs ag;
-  ag.x[0] = g;
-  ag.xc[0] = w.Cout;
-  ag.nsrc = 1;
-  ag.B = fwd.B;
-  ag.T = fwd.T;
-  ag.pad = 0;
-  ag.w.Cin = w.Cout;
-  ag.w.CinP = w.CoutP;
-  ag.w.K = 1;
-  ag.in_shuffle = fwd.shuffle > 1 ? fwd.shuffle : 0;
-  ag.pro = gmask ? PRO_MASK : PRO_NONE;
-  ag.mask = gmask;
-  if ((fwd.xh || fwd.gh) && !(w.K > 1 && !fwd.flatW && wgradp32_eligible(ax) && !fwd.gh)) {
-    set_error("wgrad: bf16-stored operand (xh %d gh %d) on a conv wgradp32_kernel does not take", fwd.xh, fwd.gh);
-    return STY_EINVAL;
-  }
-  if (w.K == 1) {
-    const W1Cfg c = w1_cfg(w, fwd.B, fwd.T);
-    const int nsplit = w1_nsplit(w, fwd.B, fwd.T, c, fwd.bf16 != 0);
-    const int cpb = cdiv(fwd.T, W1_TW);
-    ag.pad = 0;
-    ConvArgs ax1 = fwd;
-    ax1.flatW = 0;  // KH == KW == 1: the flat image is a plain [B][C][T] tensor
-    if (wgradb_eligible(ax1, gmask != nullptr)) {
-      const int chunks = wgradb_chunks(w, fwd.B, fwd.T, fwd.dil);
-      const int ns = nsplit < chunks ? nsplit : chunks;
-      const int wb = gbias != nullptr;
+  const bool bf = fwd.bf16 != 0;
+  const ConvArgs ax = wgrad_x_args(fwd);
+  ConvArgs a1;
+  WgradRoute r;
+  r.plane = (size_t)w.K * w.CinP * w.CoutP;
+  const bool blocked = w.K == 1 || (wgrad64_ok(w, fwd.dil) && wgrad64_operands_ok(fwd));
+  if (blocked) {
+    r.kernel = w.K == 1 ? WGRAD_K1 : WGRAD_64;
+    r.nsplit = w.K == 1 ? w1_nsplit(w, fwd.B, fwd.T, w1_cfg(w, fwd.B, fwd.T), bf) : wgrad64_nsplit(w, fwd.B, fwd.T, bf);
+    if (wgradb_eligible(ax, gmask != nullptr)) {
       // both operands as bf16 twins (x16: prologue applied; g16: mask applied): no conversion, half the bytes
-      int rc = wgradb16_eligible(ax1) ? launch_wgradb16(ax1, ns, partial, wb, st) : launch_wgradb(ax1, ag, ns, partial, wb, st);
-      if (rc) return rc;
-      const size_t plane = (size_t)w.CinP * w.CoutP;
-      launch_wgrad_reduce(partial, ns, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
-      if (bias_done) *bias_done = wb != 0;
-      STY_LAUNCH_CHECK();
-      return STY_OK;
+      r.kernel = wgradb16_eligible(ax) ? WGRAD_B16 : WGRAD_B;
+      if (w.K > 1 && r.kernel == WGRAD_B16 && wgradb16_blocks(ax) != cdiv(w.CinP, 64) * cdiv(w.CoutP, 64))
+        r.nsplit = wgrad16_nsplit(wgradb16_blocks(ax), w, fwd.B, fwd.T);
+      const int chunks = wgradb_chunks(w, fwd.B, fwd.T, fwd.dil);
+      if (r.nsplit > chunks) r.nsplit = chunks;
     }
-    dim3 grid(cdiv(w.CinP, c.TI), cdiv(w.CoutP, c.TO), nsplit);
-    const size_t lds = (size_t)(c.TI + c.TO) * (W1_TW + 1) * sizeof(float);
-    char detail[40];
-    snprintf(detail, sizeof(detail), "ci%d co%d k1 T%d W%d", w.Cin, w.Cout, fwd.T, fwd.flatW);
-    char fam[48];
-    snprintf(fam, sizeof(fam), fwd.bf16 ? "wgrad_k1_kernel<%d,%d,%d,%d,true>" : "wgrad_k1_kernel<%d,%d,%d,%d,false>", c.TI == 128 && c.TO == 128 ? 2 : (c.TI == 32 ? 1 : (c.TO == 32 ? 4 : 2)),
-             c.TI == 128 && c.TO == 128 ? 2 : (c.TI == 32 ? 4 : (c.TO == 32 ? 1 : 2)), c.TI == 128 && c.TO == 128 ? 2 : 1,
-             c.TI == 128 && c.TO == 128 ? 2 : 1);
-    ProfScope prof(fam, 2.0 * w.Cin * (double)fwd.B * w.Cout * fwd.T,
-                   4.0 * ((double)fwd.B * (w.Cin + w.Cout) * fwd.T), st, detail);
-    static bool raised = false;
-    if (!raised) {
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<2, 2, 2, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<2, 2, 2, 2, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-      raised = true;
+  } else {
+    const int tiles = (w.CinP / 32) * (w.CoutP / 32);
+    const int chunks = fwd.B * cdiv(fwd.T, WG_TW);
+    const int target = wg_target(bf);
+    int nsplit = cdiv(tiles >= 16 ? target : target / 2, tiles);
+    if (nsplit > chunks) nsplit = chunks;
+    r.nsplit = nsplit;  // the partial buffer is sized for this many planes
+    int cap = nsplit;
+    if (wgrad_rows32_args(fwd, a1)) {
+      r.kernel = WGRAD_ROWS32;
+      r.plane = (size_t)w.K * fwd.Cin2d * 32;
+      const size_t can = ((size_t)nsplit * ((size_t)w.K * w.CinP * w.CoutP + w.CoutP)) / (r.plane + 32);  // planes the partial buffer holds
+      r.nsplit = (int)(can < 1024 ? can : 1024);
+      cap = wgradp32_chunks(a1);
+    } else if (stem_wgrad_eligible(fwd, g, gmask)) {
+      r.kernel = WGRAD_STEM;
+      cap = fwd.B * cdiv(fwd.T / 4, 256);
+    } else if (wgradp32_eligible(ax)) {
+      r.kernel = WGRAD_P32;
+      cap = wgradp32_chunks(ax);
+      r.fuses_bias = cdiv(w.K, 4) <= 3;
+    } else {
+      r.kernel = WGRAD_TILED;
+      r.fuses_bias = cdiv(w.K, 4) <= 3;
     }
-    const int wb = gbias != nullptr;
+    if (r.nsplit > cap) r.nsplit = cap;
+  }
+  // bf16-stored operands: wgradp32_kernel reads a two-byte x, nothing reads a two-byte output gradient
+  r.refused = (fwd.xh || fwd.gh) && !(r.kernel == WGRAD_P32 && !fwd.gh);
+  r.twins_only = r.kernel == WGRAD_B16 && !r.refused;
+  return r;
+}
+
+static int launch_wgrad_k1(const ConvArgs& fwd, const ConvArgs& ax1, const ConvArgs& ag, int nsplit, float* partial, int wb,
+                           std::optional<ProfScope>& prof, hipStream_t st) {
+  const PackedConv& w = fwd.w;
+  const W1Cfg c = w1_cfg(w, fwd.B, fwd.T);
+  const int cpb = cdiv(fwd.T, W1_TW);
+  dim3 grid(cdiv(w.CinP, c.TI), cdiv(w.CoutP, c.TO), nsplit);
+  const size_t lds = (size_t)(c.TI + c.TO) * (W1_TW + 1) * sizeof(float);
+  char detail[40];
+  snprintf(detail, sizeof(detail), "ci%d co%d k1 T%d W%d", w.Cin, w.Cout, fwd.T, fwd.flatW);
+  char fam[48];
+  snprintf(fam, sizeof(fam), fwd.bf16 ? "wgrad_k1_kernel<%d,%d,%d,%d,true>" : "wgrad_k1_kernel<%d,%d,%d,%d,false>", c.TI == 128 && c.TO == 128 ? 2 : (c.TI == 32 ? 1 : (c.TO == 32 ? 4 : 2)),
+           c.TI == 128 && c.TO == 128 ? 2 : (c.TI == 32 ? 4 : (c.TO == 32 ? 1 : 2)), c.TI == 128 && c.TO == 128 ? 2 : 1,
+           c.TI == 128 && c.TO == 128 ? 2 : 1);
+  prof.emplace(fam, 2.0 * w.Cin * (double)fwd.B * w.Cout * fwd.T, 4.0 * ((double)fwd.B * (w.Cin + w.Cout) * fwd.T), st, detail);
+  static bool raised = false;
+  if (!raised) {
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<2, 2, 2, 2>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<2, 2, 2, 2, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+    raised = true;
+  }
 #define STY_W1(WI, WO, MI, MO)                                                                                      \
   do {                                                                                                              \
     if (fwd.bf16)                                                                                                   \
@@ -1117,174 +1145,116 @@ int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask,
       hipLaunchKernelGGL((wgrad_k1_kernel<WI, WO, MI, MO>), grid, dim3(256), lds, st, ax1, ag, nsplit, cpb,         \
                          partial, wb);                                                                              \
   } while (0)
-    if (c.TI == 128 && c.TO == 128)
-      STY_W1(2, 2, 2, 2);
-    else if (c.TI == 32)
-      STY_W1(1, 4, 1, 1);
-    else if (c.TO == 32)
-      STY_W1(4, 1, 1, 1);
-    else
-      STY_W1(2, 2, 1, 1);
+  if (c.TI == 128 && c.TO == 128)
+    STY_W1(2, 2, 2, 2);
+  else if (c.TI == 32)
+    STY_W1(1, 4, 1, 1);
+  else if (c.TO == 32)
+    STY_W1(4, 1, 1, 1);
+  else
+    STY_W1(2, 2, 1, 1);
 #undef STY_W1
-    const size_t plane = (size_t)w.CinP * w.CoutP;
-    launch_wgrad_reduce(partial, nsplit, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
-    if (bias_done) *bias_done = wb != 0;
-    STY_LAUNCH_CHECK();
-    return STY_OK;
+  return STY_OK;
+}
+
+static int launch_wgrad64(const ConvArgs& ax, const ConvArgs& ag, int nsplit, float* partial, int wb,
+                          std::optional<ProfScope>& prof, hipStream_t st) {
+  const PackedConv& w = ax.w;
+  const int cpb = cdiv(ax.T, WG_TW);
+  const int halo = (w.K - 1) * ax.dil;
+  const size_t lds = ((size_t)64 * ((WG_TW + halo) | 1) + (size_t)64 * (WG_TW + 1)) * sizeof(float);
+  static bool raised = false;
+  if (!raised) {
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<3>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<5>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<3, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<5, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+    raised = true;
   }
-  if (wgrad64_ok(w, fwd.dil) && wgrad64_operands_ok(fwd) && wgradb_eligible(ax, gmask != nullptr)) {
-    const int chunks = wgradb_chunks(w, fwd.B, fwd.T, fwd.dil);
-    int ns = wgrad64_nsplit(w, fwd.B, fwd.T, fwd.bf16 != 0);
-    const bool tw16 = wgradb16_eligible(ax);
-    if (tw16 && wgradb16_blocks(ax) != cdiv(w.CinP, 64) * cdiv(w.CoutP, 64)) ns = wgrad16_nsplit(wgradb16_blocks(ax), w, fwd.B, fwd.T);
-    if (ns > chunks) ns = chunks;
-    const int wb = gbias != nullptr;
-    int rc = tw16 ? launch_wgradb16(ax, ns, partial, wb, st) : launch_wgradb(ax, ag, ns, partial, wb, st);
+  dim3 grid(cdiv(w.CinP, 64), cdiv(w.CoutP, 64), nsplit);
+  char detail[40], fam[48];
+  snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", w.Cin, w.Cout, w.K, ax.T, ax.flatW);
+  snprintf(fam, sizeof(fam), ax.bf16 ? "conv1d_wgrad64_kernel<%d,true>" : "conv1d_wgrad64_kernel<%d,false>", w.K <= 3 ? 3 : 5);
+  prof.emplace(fam, 2.0 * w.Cin * w.K * (double)ax.B * w.Cout * ax.T, 4.0 * ((double)ax.B * (w.Cin + w.Cout) * ax.T), st, detail);
+  if (w.K <= 3 && ax.bf16)
+    hipLaunchKernelGGL((conv1d_wgrad64_kernel<3, true>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
+  else if (w.K <= 3)
+    hipLaunchKernelGGL((conv1d_wgrad64_kernel<3>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
+  else if (ax.bf16)
+    hipLaunchKernelGGL((conv1d_wgrad64_kernel<5, true>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
+  else
+    hipLaunchKernelGGL((conv1d_wgrad64_kernel<5>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
+  return STY_OK;
+}
+
+// (sums its planes itself, per image row, into the rows of the packed gradient)
+static int launch_wgrad_rows32(const ConvArgs& fwd, const ConvArgs& ag, int ns, size_t plane, float scale, float* gwp,
+                               float* partial, float* gbias, hipStream_t st) {
+  const PackedConv& w = fwd.w;
+  ConvArgs a1;
+  wgrad_rows32_args(fwd, a1);
+  const int KH = w.Cin / fwd.Cin2d;
+  for (int kh = 0; kh < KH; ++kh) {
+    a1.pad = fwd.pad - (kh - fwd.hpad) * fwd.flatW;
+    const int wb = (gbias != nullptr && kh == 0) ? 1 : 0;
+    int rc = launch_wgradp32(a1, ag, ns, partial, wb, st);
     if (rc) return rc;
-    const size_t plane = (size_t)w.K * w.CinP * w.CoutP;
-    launch_wgrad_reduce(partial, ns, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
-    if (bias_done) *bias_done = wb != 0;
-    STY_LAUNCH_CHECK();
-    return STY_OK;
+    const int n = w.K * fwd.Cin2d * 32 + (wb ? 32 : 0);
+    hipLaunchKernelGGL(wgrad_reduce_rows_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, partial, ns, plane + 32, w.K, fwd.Cin2d,
+                       w.CinP, kh * fwd.Cin2d, wb, scale, gwp, gbias);
   }
-  if (wgrad64_ok(w, fwd.dil) && wgrad64_operands_ok(fwd)) {
-    const int nsplit = wgrad64_nsplit(w, fwd.B, fwd.T, fwd.bf16 != 0);
-    const int cpb = cdiv(fwd.T, WG_TW);
-    const int halo = (w.K - 1) * fwd.dil;
-    const size_t lds = ((size_t)64 * ((WG_TW + halo) | 1) + (size_t)64 * (WG_TW + 1)) * sizeof(float);
-    static bool raised = false;
-    if (!raised) {
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<5>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<3, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-      STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_wgrad64_kernel<5, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-      raised = true;
-    }
-    dim3 grid(cdiv(w.CinP, 64), cdiv(w.CoutP, 64), nsplit);
-    char detail[40], fam[48];
-    snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", w.Cin, w.Cout, w.K, fwd.T, fwd.flatW);
-    snprintf(fam, sizeof(fam), fwd.bf16 ? "conv1d_wgrad64_kernel<%d,true>" : "conv1d_wgrad64_kernel<%d,false>", w.K <= 3 ? 3 : 5);
-    ProfScope prof(fam, 2.0 * w.Cin * w.K * (double)fwd.B * w.Cout * fwd.T,
-                   4.0 * ((double)fwd.B * (w.Cin + w.Cout) * fwd.T), st, detail);
-    const int wb = gbias != nullptr;
-    if (w.K <= 3 && fwd.bf16)
-      hipLaunchKernelGGL((conv1d_wgrad64_kernel<3, true>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
-    else if (w.K <= 3)
-      hipLaunchKernelGGL((conv1d_wgrad64_kernel<3>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
-    else if (fwd.bf16)
-      hipLaunchKernelGGL((conv1d_wgrad64_kernel<5, true>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
-    else
-      hipLaunchKernelGGL((conv1d_wgrad64_kernel<5>), grid, dim3(256), lds, st, ax, ag, nsplit, cpb, partial, wb);
-    const size_t plane = (size_t)w.K * w.CinP * w.CoutP;
-    launch_wgrad_reduce(partial, nsplit, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
-    if (bias_done) *bias_done = wb != 0;
-    STY_LAUNCH_CHECK();
-    return STY_OK;
-  }
-  const int tiles = (w.CinP / 32) * (w.CoutP / 32);
-  const int chunks_per_b = cdiv(fwd.T, WG_TW);
-  const int chunks = fwd.B * chunks_per_b;
-  const int target = wg_target(fwd.bf16 != 0);
-  int nsplit = cdiv(tiles >= 16 ? target : target / 2, tiles);
-  if (nsplit > chunks) nsplit = chunks;
-  // flat 2-D conv with 32 output channels (the spectrogram discriminators' 3x5 / 3x3 layers): one many-tap 32x32 launch
-  // per image row of the window -- row kh is the plain 1-D weight gradient against x shifted by (kh - hpad) rows -- summed
-  // straight into rows [kh*Cin2d, (kh+1)*Cin2d) of the packed gradient
-  if (fwd.flatW && w.CoutP == 32 && fwd.Cin2d % 32 == 0 && fwd.Cin2d <= 96 && w.Cin % fwd.Cin2d == 0 &&
-      w.CinP == w.Cin && fwd.nsrc == 1) {
-    ConvArgs a1 = ax;
-    a1.flatW = 0;
-    a1.hpad = 0;
-    a1.Cin2d = 0;
-    a1.xc[0] = fwd.Cin2d;
-    a1.w.Cin = a1.w.CinP = fwd.Cin2d;
-    if (wgradp32_eligible(a1)) {
-      const int KH = w.Cin / fwd.Cin2d;
-      const size_t sub = (size_t)w.K * fwd.Cin2d * 32 + 32;
-      size_t can = ((size_t)nsplit * ((size_t)w.K * w.CinP * w.CoutP + w.CoutP)) / sub;  // planes the partial buffer holds
-      int ns = (int)(can < 1024 ? can : 1024);
-      const int pc = wgradp32_chunks(a1);
-      if (ns > pc) ns = pc;
-      for (int kh = 0; kh < KH; ++kh) {
-        a1.pad = fwd.pad - (kh - fwd.hpad) * fwd.flatW;
-        const int wb = (gbias != nullptr && kh == 0) ? 1 : 0;
-        int rc = launch_wgradp32(a1, ag, ns, partial, wb, st);
-        if (rc) return rc;
-        const int n = w.K * fwd.Cin2d * 32 + (wb ? 32 : 0);
-        hipLaunchKernelGGL(wgrad_reduce_rows_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, partial, ns, sub, w.K, fwd.Cin2d,
-                           w.CinP, kh * fwd.Cin2d, wb, scale, gwp, gbias);
-      }
-      if (bias_done) *bias_done = gbias != nullptr;
-      STY_LAUNCH_CHECK();
-      return STY_OK;
-    }
-  }
-  if (stem_wgrad_eligible(fwd, g, gmask)) {
-    const int cpb = cdiv(fwd.T / 4, 256);
-    int ns = nsplit;  // the partial buffer is sized for this many planes
-    if (ns > fwd.B * cpb) ns = fwd.B * cpb;
-    const int wb = gbias != nullptr;
-    const size_t plane = (size_t)w.K * w.CinP * w.CoutP;
-    {
-      char detail[40];
-      snprintf(detail, sizeof(detail), "co%d T%d W%d", w.Cout, fwd.T, fwd.flatW);
-      ProfScope prof("stem_wgrad_kernel", 2.0 * 9 * (double)fwd.B * w.Cout * fwd.T, 4.0 * (double)fwd.B * (w.Cout + 2) * fwd.T, st,
-                     detail);
-      dim3 grid(w.CoutP / STEM_CO, ns);
-      if (fwd.bf16)
-        hipLaunchKernelGGL(stem_wgrad_kernel<true>, grid, dim3(256), 0, st, g, gmask, fwd.x[0], fwd.B, w.Cout, fwd.T, fwd.flatW,
-                           fwd.hpad, fwd.pad, w.CinP, w.CoutP, ns, partial, plane + w.CoutP, wb);
-      else
-        hipLaunchKernelGGL(stem_wgrad_kernel<false>, grid, dim3(256), 0, st, g, gmask, fwd.x[0], fwd.B, w.Cout, fwd.T, fwd.flatW,
-                           fwd.hpad, fwd.pad, w.CinP, w.CoutP, ns, partial, plane + w.CoutP, wb);
-    }
-    launch_wgrad_reduce(partial, ns, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
-    if (bias_done) *bias_done = wb != 0;
-    STY_LAUNCH_CHECK();
-    return STY_OK;
-  }
-  if (wgradp32_eligible(ax)) {
-    const int KTp = cdiv(w.K, 4);
-    const int wb = (gbias != nullptr && KTp <= 3) ? 1 : 0;  // (the caller's bookkeeping: wgrad_fuses_bias)
-    int ns = nsplit;  // the partial buffer is sized for this many planes
-    const int pc = wgradp32_chunks(ax);
-    if (ns > pc) ns = pc;
-    int rc = launch_wgradp32(ax, ag, ns, partial, wb, st);
-    if (rc) return rc;
-    const size_t plane = (size_t)w.K * w.CinP * w.CoutP;
-    launch_wgrad_reduce(partial, ns, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
-    if (bias_done) *bias_done = wb != 0;
-    STY_LAUNCH_CHECK();
-    return STY_OK;
-  }
-  const int halo = (w.K - 1) * fwd.dil;
+  return STY_OK;
+}
+
+static int launch_wgrad_stem(const ConvArgs& fwd, const float* g, const float* gmask, int ns, size_t plane, float* partial,
+                             int wb, hipStream_t st) {
+  const PackedConv& w = fwd.w;
+  char detail[40];
+  snprintf(detail, sizeof(detail), "co%d T%d W%d", w.Cout, fwd.T, fwd.flatW);
+  ProfScope prof("stem_wgrad_kernel", 2.0 * 9 * (double)fwd.B * w.Cout * fwd.T, 4.0 * (double)fwd.B * (w.Cout + 2) * fwd.T, st,
+                 detail);
+  dim3 grid(w.CoutP / STEM_CO, ns);
+  if (fwd.bf16)
+    hipLaunchKernelGGL(stem_wgrad_kernel<true>, grid, dim3(256), 0, st, g, gmask, fwd.x[0], fwd.B, w.Cout, fwd.T, fwd.flatW,
+                       fwd.hpad, fwd.pad, w.CinP, w.CoutP, ns, partial, plane + w.CoutP, wb);
+  else
+    hipLaunchKernelGGL(stem_wgrad_kernel<false>, grid, dim3(256), 0, st, g, gmask, fwd.x[0], fwd.B, w.Cout, fwd.T, fwd.flatW,
+                       fwd.hpad, fwd.pad, w.CinP, w.CoutP, ns, partial, plane + w.CoutP, wb);
+  return STY_OK;
+}
+
+// the fallback: one 32 x 32 tile of dW per workgroup
+static int launch_wgrad_tiled(const ConvArgs& ax, const ConvArgs& ag, int nsplit, float* partial, int wb,
+                              std::optional<ProfScope>& prof, hipStream_t st) {
+  const PackedConv& w = ax.w;
+  const int chunks_per_b = cdiv(ax.T, WG_TW);
+  const int halo = (w.K - 1) * ax.dil;
   if (halo > 128) {
     set_error("wgrad: halo %d > 128", halo);
     return STY_EINVAL;
   }
   const size_t lds = ((size_t)CI_CHUNK * ((WG_TW + halo) | 1) + (size_t)CI_CHUNK * (WG_TW + 1)) * sizeof(float);
   dim3 grid(w.CinP / 32, w.CoutP / 32, nsplit);
-  const double flops = 2.0 * w.Cin * w.K * (double)fwd.B * w.Cout * fwd.T;
-  const double bytes = 4.0 * ((double)fwd.B * (w.Cin + w.Cout) * fwd.T);
+  const double flops = 2.0 * w.Cin * w.K * (double)ax.B * w.Cout * ax.T;
+  const double bytes = 4.0 * ((double)ax.B * (w.Cin + w.Cout) * ax.T);
   char detail[40];
-  snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", w.Cin, w.Cout, w.K, fwd.T, fwd.flatW);
+  snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", w.Cin, w.Cout, w.K, ax.T, ax.flatW);
   char fam[48];
-  snprintf(fam, sizeof(fam), fwd.bf16 ? "conv1d_wgrad_kernel<%d,true>" : "conv1d_wgrad_kernel<%d,false>",
+  snprintf(fam, sizeof(fam), ax.bf16 ? "conv1d_wgrad_kernel<%d,true>" : "conv1d_wgrad_kernel<%d,false>",
            cdiv(w.K, 4) <= 3 ? cdiv(w.K, 4) : 6);
-  ProfScope prof(fam, flops, bytes, st, detail);
+  prof.emplace(fam, flops, bytes, st, detail);
   const int KT = cdiv(w.K, 4);
-  const int wb = (gbias != nullptr && KT >= 1 && KT <= 3) ? 1 : 0;
-  if (fwd.flatW && KT > 3) {
+  if (ax.flatW && KT > 3) {
     set_error("wgrad: flat 2-D mode is built for K <= 12");
     return STY_EINVAL;
   }
 #define STY_WG(KTV)                                                                                                \
   do {                                                                                                             \
-    if (fwd.bf16)                                                                                                  \
+    if (ax.bf16)                                                                                                   \
       hipLaunchKernelGGL((conv1d_wgrad_kernel<KTV, true>), grid, dim3(256), lds, st, ax, ag, nsplit, chunks_per_b, \
                          partial, wb);                                                                             \
     else                                                                                                           \
@@ -1305,8 +1275,57 @@ int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask,
       }
   }
 #undef STY_WG
-  const size_t plane = (size_t)w.K * w.CinP * w.CoutP;
-  launch_wgrad_reduce(partial, nsplit, plane, plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
+  return STY_OK;
+}
+
+// fwd: forward ConvArgs (sources, prologue, dil, pad, w); g: output gradient [B][Cout][T] (shuffled when fwd.shuffle > 1);
+// gmask: optional [B][T] multiplier of g; scale: constant factor (the forward out_scale); gwp += result.
+// gbias: packed bias gradient (+=) or nullptr; *bias_done tells the caller whether this launch produced it (the route's
+// fuses_bias; otherwise it needs launch_bias_grad)
+int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask, float scale, float* gwp,
+                        float* partial, float* gbias, bool* bias_done, hipStream_t st) {
+  if (bias_done) *bias_done = false;
+  const PackedConv& w = fwd.w;
+  const WgradRoute r = conv1d_wgrad_route(fwd, g, gmask);
+  if (r.refused) {
+    set_error("wgrad: bf16-stored operand (xh %d gh %d) on a conv wgradp32_kernel does not take", fwd.xh, fwd.gh);
+    return STY_EINVAL;
+  }
+  // a caller that hands the launch to the side stream does its bias bookkeeping with wgrad_fuses_bias, without seeing *bias_done
+  if (r.fuses_bias != wgrad_fuses_bias(w)) {
+    set_error("wgrad: the route's bias fusion (%d) is not wgrad_fuses_bias (K = %d)", (int)r.fuses_bias, w.K);
+    return STY_EINVAL;
+  }
+  const ConvArgs ax = wgrad_x_args(fwd);  // staging start t0 - pad
+  ConvArgs ag;
+  ag.x[0] = g;
+  ag.xc[0] = w.Cout;
+  ag.nsrc = 1;
+  ag.B = fwd.B;
+  ag.T = fwd.T;
+  ag.pad = 0;
+  ag.w.Cin = w.Cout;
+  ag.w.CinP = w.CoutP;
+  ag.w.K = 1;
+  ag.in_shuffle = fwd.shuffle > 1 ? fwd.shuffle : 0;
+  ag.pro = gmask ? PRO_MASK : PRO_NONE;
+  ag.mask = gmask;
+  const int ns = r.nsplit, wb = gbias != nullptr && r.fuses_bias;
+  std::optional<ProfScope> prof;  // the in-situ timer of the kernels launched here takes the reduction along
+  int rc = STY_OK;
+  switch (r.kernel) {
+    case WGRAD_B16: rc = launch_wgradb16(ax, ns, partial, wb, st); break;
+    case WGRAD_B: rc = launch_wgradb(ax, ag, ns, partial, wb, st); break;
+    case WGRAD_K1: rc = launch_wgrad_k1(fwd, ax, ag, ns, partial, wb, prof, st); break;
+    case WGRAD_64: rc = launch_wgrad64(ax, ag, ns, partial, wb, prof, st); break;
+    case WGRAD_ROWS32: rc = launch_wgrad_rows32(fwd, ag, ns, r.plane, scale, gwp, partial, gbias, st); break;
+    case WGRAD_STEM: rc = launch_wgrad_stem(fwd, g, gmask, ns, r.plane, partial, wb, st); break;
+    case WGRAD_P32: rc = launch_wgradp32(ax, ag, ns, partial, wb, st); break;
+    case WGRAD_TILED: rc = launch_wgrad_tiled(ax, ag, ns, partial, wb, prof, st); break;
+  }
+  if (rc) return rc;
+  if (r.kernel != WGRAD_ROWS32)
+    launch_wgrad_reduce(partial, ns, r.plane, r.plane + w.CoutP, wb ? w.CoutP : 0, scale, gwp, gbias, st);
   if (bias_done) *bias_done = wb != 0;
   STY_LAUNCH_CHECK();
   return STY_OK;

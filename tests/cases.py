@@ -13,7 +13,7 @@ def _pitch(g, B, T):
 # Ragged text batches (L, lengths).  The edges are those of attn_kernel (32 queries per wave, 128 per workgroup, key tiles of
 # 32): 32 / 64 / 96 / 128 each have a length on, below and above them, and two cases hold a row of length 1.  The other
 # kernels on the masked path tile the text axis by multiples of 32 as well -- conv1d_mfma_kernel 64 / 128 / 256 / 512
-# (TT_BLK = 32 * NT * WN of the configurations launch_conv1d_dispatch picks), convk1 128 samples per LDS row, the
+# (TT_BLK = 32 * NT * WN of the configurations launch_tiled picks), convk1 128 samples per LDS row, the
 # weight-gradient kernels 128 (WG_TW) and 64 (W1_TW) samples per chunk, attn_bwd 32-key tiles and 128-query workgroups --
 # so at L <= 130 every edge that applies is 64 or 128, both straddled here (63 / 64 / 65, 127 / 128 / 129, and L = 130
 # itself puts two columns into a second 128-wide tile); no further length is needed.
