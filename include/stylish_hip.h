@@ -41,6 +41,7 @@ const char *sty_last_error(void);
 /* ---- model objects -------------------------------------------------------------------------------
  * kind: "speech_predictor"   = train/models/speech_predictor.py:10-73 (text_encoder + decoder + generator)
  *       "mel_style_encoder"  = train/models/mel_style_encoder.py:121-152
+ *       "text_aligner"       = train/models/text_aligner.py:33-45 (inference only, see sty_aligner_fwd)
  * Dimensions are taken from the bound tensors' shapes (train/config/model.yml defaults are checked).   */
 int sty_model_create(const char *kind, sty_model **out);
 void sty_model_destroy(sty_model *m);
@@ -146,6 +147,31 @@ int sty_pitch_energy_fwd(sty_model *m, int B, int L, int T, const int64_t *texts
 int sty_pitch_style_workspace_bytes(const sty_model *m, int B, int T, size_t *bytes);
 int sty_pitch_style_fwd(sty_model *m, int B, int T, const float *mel, const float *pitch, const float *energy,
                         float *style, void *workspace, size_t ws_bytes, void *stream);
+
+/* ---- alignment stage, inference (train/dataprep/align_text.py; `python -m stylish_tts_amd.align`) ------------------
+ * Model kind "text_aligner" = tdnn_blstm_ctc_model_base(n_mels, tokens) in eval mode (train/models/text_aligner.py:33-45,
+ * 130-274), bound by the reference's state_dict keys (encoder.layers.{0,1,2}.0.{weight,bias}, encoder.layers.{0,1,2}.2.
+ * running_{mean,var}, encoder.layers.3.ffn.{0,3,6,9,12}.{weight,bias}, encoder_output_layer.{weight,bias});
+ * hidden_dim, n_mels and tokens are read from the bound shapes.  CTCModel.forward (text_aligner.py:73-127) + the
+ * "t b k -> b t k" of align_text.py:303:  mel [B,n_mels,T] (as sty_mel_fwd writes it), mel_lengths [B] int64 ->
+ * log_probs [B,T,tokens+1].  Frames at or beyond mel_lengths[b] are zeroed in front of each of the three TDNN convs
+ * (text_aligner.py:221-225).  fp32 operands and accumulation: sty_model_set_train_opts with compute_bf16 and
+ * sty_model_enable_training / sty_model_bind_grad return STY_EINVAL for this kind.                                     */
+int sty_aligner_workspace_bytes(const sty_model *m, int B, int T, size_t *bytes);
+int sty_aligner_fwd(sty_model *m, int B, int T, const float *mel, const int64_t *mel_lengths, float *log_probs,
+                    void *workspace, size_t ws_bytes, void *stream);
+/* CTC forced alignment: torchaudio.functional.forced_align as align_text.py:317 calls it, for a whole batch.
+ * log_probs [B,T,V1], targets [B,U] int64 (row b uses its first target_lengths[b] entries; none may equal `blank`),
+ * input_lengths / target_lengths [B] int64 -> labels [B,T] int32 = the class emitted at every frame, scores [B,T] =
+ * log_probs[b,t,labels[b,t]]; frames at or beyond input_lengths[b] get label -1 and score 0.  Viterbi over the
+ * 2 * target_length + 1 states "blank, tok, blank, ..." in fp32 max / + only (DESIGN.md has the recurrence and its tie
+ * rule).  status [B] int32: 0 = aligned; 1 = input_lengths[b] < target_lengths[b] + adjacent repeats (no alignment
+ * exists; torchaudio raises); 2 = a length or a target out of range.  Rows with a non-zero status get labels -1 and
+ * scores 0; the other rows of the batch are unaffected.  U <= 512, V1 <= 1024.                                         */
+int sty_forced_align_workspace_bytes(int B, int T, int U, size_t *bytes);
+int sty_forced_align(int B, int T, int V1, int U, const float *log_probs, const int64_t *targets,
+                     const int64_t *input_lengths, const int64_t *target_lengths, int blank, int32_t *labels,
+                     float *scores, int32_t *status, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---- fine-grained entry points for unit parity (each = one reference sub-module) ------------------ */
 /* GeneratorConvNeXtBlock (conv_next.py:80-93) of channel count C on [B,C,T]; prefix e.g.

@@ -615,6 +615,43 @@ struct Builder {
     p.np = conv("N_proj");
   }
 
+  // TextAligner (text_aligner.py:33-45, 130-274): dimensions from the bound shapes
+  void text_aligner() {
+    AlignerPlan& a = m->ali;
+    static const int kernel[3] = {5, 3, 3};
+    for (int i = 0; i < 3; ++i) {
+      const std::string p = "encoder.layers." + std::to_string(i);
+      a.tdnn[i] = conv(p + ".0");
+      const int C = a.tdnn[i].Cout;
+      if (ok && (a.tdnn[i].K != kernel[i] || (i > 0 && (a.tdnn[i].Cin != a.hidden || C != a.hidden)))) {
+        m->missing = p + ".0.weight (shape mismatch)";
+        ok = false;
+      }
+      if (i == 0) {
+        a.hidden = C;
+        a.n_mels = a.tdnn[0].Cin;
+      }
+      a.rm[i] = ptr(p + ".2.running_mean", {C});
+      a.rv[i] = ptr(p + ".2.running_var", {C});
+      a.bn_scale[i] = m->ab.take<float>(C);
+      a.bn_shift[i] = m->ab.take<float>(C);
+    }
+    for (int i = 0; i < 5; ++i) {
+      const std::string p = "encoder.layers.3.ffn." + std::to_string(3 * i);
+      a.ffn[i] = conv(p);
+      if (ok && (a.ffn[i].K != 1 || a.ffn[i].Cin != a.hidden || a.ffn[i].Cout != a.hidden)) {
+        m->missing = p + ".weight (shape mismatch)";
+        ok = false;
+      }
+    }
+    a.out = conv("encoder_output_layer");
+    if (ok && (a.out.K != 1 || a.out.Cin != a.hidden || a.out.Cout < 2)) {
+      m->missing = "encoder_output_layer.weight (shape mismatch)";
+      ok = false;
+    }
+    a.classes = a.out.Cout;
+  }
+
   void build() {
     m->gb_floats_per_batch = 0;
     if (m->kind == "speech_predictor") {
@@ -633,6 +670,8 @@ struct Builder {
       duration_predictor();
     } else if (m->kind == "pitch_energy_predictor") {
       pitch_energy_predictor();
+    } else if (m->kind == "text_aligner") {
+      text_aligner();
     }
   }
 };
@@ -1428,6 +1467,47 @@ static void pitch_energy_forward(Run& r, const int64_t* texts, const int64_t* le
   }
 }
 
+// CTCModel.forward in eval mode (text_aligner.py:73-127, 209-274): mel [B][n_mels][T], lengths [B] -> log_probs [B][T][classes].
+// Frames at or beyond a row's length are zeroed in front of each TDNN conv (the conv's mask prologue); what the convs
+// compute on those frames is kept, as the reference keeps it.  fp32 operands throughout (compute_bf16 is refused for the kind).
+static void aligner_forward(Run& r, const float* mel, const int64_t* lengths, int T, float* out) {
+  const AlignerPlan& p = r.m->ali;
+  const int B = r.B, H = p.hidden, V = p.classes;
+  const size_t n = (size_t)B * H * T;
+  float* mask = r.ws.take<float>((size_t)B * T);
+  float* a = r.ws.take<float>(n);
+  float* b = r.ws.take<float>(n);
+  float* c = r.ws.take<float>(n);
+  float* logits = r.ws.take<float>((size_t)B * V * T);
+  if (!r.live()) return;
+  r.chk(launch_length_mask(lengths, B, T, mask, r.st));
+  const float* x = mel;
+  for (int i = 0; i < 3 && r.live(); ++i) {
+    float* y = (i & 1) ? b : a;
+    ConvArgs ca = r.base(p.tdnn[i], x, T, y);
+    ca.pro = PRO_MASK;
+    ca.mask = mask;
+    ca.act = ACT_RELU;
+    r.conv(ca);
+    r.chk(launch_aligner_bn(y, B, H, T, p.bn_scale[i], p.bn_shift[i], r.st));
+    x = y;
+  }
+  // Ffn: five Linear + ReLU, the skip around all five in the last one's output stage (x = a here)
+  const float* src = a;
+  for (int i = 0; i < 5 && r.live(); ++i) {
+    float* y = (i & 1) ? c : b;
+    ConvArgs ca = r.base(p.ffn[i], src, T, y);
+    ca.act = ACT_RELU;
+    if (i == 4) ca.residual = a;
+    r.conv(ca);
+    src = y;
+  }
+  if (r.live()) {
+    r.conv(r.base(p.out, src, T, logits));
+    r.chk(launch_log_softmax_rows(logits, B, V, T, out, r.st));
+  }
+}
+
 static int run_style_fc(Run& r, const float* style) {
   sty_model* m = r.m;
   r.gb = r.ws.take<float>(m->gb_floats_per_batch * r.B);
@@ -1496,7 +1576,7 @@ int sty_model_create(const char* kind, sty_model** out) {
   }
   std::string k(kind);
   if (k != "speech_predictor" && k != "vocoder" && k != "mel_style_encoder" && k != "duration_predictor" &&
-      k != "pitch_energy_predictor" && k != "pitch_style_encoder") {
+      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner") {
     set_error("unknown model kind '%s'", kind);
     return STY_EINVAL;
   }
@@ -1609,11 +1689,19 @@ int sty_model_finalize(sty_model* m) {
   return STY_OK;
 }
 
+// the text aligner is an inference-only kind (alignment decisions are arg-max decisions: fp32 operands, no training graph)
+static int refuse_aligner(const sty_model* m, const char* what) {
+  if (m->kind != "text_aligner") return STY_OK;
+  set_error("%s: model kind 'text_aligner' is inference-only and runs fp32 operands", what);
+  return STY_EINVAL;
+}
+
 int sty_model_enable_training(sty_model* m) {
   if (!m) {
     set_error("null model");
     return STY_EINVAL;
   }
+  if (refuse_aligner(m, "sty_model_enable_training")) return STY_EINVAL;
   m->train_enabled = true;
   m->finalized = false;
   return STY_OK;
@@ -1625,6 +1713,7 @@ int sty_model_set_train_opts(sty_model* m, const sty_train_opts* o) {
     set_error("sty_model_set_train_opts: null argument or smoothing width not an odd number in [0, 63]");
     return STY_EINVAL;
   }
+  if (o->compute_bf16 && refuse_aligner(m, "sty_model_set_train_opts(compute_bf16)")) return STY_EINVAL;
   m->topts = *o;
   return STY_OK;
 }
@@ -1634,6 +1723,7 @@ int sty_model_bind_grad(sty_model* m, const char* key, float* grad) {
     set_error("sty_model_bind_grad: bad argument");
     return STY_EINVAL;
   }
+  if (refuse_aligner(m, "sty_model_bind_grad")) return STY_EINVAL;
   m->pgrad_by_key[key] = grad;
   m->train_enabled = true;
   m->finalized = false;
@@ -2074,6 +2164,13 @@ int sty_model_prepare(sty_model* m, void* stream) {
     int r = launch_prep_fnv(d.f0_g, d.f0_v, d.f0_b, d.n_g, d.n_v, d.n_b, d.v_g, d.v_v, d.v_b, d.fnv_w, st);
     if (r != STY_OK) return r;
   }
+  if (m->kind == "text_aligner") {  // BatchNorm1d(affine=False) on running statistics -> one scale / shift pair per layer
+    const AlignerPlan& a = m->ali;
+    for (int i = 0; i < 3; ++i) {
+      int r = launch_aligner_bn_prep(a.rm[i], a.rv[i], a.hidden, 1e-5f, a.bn_scale[i], a.bn_shift[i], st);
+      if (r != STY_OK) return r;
+    }
+  }
   if (m->arena) {  // the bf16 fragment buffers the persistent kernels read the packed weights through (bf16 mode)
     int r = convp16_repack_range(m->arena, m->arena + m->arena_bytes, st);
     if (r != STY_OK) return r;
@@ -2196,6 +2293,37 @@ int sty_duration_fwd(sty_model* m, int B, int L, const int64_t* texts, const int
   }
   if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
   return duration_run(m, B, L, texts, text_lengths, style, dur_pred, workspace, ws_bytes, stream, nullptr);
+}
+// ---- text aligner (inference) ----
+static int aligner_run(sty_model* m, int B, int T, const float* mel, const int64_t* lengths, float* out, void* ws,
+                       size_t ws_bytes, void* stream, size_t* need) {
+  Run r(m, B, ws, ws_bytes, stream);
+  aligner_forward(r, mel, lengths, T, out);
+  return r.finish(need, ws, ws_bytes);
+}
+int sty_aligner_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
+  int rc = model_ready(m, "text_aligner");
+  if (rc) return rc;
+  if (!bytes || B <= 0 || T <= 0) {
+    set_error("sty_aligner_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  return aligner_run(const_cast<sty_model*>(m), B, T, nullptr, nullptr, nullptr, nullptr, 0, nullptr, bytes);
+}
+int sty_aligner_fwd(sty_model* m, int B, int T, const float* mel, const int64_t* mel_lengths, float* log_probs,
+                    void* workspace, size_t ws_bytes, void* stream) {
+  int rc = model_ready(m, "text_aligner");
+  if (rc) return rc;
+  if (!mel || !mel_lengths || !log_probs || !workspace || B <= 0 || T <= 0) {
+    set_error("sty_aligner_fwd: bad argument");
+    return STY_EINVAL;
+  }
+  if (m->topts.compute_bf16) {
+    set_error("sty_aligner_fwd: compute_bf16 is refused for the text aligner");
+    return STY_EINVAL;
+  }
+  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  return aligner_run(m, B, T, mel, mel_lengths, log_probs, workspace, ws_bytes, stream, nullptr);
 }
 static int pitch_energy_run(sty_model* m, int B, int L, int T, const int64_t* texts, const int64_t* lengths,
                             const float* alignment, const float* style, float* f0, float* energy, void* ws,

@@ -193,6 +193,19 @@ struct PitchEnergyPlan {  // pitch_energy_predictor.py:8-60
   int heads = 2;
 };
 
+// TextAligner = tdnn_blstm_ctc_model_base (text_aligner.py:33-45), eval mode: three TDNN convs (k = 5, 3, 3) each followed by
+// ReLU and BatchNorm1d(affine=False) on running statistics, an Ffn of five Linear + ReLU with one skip, the output Linear
+struct AlignerPlan {
+  PackedConv tdnn[3], ffn[5], out;
+  const float *rm[3] = {nullptr, nullptr, nullptr}, *rv[3] = {nullptr, nullptr, nullptr};
+  float *bn_scale[3] = {nullptr, nullptr, nullptr}, *bn_shift[3] = {nullptr, nullptr, nullptr};  // prepared: 1 / sqrt(var + eps), -mean * scale
+  int hidden = 640, n_mels = 80, classes = 179;
+};
+// align.hip
+int launch_aligner_bn_prep(const float* mean, const float* var, int C, float eps, float* scale, float* shift, hipStream_t st);
+int launch_aligner_bn(float* x, int B, int C, int T, const float* scale, const float* shift, hipStream_t st);
+int launch_log_softmax_rows(const float* x, int B, int V, int T, float* out, hipStream_t st);
+
 struct Trainer;
 struct StyleResBlk {  // mel_style_encoder.py:69-118
   int Cin = 0, Cout = 0;
@@ -234,6 +247,7 @@ struct sty_model {
   sty::StylePlan sty_enc;
   sty::DurationPlan dur;
   sty::PitchEnergyPlan pe;
+  sty::AlignerPlan ali;
   sty::PackedConv pse_pre;  // PitchStyleEncoder.preconv (mel_style_encoder.py:166)
   float* stft_default = nullptr;  // device [4][33][64]
   // ---- training ----

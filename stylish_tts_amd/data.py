@@ -72,9 +72,10 @@ class SampleDataset(torch.utils.data.Dataset):
     def __init__(self, *, data_list, root_path, pitch_path, alignment_path, text_cleaner=None, sample_rate=24000,
                  hop_length=300, coarse_multiplier=1):
         self.pitch, self.alignment = {}, {}
-        with safe_open(pitch_path, framework="pt", device="cpu") as f:
-            for k in f.keys():
-                self.pitch[k] = f.get_tensor(k)
+        if pitch_path is not None:  # None: a pass that reads no pitch (the alignment command runs before pitch exists)
+            with safe_open(pitch_path, framework="pt", device="cpu") as f:
+                for k in f.keys():
+                    self.pitch[k] = f.get_tensor(k)
         if alignment_path and osp.isfile(alignment_path):
             with safe_open(alignment_path, framework="pt", device="cpu") as f:
                 for k in f.keys():

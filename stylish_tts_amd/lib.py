@@ -163,6 +163,10 @@ SYMBOLS = {
     "sty_comm_destroy": (C.c_int, [_P]),
     "sty_pack_accumulate": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P]),
     "sty_pack_finalize": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, _P]),
+    "sty_aligner_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
+    "sty_aligner_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_forced_align_workspace_bytes": (C.c_int, [_I, _I, _I, _SZP]),
+    "sty_forced_align": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_prof_enable": (C.c_int, [_I]),
     "sty_prof_only": (C.c_int, [C.c_char_p]),
     "sty_set_single_stream": (C.c_int, [_I]),

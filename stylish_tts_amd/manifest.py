@@ -316,3 +316,23 @@ def pitch_style_encoder_manifest(cfg=None):
     _wn(m, "preconv", [d, d + 2, 1])
     m.update(style_encoder_manifest(c))
     return m
+
+
+def text_aligner_manifest(n_mels=80, tokens=178, hidden_dim=640):
+    """tdnn_blstm_ctc_model_base (text_aligner.py:33-45): three TDNN layers Conv1d(k = 5, 3, 3) -> ReLU ->
+    BatchNorm1d(affine=False) (buffers only), an Ffn of five Linear + ReLU (Sequential indices 0, 3, 6, 9, 12: ReLU and
+    Dropout sit in between), the output Linear over tokens + 1 classes (the blank is the last one)."""
+    m = OrderedDict()
+    cin = n_mels
+    for i, k in enumerate((5, 3, 3)):
+        _conv(m, f"encoder.layers.{i}.0", hidden_dim, cin, k)
+        m[f"encoder.layers.{i}.2.running_mean"] = [hidden_dim]
+        m[f"encoder.layers.{i}.2.running_var"] = [hidden_dim]
+        m[f"encoder.layers.{i}.2.num_batches_tracked"] = []
+        cin = hidden_dim
+    for j in range(5):
+        m[f"encoder.layers.3.ffn.{3 * j}.weight"] = [hidden_dim, hidden_dim]
+        m[f"encoder.layers.3.ffn.{3 * j}.bias"] = [hidden_dim]
+    m["encoder_output_layer.weight"] = [tokens + 1, hidden_dim]
+    m["encoder_output_layer.bias"] = [tokens + 1]
+    return m
