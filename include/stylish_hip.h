@@ -42,6 +42,7 @@ const char *sty_last_error(void);
  * kind: "speech_predictor"   = train/models/speech_predictor.py:10-73 (text_encoder + decoder + generator)
  *       "mel_style_encoder"  = train/models/mel_style_encoder.py:121-152
  *       "text_aligner"       = train/models/text_aligner.py:33-45 (inference only, see sty_aligner_fwd)
+ *       "text_aligner_train" = the same module with a training graph (see sty_aligner_fwd_train)
  * Dimensions are taken from the bound tensors' shapes (train/config/model.yml defaults are checked).   */
 int sty_model_create(const char *kind, sty_model **out);
 void sty_model_destroy(sty_model *m);
@@ -172,6 +173,39 @@ int sty_forced_align_workspace_bytes(int B, int T, int U, size_t *bytes);
 int sty_forced_align(int B, int T, int V1, int U, const float *log_probs, const int64_t *targets,
                      const int64_t *input_lengths, const int64_t *target_lengths, int blank, int32_t *labels,
                      float *scores, int32_t *status, void *workspace, size_t ws_bytes, void *stream);
+
+/* ---- alignment stage, training (train_alignment, train/stage_type.py:268-341; `python -m stylish_tts_amd.train_align`) --
+ * Model kind "text_aligner_train": the keys and shapes of "text_aligner", with sty_model_enable_training /
+ * sty_model_bind_grad accepted (compute_bf16 is refused as for its sibling).  sty_aligner_fwd serves this kind too (the
+ * eval-mode forward on running statistics: validation).
+ * sty_aligner_fwd_train = CTCModel.forward under module.train() (train/models/text_aligner.py:73-127, 209-274): per TDNN
+ * layer the masked conv + ReLU, BatchNorm1d(affine=False) on the batch statistics of all B*T positions -- the bound
+ * running_mean / running_var are updated in place (momentum sty_train_opts.bn_momentum, unbiased variance) -- and
+ * Dropout(drop_p); the Ffn of five Linear + ReLU + Dropout with its skip; the output Linear and log_softmax.  Dropout masks
+ * are the library's hash u(drop_seed, site, element) (its dropout everywhere): sites 0-2 behind the BatchNorms, 3-7 behind the Ffn's ReLUs, element = linear
+ * index in [B][hidden][T]; keep = u >= drop_p, scaled by 1 / (1 - drop_p); drop_p = 0 skips them.
+ * sty_aligner_bwd: d_logits [B][tokens+1][T] = d loss / d (input of the log_softmax), channel-major as sty_ctc_loss_fwd_bwd
+ * writes it; parameter gradients are added to the bound gradient buffers.  One backward per forward (STY_ESTATE otherwise). */
+int sty_aligner_train_workspace_bytes(sty_model *m, int B, int T, size_t *bytes);
+int sty_aligner_fwd_train(sty_model *m, int B, int T, const float *mel, const int64_t *mel_lengths, float drop_p,
+                          unsigned drop_seed, float *log_probs, void *workspace, size_t ws_bytes, void *stream);
+int sty_aligner_bwd(sty_model *m, const float *d_logits, void *stream);
+/* CTC loss and its gradient: CTCLossWithLabelPriors.forward (train/losses.py:478-653; k2.ctc_loss(reduction="mean",
+ * use_double_scores=True, target_lengths=...) at losses.py:600-615) with the semantics of
+ * torch.nn.functional.ctc_loss(reduction="mean", zero_infinity=False): exact CTC in float64 log-space, no beam (k2 prunes
+ * with output_beam = 10: not reproduced).  log_probs [B,T,V1] (what sty_aligner_fwd[_train] writes); log_priors [V1] or
+ * NULL: the scores are log_probs - prior_scale * log_priors (losses.py:585-588), the priors are constants; targets [B,U]
+ * int64, input_lengths / target_lengths [B] int64.  nll [B] double = -log p(target | input); loss [1] =
+ * mean_b(nll_b / max(U_b, 1)), unweighted; d_logits [B,V1,T] (NULL: loss only) = weight / (B max(U_b, 1)) *
+ * (exp(log_probs) - occupancy), the log_softmax backward folded in, zero at and beyond input_lengths[b].
+ * status [B] int32: 0 ok; 1 no valid path; 2 a length or a target out of range.  Rows with a non-zero status get
+ * nll = +inf and a zero gradient (loss is then +inf); the other rows are unaffected.  U <= 512, V1 <= 1024.
+ * workspace: alpha of every frame, [B][T][2U+1] double (read only with d_logits).                                      */
+int sty_ctc_loss_workspace_bytes(int B, int T, int V1, int U, size_t *bytes);
+int sty_ctc_loss_fwd_bwd(int B, int T, int V1, int U, const float *log_probs, const float *log_priors, float prior_scale,
+                         const int64_t *targets, const int64_t *input_lengths, const int64_t *target_lengths, int blank,
+                         float weight, double *nll, float *loss, int32_t *status, float *d_logits, void *workspace,
+                         size_t ws_bytes, void *stream);
 
 /* ---- fine-grained entry points for unit parity (each = one reference sub-module) ------------------ */
 /* GeneratorConvNeXtBlock (conv_next.py:80-93) of channel count C on [B,C,T]; prefix e.g.

@@ -8,3 +8,4 @@ from .lib import LIB, StyError, load  # noqa: F401
 from .modules import (DurationPredictor, DurationProcessor, ExportModel, MelStyleEncoder, MultiGenerator,  # noqa: F401
                       PitchEnergyPredictor, PitchStyleEncoder, SpeechPredictor)
 from .align import TextAligner  # noqa: F401,E402
+from .alignment import TrainableTextAligner  # noqa: F401,E402

@@ -1,6 +1,6 @@
 """The `align` entry point on the reference's unchanged YAML files (train/cli.py:114-153 `align`,
 train/dataprep/align_text.py): a trained `alignment_model.safetensors` + a dataset -> `alignment.safetensors` (the durations
-`train` reads), `scores_val.txt` and `scores_train.txt`.  Inference only: training the aligner (`train-align`) is not built.
+`train` reads), `scores_val.txt` and `scores_train.txt`.  Inference only: training the aligner is `train_align.py`.
 
     python -m stylish_tts_amd.align CONFIG.yml --model-config MODEL.yml [--method torch] [-bs 8]
 
@@ -55,7 +55,7 @@ class TextAligner(_HipModule):
         self._build(text_aligner_manifest(self.n_mels, self.tokens, self.hidden_dim))
 
     def enable_training(self):
-        raise L.StyError("TextAligner: inference only (train-align is not built)")
+        raise L.StyError("TextAligner: inference only (the training graph is alignment.TrainableTextAligner)")
 
     def set_train_opts(self, **kw):
         if kw.get("compute_bf16"):

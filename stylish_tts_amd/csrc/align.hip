@@ -1,4 +1,5 @@
-// The alignment stage's device code (train/dataprep/align_text.py, train/models/text_aligner.py), inference only.
+// The alignment stage's device code (train/dataprep/align_text.py, train/models/text_aligner.py): the inference forward's
+// glue and the forced alignment.  The training graph is in train.hip (Trainer::aligner), the CTC loss in ctc.hip.
 //
 // (1) Element-wise / row kernels of the TextAligner forward (the convs and Linears run on launch_conv1d):
 //       aligner_bn_prep_kernel   running_mean / running_var -> scale = 1 / sqrt(var + eps), shift = -mean * scale   (prepare)
@@ -37,6 +38,16 @@ __global__ __launch_bounds__(256) void aligner_bn_prep_kernel(const float* __res
 int launch_aligner_bn_prep(const float* mean, const float* var, int C, float eps, float* scale, float* shift,
                            hipStream_t st) {
   hipLaunchKernelGGL(aligner_bn_prep_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, mean, var, C, eps, scale, shift);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+__global__ __launch_bounds__(256) void fill_f32_kernel(float* __restrict__ x, int n, float v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+int launch_fill_f32(float* x, int n, float v, hipStream_t st) {
+  hipLaunchKernelGGL(fill_f32_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, x, n, v);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

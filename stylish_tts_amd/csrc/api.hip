@@ -636,6 +636,10 @@ struct Builder {
       a.bn_scale[i] = m->ab.take<float>(C);
       a.bn_shift[i] = m->ab.take<float>(C);
     }
+    if (m->kind == "text_aligner_train") {  // BatchNorm1d(affine=False) for kernels that take a weight and a bias
+      a.bn_one = m->ab.take<float>(a.hidden);
+      a.bn_zero = m->ab.take<float>(a.hidden);
+    }
     for (int i = 0; i < 5; ++i) {
       const std::string p = "encoder.layers.3.ffn." + std::to_string(3 * i);
       a.ffn[i] = conv(p);
@@ -670,7 +674,7 @@ struct Builder {
       duration_predictor();
     } else if (m->kind == "pitch_energy_predictor") {
       pitch_energy_predictor();
-    } else if (m->kind == "text_aligner") {
+    } else if (m->kind == "text_aligner" || m->kind == "text_aligner_train") {
       text_aligner();
     }
   }
@@ -1576,7 +1580,7 @@ int sty_model_create(const char* kind, sty_model** out) {
   }
   std::string k(kind);
   if (k != "speech_predictor" && k != "vocoder" && k != "mel_style_encoder" && k != "duration_predictor" &&
-      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner") {
+      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner" && k != "text_aligner_train") {
     set_error("unknown model kind '%s'", kind);
     return STY_EINVAL;
   }
@@ -1714,6 +1718,10 @@ int sty_model_set_train_opts(sty_model* m, const sty_train_opts* o) {
     return STY_EINVAL;
   }
   if (o->compute_bf16 && refuse_aligner(m, "sty_model_set_train_opts(compute_bf16)")) return STY_EINVAL;
+  if (o->compute_bf16 && m->kind == "text_aligner_train") {  // its sibling's reason: alignment decisions are arg-max decisions
+    set_error("sty_model_set_train_opts(compute_bf16): model kind 'text_aligner_train' runs fp32 operands");
+    return STY_EINVAL;
+  }
   m->topts = *o;
   return STY_OK;
 }
@@ -2164,10 +2172,15 @@ int sty_model_prepare(sty_model* m, void* stream) {
     int r = launch_prep_fnv(d.f0_g, d.f0_v, d.f0_b, d.n_g, d.n_v, d.n_b, d.v_g, d.v_v, d.v_b, d.fnv_w, st);
     if (r != STY_OK) return r;
   }
-  if (m->kind == "text_aligner") {  // BatchNorm1d(affine=False) on running statistics -> one scale / shift pair per layer
+  if (m->kind == "text_aligner" || m->kind == "text_aligner_train") {
+    // BatchNorm1d(affine=False) on running statistics -> one scale / shift pair per layer
     const AlignerPlan& a = m->ali;
     for (int i = 0; i < 3; ++i) {
       int r = launch_aligner_bn_prep(a.rm[i], a.rv[i], a.hidden, 1e-5f, a.bn_scale[i], a.bn_shift[i], st);
+      if (r != STY_OK) return r;
+    }
+    if (a.bn_one) {  // (bn_zero is the arena's zero fill)
+      int r = launch_fill_f32(a.bn_one, a.hidden, 1.0f, st);
       if (r != STY_OK) return r;
     }
   }
@@ -2302,7 +2315,7 @@ static int aligner_run(sty_model* m, int B, int T, const float* mel, const int64
   return r.finish(need, ws, ws_bytes);
 }
 int sty_aligner_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "text_aligner");
+  int rc = model_ready(m, "text_aligner", "text_aligner_train");
   if (rc) return rc;
   if (!bytes || B <= 0 || T <= 0) {
     set_error("sty_aligner_workspace_bytes: bad argument");
@@ -2312,7 +2325,7 @@ int sty_aligner_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes)
 }
 int sty_aligner_fwd(sty_model* m, int B, int T, const float* mel, const int64_t* mel_lengths, float* log_probs,
                     void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "text_aligner");
+  int rc = model_ready(m, "text_aligner", "text_aligner_train");
   if (rc) return rc;
   if (!mel || !mel_lengths || !log_probs || !workspace || B <= 0 || T <= 0) {
     set_error("sty_aligner_fwd: bad argument");
@@ -2324,6 +2337,46 @@ int sty_aligner_fwd(sty_model* m, int B, int T, const float* mel, const int64_t*
   }
   if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
   return aligner_run(m, B, T, mel, mel_lengths, log_probs, workspace, ws_bytes, stream, nullptr);
+}
+// ---- text aligner in the training graph (train_alignment, stage_type.py:268-341): forward, then sty_aligner_bwd ----
+int sty_aligner_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {
+  int rc = train_ready(m, STY_EINVAL, "text_aligner_train");
+  if (rc) return rc;
+  if (!bytes || B <= 0 || T <= 0) {
+    set_error("sty_aligner_train_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  return trainer_aligner_forward(m->trainer, B, T, nullptr, nullptr, 0.1f, 0u, nullptr, nullptr, 0, nullptr, bytes);
+}
+int sty_aligner_fwd_train(sty_model* m, int B, int T, const float* mel, const int64_t* mel_lengths, float drop_p,
+                          unsigned drop_seed, float* log_probs, void* workspace, size_t ws_bytes, void* stream) {
+  int rc = train_ready(m, STY_ESTATE, "text_aligner_train");
+  if (rc) return rc;
+  if (!mel || !mel_lengths || !log_probs || !workspace || B <= 0 || T <= 0 || !(drop_p >= 0.f && drop_p < 1.f) ||
+      (size_t)B * T < 2) {
+    set_error("sty_aligner_fwd_train: bad argument (no null buffer, 0 <= drop_p < 1, at least two positions for the "
+              "batch statistics)");
+    return STY_EINVAL;
+  }
+  if (m->topts.compute_bf16) {
+    set_error("sty_aligner_fwd_train: compute_bf16 is refused for the text aligner");
+    return STY_EINVAL;
+  }
+  if ((rc = sty_model_prepare(m, stream))) return rc;
+  m->prepared = false;
+  return trainer_aligner_forward(m->trainer, B, T, mel, mel_lengths, drop_p, drop_seed, log_probs, workspace, ws_bytes,
+                                 S(stream), nullptr);
+}
+int sty_aligner_bwd(sty_model* m, const float* d_logits, void* stream) {
+  int rc = model_ready(m, "text_aligner_train");
+  if (rc) return rc;
+  if (!m->trainer || !d_logits) {
+    set_error("sty_aligner_bwd: no recorded forward or null gradient");
+    return STY_ESTATE;
+  }
+  rc = trainer_aligner_backward(m->trainer, d_logits, S(stream));
+  if (rc) return rc;
+  return finish_bwd(m, S(stream));
 }
 static int pitch_energy_run(sty_model* m, int B, int L, int T, const int64_t* texts, const int64_t* lengths,
                             const float* alignment, const float* style, float* f0, float* energy, void* ws,

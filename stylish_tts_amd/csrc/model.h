@@ -26,6 +26,9 @@ int launch_dur_post_bwd(const float* d, const float* mask, const float* go, int 
 int trainer_duration_forward(struct Trainer* t, int B, int L, const int64_t* texts, const int64_t* lengths, const float* style,
                              float* out, void* ws, size_t ws_bytes, hipStream_t st, size_t* need);
 int trainer_duration_backward(struct Trainer* t, const float* d_out, float* d_style, hipStream_t st);
+int trainer_aligner_forward(struct Trainer* t, int B, int T, const float* mel, const int64_t* lengths, float drop_p,
+                            unsigned drop_seed, float* log_probs, void* ws, size_t ws_bytes, hipStream_t st, size_t* need);
+int trainer_aligner_backward(struct Trainer* t, const float* d_logits, hipStream_t st);
 int launch_scale_copy(const float* x, float a, size_t n, float* y, hipStream_t st);
 int launch_mask_mul(float* x, const float* mask, int B, int C, int T, hipStream_t st);
 int launch_wn_dw(const float* g, const float* v, int C, int K, float* w, hipStream_t st);
@@ -199,12 +202,14 @@ struct AlignerPlan {
   PackedConv tdnn[3], ffn[5], out;
   const float *rm[3] = {nullptr, nullptr, nullptr}, *rv[3] = {nullptr, nullptr, nullptr};
   float *bn_scale[3] = {nullptr, nullptr, nullptr}, *bn_shift[3] = {nullptr, nullptr, nullptr};  // prepared: 1 / sqrt(var + eps), -mean * scale
+  float *bn_one = nullptr, *bn_zero = nullptr;  // kind text_aligner_train: the weight / bias of affine=False for the BatchNorm kernels
   int hidden = 640, n_mels = 80, classes = 179;
 };
 // align.hip
 int launch_aligner_bn_prep(const float* mean, const float* var, int C, float eps, float* scale, float* shift, hipStream_t st);
 int launch_aligner_bn(float* x, int B, int C, int T, const float* scale, const float* shift, hipStream_t st);
 int launch_log_softmax_rows(const float* x, int B, int V, int T, float* out, hipStream_t st);
+int launch_fill_f32(float* x, int n, float v, hipStream_t st);
 
 struct Trainer;
 struct StyleResBlk {  // mel_style_encoder.py:69-118

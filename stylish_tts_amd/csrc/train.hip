@@ -89,6 +89,7 @@ struct Trainer {
     side_need = 0;
     wg_sum = 0;
     drop_site = 0;
+    drop_seed_arg = nullptr;
   }
   // the sizing pass (the entry has run its backward dry by now) reports the peak and drops the tape; the live pass reports
   // an overflow of the caller's workspace
@@ -732,11 +733,13 @@ struct Trainer {
   // nn.Dropout(p) with the counter-based hash mask (sty_hash_u), optionally fused with a residual add:
   // y = drop(x) (+ residual).  Sites are numbered in execution order; the backward recomputes the mask.
   unsigned drop_site = 0;
+  const unsigned* drop_seed_arg = nullptr;  // the seed is an argument of the entry point (the aligner), not a train option
+  unsigned drop_seed_val = 0;
   bool dropout_on() const { return m->topts.dropout_seed != 0; }
   float* dropout(const float* x, float p, int C, int Tt, const float* residual, size_t group = 1) {
     const size_t n = (size_t)B * C * Tt;
     float* y = take<float>(n);
-    const unsigned seed = m->topts.dropout_seed, site = drop_site++;
+    const unsigned seed = drop_seed_arg ? *drop_seed_arg : m->topts.dropout_seed, site = drop_site++;
     if (live()) chk(launch_dropout(x, residual, n, p, seed, site, y, 0, st, group));
     tape.push_back([=]() {
       float* gY = G(y, n);
@@ -1878,6 +1881,97 @@ struct Trainer {
     run_tape([&]() { seed(du_out, d_out, n); }, /*flush_up=*/false, /*fc=*/true, d_style);
   }
 
+  // ---- TextAligner under module.train() (text_aligner.py:209-274; train_alignment, stage_type.py:268-341) ----
+  // y = relu(conv(x)) with the ReLU in the conv's output stage, as the inference plan runs it.  Only y is kept: y > 0
+  // exactly where the pre-activation is, so the gate of the backward reads y, and the pre-activation's gradient is keyed
+  // by an address inside y that nothing else uses as a key.
+  void conv_relu(const ConvArgs& a0) {
+    ConvArgs a = a0;
+    a.act = ACT_RELU;
+    conv(a);
+    tape.pop_back();  // conv()'s entry knows nothing of the output stage's activation: record the two steps instead
+    ConvArgs f = a;
+    f.bf16 = m->topts.compute_bf16;
+    f.act = ACT_NONE;
+    const float* y = a.y;
+    const float* z = a.y + 1;
+    f.y = const_cast<float*>(z);
+    const int C = a.w.Cout, Tt = a.T;
+    tape.push_back([this, f]() { conv_bwd(f); });
+    tape.push_back([=]() {
+      const size_t n = (size_t)B * C * Tt;
+      float* gY = G(y, n);
+      int acc = 1;
+      float* gZ = Gw(z, n, acc);
+      if (live()) chk(launch_act_bwd(ACT_RELU, y, gY, nullptr, B, C, Tt, gZ, acc, nullptr, st));
+    });
+  }
+  // BatchNorm1d(affine=False) on batch statistics over all B * T positions (frames beyond a row's length included, as the
+  // reference has them); the bound running buffers are updated in place
+  float* bn_train_plain(const float* x, int C, int Tt, const float* rm, const float* rv, const float* one, const float* zero) {
+    float* y = take<float>((size_t)B * C * Tt);
+    float* mean = take<float>(C);
+    float* rstd = take<float>(C);
+    double* part = take<double>((size_t)B * C * row_stats_nseg(Tt) * 2);
+    if (live())
+      chk(launch_bn_train_fwd(x, one, zero, const_cast<float*>(rm), const_cast<float*>(rv), 1e-5f, m->topts.bn_momentum, B, C,
+                              Tt, y, mean, rstd, part, st));
+    tape.push_back([=]() {
+      float* gY = G(y, (size_t)B * C * Tt);
+      int acc = 1;
+      float* gX = Gw(x, (size_t)B * C * Tt, acc);
+      const size_t mark = ws.off;
+      float* sums = take<float>(2 * C);
+      if (live()) chk(launch_bn_train_bwd(x, gY, one, mean, rstd, B, C, Tt, gX, acc, nullptr, nullptr, sums, st));
+      ws.off = mark;
+    });
+    return y;
+  }
+  float* al_logits = nullptr;
+  bool al_pending = false;  // a forward whose backward has not run yet
+  void aligner(const float* mel, const int64_t* lengths, int Tt, float drop_p, unsigned drop_seed, float* log_probs) {
+    const AlignerPlan& p = m->ali;
+    const int H = p.hidden, V = p.classes;
+    const size_t n = (size_t)B * H * Tt;
+    begin(nullptr);
+    drop_seed_val = drop_seed;
+    drop_seed_arg = &drop_seed_val;
+    const bool drop = drop_p > 0.f;
+    float* mask = take<float>((size_t)B * Tt);
+    if (live()) chk(launch_length_mask(lengths, B, Tt, mask, st));
+    nograd.insert(mel);  // layer 0: weight and bias gradient only
+    const float* x = mel;
+    for (int i = 0; i < 3; ++i) {
+      float* y = take<float>(n);
+      ConvArgs ca = base(p.tdnn[i], x, Tt, y);
+      ca.pro = PRO_MASK;  // the mask in front of the conv is also the mask of its input gradient (conv_bwd)
+      ca.mask = mask;
+      conv_relu(ca);
+      x = bn_train_plain(y, H, Tt, p.rm[i], p.rv[i], p.bn_one, p.bn_zero);
+      if (drop) x = dropout(x, drop_p, H, Tt, nullptr);  // sites 0-2
+    }
+    // Ffn: five Linear + ReLU + Dropout, the skip around all five.  The skip's add is the dropout kernel's residual
+    // operand (with drop_p = 0 the kernel keeps every element and divides by 1: a plain add)
+    const float* skip = x;
+    for (int i = 0; i < 5; ++i) {
+      float* y = take<float>(n);
+      conv_relu(base(p.ffn[i], x, Tt, y));
+      x = y;
+      if (drop || i == 4) {
+        drop_site = 3 + i;
+        x = dropout(y, drop ? drop_p : 0.f, H, Tt, i == 4 ? skip : nullptr);  // sites 3-7
+      }
+    }
+    float* logits = take<float>((size_t)B * V * Tt);
+    conv(base(p.out, x, Tt, logits));
+    if (live()) chk(launch_log_softmax_rows(logits, B, V, Tt, log_probs, st));
+    al_logits = logits;
+  }
+  void aligner_backward(const float* d_logits) {
+    const size_t n = (size_t)B * m->ali.classes * T;
+    run_tape([&]() { seed(al_logits, d_logits, n); }, /*flush_up=*/false, /*fc=*/false, nullptr);
+  }
+
   // text_encoding @ alignment (speech_predictor.py:60)
   float* expand(const float* enc, const float* ali, int C, int L, int Tt) {
     float* asr = take<float>((size_t)B * C * Tt);
@@ -2658,6 +2752,27 @@ int trainer_duration_forward(Trainer* t, int B, int L, const int64_t* texts, con
 int trainer_duration_backward(Trainer* t, const float* d_out, float* d_style, hipStream_t st) {
   t->st = st;
   t->duration_backward(d_out, d_style);
+  return t->close_backward();
+}
+
+int trainer_aligner_forward(Trainer* t, int B, int T, const float* mel, const int64_t* lengths, float drop_p,
+                            unsigned drop_seed, float* log_probs, void* ws, size_t ws_bytes, hipStream_t st, size_t* need) {
+  t->open(B, T, ws, ws_bytes, st, need != nullptr);
+  t->aligner(need ? &Trainer::kDryMel : mel, lengths, T, drop_p, drop_seed, log_probs);
+  if (need && t->rc == STY_OK) t->aligner_backward(nullptr);
+  const int rc = t->close_forward(need, ws_bytes, Trainer::kSlackStyle, "training");
+  if (!need) t->al_pending = rc == STY_OK;
+  return rc;
+}
+
+int trainer_aligner_backward(Trainer* t, const float* d_logits, hipStream_t st) {
+  if (!t->al_pending) {
+    set_error("sty_aligner_bwd: no forward is waiting for its backward (one backward per sty_aligner_fwd_train)");
+    return STY_ESTATE;
+  }
+  t->al_pending = false;
+  t->st = st;
+  t->aligner_backward(d_logits);
   return t->close_backward();
 }
 

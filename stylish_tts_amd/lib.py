@@ -167,6 +167,12 @@ SYMBOLS = {
     "sty_aligner_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_forced_align_workspace_bytes": (C.c_int, [_I, _I, _I, _SZP]),
     "sty_forced_align": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_aligner_train_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
+    "sty_aligner_fwd_train": (C.c_int, [_P, _I, _I, _P, _P, C.c_float, C.c_uint, _P, _P, C.c_size_t, _P]),
+    "sty_aligner_bwd": (C.c_int, [_P, _P, _P]),
+    "sty_ctc_loss_workspace_bytes": (C.c_int, [_I, _I, _I, _I, _SZP]),
+    "sty_ctc_loss_fwd_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P, _I, C.c_float, _P, _P, _P, _P, _P,
+                                       C.c_size_t, _P]),
     "sty_prof_enable": (C.c_int, [_I]),
     "sty_prof_only": (C.c_int, [C.c_char_p]),
     "sty_set_single_stream": (C.c_int, [_I]),

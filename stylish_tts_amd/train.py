@@ -10,8 +10,8 @@ command's arguments in the reference command's order.  What is joined here exist
 The reference's other two commands on the same files: `convert` is below (--convert), `voicepack` is
 stylish_tts_amd/voicepack.py (its consumer, `speak`, is stylish_tts_amd/speak.py); both take the last stage's checkpoint.
 
-What the reference's loop does and this one does NOT (out of scope): the alignment stage (its model is
-not on this path), validation audio / tensorboard, the WavLM loss term (third-party weights), the batch-size PROBE
+What the reference's loop does and this one does NOT (out of scope): the alignment stage (its own command, as in
+the reference: train_align.py), validation audio / tensorboard, the WavLM loss term (third-party weights), the batch-size PROBE
 (train/batch_manager.py probe_loop: an out-of-memory search for 24-80 GB cards) -- with 288 GB of HBM every length bin runs at
 `training_plan.<stage>.probe_batch_max` and that table is written to `<stage>_batch_sizes.json` exactly where the probe
 would have left it, so a table the reference probed is used as it is when the file is already there.
