@@ -320,6 +320,10 @@ int sty_speech_bwd_pe(sty_model *m, const float *d_audio, float *d_style, float 
  * for exactly that point, so that the style encoder's backward can start on `stream` while the call's own stream still
  * works through the text encoder (AcousticTrainer does this).                                                    */
 int sty_speech_d_style_ready(sty_model *m, void *stream);
+/* Where the harmonic-prior branch of the last sty_speech_fwd_train ran (and its backward runs): io.style_stream when the
+ * branch was issued beside the trunk AND its tape entries are marked for the backward to issue there too, NULL when it is
+ * issued in place on the call's own stream (no style stream given, sty_set_single_stream(1)).  For tests and timelines. */
+int sty_speech_branch_stream(sty_model *m, void **stream);
 /* Same for MelStyleEncoder.forward: gradients of every parameter (through the eval-mode spectral norm
  * W/sigma(W) with fixed u, v: torch.nn.utils.spectral_norm, mel_style_encoder.py:67-152) from d loss / d style. */
 int sty_style_train_workspace_bytes(sty_model *m, int B, int T, size_t *bytes);
@@ -382,11 +386,17 @@ int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float 
                    float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
 /* Gradients of the same conv on the kernels the training graph uses: dw [Cout,Cin,K] and dbias [Cout] (or NULL) from
  * (x, gy [B,Cout,T]) on the weight-gradient kernels (wgrad.hip), dx [B,Cin,T] (or NULL) on the implicit-GEMM kernel
- * with the flipped weights.  compute_bf16 as in sty_train_opts.                                                   */
+ * with the flipped weights.  compute_bf16 as in sty_train_opts; 3: bf16 mode with x a bf16 tensor [B,Cin,T] (two-byte
+ * storage; dw / dbias only, dx NULL, T even), as the many-tap 32-channel weight gradient reads the 75T-rate activations.
+ * sty_conv1d_bwd_workspace_bytes takes no mode: its figure covers every compute_bf16 value, 3 included.                */
 int sty_conv1d_bwd_workspace_bytes(int B, int Cin, int Cout, int K, int T, size_t *bytes);
 int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float *x, const float *w, const float *gy,
                    float *dw, float *dbias, float *dx, void *workspace, size_t ws_bytes, int compute_bf16,
                    void *stream);
+/* The second stage of the two-stage reductions (bias gradient of a dense conv, weight / bias gradient of a depthwise conv)
+ * alone, for unit tests: fixed-order float64 sums of nblk partials per output.  dw_form == 0: part [C][nblk] -> db[c] +=;
+ * dw_form != 0: part [C][nblk][K+1] -> dw[c][k] += (k < K), db[c] += (k == K).                                      */
+int sty_partial_sum(int dw_form, const float *part, int C, int K, int nblk, float *dw, float *db, void *stream);
 
 /* ---- optimizer: torch.optim.AdamW (train/optimizers.py:110-118) over one flat fp32 bucket ------------------
  * p, g, m, v: n floats each, 16-byte aligned, identically laid out; step = 1, 2, ... (bias correction).

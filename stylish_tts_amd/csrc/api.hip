@@ -1914,6 +1914,16 @@ int sty_speech_d_style_ready(sty_model* m, void* stream) {
   }
   return trainer_wait_d_style(m->trainer, S(stream));
 }
+int sty_speech_branch_stream(sty_model* m, void** stream) {
+  int rc = model_ready(m, "speech_predictor");
+  if (rc) return rc;
+  if (!m->trainer || !stream) {
+    set_error("sty_speech_branch_stream: no training forward has run, or stream == NULL");
+    return STY_ESTATE;
+  }
+  *stream = trainer_branch_stream(m->trainer);
+  return STY_OK;
+}
 int sty_vocoder_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {
   int rc = train_ready(m, STY_EINVAL, "speech_predictor", "vocoder");
   if (rc) return rc;
@@ -3001,6 +3011,13 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   a.dil = dil;
   a.pad = (K - 1) * dil / 2;
   a.bf16 = compute_bf16 != 0;
+  if (compute_bf16 == 3) {  // x is a bf16 TENSOR (two-byte storage, ConvArgs::xh): the weight gradient alone has a form for it here
+    if (dx || T % 2) {
+      set_error("sty_conv1d_bwd: a two-byte x (compute_bf16 = 3) is for dw / dbias only (dx == NULL), T even");
+      return STY_EINVAL;
+    }
+    a.xh = 1;
+  }
   if (compute_bf16 == 2) {  // bf16 operand twins of x and gy (ConvArgs::x16 / g16), made here by the cast pass
     __bf16* x16 = reinterpret_cast<__bf16*>(align_up(reinterpret_cast<size_t>(partial + wgrad_partial_floats(pc, B, T)), 256));
     __bf16* g16 = x16 + (size_t)B * Cin * T;
@@ -3013,7 +3030,7 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   rc = launch_conv1d_wgrad(a, gy, nullptr, 1.0f, gwp, partial, dbias ? gbp : nullptr, &bias_done, st);
   if (rc) return rc;
   if (dbias && !bias_done) {
-    set_error("sty_conv1d_bwd: bias gradient of K > 12 is a separate pass (launch_bias_grad), not wired here");
+    set_error("sty_conv1d_bwd: this conv's bias gradient is a separate pass (launch_bias_grad), not wired here");
     return STY_EINVAL;
   }
   STY_HIP(hipMemsetAsync(dw, 0, (size_t)Cout * Cin * K * sizeof(float), st));
@@ -3041,6 +3058,13 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
     rc = launch_conv1d(d, st);
   }
   return rc;
+}
+int sty_partial_sum(int dw_form, const float* part, int C, int K, int nblk, float* dw, float* db, void* stream) {
+  if (!part || !db || C <= 0 || nblk <= 0 || (dw_form && (!dw || K <= 0))) {
+    set_error("sty_partial_sum: bad argument");
+    return STY_EINVAL;
+  }
+  return launch_partial_sum(dw_form, part, C, K, nblk, dw, db, S(stream));
 }
 int sty_mel_workspace_bytes(int B, int N, int n_fft, int hop, size_t* bytes) {
   if (!bytes || B <= 0 || N <= n_fft / 2 || n_fft <= 0 || hop <= 0) {

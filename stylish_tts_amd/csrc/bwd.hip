@@ -1220,13 +1220,19 @@ __global__ __launch_bounds__(256) void dwconv_bwd_w_part_kernel(const void* __re
     out[k == MAXK ? K : k] = (float)(redk[0][k] + redk[1][k] + redk[2][k] + redk[3][k]);
   }
 }
-__global__ void dwconv_bwd_w_sum_kernel(const float* __restrict__ part, int C, int K, int nblk, float* __restrict__ dw,
-                                        float* __restrict__ db) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * (K + 1)) return;
+// one wave per output element (c, k): lanes stride over the nblk partials, fp64 shuffle reduction -- a fixed order, so two runs
+// give the same bits.  (One thread per output walked the partials alone: 320 dependent loads at the 75T rate, 53-69 us a launch.)
+constexpr int SUM_WAVES = 4;  // waves (= output elements) per workgroup of the two sum kernels
+__global__ __launch_bounds__(64 * SUM_WAVES) void dwconv_bwd_w_sum_kernel(const float* __restrict__ part, int C, int K, int nblk,
+                                                                          float* __restrict__ dw, float* __restrict__ db) {
+  const int i = blockIdx.x * SUM_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= C * (K + 1)) return;  // (whole waves leave: the shuffles below see all 64 lanes)
   const int c = i / (K + 1), k = i % (K + 1);
+  const float* p = part + (size_t)c * nblk * (K + 1) + k;
   double s = 0.0;
-  for (int j = 0; j < nblk; ++j) s += part[((size_t)c * nblk + j) * (K + 1) + k];
+  for (int j = lane; j < nblk; j += 64) s += p[(size_t)j * (K + 1)];
+  s = wave_sum(s);
+  if (lane) return;
   if (k == K) {
     if (db) db[c] += (float)s;
   } else {
@@ -1270,8 +1276,8 @@ int launch_dwconv_bwd(const float* x, const float* dy, const float* w, int B, in
       set_error("dwconv_bwd: kernel size %d > 31", K);
       return STY_EINVAL;
     }
-    hipLaunchKernelGGL(dwconv_bwd_w_sum_kernel, dim3(cdiv(C * (K + 1), 64)), dim3(64), 0, st, scratch, C, K, nseg * B,
-                       dw, db);
+    hipLaunchKernelGGL(dwconv_bwd_w_sum_kernel, dim3(cdiv(C * (K + 1), SUM_WAVES)), dim3(64 * SUM_WAVES), 0, st, scratch, C, K,
+                       nseg * B, dw, db);
   }
   STY_LAUNCH_CHECK();
   return STY_OK;
@@ -1477,20 +1483,34 @@ __global__ __launch_bounds__(256) void bias_grad_part_kernel(const float* __rest
   block_sum<1>(acc, red);
   if (threadIdx.x == 0) part[(size_t)co * gridDim.x + blockIdx.x] = (float)acc[0];
 }
-__global__ void bias_grad_sum_kernel(const float* __restrict__ part, int C, int nblk, float scale,
-                                     float* __restrict__ db) {
-  const int co = blockIdx.x * blockDim.x + threadIdx.x;
+// (one wave per channel, as dwconv_bwd_w_sum_kernel)
+__global__ __launch_bounds__(64 * SUM_WAVES) void bias_grad_sum_kernel(const float* __restrict__ part, int C, int nblk, float scale,
+                                                                       float* __restrict__ db) {
+  const int co = blockIdx.x * SUM_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (co >= C) return;
+  const float* p = part + (size_t)co * nblk;
   double s = 0.0;
-  for (int j = 0; j < nblk; ++j) s += part[(size_t)co * nblk + j];
-  db[co] += (float)s * scale;
+  for (int j = lane; j < nblk; j += 64) s += p[j];
+  s = wave_sum(s);
+  if (lane == 0) db[co] += (float)s * scale;
 }
 size_t bias_grad_scratch_floats(int B, int C, int T) { return (size_t)C * B * cdiv(T, DW_SEG); }
 int launch_bias_grad(const float* g, const float* mask, int B, int C, int T, int shuffle, float scale, float* db,
                      float* scratch, hipStream_t st) {
   const int nseg = cdiv(T, DW_SEG);
   hipLaunchKernelGGL(bias_grad_part_kernel, dim3(nseg * B, C), dim3(256), 0, st, g, mask, C, T, shuffle, nseg, scratch);
-  hipLaunchKernelGGL(bias_grad_sum_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, scratch, C, nseg * B, scale, db);
+  hipLaunchKernelGGL(bias_grad_sum_kernel, dim3(cdiv(C, SUM_WAVES)), dim3(64 * SUM_WAVES), 0, st, scratch, C, nseg * B, scale, db);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// the two sums alone, on partials the caller supplies (unit entry point sty_partial_sum)
+int launch_partial_sum(int dw_form, const float* part, int C, int K, int nblk, float* dw, float* db, hipStream_t st) {
+  if (dw_form)
+    hipLaunchKernelGGL(dwconv_bwd_w_sum_kernel, dim3(cdiv(C * (K + 1), SUM_WAVES)), dim3(64 * SUM_WAVES), 0, st, part, C, K, nblk, dw,
+                       db);
+  else
+    hipLaunchKernelGGL(bias_grad_sum_kernel, dim3(cdiv(C, SUM_WAVES)), dim3(64 * SUM_WAVES), 0, st, part, C, nblk, 1.0f, db);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

@@ -330,6 +330,7 @@ int launch_bn_eval_fwd(const float* x, const float* w, const float* b, const flo
 int launch_bn_eval_bwd(const float* x, const float* dy, const float* w, const float* rm, const float* rv, float eps,
                        int B, int C, int T, float* dx, float* dw, float* db, hipStream_t st);
 size_t bias_grad_scratch_floats(int B, int C, int T);
+int launch_partial_sum(int dw_form, const float* part, int C, int K, int nblk, float* dw, float* db, hipStream_t st);
 int launch_bias_grad(const float* g, const float* mask, int B, int C, int T, int shuffle, float scale, float* db,
                      float* scratch, hipStream_t st);
 int launch_style_fc_bwd(const void* descs_dev, int nlayers, int B, int style_dim, const float* style,
@@ -422,6 +423,7 @@ int trainer_block_fwd_bwd(Trainer* t, int kind, const void* blk, int B, int C, i
 void trainer_set_segment_hook(Trainer* t, std::function<void(int)> fn);  // called once segment 0's gradients are final
 bool single_stream_mode();  // sty_set_single_stream: no internal side streams (measurement aid)
 int trainer_wait_d_style(Trainer* t, hipStream_t stream);
+void* trainer_branch_stream(Trainer* t);  // where the prior branch of the last speech forward ran and its backward will (nullptr: in place)
 int trainer_pitch_energy_forward(Trainer* t, int B, int L, int T, const int64_t* texts, const int64_t* lengths,
                                  const float* alignment, const float* style, float* pitch, float* energy, void* ws,
                                  size_t ws_bytes, hipStream_t st, size_t* need);

@@ -316,8 +316,9 @@ struct WgradRoute {
 };
 WgradRoute conv1d_wgrad_route(const ConvArgs& fwd, const float* g, const float* gmask);
 // fuses_bias of every route, for callers that hand the launch to another stream and do not see *bias_done (every kernel for
-// K <= 12 produces the bias gradient; launch_conv1d_wgrad refuses a route that disagrees)
-inline bool wgrad_fuses_bias(const PackedConv& w) { return w.K <= 12; }
+// K <= 12 produces the bias gradient, and so does the many-tap 32 x 32 form for its K <= 24; launch_conv1d_wgrad refuses a
+// route that disagrees)
+bool wgrad_fuses_bias(const ConvArgs& fwd);
 int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask, float scale, float* gwp,
                         float* partial, float* gbias, bool* bias_done, hipStream_t st);
 int launch_wgradb(const ConvArgs& ax, const ConvArgs& ag, int nsplit, float* partial, int want_bias, hipStream_t st);

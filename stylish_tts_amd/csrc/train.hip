@@ -90,6 +90,9 @@ struct Trainer {
     wg_sum = 0;
     drop_site = 0;
     drop_seed_arg = nullptr;
+    branch_st = nullptr;
+    branch_can_beside = false;
+    branch_lo = branch_hi = branch_join = 0;
   }
   // the sizing pass (the entry has run its backward dry by now) reports the peak and drops the tape; the live pass reports
   // an overflow of the caller's workspace
@@ -134,14 +137,57 @@ struct Trainer {
       fc_bwd_done = false;
     }
     seeds();
-    for (auto it = tape.rbegin(); it != tape.rend(); ++it) {
-      (*it)();
-      if (rc != STY_OK) break;
+    // The prior branch's entries [branch_lo, branch_hi) need nothing but G(lap) / G(pp), which the entry
+    // branch_join (phase_input_conv) writes, and nothing on the main stream needs them before fc(style)'s backward: with a
+    // branch stream they are issued there as soon as branch_join has run, in their own reverse order, and skipped at their place,
+    // where the main stream waits for their end instead.  The sizing pass of a graph that can be given a style stream (the speech
+    // graph: branch_can_beside) always walks the tape in that order (the larger need).
+    const bool br = branch_lo < branch_hi && branch_hi <= branch_join && branch_join < tape.size();
+    const bool br_beside = br && (branch_st || (dry && branch_can_beside));
+    hipEvent_t br_end = nullptr;
+    for (size_t i = tape.size(); i-- > 0 && rc == STY_OK;) {
+      if (br_beside && i >= branch_lo && i < branch_hi) {
+        if (i + 1 == branch_hi && br_end) {
+          hipError_t r = hipStreamWaitEvent(st, br_end, 0);
+          if (r != hipSuccess) rc = hip_fail(r, "prior branch backward join");
+          br_end = nullptr;
+        }
+        continue;
+      }
+      tape[i]();
+      if (rc != STY_OK || !br_beside || i != branch_join) continue;
+      hipStream_t const main_st = st;
+      if (branch_st) {
+        stream_after(branch_st, main_st, "prior branch backward fork");
+        st = branch_st;  // side_push, fresh_copy, the zero-fills of G and every launch of the entries follow
+      }
+      keep_temps = true;
+      for (size_t j = branch_hi; j-- > branch_lo && rc == STY_OK;) tape[j]();
+      keep_temps = false;
+      st = main_st;
+      if (branch_st && live()) {  // (also behind an entry that failed: what it did issue is joined below)
+        const int rc0 = rc;
+        rc = STY_OK;
+        br_end = next_event();
+        if (rc == STY_OK && hipEventRecord(br_end, branch_st) != hipSuccess) {
+          br_end = nullptr;
+          rc = hip_fail(hipGetLastError(), "prior branch backward end");
+        }
+        if (rc0 != STY_OK) rc = rc0;
+      }
     }
+    // an error left the loop before the branch's place: the caller's style stream is joined all the same
+    if (br_end) (void)hipStreamWaitEvent(st, br_end, 0);
     while (flush_up && rc == STY_OK && !pend_up.empty()) up_flush(pend_up.begin()->first);
     side_join();
     if (fc && rc == STY_OK) style_fc_backward();
   }
+
+  // the prior branch of the vocoder graph (see Trainer::forward): where its resblocks run this step (nullptr: the main stream;
+  // kept from the forward for the backward), its tape entries [branch_lo, branch_hi) and the entry of the conv it joins the trunk at
+  hipStream_t branch_st = nullptr;
+  bool branch_can_beside = false;  // the graph takes a style stream (its workspace is sized without one)
+  size_t branch_lo = 0, branch_hi = 0, branch_join = 0;
 
   // ---- side stream for the weight gradients ----
   // A weight gradient is a leaf of the backward graph: it reads (x, gY) and nothing reads it before the optimizer.
@@ -377,6 +423,12 @@ struct Trainer {
     peak = ws.off > peak ? ws.off : peak;
     return p;
   }
+  // a tape entry gives its temporaries back -- unless it belongs to the prior branch's backward running beside the main stream
+  // (keep_temps): the main stream's later entries would be handed the addresses while the branch's kernels still use them
+  bool keep_temps = false;
+  void release(size_t mark) {
+    if (!keep_temps) ws.off = mark;
+  }
   // ---- bf16 STORAGE of the 75T-rate activations (bf16 compute mode) ----
   // What autocast stores: conv outputs live in HBM as bf16 (config/config.yml:9-12, train/train_context.py:97-103).  A tensor
   // taken with take_act(n, true) IS two bytes per element -- there is no fp32 copy -- and travels through the graph as an
@@ -518,12 +570,21 @@ struct Trainer {
     const size_t pn = wgrad_partial_floats(a.w, B, a.T);
     side_need = pn > side_need ? pn : side_need;
     wg_need(pn);
+    bias_pass_sizing(a);
     if (live()) chk(launch_conv1d(a, st));
     ConvArgs f = a;
     tape.push_back([this, f]() { conv_bwd(f); });
   }
   // Weight gradient of conv f from its output gradient gY (times gmask), on the side stream where there is one.  The bias gradient
-  // is a by-product of the same pass over gY where the kernel fuses it (every route for K <= 12), a pass of its own otherwise.
+  // is a by-product of the same pass over gY where the kernel fuses it (every route for K <= 12, the many-tap 32 x 32 form for
+  // K <= 24), a pass of its own otherwise -- a leaf like the weight gradient (it reads gY alone), so it goes to the side stream
+  // too, with scratch of its own there: the main stream recycles its temporaries while side-stream launches are pending.
+  void bias_pass_sizing(const ConvArgs& a) {  // forward: room for that pass's partials where conv_wgrad will take it
+    if (!a.w.bias || wgrad_fuses_bias(a)) return;
+    const size_t bn = bias_grad_scratch_floats(B, a.w.Cout, a.T);
+    side_need = bn > side_need ? bn : side_need;
+    wg_need(bn);
+  }
   void conv_wgrad(const ConvArgs& f, float* gY, const float* gmask, int shuffle) {
     const PackedConv& w = f.w;
     const int Tt = f.T;
@@ -536,7 +597,14 @@ struct Trainer {
       float* gwp = PGpacked(w.wp);
       const float osc = f.out_scale;
       side_push(gY, [=](hipStream_t s) { chk(launch_conv1d_wgrad(f, gY, gmask, osc, gwp, sp, gbias, nullptr, s)); });
-      bias_done = wgrad_fuses_bias(w);  // (the launch is not made yet: launch_conv1d_wgrad holds every route to this)
+      bias_done = wgrad_fuses_bias(f);  // (the launch is not made yet: launch_conv1d_wgrad holds every route to this)
+      if (w.bias && !bias_done) {
+        // behind the weight gradient on the same stream: side_partial is free again by then (its reduction is not deferred
+        // when the buffer is shared)
+        float* bs = deferring() ? wg_take(bias_grad_scratch_floats(B, w.Cout, Tt)) : side_partial;
+        side_push(gY, [=](hipStream_t s) { chk(launch_bias_grad(gY, gmask, B, w.Cout, Tt, shuffle, osc, gbias, bs, s)); });
+        bias_done = true;
+      }
     } else {
       const size_t pn = wgrad_partial_floats(w, B, Tt);
       float* partial = deferring() ? wg_take(pn) : take<float>(pn);
@@ -646,7 +714,7 @@ struct Trainer {
         size_t mark;
         ~UGuard() {
           t->half_.erase(U);
-          t->ws.off = mark;
+          t->release(mark);
         }
       } u_guard{this, U, mark};
       ConvArgs d;
@@ -680,7 +748,7 @@ struct Trainer {
           d.out_mask_post = 0;
         }
         if (live()) chk(launch_conv1d(d, st));
-        ws.off = mark;
+        release(mark);
         return;
       }
       if (live()) chk(launch_conv1d(d, st));
@@ -690,7 +758,7 @@ struct Trainer {
           chk(launch_pro_bwd_adain(U, u16, f.x[0], f.xh, B, w.Cin, Tt, f.pa, f.ps, f.palpha, fuse->mean, fuse->rstd, fuse->gbl,
                                    gX[0], is16(gX[0]), accX[0], fuse->dgl, dal, f.bf16 ? 1 : 0, st, gX_src));
         half_.erase(U);  // (a temporary: the address is handed out again as soon as the mark is restored)
-        ws.off = mark;
+        release(mark);
         return;
       }
       if (gX_src) {
@@ -712,7 +780,7 @@ struct Trainer {
         c0 += f.xc[i];
       }
     }
-    ws.off = mark;
+    release(mark);
   }
 
   // pointwise activation y = act(x)
@@ -850,7 +918,7 @@ struct Trainer {
         chk(launch_adain_fold_bwd(da, ds, mean, rstd, gbl, B, C, Tt, dgl, c0, c1, st));
         chk(launch_row_axpb(x, c0, c1, B * C, Tt, gX, st));
       }
-      ws.off = mark;
+      release(mark);
     });
   }
 
@@ -1192,6 +1260,7 @@ struct Trainer {
     const size_t pn = wgrad_partial_floats(a3.w, B, a3.T);
     side_need = pn > side_need ? pn : side_need;
     wg_need(pn);
+    bias_pass_sizing(a3);
     for (int i = 0; i < 3 && live(); ++i) {
       ConvArgs s = cat3_slice(a3, a3.w, i, false);
       s.x[0] = a3.x[i];
@@ -2102,6 +2171,7 @@ struct Trainer {
     const size_t pn = wgrad_partial_floats(w, B, n);
     side_need = pn > side_need ? pn : side_need;
     wg_need(pn);
+    bias_pass_sizing(a);
     if (live()) chk(launch_conv1d(a, st));
     if (a.x16 && bwd_reads_twin_only(a)) g_twin_only.insert(y);
     tape.push_back([this, a]() { conv2d_bwd(a); });
@@ -2501,15 +2571,41 @@ struct Trainer {
     if (!m->fcs.empty()) chk(launch_style_fc(m->fcs_dev, (int)m->fcs.size(), B, m->style_dim, style, gb, st));
   }
 
-  void forward(const sty_vocoder_io& io, bool fresh = true) {
+  // ---- the harmonic-prior branch beside the trunk ----
+  // source -> stft64 -> the two prior convs -> the two prior resblocks reads pitch / voiced / noise and, from the resblocks on,
+  // the AdaIN coefficients; it meets the trunk at phase_input_conv.  In the speech graph with a style stream (and the internal
+  // streams on) its style-independent head is issued on the main stream BEFORE the wait for `style` -- it fills that wait --
+  // and the two resblocks go to the caller's style stream, idle from the end of the style encoder's forward to d_style, behind
+  // an event that orders them after fc(style) and the prior convs; the main stream waits for them in front of
+  // phase_input_conv.  No stream of the library's own: a fifth concurrently active stream costs the step more than any overlap
+  // returns.  Otherwise (no style stream, single-stream mode, the vocoder alone) everything is issued in place on the main stream.
+  // (branch_st, branch_lo / branch_hi / branch_join: declared with the step state above)
+  struct PriorHead {
+    bool done = false;
+    float* out[2] = {nullptr, nullptr};  // the prior convs' outputs (+ their statistics partials)
+    const double* part[2] = {nullptr, nullptr};
+    float *lap = nullptr, *pp = nullptr;  // the resblocks' outputs
+    hipEvent_t end = nullptr;             // recorded behind them on branch_st
+  } prior_head_;
+  void branch_begin(hipStream_t style_stream) {  // per step, before anything of the branch is issued
+    prior_head_ = PriorHead();
+    branch_lo = branch_hi = branch_join = 0;
+    branch_st = style_stream && style_stream != st && !single_stream_mode() ? style_stream : nullptr;
+  }
+  // `to` waits for what `from` holds so far
+  void stream_after(hipStream_t to, hipStream_t from, const char* what) {
+    if (!live() || rc != STY_OK) return;
+    hipEvent_t e = next_event();  // (the pool is reset at the start of the backward; the forward's events come behind its last)
+    if (rc != STY_OK) return;
+    hipError_t r = hipEventRecord(e, from);
+    if (r == hipSuccess) r = hipStreamWaitEvent(to, e, 0);
+    if (r != hipSuccess) rc = hip_fail(r, what);
+  }
+  // harmonic source branch up to the prior convs: no gradient at its input (torch.no_grad in the reference, generator.py:711-729)
+  void prior_head(const sty_vocoder_io& io) {
     const VocoderPlan& v = m->voc;
-    const int Tt = io.T, Tu = 75 * Tt, N = 300 * Tt, C = v.hidden;
-    if (fresh) {
-      begin(io.style);
-      style_fc(nullptr);
-    }
-    mel_in = io.mel;
-    // harmonic source branch: no gradient (torch.no_grad in the reference, generator.py:711-729)
+    const int Tt = io.T, Tu = 75 * Tt, N = 300 * Tt;
+    branch_lo = tape.size();
     float* prior = take<float>((size_t)B * N);
     float* srcws = take<float>(source_workspace_floats(B, Tt));
     float* hs = take<float>((size_t)B * 32 * Tu);
@@ -2524,24 +2620,63 @@ struct Trainer {
     nograd.insert(hp);
     // the prior convs' outputs are the resblocks' inputs: bf16 tensors when the blocks run the two-byte path (the persistent
     // kernel then also leaves the instance-norm statistics of what it stored behind: no statistics pass over a bf16 tensor)
-    float* prior_out[2];
-    const double* prior_part[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; ++i) {
       const PackedConv& pc = i ? v.phase_prior_conv : v.amp_prior_conv;
       ConvArgs ca = base(pc, i ? hp : hs, Tu, nullptr);
       ConvArgs probe = ca;
       probe.yh = 1;
       const bool h16 = resblock16(i ? v.phase_prior_block : v.amp_prior_block, Tu) && plan_route(m, probe).two_byte();
-      prior_out[i] = ca.y = take_act((size_t)B * 32 * Tu, h16);
+      prior_head_.out[i] = ca.y = take_act((size_t)B * 32 * Tu, h16);
       if (h16) {
         double* p = take<double>((size_t)B * 32 * conv32p_stat_nseg(Tu) * 2);
         ca.stat_part = p;
-        prior_part[i] = p;
+        prior_head_.part[i] = p;
       }
       conv(ca);
     }
-    float* lap = resblock(v.amp_prior_block, prior_out[0], Tu, prior_part[0]);
-    float* pp = resblock(v.phase_prior_block, prior_out[1], Tu, prior_part[1]);
+    prior_head_.done = true;
+    branch_hi = tape.size();
+  }
+  // the two prior resblocks, on branch_st where there is one: behind fc(style) and the prior convs, both on the main stream by now
+  void prior_blocks(const sty_vocoder_io& io) {
+    const VocoderPlan& v = m->voc;
+    const int Tu = 75 * io.T;
+    hipStream_t const main_st = st;
+    if (branch_st) {
+      stream_after(branch_st, main_st, "prior branch fork");
+      st = branch_st;
+    }
+    const bool contiguous = tape.size() == branch_hi;  // (nothing recorded between the head and the blocks)
+    prior_head_.lap = resblock(v.amp_prior_block, prior_head_.out[0], Tu, prior_head_.part[0]);
+    prior_head_.pp = resblock(v.phase_prior_block, prior_head_.out[1], Tu, prior_head_.part[1]);
+    if (contiguous)
+      branch_hi = tape.size();
+    else
+      branch_lo = branch_hi = 0;  // the backward then runs the entries in place
+    st = main_st;
+    if (branch_st && live() && rc == STY_OK) {
+      prior_head_.end = next_event();
+      if (rc == STY_OK) {
+        hipError_t r = hipEventRecord(prior_head_.end, branch_st);
+        if (r != hipSuccess) rc = hip_fail(r, "prior branch end");
+      }
+    }
+  }
+
+  void forward(const sty_vocoder_io& io, bool fresh = true) {
+    const VocoderPlan& v = m->voc;
+    const int Tt = io.T, Tu = 75 * Tt, C = v.hidden;
+    if (fresh) {
+      begin(io.style);
+      branch_begin(nullptr);
+      style_fc(nullptr);
+    }
+    mel_in = io.mel;
+    if (!prior_head_.done) prior_head(io);
+    if (!prior_head_.lap) prior_blocks(io);
+    float* lap = prior_head_.lap;
+    float* pp = prior_head_.pp;
+    hipEvent_t branch_end = prior_head_.end;
     // stage A
     float* x0 = take<float>((size_t)B * C * Tt);
     conv(base(v.amp_input_conv, io.mel, Tt, x0));
@@ -2571,10 +2706,16 @@ struct Trainer {
     p.x[1] = lap;
     p.x[2] = pp;
     p.xc[0] = p.xc[1] = p.xc[2] = 32;
+    if (branch_end && rc == STY_OK) {  // lap / pp come from the style stream
+      hipError_t r = hipStreamWaitEvent(st, branch_end, 0);
+      if (r != hipSuccess) rc = hip_fail(r, "prior branch join");
+      prior_head_.end = nullptr;  // joined
+    }
     if (cat3_ok(p))
       conv_cat3(p);
     else
       conv(p);
+    branch_join = tape.size() - 1;
     float* ph = layernorm(ph0, 32, Tu, 1e-6f, nullptr, v.phase_norm_w, v.phase_norm_b);
     for (const ConvNeXt& c : v.phase_convnext) ph = convnext(c, ph, Tu);
     float* lnP = layernorm(ph, 32, Tu, 1e-6f, nullptr, v.phase_fln_w, v.phase_fln_b);
@@ -2693,14 +2834,20 @@ int trainer_speech_forward(Trainer* t, const sty_speech_io* io, void* ws, size_t
       t->side_reduce_nowait();
     }
   });
+  t->branch_begin(reinterpret_cast<hipStream_t>(io->style_stream));
+  t->branch_can_beside = true;
+  sty_vocoder_io v = vocoder_io_of(*io);
+  if (t->branch_st) t->prior_head(v);  // needs neither mel nor style: in front of the wait for the style stream
   t->style_fc(reinterpret_cast<hipStream_t>(io->style_stream));
+  if (t->branch_st && t->rc == STY_OK) t->prior_blocks(v);  // beside expand, the decoder and the vocoder's trunk
   float* asr = t->expand(mu, io->alignment, inter, io->L, io->T);
   float* mel = t->decoder(asr, io->pitch, io->energy, io->voiced, io->T);
   if (mel) {
-    sty_vocoder_io v = vocoder_io_of(*io);
     v.mel = mel;
     t->forward(v, false);
   }
+  // an error in front of phase_input_conv: the style stream's share of the forward is joined all the same
+  if (t->prior_head_.end && t->live()) (void)hipStreamWaitEvent(st, t->prior_head_.end, 0);
   if (need) t->backward(nullptr, Trainer::MEL_GRAD_INTERNAL, nullptr, nullptr);
   return t->close_forward(need, ws_bytes, Trainer::kSlack, "training");
 }
@@ -2775,6 +2922,8 @@ int trainer_aligner_backward(Trainer* t, const float* d_logits, hipStream_t st) 
   t->aligner_backward(d_logits);
   return t->close_backward();
 }
+
+void* trainer_branch_stream(Trainer* t) { return t->branch_lo < t->branch_hi ? t->branch_st : nullptr; }
 
 int trainer_wait_d_style(Trainer* t, hipStream_t stream) {
   if (!t->d_style_done) {

@@ -1100,8 +1100,7 @@ WgradRoute conv1d_wgrad_route(const ConvArgs& fwd, const float* g, const float* 
       cap = fwd.B * cdiv(fwd.T / 4, 256);
     } else if (wgradp32_eligible(ax)) {
       r.kernel = WGRAD_P32;
-      cap = wgradp32_chunks(ax);
-      r.fuses_bias = cdiv(w.K, 4) <= 3;
+      cap = wgradp32_chunks(ax);  // (the staging threads sum the G samples they hold: the bias gradient at every K it takes)
     } else {
       r.kernel = WGRAD_TILED;
       r.fuses_bias = cdiv(w.K, 4) <= 3;
@@ -1112,6 +1111,10 @@ WgradRoute conv1d_wgrad_route(const ConvArgs& fwd, const float* g, const float* 
   r.refused = (fwd.xh || fwd.gh) && !(r.kernel == WGRAD_P32 && !fwd.gh);
   r.twins_only = r.kernel == WGRAD_B16 && !r.refused;
   return r;
+}
+// (said without the route: K > 12 is blocked by nothing above, and a flat 2-D conv of that many taps has no kernel that fuses)
+bool wgrad_fuses_bias(const ConvArgs& fwd) {
+  return fwd.w.K <= 12 || (!fwd.flatW && wgradp32_eligible(wgrad_x_args(fwd)));
 }
 
 static int launch_wgrad_k1(const ConvArgs& fwd, const ConvArgs& ax1, const ConvArgs& ag, int nsplit, float* partial, int wb,
@@ -1292,7 +1295,7 @@ int launch_conv1d_wgrad(const ConvArgs& fwd, const float* g, const float* gmask,
     return STY_EINVAL;
   }
   // a caller that hands the launch to the side stream does its bias bookkeeping with wgrad_fuses_bias, without seeing *bias_done
-  if (r.fuses_bias != wgrad_fuses_bias(w)) {
+  if (r.fuses_bias != wgrad_fuses_bias(fwd)) {
     set_error("wgrad: the route's bias fusion (%d) is not wgrad_fuses_bias (K = %d)", (int)r.fuses_bias, w.K);
     return STY_EINVAL;
   }

@@ -103,6 +103,7 @@ SYMBOLS = {
     "sty_speech_prepare_train": (C.c_int, [_P, _P]),
     "sty_speech_bwd_pe": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "sty_speech_d_style_ready": (C.c_int, [_P, _P]),
+    "sty_speech_branch_stream": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "sty_style_train_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
     "sty_style_fwd_train": (C.c_int, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "sty_style_prepare_train": (C.c_int, [_P, _P]),
@@ -118,6 +119,7 @@ SYMBOLS = {
     "sty_conv1d_fwd": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
     "sty_conv1d_bwd_workspace_bytes": (C.c_int, [_I, _I, _I, _I, _I, _SZP]),
     "sty_conv1d_bwd": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
+    "sty_partial_sum": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
     "sty_adamw_step": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                  _I, C.c_float, _P]),
     "sty_adamw_step_scaled": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_double, _P, C.c_float, C.c_float, C.c_float,
