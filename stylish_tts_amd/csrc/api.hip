@@ -154,22 +154,9 @@ struct Builder {
     float* bp = m->ab.take<float>(pc.CoutP);
     pc.wp = wp;
     pc.bias = (bias || bias_override_src) ? bp : nullptr;
-    if (!dry) {
-      PackJob j;
-      j.kind = glu ? PK_CONV_GLU : (wn ? PK_CONV_WN : PK_CONV);
-      j.w = wn ? nullptr : w->p;
-      j.g = g ? g->p : nullptr;
-      j.v = wn ? w->p : nullptr;
-      j.bias = b;
-      j.Cout = pc.Cout;
-      j.Cin = pc.Cin;
-      j.K = pc.K;
-      j.CinP = pc.CinP;
-      j.CoutP = pc.CoutP;
-      j.wp = wp;
-      j.bp = bp;
-      m->jobs.push_back(j);
-    }
+    if (!dry)
+      m->jobs.push_back(PackJob::conv(glu ? PK_CONV_GLU : (wn ? PK_CONV_WN : PK_CONV), pc, wn ? nullptr : w->p,
+                                      g ? g->p : nullptr, wn ? w->p : nullptr, b, wp, bp));
     if (m->train_enabled) {
       if (glu) {  // the training graph runs GLU as a separate op: it needs the plain channel order
         PackedConv pl = pc;
@@ -179,18 +166,7 @@ struct Builder {
         pl.wp = wp2;
         pl.bias = bias ? bp2 : nullptr;
         if (!dry) {
-          PackJob j;
-          j.kind = PK_CONV;
-          j.w = w->p;
-          j.bias = b;
-          j.Cout = pc.Cout;
-          j.Cin = pc.Cin;
-          j.K = pc.K;
-          j.CinP = pc.CinP;
-          j.CoutP = pl.CoutP;
-          j.wp = wp2;
-          j.bp = bp2;
-          m->jobs.push_back(j);
+          m->jobs.push_back(PackJob::conv(PK_CONV, pl, w->p, nullptr, nullptr, b, wp2, bp2));
           m->plain_of[wp] = pl;
         }
         add_dgrad(pl);
@@ -213,14 +189,7 @@ struct Builder {
     d.wp = wd;
     d.bias = nullptr;
     if (!dry) {
-      PackJob j;
-      j.kind = PK_DGRAD;
-      j.w = pc.wp;
-      j.K = pc.K;
-      j.CinP = pc.CinP;
-      j.CoutP = pc.CoutP;
-      j.wp = wd;
-      m->jobs.push_back(j);
+      m->jobs.push_back(PackJob::dgrad(pc, wd));
       m->dgrad[pc.wp] = d;
     }
   }
@@ -277,27 +246,8 @@ struct Builder {
     c.pw2 = pc;
     c.w2a = w2a;
     if (!dry && w2) {
-      PackJob j;
-      j.kind = PK_CONV;
-      j.w = w2;
-      j.bias = nullptr;
-      j.Cout = C;
-      j.Cin = 4 * C;
-      j.K = 1;
-      j.CinP = pc.CinP;
-      j.CoutP = pc.CoutP;
-      j.wp = wp;
-      j.bp = nullptr;
-      m->jobs.push_back(j);
-      PackJob k;
-      k.kind = PK_W2A;
-      k.w = w2;
-      k.bias = b2;
-      k.extra = grn_beta;
-      k.Cout = C;
-      k.wp = w2a;
-      k.bp = bp;
-      m->jobs.push_back(k);
+      m->jobs.push_back(PackJob::conv(PK_CONV, pc, w2, nullptr, nullptr, nullptr, wp, nullptr));
+      m->jobs.push_back(PackJob::w2a(w2, b2, grn_beta, C, w2a, bp));
     }
     if (m->train_enabled) add_dgrad(pc);
     return c;
@@ -473,25 +423,7 @@ struct Builder {
     float* ts2 = m->train_enabled ? m->ab.take<float>(sn_power_iter_scratch_floats(Cout, Cin * KH * KW)) : nullptr;
     pc.wp = wp;
     pc.bias = bias ? bp : nullptr;
-    if (!dry) {
-      PackJob j;
-      j.kind = PK_CONV2D_SN;
-      j.w = w->p;
-      j.g = u;
-      j.v = v;
-      j.bias = b;
-      j.Cout = Cout;
-      j.Cin = Cin;
-      j.K = KW;
-      j.KH = KH;
-      j.CinP = pc.CinP;
-      j.CoutP = pc.CoutP;
-      j.wp = wp;
-      j.bp = bp;
-      j.scratch = ts;
-      j.scratch2 = ts2;
-      m->jobs.push_back(j);
-    }
+    if (!dry) m->jobs.push_back(PackJob::conv2d_sn(pc, Cin, KH, w->p, u, v, b, wp, bp, ts, ts2));
     if (m->train_enabled) {  // input-gradient weights: rows (kh', co), columns ci, taps flipped in both directions
       PackedConv d;
       d.Cin = KH * Cout;
@@ -503,17 +435,7 @@ struct Builder {
       d.wp = wd;
       d.bias = nullptr;
       if (!dry) {
-        PackJob j;
-        j.kind = PK_DGRAD2D;
-        j.w = wp;
-        j.Cout = Cout;
-        j.Cin = Cin;
-        j.K = KW;
-        j.KH = KH;
-        j.CinP = pc.CinP;
-        j.CoutP = pc.CoutP;
-        j.wp = wd;
-        m->jobs.push_back(j);
+        m->jobs.push_back(PackJob::dgrad2d(pc, Cin, KH, wd));
         m->dgrad[wp] = d;
       }
     }
@@ -544,18 +466,7 @@ struct Builder {
         float* ts = m->ab.take<float>(r.Cin);
         float* ts2 = m->train_enabled ? m->ab.take<float>(sn_power_iter_scratch_floats(r.Cin, 9)) : nullptr;
         r.dw_w9 = w9;
-        if (!dry) {
-          PackJob j;
-          j.kind = PK_DW2D_SN;
-          j.w = w;
-          j.g = u;
-          j.v = v;
-          j.Cout = r.Cin;
-          j.wp = w9;
-          j.scratch = ts;
-          j.scratch2 = ts2;
-          m->jobs.push_back(j);
-        }
+        if (!dry) m->jobs.push_back(PackJob::dw2d_sn(r.Cin, w, u, v, w9, ts, ts2));
       }
     }
     sp.head = conv2d_sn("shared.6");
@@ -1600,11 +1511,7 @@ void sty_model_destroy(sty_model* m) {
   if (m->stft_default) (void)hipFree(m->stft_default);
   if (m->garena) (void)hipFree(m->garena);
   if (m->fcs_bwd_dev) (void)hipFree(m->fcs_bwd_dev);
-  for (int i = 0; i < 5; ++i) {
-    if (m->mj_dev[i]) (void)hipFree(m->mj_dev[i]);
-    if (m->mj_blk_dev[i]) (void)hipFree(m->mj_blk_dev[i]);
-  }
-  if (m->mj_blk1_dev) (void)hipFree(m->mj_blk1_dev);
+  m->wt.free();
   if (m->trainer) trainer_destroy(m->trainer);
   delete m;
 }
@@ -1641,7 +1548,7 @@ int sty_model_finalize(sty_model* m) {
   }
   m->requested.clear();
   m->jobs.clear();
-  m->mj_ready = false;
+  m->wt.free();
   m->fcs.clear();
   m->missing.clear();
   m->ab = Bump();
@@ -1738,64 +1645,6 @@ int sty_model_bind_grad(sty_model* m, const char* key, float* grad) {
   return STY_OK;
 }
 
-static int build_multi_tables(sty_model* m);
-// packed gradients -> the caller's parameter gradients (+=)
-// seg: -1 = every parameter; 1 = the pack jobs before seg_job_split (text encoder of a speech predictor);
-//      0 = everything else
-static int unpack_grads(sty_model* m, hipStream_t st, int seg = -1) {
-  auto PG = [&](const float* p) -> float* {
-    auto it = m->pgrad.find(p);
-    return it == m->pgrad.end() ? nullptr : it->second;
-  };
-  auto GA = [&](const float* packed) -> float* {
-    return reinterpret_cast<float*>(m->garena + (reinterpret_cast<const char*>(packed) - m->arena));
-  };
-  if (!m->mj_ready) {
-    int r = build_multi_tables(m);
-    if (r != STY_OK) return r;
-  }
-  {  // every plain / weight-norm conv (weights and biases) of the segment in one launch
-    const int b0 = seg == 0 ? m->seg_blk_split : 0;
-    const int b1 = seg == 1 ? m->seg_blk_split : m->mj_nblk[2];
-    int r = launch_multi(2, m->mj_dev[2], m->mj_blk_dev[2], b1 - b0, st, b0);
-    if (r != STY_OK) return r;
-  }
-  size_t job_index = 0;
-  for (const PackJob& j : m->jobs) {
-    const bool in_seg1 = job_index++ < m->seg_job_split;
-    if ((seg == 0 && in_seg1) || (seg == 1 && !in_seg1)) continue;
-    if (j.kind == PK_CONV || j.kind == PK_CONV_WN) {
-      // batched above
-    } else if (j.kind == PK_CONV2D_SN) {
-      // batched below (table 3)
-    } else if (j.kind == PK_DW2D_SN) {
-      float* dW = PG(j.w);
-      if (dW) {
-        int r = launch_dw2d_sn_unpack(GA(j.wp), j.w, j.g, j.v, j.scratch, j.Cout, dW, st);
-        if (r) return r;
-      }
-    } else if (j.kind == PK_W2A) {
-      // b2eff = b2 + W2 . grn_beta:  db2 += g, dbeta += W2^T g, dW2 += g beta^T   (g = gradient of b2eff)
-      float* db2 = PG(j.bias);
-      float* dbeta = PG(j.extra);
-      float* dW2 = PG(j.w);
-      int r = launch_b2eff_bwd(GA(j.bp), j.w, j.extra, j.Cout, db2, dbeta, dW2, st);
-      if (r) return r;
-    }
-  }
-  if (seg != 1) {  // every spectral-norm conv (weights and biases) in two launches; no model has them in segment 1
-    int r = launch_sn_unpack_multi(m->mj_dev[3], m->mj_blk_dev[3], m->mj_nblk[3], st);
-    if (r != STY_OK) return r;
-  }
-  if (m->kind == "speech_predictor" && m->dec.fnv_w && seg != 1) {
-    const DecoderPlan& d = m->dec;
-    int r = launch_fnv_unpack(GA(d.fnv_w), d.f0_g, d.f0_v, d.n_g, d.n_v, d.v_g, d.v_v, PG(d.f0_g), PG(d.f0_v),
-                              PG(d.f0_b), PG(d.n_g), PG(d.n_v), PG(d.n_b), PG(d.v_g), PG(d.v_v), PG(d.v_b), st);
-    if (r) return r;
-  }
-  return STY_OK;
-}
-
 // ready for a training forward or its sizing call: the model is finalized and of the right kind, training is enabled
 // (not_enabled: the status when it is not) and the trainer exists
 static int train_ready(sty_model* m, int not_enabled, const char* kind_a, const char* kind_b = nullptr) {
@@ -1810,7 +1659,7 @@ static int train_ready(sty_model* m, int not_enabled, const char* kind_a, const 
 }
 // the end of a backward: the packed gradients of a segment (-1: all) go to the caller's buffers, then the gradient hook
 static int finish_bwd(sty_model* m, hipStream_t st, int seg = -1) {
-  int rc = unpack_grads(m, st, seg);
+  int rc = weights_unpack(m, st, seg);
   if (rc) return rc;
   if (m->grad_hook) m->grad_hook(m->grad_hook_user, seg < 0 ? 0 : seg);
   return STY_OK;
@@ -1969,150 +1818,6 @@ const char* sty_model_key(const sty_model* m, int i) {
   return m->requested[i].c_str();
 }
 
-// device tables for the batched pack / input-gradient pack / gradient un-pack launches
-static int build_multi_tables(sty_model* m) {
-  std::vector<MultiJob> jobs[5];
-  std::vector<int> blk[5];
-  std::vector<int> blk1;  // table 4: the W^T u grid of the power iteration (SN_SLICES x ceil(n / 256) blocks per layer)
-  auto PG = [&](const float* p) -> float* {
-    auto it = p ? m->pgrad.find(p) : m->pgrad.end();
-    return it == m->pgrad.end() ? nullptr : it->second;
-  };
-  auto GA = [&](const float* packed) -> float* {
-    return (packed && m->garena) ? reinterpret_cast<float*>(m->garena + (reinterpret_cast<const char*>(packed) - m->arena))
-                                 : nullptr;
-  };
-  auto add = [&](int which, MultiJob j, int nblocks) {
-    j.blk0 = (int)blk[which].size();
-    for (int i = 0; i < nblocks; ++i) blk[which].push_back((int)jobs[which].size());
-    jobs[which].push_back(j);
-  };
-  size_t job_index = 0;
-  m->seg_blk_split = 0;
-  for (const PackJob& j : m->jobs) {
-    if (job_index++ == m->seg_job_split) m->seg_blk_split = (int)blk[2].size();
-    if (j.kind == PK_CONV || j.kind == PK_CONV_WN || j.kind == PK_CONV_GLU) {
-      MultiJob a;
-      a.p0 = j.w;
-      a.p1 = j.g;
-      a.p2 = j.v;
-      a.p3 = j.bias;
-      a.q0 = j.wp;
-      a.q1 = j.bp;
-      a.Cout = j.Cout;
-      a.Cin = j.Cin;
-      a.K = j.K;
-      a.CinP = j.CinP;
-      a.CoutP = j.CoutP;
-      a.glu = j.kind == PK_CONV_GLU;
-      add(0, a, j.Cout);
-      if (m->garena && j.kind != PK_CONV_GLU) {  // GLU-ordered packs are not used by the training graph
-        MultiJob u;
-        u.p0 = GA(j.wp);
-        u.p1 = j.g;
-        u.p2 = j.kind == PK_CONV_WN ? j.v : nullptr;
-        u.p3 = (j.bias && j.bp) ? GA(j.bp) : nullptr;
-        u.q0 = j.kind == PK_CONV ? PG(j.w) : nullptr;
-        u.q1 = j.kind == PK_CONV_WN ? PG(j.g) : nullptr;
-        u.q2 = j.kind == PK_CONV_WN ? PG(j.v) : nullptr;
-        u.q3 = (j.bias && j.bp) ? PG(j.bias) : nullptr;
-        u.Cout = j.Cout;
-        u.Cin = j.Cin;
-        u.K = j.K;
-        u.CinP = j.CinP;
-        u.CoutP = j.CoutP;
-        if (u.q0 || (u.q1 && u.q2) || u.q3) add(2, u, j.Cout);
-      }
-    } else if (j.kind == PK_DGRAD) {
-      MultiJob a;
-      a.p0 = j.w;
-      a.q0 = j.wp;
-      a.K = j.K;
-      a.CinP = j.CinP;
-      a.CoutP = j.CoutP;
-      add(1, a, (int)(((size_t)j.K * j.CinP * j.CoutP + 255) / 256));
-    } else if (j.kind == PK_DGRAD2D) {  // (source: the spectral-norm pack of table 4, launched before table 1)
-      MultiJob a;
-      a.p0 = j.w;
-      a.q0 = j.wp;
-      a.K = j.K;
-      a.KH = j.KH;
-      a.Cin = j.Cin;
-      a.Cout = j.Cout;
-      a.CinP = j.CinP;
-      a.CoutP = j.CoutP;
-      a.glu = 2;
-      a.blk1 = (int)align_up(j.KH * j.Cout, CI_CHUNK);
-      a.pad = (int)align_up(j.Cin, 32);
-      add(1, a, (int)(((size_t)j.K * j.KH * j.Cout * j.Cin + 255) / 256));
-    }
-    if (j.kind == PK_CONV2D_SN || j.kind == PK_DW2D_SN) {  // launch_sn_prep_multi
-      MultiJob a;
-      a.p0 = j.w;
-      a.p1 = j.bias;
-      a.p2 = j.kind == PK_CONV2D_SN ? j.bp : nullptr;
-      a.q0 = const_cast<float*>(j.g);
-      a.q1 = const_cast<float*>(j.v);
-      a.q2 = j.scratch;
-      a.q3 = j.scratch2;
-      a.q4 = j.wp;
-      a.Cout = j.Cout;
-      a.Cin = j.Cin;
-      a.K = j.K;
-      a.KH = j.KH;
-      a.CinP = j.CinP;
-      a.CoutP = j.CoutP;
-      a.glu = j.kind == PK_DW2D_SN;
-      const int n = a.glu ? 9 : j.Cin * j.KH * j.K;
-      a.blk1 = (int)blk1.size();
-      for (int i = 0; i < 8 * ((n + 255) / 256); ++i) blk1.push_back((int)jobs[4].size());  // (SN_SLICES = 8, conv2d.hip)
-      add(4, a, j.Cout);
-    }
-    if (j.kind == PK_CONV2D_SN && m->garena) {
-      MultiJob u;  // sn_unpack_multi_kernel
-      u.p0 = GA(j.wp);
-      u.p1 = j.w;
-      u.p2 = j.g;
-      u.p3 = j.v;
-      u.p4 = j.scratch;
-      u.q0 = PG(j.w);
-      u.q1 = GA(j.scratch);  // the gradient-arena twin of the sigma scratch holds the <G, W> row sums
-      u.q3 = (j.bias && j.bp) ? PG(j.bias) : nullptr;
-      u.q4 = (j.bias && j.bp) ? GA(j.bp) : nullptr;
-      u.Cout = j.Cout;
-      u.Cin = j.Cin;
-      u.K = j.K;
-      u.KH = j.KH;
-      u.CinP = j.CinP;
-      u.CoutP = j.CoutP;
-      if (u.q0 || u.q3) add(3, u, j.Cout);
-    }
-  }
-  if (m->mj_blk1_dev) (void)hipFree(m->mj_blk1_dev);
-  m->mj_blk1_dev = nullptr;
-  m->mj_nblk1 = (int)blk1.size();
-  m->mj_nsn = (int)jobs[4].size();
-  if (!blk1.empty()) {
-    STY_HIP(hipMalloc((void**)&m->mj_blk1_dev, blk1.size() * sizeof(int)));
-    STY_HIP(hipMemcpy(m->mj_blk1_dev, blk1.data(), blk1.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  for (int i = 0; i < 5; ++i) {
-    if (m->mj_dev[i]) (void)hipFree(m->mj_dev[i]);
-    if (m->mj_blk_dev[i]) (void)hipFree(m->mj_blk_dev[i]);
-    m->mj_dev[i] = nullptr;
-    m->mj_blk_dev[i] = nullptr;
-    m->mj_nblk[i] = (int)blk[i].size();
-    if (i == 2 && m->seg_job_split >= m->jobs.size()) m->seg_blk_split = (int)blk[2].size();
-    if (blk[i].empty()) continue;
-    STY_HIP(hipMalloc((void**)&m->mj_dev[i], jobs[i].size() * sizeof(MultiJob)));
-    STY_HIP(hipMalloc((void**)&m->mj_blk_dev[i], blk[i].size() * sizeof(int)));
-    STY_HIP(hipMemcpy(m->mj_dev[i], jobs[i].data(), jobs[i].size() * sizeof(MultiJob), hipMemcpyHostToDevice));
-    STY_HIP(hipMemcpy(m->mj_blk_dev[i], blk[i].data(), blk[i].size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  m->mj_ready = true;
-  return STY_OK;
-}
-
 int sty_model_set_grad_hook(sty_model* m, sty_grad_hook hook, void* user) {
   if (!m) {
     set_error("sty_model_set_grad_hook: null model");
@@ -2138,66 +1843,8 @@ int sty_model_prepare(sty_model* m, void* stream) {
     set_error("sty_model_prepare: model not finalized");
     return STY_ESTATE;
   }
-  hipStream_t st = S(stream);
-  if (!m->mj_ready) {
-    int r = build_multi_tables(m);
-    if (r != STY_OK) return r;
-  }
-  {  // every plain / weight-norm / GLU conv pack in one launch
-    int r = launch_multi(0, m->mj_dev[0], m->mj_blk_dev[0], m->mj_nblk[0], st);
-    if (r != STY_OK) return r;
-  }
-  {  // the pwconv2 fragment packs of the fused ConvNeXt blocks: one launch per W2A_MAXJ blocks (every other kind is batched
-     // through the device-side job tables above / below)
-    W2aJobs wj;
-    for (const PackJob& j : m->jobs) {
-      if (j.kind != PK_W2A) continue;
-      const int k = wj.n++;
-      wj.w2[k] = j.w;
-      wj.b2[k] = j.bias;
-      wj.gb[k] = j.extra;
-      wj.w2a[k] = j.wp;
-      wj.b2eff[k] = j.bp;
-      wj.C[k] = j.Cout;
-      if (wj.n == W2A_MAXJ) {
-        int r = launch_pack_w2a_multi(wj, st);
-        if (r != STY_OK) return r;
-        wj.n = 0;
-      }
-    }
-    int r = launch_pack_w2a_multi(wj, st);
-    if (r != STY_OK) return r;
-  }
-  {  // sigma and W / sigma of every spectral-norm layer: two launches
-    int r = launch_sn_prep_multi(m->mj_dev[4], m->mj_nsn, m->mj_blk_dev[4], m->mj_nblk[4], m->mj_blk1_dev, m->mj_nblk1, false,
-                                 true, st);
-    if (r != STY_OK) return r;
-  }
-  {
-    int r = launch_multi(1, m->mj_dev[1], m->mj_blk_dev[1], m->mj_nblk[1], st);
-    if (r != STY_OK) return r;
-  }
-  if (m->kind == "speech_predictor") {
-    const DecoderPlan& d = m->dec;
-    int r = launch_prep_fnv(d.f0_g, d.f0_v, d.f0_b, d.n_g, d.n_v, d.n_b, d.v_g, d.v_v, d.v_b, d.fnv_w, st);
-    if (r != STY_OK) return r;
-  }
-  if (m->kind == "text_aligner" || m->kind == "text_aligner_train") {
-    // BatchNorm1d(affine=False) on running statistics -> one scale / shift pair per layer
-    const AlignerPlan& a = m->ali;
-    for (int i = 0; i < 3; ++i) {
-      int r = launch_aligner_bn_prep(a.rm[i], a.rv[i], a.hidden, 1e-5f, a.bn_scale[i], a.bn_shift[i], st);
-      if (r != STY_OK) return r;
-    }
-    if (a.bn_one) {  // (bn_zero is the arena's zero fill)
-      int r = launch_fill_f32(a.bn_one, a.hidden, 1.0f, st);
-      if (r != STY_OK) return r;
-    }
-  }
-  if (m->arena) {  // the bf16 fragment buffers the persistent kernels read the packed weights through (bf16 mode)
-    int r = convp16_repack_range(m->arena, m->arena + m->arena_bytes, st);
-    if (r != STY_OK) return r;
-  }
+  int rc = weights_prepare(m, S(stream));
+  if (rc) return rc;
   m->prepared = true;
   return STY_OK;
 }
@@ -2626,7 +2273,7 @@ int sty_block_fwd_bwd(sty_model* m, const char* kind, const char* prefix, int B,
   rc = trainer_block_fwd_bwd(m->trainer, k, blk, B, C, T, x, style, gy, y, gx, d_style, workspace, ws_bytes, S(stream),
                              nullptr);
   if (rc) return rc;
-  return unpack_grads(m, S(stream));
+  return weights_unpack(m, S(stream));
 }
 
 // softmax attention forward + backward on separate q / k / v [B][H*DH][T] (DH = 16: the text encoder's VALU backward with
@@ -2810,12 +2457,7 @@ static int style_train_prepare(sty_model* m, void* stream) {
   if (m->train_prepared)  // done by sty_style_prepare_train since the last forward
     return prepared_consume(m, stream);
   int rc;
-  if (m->topts.sn_power_iter) {  // every spectral-norm layer in four launches (u, v in the caller's buffers)
-    if (!m->mj_ready && (rc = build_multi_tables(m))) return rc;
-    rc = launch_sn_prep_multi(m->mj_dev[4], m->mj_nsn, m->mj_blk_dev[4], m->mj_nblk[4], m->mj_blk1_dev, m->mj_nblk1, true,
-                              false, S(stream));
-    if (rc) return rc;
-  }
+  if (m->topts.sn_power_iter && (rc = weights_sn_power_iter(m, S(stream)))) return rc;  // (u, v in the caller's buffers)
   // weights change between steps: re-derive the prepared form every step
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
@@ -3034,7 +2676,7 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
     return STY_EINVAL;
   }
   STY_HIP(hipMemsetAsync(dw, 0, (size_t)Cout * Cin * K * sizeof(float), st));
-  rc = launch_unpack_grad(gwp, nullptr, nullptr, Cout, Cin, K, pc.CinP, pc.CoutP, 0, dw, nullptr, nullptr, st);
+  rc = launch_unpack_grad(gwp, nullptr, nullptr, Cout, Cin, K, pc.CinP, pc.CoutP, dw, nullptr, nullptr, st);
   if (rc) return rc;
   if (dbias) STY_HIP(hipMemcpyAsync(dbias, gbp, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (dx) {

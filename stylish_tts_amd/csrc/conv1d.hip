@@ -536,61 +536,4 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
   return rc;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Weight packing (+ weight_norm): one block per output channel.
-//   w: [Cout][Cin][K] plain weight, or nullptr with (g [Cout], v [Cout][Cin][K]) for weight_norm
-//   glu != 0: output-channel order is interleaved in 32-blocks (value block, gate block) for ACT_GLU.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pack_conv_kernel(const float* __restrict__ w, const float* __restrict__ g,
-                                                        const float* __restrict__ v, const float* __restrict__ bias,
-                                                        int Cout, int Cin, int K, float* __restrict__ wp,
-                                                        float* __restrict__ bp, int CinP, int CoutP, int glu) {
-  __shared__ float red[256];
-  const int co = blockIdx.x;
-  const int n = Cin * K;
-  int cp = co;
-  if (glu) {
-    const int Ch = Cout / 2;
-    const int half = co >= Ch, c = half ? co - Ch : co;
-    cp = (c >> 5) * 64 + half * 32 + (c & 31);
-  }
-  float scale = 1.f;
-  const float* src = w;
-  if (!w) {
-    src = v;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-      float x = v[(size_t)co * n + i];
-      s += x * x;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
-    scale = g[co] / sqrtf(red[0]);
-  }
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int ci = i / K, k = i % K;
-    wp[((size_t)k * CinP + ci) * CoutP + cp] = src[(size_t)co * n + i] * scale;
-  }
-  if (threadIdx.x == 0 && bp) bp[cp] = bias ? bias[co] : 0.f;
-}
-
-int launch_pack_conv(const float* w, const float* g, const float* v, const float* bias, int Cout, int Cin, int K,
-                     float* wp, float* bp, int CinP, int CoutP, hipStream_t st) {
-  hipLaunchKernelGGL(pack_conv_kernel, dim3(Cout), dim3(256), 0, st, w, g, v, bias, Cout, Cin, K, wp, bp, CinP, CoutP, 0);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-int launch_pack_conv_glu(const float* w, const float* bias, int Cout, int Cin, int K, float* wp, float* bp, int CinP,
-                         int CoutP, hipStream_t st) {
-  hipLaunchKernelGGL(pack_conv_kernel, dim3(Cout), dim3(256), 0, st, w, (const float*)nullptr, (const float*)nullptr,
-                     bias, Cout, Cin, K, wp, bp, CinP, CoutP, 1);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
 }  // namespace sty

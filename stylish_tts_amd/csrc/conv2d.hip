@@ -3,7 +3,7 @@
 // global-pool + Linear head.  Reference: train/models/mel_style_encoder.py:9-152.
 #include <stdlib.h>
 
-#include "sty_common.h"
+#include "weights.h"
 
 namespace sty {
 
@@ -18,27 +18,26 @@ size_t sn_power_iter_scratch_floats(int Cout, int n) { return (size_t)SN_SLICES 
 // ---- every spectral-norm layer of a model in one launch per step of the recipe (device-side job table) ----
 // The style encoder has 13 spectral-norm convs and 3 depthwise ones: layer by layer that was ~96 launches of a few
 // microseconds each at the head of its forward, i.e. ~1 ms in front of the kernel the whole step waits for (style).
-// MultiJob: p0 = W, p1 = bias, p2 = packed bias (written), q0 = u, q1 = v, q2 = t [Cout] (sigma row terms), q3 = power
-// iteration scratch (SN_SLICES n + Cout), q4 = packed weights (written); K = KW, glu = 1: depthwise [C][9];
-// blk0: first block of the layer in the row list (one block per output channel), blk1: in the W^T u list.
-__device__ __forceinline__ int snj_n(const MultiJob& j) { return j.glu ? 9 : j.Cin * j.KH * j.K; }
-__global__ __launch_bounds__(256) void sn_wt_u_multi_kernel(const MultiJob* __restrict__ jobs, const int* __restrict__ job_of_blk) {
-  const MultiJob j = jobs[job_of_blk[blockIdx.x]];
+// SnPrepJob (weights.h): blk0 = first block of the layer in the row list (one block per output channel), wtu0 = in the W^T u list.
+int sn_wtu_blocks(int n) { return SN_SLICES * ((n + 255) / 256); }
+__device__ __forceinline__ int snj_n(const SnPrepJob& j) { return j.depthwise ? 9 : j.Cin * j.KH * j.K; }
+__global__ __launch_bounds__(256) void sn_wt_u_multi_kernel(const SnPrepJob* __restrict__ jobs, const int* __restrict__ job_of_blk) {
+  const SnPrepJob j = jobs[job_of_blk[blockIdx.x]];
   const int n = snj_n(j), nib = (n + 255) / 256;
-  const int local = (int)blockIdx.x - j.blk1, slice = local / nib, i = (local - slice * nib) * 256 + threadIdx.x;
+  const int local = (int)blockIdx.x - j.wtu0, slice = local / nib, i = (local - slice * nib) * 256 + threadIdx.x;
   if (i >= n) return;
   float s = 0.f;
-  for (int co = slice; co < j.Cout; co += SN_SLICES) s = fmaf(j.p0[(size_t)co * n + i], j.q0[co], s);
-  j.q3[(size_t)slice * n + i] = s;
+  for (int co = slice; co < j.Cout; co += SN_SLICES) s = fmaf(j.w[(size_t)co * n + i], j.u[co], s);
+  j.power[(size_t)slice * n + i] = s;
 }
 // which = 0: v = normalize(sum of the slices of W^T u); which = 1: u = normalize(W v)
-__global__ __launch_bounds__(256) void sn_normalize_multi_kernel(const MultiJob* __restrict__ jobs, int which) {
+__global__ __launch_bounds__(256) void sn_normalize_multi_kernel(const SnPrepJob* __restrict__ jobs, int which) {
   __shared__ double red[256];
-  const MultiJob j = jobs[blockIdx.x];
+  const SnPrepJob j = jobs[blockIdx.x];
   const int nv = snj_n(j);
   const int n = which ? j.Cout : nv, slices = which ? 1 : SN_SLICES;
-  const float* raw = which ? j.q3 + (size_t)SN_SLICES * nv : j.q3;
-  float* out = which ? j.q0 : j.q1;
+  const float* raw = which ? j.power + (size_t)SN_SLICES * nv : j.power;
+  float* out = which ? j.u : j.v;
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
     float v = 0.f;
@@ -56,13 +55,13 @@ __global__ __launch_bounds__(256) void sn_normalize_multi_kernel(const MultiJob*
   for (int i = threadIdx.x; i < n; i += 256) out[i] = out[i] / nrm;
 }
 // what = 0: uraw[co] = <W[co,:], v>;  what = 1: t[co] = u[co] <W[co,:], v>
-__global__ __launch_bounds__(256) void sn_rowdot_multi_kernel(const MultiJob* __restrict__ jobs, const int* __restrict__ job_of_row,
+__global__ __launch_bounds__(256) void sn_rowdot_multi_kernel(const SnPrepJob* __restrict__ jobs, const int* __restrict__ job_of_row,
                                                               int what) {
   __shared__ float red[256];
-  const MultiJob j = jobs[job_of_row[blockIdx.x]];
+  const SnPrepJob j = jobs[job_of_row[blockIdx.x]];
   const int co = (int)blockIdx.x - j.blk0, n = snj_n(j);
   float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s = fmaf(j.p0[(size_t)co * n + i], j.q1[i], s);
+  for (int i = threadIdx.x; i < n; i += 256) s = fmaf(j.w[(size_t)co * n + i], j.v[i], s);
   red[threadIdx.x] = s;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -71,45 +70,45 @@ __global__ __launch_bounds__(256) void sn_rowdot_multi_kernel(const MultiJob* __
   }
   if (threadIdx.x == 0) {
     if (what)
-      j.q2[co] = j.q0[co] * red[0];
+      j.t[co] = j.u[co] * red[0];
     else
-      j.q3[(size_t)SN_SLICES * n + co] = red[0];
+      j.power[(size_t)SN_SLICES * n + co] = red[0];
   }
 }
-__global__ __launch_bounds__(256) void sn_pack_multi_kernel(const MultiJob* __restrict__ jobs, const int* __restrict__ job_of_row) {
+__global__ __launch_bounds__(256) void sn_pack_multi_kernel(const SnPrepJob* __restrict__ jobs, const int* __restrict__ job_of_row) {
   __shared__ float sig;
-  const MultiJob j = jobs[job_of_row[blockIdx.x]];
+  const SnPrepJob j = jobs[job_of_row[blockIdx.x]];
   const int co = (int)blockIdx.x - j.blk0;
   if (threadIdx.x == 0) {
     float s = 0.f;
-    for (int i = 0; i < j.Cout; ++i) s += j.q2[i];
+    for (int i = 0; i < j.Cout; ++i) s += j.t[i];
     sig = s;
   }
   __syncthreads();
   const float inv = 1.0f / sig;
-  if (j.glu) {  // depthwise [C][1][3][3] / sigma -> w9[c][9]
-    if (threadIdx.x < 9) j.q4[co * 9 + threadIdx.x] = j.p0[co * 9 + threadIdx.x] * inv;
+  if (j.depthwise) {  // depthwise [C][1][3][3] / sigma -> w9[c][9]
+    if (threadIdx.x < 9) j.wp[co * 9 + threadIdx.x] = j.w[co * 9 + threadIdx.x] * inv;
     return;
   }
   const int KW = j.K, KH = j.KH, n = j.Cin * KH * KW;
   for (int i = threadIdx.x; i < n; i += 256) {
     const int kw = i % KW, kh = (i / KW) % KH, ci = i / (KW * KH);
-    j.q4[((size_t)kw * j.CinP + kh * j.Cin + ci) * j.CoutP + co] = j.p0[(size_t)co * n + i] * inv;
+    j.wp[((size_t)kw * j.CinP + kh * j.Cin + ci) * j.CoutP + co] = j.w[(size_t)co * n + i] * inv;
   }
-  if (threadIdx.x == 0 && j.p2) const_cast<float*>(j.p2)[co] = j.p1 ? j.p1[co] : 0.f;
+  if (threadIdx.x == 0 && j.bp) j.bp[co] = j.bias ? j.bias[co] : 0.f;
 }
-int launch_sn_prep_multi(const MultiJob* jobs, int njobs, const int* job_of_row, int nrows, const int* job_of_blk1, int nblk1,
-                         bool power_iter, bool pack, hipStream_t st) {
-  if (njobs <= 0) return STY_OK;
+int launch_sn_prep_table(const JobTable<SnPrepJob>& t, const BlockList& wtu, bool power_iter, bool pack, hipStream_t st) {
+  if (t.njobs <= 0) return STY_OK;
+  const int nrows = t.blocks.n;
   if (power_iter) {
-    hipLaunchKernelGGL(sn_wt_u_multi_kernel, dim3(nblk1), dim3(256), 0, st, jobs, job_of_blk1);
-    hipLaunchKernelGGL(sn_normalize_multi_kernel, dim3(njobs), dim3(256), 0, st, jobs, 0);
-    hipLaunchKernelGGL(sn_rowdot_multi_kernel, dim3(nrows), dim3(256), 0, st, jobs, job_of_row, 0);
-    hipLaunchKernelGGL(sn_normalize_multi_kernel, dim3(njobs), dim3(256), 0, st, jobs, 1);
+    hipLaunchKernelGGL(sn_wt_u_multi_kernel, dim3(wtu.n), dim3(256), 0, st, t.jobs, wtu.dev);
+    hipLaunchKernelGGL(sn_normalize_multi_kernel, dim3(t.njobs), dim3(256), 0, st, t.jobs, 0);
+    hipLaunchKernelGGL(sn_rowdot_multi_kernel, dim3(nrows), dim3(256), 0, st, t.jobs, t.blocks.dev, 0);
+    hipLaunchKernelGGL(sn_normalize_multi_kernel, dim3(t.njobs), dim3(256), 0, st, t.jobs, 1);
   }
   if (pack) {
-    hipLaunchKernelGGL(sn_rowdot_multi_kernel, dim3(nrows), dim3(256), 0, st, jobs, job_of_row, 1);
-    hipLaunchKernelGGL(sn_pack_multi_kernel, dim3(nrows), dim3(256), 0, st, jobs, job_of_row);
+    hipLaunchKernelGGL(sn_rowdot_multi_kernel, dim3(nrows), dim3(256), 0, st, t.jobs, t.blocks.dev, 1);
+    hipLaunchKernelGGL(sn_pack_multi_kernel, dim3(nrows), dim3(256), 0, st, t.jobs, t.blocks.dev);
   }
   STY_LAUNCH_CHECK();
   return STY_OK;

@@ -43,31 +43,7 @@ int launch_convnext32(const Cnx32Args& a, int B, int pass, hipStream_t st) {
 
 // pwconv2 [C][4C] -> A fragments of the chained GEMM: w2a[j][q][hi][co] = W2[co][32j + (q&3)+8(q>>2) + 4hi]
 // and b2eff[co] = b2[co] + sum_ch W2[co][ch] * grn_beta[ch].
-__global__ void pack_w2a_kernel(const float* __restrict__ w2, const float* __restrict__ b2,
-                                const float* __restrict__ grn_beta, int C, float* __restrict__ w2a,
-                                float* __restrict__ b2eff) {
-  const int C4 = 4 * C;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < C4 * C) {
-    const int co = i % C, rest = i / C;
-    const int hi = rest & 1, q = (rest >> 1) & 15, j = rest >> 5;
-    const int ch = 32 * j + (q & 3) + 8 * (q >> 2) + 4 * hi;
-    w2a[i] = w2[(size_t)co * C4 + ch];
-  }
-}
-// one wave per output channel (coalesced row read + shuffle reduction; the per-thread serial loop this replaces
-// took 56 us at C = 256)
-__global__ __launch_bounds__(64) void b2eff_kernel(const float* __restrict__ w2, const float* __restrict__ b2,
-                                                   const float* __restrict__ grn_beta, int C4,
-                                                   float* __restrict__ b2eff) {
-  const int co = blockIdx.x, lane = threadIdx.x;
-  float acc = 0.f;
-  for (int ch = lane; ch < C4; ch += 64) acc = fmaf(w2[(size_t)co * C4 + ch], grn_beta[ch], acc);
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (lane == 0) b2eff[co] = b2[co] + acc;
-}
-
-// the same two kernels for up to W2A_MAXJ blocks in ONE launch (the job list travels as a kernel argument): sixteen ConvNeXt
+// Both for up to W2A_MAXJ blocks in ONE launch (the job list travels as a kernel argument): block by block, sixteen ConvNeXt
 // blocks made 32 launches of a few microseconds at the head of every training step's forward
 __global__ __launch_bounds__(256) void pack_w2a_multi_kernel(W2aJobs jobs) {
   const int j = blockIdx.y;
@@ -88,7 +64,7 @@ __global__ __launch_bounds__(256) void pack_w2a_multi_kernel(W2aJobs jobs) {
   if (co >= C) return;
   const float* gb = jobs.gb[j];
   float acc = 0.f;
-  for (int ch = lane; ch < C4; ch += 64) acc = fmaf(w2[(size_t)co * C4 + ch], gb[ch], acc);  // (b2eff_kernel's order)
+  for (int ch = lane; ch < C4; ch += 64) acc = fmaf(w2[(size_t)co * C4 + ch], gb[ch], acc);
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
   if (lane == 0) jobs.b2eff[j][co] = jobs.b2[j][co] + acc;
 }
@@ -100,14 +76,6 @@ int launch_pack_w2a_multi(const W2aJobs& jobs, hipStream_t st) {
     maxb = nb > maxb ? nb : maxb;
   }
   hipLaunchKernelGGL(pack_w2a_multi_kernel, dim3(maxb, jobs.n), dim3(256), 0, st, jobs);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-int launch_pack_w2a(const float* w2, const float* b2, const float* grn_beta, int C, float* w2a, float* b2eff,
-                    hipStream_t st) {
-  hipLaunchKernelGGL(pack_w2a_kernel, dim3(cdiv(4 * C * C, 256)), dim3(256), 0, st, w2, b2, grn_beta, C, w2a, b2eff);
-  hipLaunchKernelGGL(b2eff_kernel, dim3(C), dim3(64), 0, st, w2, b2, grn_beta, 4 * C, b2eff);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "sty_common.h"
+#include "weights.h"
 
 namespace sty {
 
@@ -15,8 +16,6 @@ struct Param {
 
 int convnext32_ntiles(int T);
 int launch_convnext32(const Cnx32Args& a, int B, int pass, hipStream_t st);
-int launch_pack_w2a(const float* w2, const float* b2, const float* grn_beta, int C, float* w2a, float* b2eff,
-                    hipStream_t st);
 int launch_attention(const AttnArgs& a, int B, int DH, hipStream_t st);
 int launch_rope_n(float* q, float* k, int B, int H, int DH, int L, int d, hipStream_t st, float sgn = 1.0f);
 int launch_style_expand(const float* style, int B, int S, int L, float* y, hipStream_t st);
@@ -89,7 +88,6 @@ struct Bump {
   }
 };
 
-enum PackKind { PK_CONV, PK_CONV_WN, PK_CONV_GLU, PK_W2A, PK_CONV2D_SN, PK_DW2D_SN, PK_DGRAD, PK_DGRAD2D };
 // y16 (optional): the bf16 operand twin of the output for the conv that reads it next (ConvArgs::x16) -- bf16(lrelu(y))
 // behind the learned down-sampling, bf16(y) behind the pooling
 int launch_dwconv2d_s2(const float* x, const float* w9, const float* bias, int B, int C, int H, int W, float* y,
@@ -97,16 +95,6 @@ int launch_dwconv2d_s2(const float* x, const float* w9, const float* bias, int B
 int launch_avgpool2(const float* x, int BC, int H, int W, float scale, float* y, hipStream_t st, __bf16* y16 = nullptr);
 int launch_pool_fc(const float* x, int B, int C, int n, int count, const float* W, const float* bvec, int S,
                    float* out, hipStream_t st);
-struct PackJob {
-  PackKind kind;
-  const float *w = nullptr, *g = nullptr, *v = nullptr, *bias = nullptr, *extra = nullptr;
-  int Cout = 0, Cin = 0, K = 1, CinP = 0, CoutP = 0, KH = 1;
-  float* wp = nullptr;
-  float* bp = nullptr;
-  float* scratch = nullptr;
-  float* scratch2 = nullptr;  // spectral norm, training: n + Cout floats for the power iteration
-};
-
 struct AdaFc {      // one AdaIN / AdaLN style projection
   int idx = -1;     // index in the module's fc table
   int C = 0;        // channels (fc produces 2C)
@@ -263,19 +251,11 @@ struct sty_model {
   std::unordered_map<const float*, sty::PackedConv> dgrad;      // forward packed weights -> input-gradient weights
   std::unordered_map<const float*, sty::PackedConv> plain_of;   // GLU-ordered packed conv -> plain-ordered copy
   void* fcs_bwd_dev = nullptr;
-  // batched weight-side launches: device tables [0] pack, [1] input-gradient pack, [2] gradient un-pack
-  sty::MultiJob* mj_dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int* mj_blk_dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int mj_nblk[5] = {0, 0, 0, 0, 0};  // 0 pack, 1 input-gradient pack, 2 gradient un-pack, 3 spectral-norm gradient un-pack,
-                                    // 4 spectral-norm weight preparation (rows; mj_blk1_dev: its W^T u block list)
-  int* mj_blk1_dev = nullptr;
-  int mj_nblk1 = 0, mj_nsn = 0;
-  bool mj_ready = false;
+  sty::WeightTables wt;  // device tables of the batched weight-side launches (weights.h)
   // gradient segments (data-parallel overlap): pack jobs [0, seg_job_split) belong to the module that runs its backward
-  // LAST (the text encoder of a speech predictor); the un-pack table splits at block seg_blk_split.  Segment 0 = every
-  // other parameter: complete, un-packed and announced through grad_hook while the last module's backward still runs.
+  // LAST (the text encoder of a speech predictor).  Segment 0 = every other parameter: complete, un-packed and announced
+  // through grad_hook while the last module's backward still runs.
   size_t seg_job_split = 0;
-  int seg_blk_split = 0;
   sty_grad_hook grad_hook = nullptr;
   void* grad_hook_user = nullptr;
   sty_train_opts topts = {0, 0, 0, 0, 0.1f, 0u, 0.2f, 0, 0};  // train-mode behaviour of the *_fwd_train entry points
@@ -348,11 +328,6 @@ void wgrad_defer_destroy(WgReduceDefer* d);
 WgReduceDefer* wgrad_defer_set(WgReduceDefer* d);  // returns the previous one (nullptr = immediate reductions)
 size_t wgrad_defer_pending(const WgReduceDefer* d);
 int wgrad_defer_flush(WgReduceDefer* d, int site, hipStream_t st);
-int launch_pack_dgrad(const float* wp, int K, int CinP, int CoutP, float* wd, hipStream_t st);
-int launch_b2eff_bwd(const float* g, const float* w2, const float* beta, int C, float* db2, float* dbeta, float* dW2,
-                     hipStream_t st);
-int launch_unpack_grad(const float* gwp, const float* g, const float* v, int Cout, int Cin, int K, int CinP, int CoutP,
-                       int glu, float* dW, float* dg, float* dv, hipStream_t st);
 int launch_attention_bwd(const AttnArgs& a, const float* dO, float* dQ, float* dK, float* dV, size_t dqbs, size_t dkbs,
                          size_t dvbs, size_t dobs, int B, int DH, float* ws, hipStream_t st, int overwrite = 0);
 bool attention_bwd_can_overwrite(const AttnArgs& a, int DH);
@@ -369,8 +344,6 @@ int launch_fnv_bwd(const float* pitch, const float* energy, const float* voiced,
 int launch_fnv_unpack(const float* dw34, const float* g0, const float* v0, const float* g1, const float* v1,
                       const float* g2, const float* v2, float* dg0, float* dv0, float* db0, float* dg1, float* dv1,
                       float* db1, float* dg2, float* dv2, float* db2, hipStream_t st);
-int launch_pack_dgrad2d(const float* wp, int KW, int KH, int Cin, int Cout, int CinP, int CoutP, int CinPd, int CoutPd,
-                        float* wd, hipStream_t st);
 size_t dwconv2d_s2_bwd_scratch_floats(int B, int C, int H, int W);
 // dx16 / mask16 (optional; overwriting form only): also write bf16(dx * mask16[b][n]), the operand twin of dx
 // dx == nullptr (with dx16): the twin alone -- the caller knows that every reader of dx takes the twin

@@ -1347,313 +1347,4 @@ int launch_conv_wgrad_cnx(int x_wide, const void* wide, const float* narrow, int
   return STY_OK;
 }
 
-// ---- input-gradient weights: Wd[k'][co][ci] = Wp[K-1-k'][ci][co] ----
-__global__ void pack_dgrad_kernel(const float* __restrict__ wp, int K, int CinP, int CoutP, float* __restrict__ wd) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t n = (size_t)K * CinP * CoutP;
-  if (i >= n) return;
-  const int ci = (int)(i % CinP);
-  const int co = (int)((i / CinP) % CoutP);
-  const int kd = (int)(i / ((size_t)CinP * CoutP));
-  wd[i] = wp[((size_t)(K - 1 - kd) * CinP + ci) * CoutP + co];
-}
-int launch_pack_dgrad(const float* wp, int K, int CinP, int CoutP, float* wd, hipStream_t st) {
-  const size_t n = (size_t)K * CinP * CoutP;
-  hipLaunchKernelGGL(pack_dgrad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wp, K, CinP, CoutP, wd);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-// ---- packed gradient -> parameter gradients (+=); one workgroup per output channel ----
-//   plain:        dW[co][ci][k] += gwp[k][ci][cp]
-//   weight_norm:  w = g v/|v|:  dg[co] += <gw, v>/|v|,  dv += g/|v| (gw - v <gw, v>/|v|^2)
-//   glu != 0: packed output order (value/gate 32-blocks), as in pack_conv_kernel
-__global__ __launch_bounds__(256) void unpack_grad_kernel(const float* __restrict__ gwp, const float* __restrict__ gv,
-                                                          const float* __restrict__ vv, int Cout, int Cin, int K,
-                                                          int CinP, int CoutP, int glu, float* __restrict__ dW,
-                                                          float* __restrict__ dg, float* __restrict__ dv) {
-  __shared__ float r1[256], r2[256];
-  const int co = blockIdx.x;
-  const int n = Cin * K;
-  int cp = co;
-  if (glu) {
-    const int Ch = Cout / 2;
-    const int half = co >= Ch, c = half ? co - Ch : co;
-    cp = (c >> 5) * 64 + half * 32 + (c & 31);
-  }
-  if (!vv) {
-    for (int i = threadIdx.x; i < n; i += 256) {
-      const int ci = i / K, k = i % K;
-      dW[(size_t)co * n + i] += gwp[((size_t)k * CinP + ci) * CoutP + cp];
-    }
-    return;
-  }
-  float dot = 0.f, nn = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int ci = i / K, k = i % K;
-    const float v = vv[(size_t)co * n + i];
-    dot = fmaf(gwp[((size_t)k * CinP + ci) * CoutP + cp], v, dot);
-    nn = fmaf(v, v, nn);
-  }
-  r1[threadIdx.x] = dot;
-  r2[threadIdx.x] = nn;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      r1[threadIdx.x] += r1[threadIdx.x + o];
-      r2[threadIdx.x] += r2[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  const float norm = sqrtf(r2[0]), d = r1[0], gg = gv[co];
-  if (threadIdx.x == 0) dg[co] += d / norm;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int ci = i / K, k = i % K;
-    const float v = vv[(size_t)co * n + i];
-    dv[(size_t)co * n + i] += gg / norm * (gwp[((size_t)k * CinP + ci) * CoutP + cp] - v * d / (norm * norm));
-  }
-}
-int launch_unpack_grad(const float* gwp, const float* g, const float* v, int Cout, int Cin, int K, int CinP, int CoutP,
-                       int glu, float* dW, float* dg, float* dv, hipStream_t st) {
-  hipLaunchKernelGGL(unpack_grad_kernel, dim3(Cout), dim3(256), 0, st, gwp, g, v, Cout, Cin, K, CinP, CoutP, glu, dW,
-                     dg, dv);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-// ---- the same three weight-side steps for MANY convs in one launch (the speech predictor has ~130 dense convs:
-//      ~400 launches of 4-5 us each per optimizer step when issued one by one) ----
-// job_of_block[blockIdx.x] selects the job, blockIdx.x - job.blk0 is the block index inside it.
-__global__ __launch_bounds__(256) void pack_conv_multi_kernel(const MultiJob* __restrict__ jobs,
-                                                              const int* __restrict__ job_of_block) {
-  __shared__ float red[256];
-  const MultiJob j = jobs[job_of_block[blockIdx.x]];
-  const int co = blockIdx.x - j.blk0;
-  const int n = j.Cin * j.K;
-  int cp = co;
-  if (j.glu) {
-    const int Ch = j.Cout / 2;
-    const int half = co >= Ch, c = half ? co - Ch : co;
-    cp = (c >> 5) * 64 + half * 32 + (c & 31);
-  }
-  float scale = 1.f;
-  const float* src = j.p0;  // plain weight, or (p1 = g, p2 = v) of weight norm
-  if (!src) {
-    src = j.p2;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-      const float x = src[(size_t)co * n + i];
-      s += x * x;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-      __syncthreads();
-    }
-    scale = j.p1[co] / sqrtf(red[0]);
-  }
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int ci = i / j.K, k = i % j.K;
-    j.q0[((size_t)k * j.CinP + ci) * j.CoutP + cp] = src[(size_t)co * n + i] * scale;
-  }
-  if (threadIdx.x == 0 && j.q1) j.q1[cp] = j.p3 ? j.p3[co] : 0.f;
-}
-__global__ __launch_bounds__(256) void pack_dgrad_multi_kernel(const MultiJob* __restrict__ jobs,
-                                                               const int* __restrict__ job_of_block) {
-  const MultiJob j = jobs[job_of_block[blockIdx.x]];
-  const size_t i = (size_t)(blockIdx.x - j.blk0) * 256 + threadIdx.x;
-  if (j.glu == 2) {  // 2-D (flat layout): Wd[kw'][kh' Cout + co][ci] = Wp[KW-1-kw'][(KH-1-kh') Cin + ci][co]; blk1 / pad = CinPd / CoutPd
-    const size_t n2 = (size_t)j.K * j.KH * j.Cout * j.Cin;
-    if (i >= n2) return;
-    const int ci = (int)(i % j.Cin);
-    const int co = (int)((i / j.Cin) % j.Cout);
-    const int kh = (int)((i / ((size_t)j.Cin * j.Cout)) % j.KH);
-    const int kw = (int)(i / ((size_t)j.Cin * j.Cout * j.KH));
-    j.q0[((size_t)kw * j.blk1 + kh * j.Cout + co) * j.pad + ci] =
-        j.p0[((size_t)(j.K - 1 - kw) * j.CinP + (j.KH - 1 - kh) * j.Cin + ci) * j.CoutP + co];
-    return;
-  }
-  const size_t n = (size_t)j.K * j.CinP * j.CoutP;
-  if (i >= n) return;
-  const int ci = (int)(i % j.CinP);
-  const int co = (int)((i / j.CinP) % j.CoutP);
-  const int kd = (int)(i / ((size_t)j.CinP * j.CoutP));
-  j.q0[i] = j.p0[((size_t)(j.K - 1 - kd) * j.CinP + ci) * j.CoutP + co];
-}
-// p0 = packed weight gradient, p1 = g, p2 = v (weight norm) or null, p3 = packed bias gradient or null;
-// q0 = dW, q1 = dg, q2 = dv, q3 = db
-__global__ __launch_bounds__(256) void unpack_grad_multi_kernel(const MultiJob* __restrict__ jobs,
-                                                                const int* __restrict__ job_of_block, int blk_base) {
-  __shared__ float r1[256], r2[256];
-  const int blk = (int)blockIdx.x + blk_base;  // a launch may cover a sub-range of the table (one gradient segment)
-  const MultiJob j = jobs[job_of_block[blk]];
-  const int co = blk - j.blk0;
-  const int n = j.Cin * j.K;
-  const int cp = co;
-  if (threadIdx.x == 0 && j.q3 && j.p3) j.q3[co] += j.p3[cp];
-  if (!j.p2) {
-    if (!j.q0) return;
-    for (int i = threadIdx.x; i < n; i += 256) {
-      const int ci = i / j.K, k = i % j.K;
-      j.q0[(size_t)co * n + i] += j.p0[((size_t)k * j.CinP + ci) * j.CoutP + cp];
-    }
-    return;
-  }
-  if (!j.q1 || !j.q2) return;
-  float dot = 0.f, nn = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int ci = i / j.K, k = i % j.K;
-    const float v = j.p2[(size_t)co * n + i];
-    dot = fmaf(j.p0[((size_t)k * j.CinP + ci) * j.CoutP + cp], v, dot);
-    nn = fmaf(v, v, nn);
-  }
-  r1[threadIdx.x] = dot;
-  r2[threadIdx.x] = nn;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      r1[threadIdx.x] += r1[threadIdx.x + o];
-      r2[threadIdx.x] += r2[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  const float norm = sqrtf(r2[0]), d = r1[0], gg = j.p1[co];
-  if (threadIdx.x == 0) j.q1[co] += d / norm;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int ci = i / j.K, k = i % j.K;
-    const float v = j.p2[(size_t)co * n + i];
-    j.q2[(size_t)co * n + i] += gg / norm * (j.p0[((size_t)k * j.CinP + ci) * j.CoutP + cp] - v * d / (norm * norm));
-  }
-}
-int launch_multi(int which, const MultiJob* jobs, const int* job_of_block, int nblocks, hipStream_t st, int blk_base) {
-  if (nblocks <= 0) return STY_OK;
-  if (which == 0)
-    hipLaunchKernelGGL(pack_conv_multi_kernel, dim3(nblocks), dim3(256), 0, st, jobs, job_of_block);
-  else if (which == 1)
-    hipLaunchKernelGGL(pack_dgrad_multi_kernel, dim3(nblocks), dim3(256), 0, st, jobs, job_of_block);
-  else
-    hipLaunchKernelGGL(unpack_grad_multi_kernel, dim3(nblocks), dim3(256), 0, st, jobs, job_of_block, blk_base);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-// 2-D: Wd[kw'][kh'*Cout + co][ci] = Wp[KW-1-kw'][(KH-1-kh')*Cin + ci][co]   (one layer: the spectrogram discriminators,
-// disc.hip; a model's layers go through pack_dgrad_multi_kernel)
-__global__ void pack_dgrad2d_kernel(const float* __restrict__ wp, int KW, int KH, int Cin, int Cout, int CinP,
-                                    int CoutP, int CinPd, int CoutPd, float* __restrict__ wd) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t n = (size_t)KW * KH * Cout * Cin;
-  if (i >= n) return;
-  const int ci = (int)(i % Cin);
-  const int co = (int)((i / Cin) % Cout);
-  const int kh = (int)((i / ((size_t)Cin * Cout)) % KH);
-  const int kw = (int)(i / ((size_t)Cin * Cout * KH));
-  wd[((size_t)kw * CinPd + kh * Cout + co) * CoutPd + ci] =
-      wp[((size_t)(KW - 1 - kw) * CinP + (KH - 1 - kh) * Cin + ci) * CoutP + co];
-}
-int launch_pack_dgrad2d(const float* wp, int KW, int KH, int Cin, int Cout, int CinP, int CoutP, int CinPd, int CoutPd,
-                        float* wd, hipStream_t st) {
-  const size_t n = (size_t)KW * KH * Cout * Cin;
-  hipLaunchKernelGGL(pack_dgrad2d_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wp, KW, KH, Cin, Cout,
-                     CinP, CoutP, CinPd, CoutPd, wd);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-// spectral norm (fixed u, v within a step): W_eff = W / sigma, sigma = u^T W v
-//   dW[co][i] += G[co][i]/sigma - (<G, W>/sigma^2) u[co] v[i],   G taken from the packed gradient.
-// t[co] = u[co] <W[co,:], v> (sn_rowdot_multi_kernel) gives sigma = sum t.  Two steps: <G,W> per row, then apply -- for EVERY
-// spectral-norm conv of a model in two launches (one block per output row of every layer;
-// the style encoder has 13 such layers, and its un-pack is the last thing of the c3 step: 40 serial launches before).
-// p0 = packed weight gradient, p1 = W, p2 = u, p3 = v, p4 = t (sigma row terms), q0 = dW, q1 = <G,W> row sums (scratch),
-// q3 = db, q4 = packed bias gradient (read only)
-__global__ __launch_bounds__(256) void sn_gw_rowdot_multi_kernel(const MultiJob* __restrict__ jobs,
-                                                                 const int* __restrict__ job_of_block) {
-  __shared__ float red[256];
-  const MultiJob j = jobs[job_of_block[blockIdx.x]];
-  const int co = (int)blockIdx.x - j.blk0;
-  const int KW = j.K, KH = j.KH, n = j.Cin * KH * KW;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int kw = i % KW, kh = (i / KW) % KH, ci = i / (KW * KH);
-    s = fmaf(j.p0[((size_t)kw * j.CinP + kh * j.Cin + ci) * j.CoutP + co], j.p1[(size_t)co * n + i], s);
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) j.q1[co] = red[0];
-}
-__global__ __launch_bounds__(256) void sn_unpack_multi_kernel(const MultiJob* __restrict__ jobs,
-                                                              const int* __restrict__ job_of_block) {
-  __shared__ float sig, dot;
-  const MultiJob j = jobs[job_of_block[blockIdx.x]];
-  const int co = (int)blockIdx.x - j.blk0;
-  if (threadIdx.x == 0) {
-    float s = 0.f, d = 0.f;
-    for (int i = 0; i < j.Cout; ++i) {
-      s += j.p4[i];
-      d += j.q1[i];
-    }
-    sig = s;
-    dot = d;
-    if (j.q3 && j.q4) j.q3[co] += j.q4[co];
-  }
-  __syncthreads();
-  if (!j.q0) return;
-  const int KW = j.K, KH = j.KH, n = j.Cin * KH * KW;
-  const float inv = 1.0f / sig, k = dot * inv * inv;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const int kw = i % KW, kh = (i / KW) % KH, ci = i / (KW * KH);
-    j.q0[(size_t)co * n + i] += j.p0[((size_t)kw * j.CinP + kh * j.Cin + ci) * j.CoutP + co] * inv - k * j.p2[co] * j.p3[i];
-  }
-}
-int launch_sn_unpack_multi(const MultiJob* jobs, const int* job_of_block, int nblocks, hipStream_t st) {
-  if (nblocks <= 0) return STY_OK;
-  hipLaunchKernelGGL(sn_gw_rowdot_multi_kernel, dim3(nblocks), dim3(256), 0, st, jobs, job_of_block);
-  hipLaunchKernelGGL(sn_unpack_multi_kernel, dim3(nblocks), dim3(256), 0, st, jobs, job_of_block);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
-// ConvNeXt pwconv2 bias folding b2eff = b2 + W2 . beta (convnext.hip): g = d loss / d b2eff [C]
-// grid: x = 64-channel slice of the 4C axis (dbeta, one wave-quarter of the co loop each, summed through LDS),
-// plus C*4C/256 blocks for the rank-1 dW2 update
-__global__ __launch_bounds__(256) void b2eff_bwd_kernel(const float* __restrict__ g, const float* __restrict__ w2,
-                                                        const float* __restrict__ beta, int C, int nbeta_blocks,
-                                                        float* __restrict__ db2, float* __restrict__ dbeta,
-                                                        float* __restrict__ dW2) {
-  __shared__ float red[4][64];
-  const int C4 = 4 * C;
-  if ((int)blockIdx.x < nbeta_blocks) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ch = blockIdx.x * 64 + lane;
-    float acc = 0.f;
-    if (ch < C4)
-      for (int co = wave; co < C; co += 4) acc = fmaf(w2[(size_t)co * C4 + ch], g[co], acc);
-    red[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && ch < C4 && dbeta) dbeta[ch] += red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-    if (blockIdx.x == 0 && db2)
-      for (int i = threadIdx.x; i < C; i += 256) db2[i] += g[i];
-    return;
-  }
-  const int i = (blockIdx.x - nbeta_blocks) * 256 + threadIdx.x;
-  if (i < C * C4 && dW2) {
-    const int co = i / C4, ch = i % C4;
-    dW2[i] += g[co] * beta[ch];
-  }
-}
-int launch_b2eff_bwd(const float* g, const float* w2, const float* beta, int C, float* db2, float* dbeta, float* dW2,
-                     hipStream_t st) {
-  const int nb = cdiv(4 * C, 64);
-  hipLaunchKernelGGL(b2eff_bwd_kernel, dim3(nb + cdiv(4 * C * C, 256)), dim3(256), 0, st, g, w2, beta, C, nb, db2, dbeta,
-                     dW2);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
 }  // namespace sty

@@ -18,7 +18,7 @@ the mean of the rows in a window that starts at [i, i + 1) and widens by one on 
 table -- for a dataset whose texts are 16..200 tokens long the pack's first rows are the mean over the LONGEST texts, not
 the shortest -- and the process gives up only once `lower < 0 and upper > 512` with the window still short.  That arithmetic
 is reproduced exactly (`resolve_windows`), so a voicepack made here from a reference checkpoint is the one the reference
-would have made; there is no "fixed" mode.  The sums are float64 on the device (csrc/pack.hip), each row of the pack is
+would have made; there is no "fixed" mode.  The sums are float64 on the device (csrc/voicepack.hip), each row of the pack is
 rounded to fp32 once; the reference averages in fp32.
 
 NOT KEPT: tts/cli.py:78 picks row `max(511, min(2, len(tokens)))` with tokens of shape [1, n], which is 511 for every
