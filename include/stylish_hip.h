@@ -247,6 +247,23 @@ int sty_source_fwd(int B, int T, const float *pitch, const float *voiced, const 
                    const float *lin_w, const float *lin_b, float *prior, void *workspace, size_t ws_bytes,
                    void *stream);
 int sty_source_workspace_bytes(int B, int T, size_t *bytes);
+/* Kernels of the backward's normalisation / activation glue alone, for unit tests.                     */
+/* GRN (conv_next.py:15-18) backward on h [B,C4,T], C4 <= 1024: the forward's statistics and scale, then from ds [B,C4]
+ * (= d loss / d scale) coef [B,C4] (d loss / d h += coef[b][c] h) and dgamma [C4] +=.  from_gx != 0: the backward starts
+ * from the per-channel norms the forward kept (as the training graph does); 0: it rebuilds them from the partial sums. */
+int sty_grn_bwd_workspace_bytes(int B, int C4, int T, size_t *bytes);
+int sty_grn_bwd(int B, int C4, int T, const float *h, const float *ds, const float *gamma, int from_gx, float *coef,
+                float *dgamma, void *workspace, size_t ws_bytes, void *stream);
+/* Pointwise activation backward (kind: 1 ReLU, 2 Swish, 3 Snake with alpha [C], 5 exact GELU) on x, dy [B,C,T] -> dx
+ * (accumulate: added to it), dalpha [C] += (Snake; may be NULL).  h [B,C,T], coef [B,C] (both or neither): the output
+ * gradient is dy + coef[b][c] h; fused != 0: formed inside the activation kernel, 0: added to dy IN PLACE by a pass of
+ * its own first.                                                                                                         */
+int sty_act_bwd(int kind, int B, int C, int T, const float *x, float *dy, const float *alpha, const float *h,
+                const float *coef, int fused, float *dx, int accumulate, float *dalpha, void *stream);
+/* AdaIN fold from per-row partial sums part [B*C][nseg][2] doubles (sum, sum of squares over T samples), gb [B,2C] ->
+ * a = (1 + gamma) rstd, s = beta - a mean [B,C]; mean, rstd [B,C] (both or neither): the statistics themselves.       */
+int sty_adain_finalize(int B, int C, int T, int nseg, const double *part, const float *gb, float eps, float *a, float *s,
+                       float *mean, float *rstd, void *stream);
 
 /* ---- training (backward, K15): vocoder first ---------------------------------------------------------
  * sty_model_bind_grad: where the gradient of a bound parameter is ACCUMULATED (zero it yourself, e.g.

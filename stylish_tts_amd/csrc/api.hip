@@ -2708,6 +2708,60 @@ int sty_partial_sum(int dw_form, const float* part, int C, int K, int nblk, floa
   }
   return launch_partial_sum(dw_form, part, C, K, nblk, dw, db, S(stream));
 }
+// ---- unit entries of the backward's normalisation / activation kernels (tests/test_backward_chain.py) ----
+static size_t grn_bwd_ws_bytes(int B, int C4, int T) {  // partials (doubles) | scale | gx
+  return (size_t)B * C4 * row_stats_nseg(T) * 2 * sizeof(double) + (size_t)2 * B * C4 * sizeof(float);
+}
+int sty_grn_bwd_workspace_bytes(int B, int C4, int T, size_t* bytes) {
+  if (!bytes || B <= 0 || C4 <= 0 || T <= 0) {
+    set_error("sty_grn_bwd_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  *bytes = grn_bwd_ws_bytes(B, C4, T);
+  return STY_OK;
+}
+int sty_grn_bwd(int B, int C4, int T, const float* h, const float* ds, const float* gamma, int from_gx, float* coef,
+                float* dgamma, void* workspace, size_t ws_bytes, void* stream) {
+  if (!h || !ds || !gamma || !coef || !dgamma || !workspace || B <= 0 || C4 <= 0 || T <= 0) {
+    set_error("sty_grn_bwd: bad argument");
+    return STY_EINVAL;
+  }
+  if (ws_bytes < grn_bwd_ws_bytes(B, C4, T)) {
+    set_error("sty_grn_bwd: workspace too small");
+    return STY_ENOMEM;
+  }
+  hipStream_t st = S(stream);
+  const int nseg = row_stats_nseg(T);
+  double* part = (double*)workspace;
+  float* scale = (float*)(part + (size_t)B * C4 * nseg * 2);
+  float* gx = scale + (size_t)B * C4;
+  int rc = launch_row_stats(h, B * C4, T, part, st);
+  if (rc) return rc;
+  if ((rc = launch_grn_finalize(part, nseg, gamma, B, C4, scale, st, gx))) return rc;
+  return launch_grn_bwd(from_gx ? gx : nullptr, part, nseg, gamma, ds, B, C4, coef, dgamma, st);
+}
+int sty_act_bwd(int kind, int B, int C, int T, const float* x, float* dy, const float* alpha, const float* h,
+                const float* coef, int fused, float* dx, int accumulate, float* dalpha, void* stream) {
+  if (!x || !dy || !dx || B <= 0 || C <= 0 || T <= 0 || (kind == ACT_SNAKE && !alpha) || ((h != nullptr) != (coef != nullptr))) {
+    set_error("sty_act_bwd: bad argument");
+    return STY_EINVAL;
+  }
+  hipStream_t st = S(stream);
+  if (h && !fused) {  // the row term as a pass of its own: dy += coef[row] * h IN PLACE, then the plain activation backward
+    const int rc = launch_row_scale_add(h, coef, 0.f, B * C, T, dy, st);
+    if (rc) return rc;
+    h = coef = nullptr;
+  }
+  return launch_act_bwd(kind, x, dy, alpha, B, C, T, dx, accumulate, dalpha, st, h, coef);
+}
+int sty_adain_finalize(int B, int C, int T, int nseg, const double* part, const float* gb, float eps, float* a, float* s,
+                       float* mean, float* rstd, void* stream) {
+  if (!part || !gb || !a || !s || B <= 0 || C <= 0 || T <= 0 || nseg <= 0 || ((mean != nullptr) != (rstd != nullptr))) {
+    set_error("sty_adain_finalize: bad argument");
+    return STY_EINVAL;
+  }
+  return launch_adain_finalize(part, nseg, gb, B, C, T, eps, a, s, S(stream), mean, rstd);
+}
 int sty_mel_workspace_bytes(int B, int N, int n_fft, int hop, size_t* bytes) {
   if (!bytes || B <= 0 || N <= n_fft / 2 || n_fft <= 0 || hop <= 0) {
     set_error("sty_mel_workspace_bytes: bad argument");

@@ -359,34 +359,6 @@ int launch_row_axpb(const float* x, const float* c0, const float* c1, int rows, 
   return STY_OK;
 }
 
-// ---- per-row mean / rstd (InstanceNorm statistics kept for the backward) ----
-__global__ __launch_bounds__(256) void adain_stats_kernel(const double* __restrict__ part, int nseg, int rows, int T,
-                                                          float eps, float* __restrict__ mean, float* __restrict__ rstd) {
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;  // one wave per row (see adain_finalize_kernel)
-  if (i >= rows) return;
-  double sum = 0.0, sq = 0.0;
-  for (int k = lane; k < nseg; k += 64) {
-    sum += part[((size_t)i * nseg + k) * 2];
-    sq += part[((size_t)i * nseg + k) * 2 + 1];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o);
-    sq += __shfl_xor(sq, o);
-  }
-  if (lane) return;
-  const double m = sum / T;
-  double var = sq / T - m * m;
-  if (var < 0.0) var = 0.0;
-  mean[i] = (float)m;
-  rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
-}
-int launch_adain_stats(const double* part, int nseg, int rows, int T, float eps, float* mean, float* rstd,
-                       hipStream_t st) {
-  hipLaunchKernelGGL(adain_stats_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, part, nseg, rows, T, eps, mean, rstd);
-  STY_LAUNCH_CHECK();
-  return STY_OK;
-}
-
 // ---- LayerNorm over channels, backward.  dx per column; parameter sums per row. ----
 // y = xhat * A + Bv,  A = w[c] (ada = 0) or 1 + gb[b][c] (ada = 1);  relu / out_mask as in the forward.
 // TC time columns x (256/TC) channel groups per workgroup; the per-column sums are combined through LDS in a fixed
@@ -738,16 +710,19 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
 // ---- GRN backward (conv_next.py:15-18).  Forward: gx = ||h||_2 over time, nx = gx/(mean_c gx + eps),
 // s = 1 + gamma nx, out = h s (+ beta, folded into the next conv's bias).  Input ds[b][c] = d loss / d s. ----
 // One workgroup per batch row -> coef[b][c] = dgx/gx (so that dh += coef * h), dgamma += sum_b ds nx.
-__global__ __launch_bounds__(256) void grn_bwd_kernel(const double* __restrict__ part, int nseg,
+// gx[b][c] = ||h||_2 as the forward's grn_finalize_kernel kept it.  (Rebuilding it here from the forward's double partials --
+// a wave walking 32 channels of 150 segments one after the other on the ConvNeXt32 blocks -- was 40-50 us of latency per
+// launch on the backward's chain; that form stays behind gx == nullptr for the unit entry's comparison only.)
+__global__ __launch_bounds__(256) void grn_bwd_kernel(const float* __restrict__ gx, const double* __restrict__ part, int nseg,
                                                       const float* __restrict__ gamma,
                                                       const float* __restrict__ ds, int C4,
                                                       float* __restrict__ coef, float* __restrict__ dgamma) {
   __shared__ float gxs[1024];
   __shared__ double red[2][4];
   const int b = blockIdx.x;
-  // ||h||^2 per channel: a wave per channel, lanes over the row's segments (one thread per channel walking the 150
-  // segments of a 75T-rate row alone made this 50 us of latency, sixteen times per step, on a tensor of a few KB)
-  if (nseg < 32) {  // short rows (decoder, T = 520: three segments, 1024 channels): a thread per channel
+  if (gx) {
+    for (int c = threadIdx.x; c < C4; c += 256) gxs[c] = gx[(size_t)b * C4 + c];
+  } else if (nseg < 32) {  // short rows (decoder, T = 520: three segments, 1024 channels): a thread per channel
     for (int c = threadIdx.x; c < C4; c += 256) {
       double sq = 0.0;
       for (int k = 0; k < nseg; ++k) sq += part[(((size_t)b * C4 + c) * nseg + k) * 2 + 1];
@@ -787,13 +762,18 @@ __global__ __launch_bounds__(256) void grn_bwd_kernel(const double* __restrict__
     coef[(size_t)b * C4 + c] = gxs[c] > 0.f ? dgx / gxs[c] : 0.f;
   }
 }
-int launch_grn_bwd(const double* part, int nseg, const float* gamma, const float* ds, int B, int C4, float* coef,
-                   float* dgamma, hipStream_t st) {
+int launch_grn_bwd(const float* gx, const double* part, int nseg, const float* gamma, const float* ds, int B, int C4,
+                   float* coef, float* dgamma, hipStream_t st) {
   if (C4 > 1024) {
     set_error("grn_bwd: 4C > 1024");
     return STY_EINVAL;
   }
-  hipLaunchKernelGGL(grn_bwd_kernel, dim3(B), dim3(256), 0, st, part, nseg, gamma, ds, C4, coef, dgamma);
+  if (!gx && !part) {
+    set_error("grn_bwd: neither the forward's norms nor its partials");
+    return STY_EINVAL;
+  }
+  ProfScope prof("grn_bwd_kernel", 0.0, 4.0 * B * C4 * 4, st, gx ? "gx" : "part");
+  hipLaunchKernelGGL(grn_bwd_kernel, dim3(B), dim3(256), 0, st, gx, part, nseg, gamma, ds, C4, coef, dgamma);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -859,10 +839,14 @@ int launch_act_fwd(int kind, const float* x, const float* alpha, int B, int C, i
   return STY_OK;
 }
 // one workgroup per (b,c) row: dx (write / accumulate) and the snake alpha gradient
+// h, coef (optional; not for GLU): a row term the output gradient is still owed, d = dy + coef[b][c] * h (the GRN term of the
+// ConvNeXt block, h = the activation's own output as the forward stored it) -- formed in registers here as the fma that
+// row_scale_add4_kernel compiles to, instead of a pass of its own that reads h and dy and writes dy for this kernel to read
 __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __restrict__ x,
                                                       const float* __restrict__ dy, const float* __restrict__ alpha,
                                                       int C, int T, float* __restrict__ dx, int accumulate,
-                                                      float* __restrict__ dalpha) {
+                                                      float* __restrict__ dalpha, const float* __restrict__ h,
+                                                      const float* __restrict__ coef) {
   __shared__ double red[1][4];
   const int c = blockIdx.x, b = blockIdx.y;
   double acc[1] = {0.0};
@@ -879,6 +863,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __r
   }
   const size_t row = ((size_t)b * C + c) * T;
   const float al = kind == ACT_SNAKE ? alpha[c] : 1.f;
+  const float cf = h ? coef[(size_t)b * C + c] : 0.f;
   auto one = [&](float v, float d) -> float {  // d loss / d x of one element; the Snake alpha term goes to acc
     float g = d;
     if (kind == ACT_RELU) g = v > 0.f ? d : 0.f;
@@ -899,13 +884,19 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __r
     }
     return g;
   };
-  if ((T & 3) == 0 && ((((size_t)(x + row) | (size_t)(dy + row) | (size_t)(dx + row)) & 15) == 0)) {
+  if ((T & 3) == 0 && ((((size_t)(x + row) | (size_t)(dy + row) | (size_t)(dx + row) | (size_t)(h ? h + row : nullptr)) & 15) == 0)) {
     // 16 bytes per lane (rows of 520 samples: three passes of 4-byte accesses before, the third with eight live lanes)
     const float4* x4 = reinterpret_cast<const float4*>(x + row);
     const float4* d4 = reinterpret_cast<const float4*>(dy + row);
     float4* o4 = reinterpret_cast<float4*>(dx + row);
+    const float4* h4 = h ? reinterpret_cast<const float4*>(h + row) : nullptr;
     for (int t = threadIdx.x; t < T / 4; t += 256) {
-      const float4 v = x4[t], d = d4[t];
+      const float4 v = x4[t];
+      float4 d = d4[t];
+      if (h) {
+        const float4 hv = h4[t];
+        d = make_float4(fmaf(hv.x, cf, d.x), fmaf(hv.y, cf, d.y), fmaf(hv.z, cf, d.z), fmaf(hv.w, cf, d.w));
+      }
       float4 g;
       g.x = one(v.x, d.x);
       g.y = one(v.y, d.y);
@@ -919,7 +910,9 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __r
     }
   } else
   for (int t = threadIdx.x; t < T; t += 256) {
-    const float v = x[row + t], d = dy[row + t];
+    const float v = x[row + t];
+    float d = dy[row + t];
+    if (h) d = fmaf(h[row + t], cf, d);
     float g = d;
     if (kind == ACT_RELU) g = v > 0.f ? d : 0.f;
     else if (kind == ACT_SWISH) {
@@ -945,8 +938,13 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __r
   }
 }
 int launch_act_bwd(int kind, const float* x, const float* dy, const float* alpha, int B, int C, int T, float* dx,
-                   int accumulate, float* dalpha, hipStream_t st) {
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(C, B), dim3(256), 0, st, kind, x, dy, alpha, C, T, dx, accumulate, dalpha);
+                   int accumulate, float* dalpha, hipStream_t st, const float* h, const float* coef) {
+  if (h && (kind == ACT_GLU || !coef)) {
+    set_error("act_bwd: a row term needs its coefficients and a one-to-one activation");
+    return STY_EINVAL;
+  }
+  ProfScope prof("act_bwd_kernel", 0.0, 4.0 * B * C * T * (3.0 + (accumulate ? 1 : 0) + (h ? 1 : 0)), st, h ? "row term" : nullptr);
+  hipLaunchKernelGGL(act_bwd_kernel, dim3(C, B), dim3(256), 0, st, kind, x, dy, alpha, C, T, dx, accumulate, dalpha, h, coef);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -973,6 +971,7 @@ __global__ __launch_bounds__(256) void row_scale_add4_kernel(const float* __rest
   reinterpret_cast<float4*>(dst)[idx] = d;
 }
 int launch_row_scale_add(const float* src, const float* coef, float k, int rows, int T, float* dst, hipStream_t st) {
+  ProfScope prof(coef ? "row_scale_add_kernel[coef]" : "row_scale_add_kernel", 0.0, 12.0 * rows * T, st);
   const size_t n4 = (size_t)rows * (T / 4);
   if (vec4_ok(n4, T, src, dst)) {
     hipLaunchKernelGGL(row_scale_add4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, src, coef, k,

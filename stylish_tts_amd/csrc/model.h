@@ -283,8 +283,6 @@ int launch_row_axpb(const float* x, const float* c0, const float* c1, int rows, 
 int launch_pro_bwd_adain(const void* u, int uh, const void* x, int xh, int B, int C, int T, const float* pa, const float* ps,
                          const float* alpha, const float* mean, const float* rstd, const float* gb, void* dx, int dh,
                          int accumulate, float* dgb, float* dalpha, int hw, hipStream_t st, const void* dsrc = nullptr);
-int launch_adain_stats(const double* part, int nseg, int rows, int T, float eps, float* mean, float* rstd,
-                       hipStream_t st);
 // plain casts between an fp32 tensor and a two-byte one (test aids of the block entry point)
 int launch_cast_f32_to_16(const float* x, size_t n, void* y16, hipStream_t st);
 int launch_cast_16_to_f32(const void* x16, size_t n, float* y, hipStream_t st);
@@ -293,11 +291,14 @@ bool chan_ln32_eligible(int B, int C, int T, int relu);  // the one-thread-per-c
 int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, int C, int T, float eps, int ada,
                        const float* w, const float* gb, int relu, const float* out_mask, float* dx, int accumulate,
                        float* mu_tmp, float* r_tmp, float* dgb, float* dw, float* db, hipStream_t st, int h16 = 0);
-int launch_grn_bwd(const double* part, int nseg, const float* gamma, const float* ds, int B, int C4, float* coef,
-                   float* dgamma, hipStream_t st);
+// gx [B][C4]: the forward's per-channel norms (launch_grn_finalize).  gx == nullptr (the unit entry's comparison only): they
+// are rebuilt from the forward's partials (part, nseg)
+int launch_grn_bwd(const float* gx, const double* part, int nseg, const float* gamma, const float* ds, int B, int C4,
+                   float* coef, float* dgamma, hipStream_t st);
 int launch_act_fwd(int kind, const float* x, const float* alpha, int B, int C, int T, float* y, hipStream_t st);
+// h, coef [B][C] (optional): the output gradient is dy + coef[b][c] * h, formed in the kernel (the GRN term)
 int launch_act_bwd(int kind, const float* x, const float* dy, const float* alpha, int B, int C, int T, float* dx,
-                   int accumulate, float* dalpha, hipStream_t st);
+                   int accumulate, float* dalpha, hipStream_t st, const float* h = nullptr, const float* coef = nullptr);
 int launch_row_scale_add(const float* src, const float* coef, float k, int rows, int T, float* dst, hipStream_t st);
 int launch_dwconv_fwd(const float* x, const float* w, const float* bias, int B, int C, int T, int K, int pad, float* y,
                       hipStream_t st);

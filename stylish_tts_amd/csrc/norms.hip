@@ -80,7 +80,8 @@ int launch_row_stats(const float* x, int rows, int T, double* part, hipStream_t 
 // took 20-50 us per call at 235 segments: a 256-thread launch of serial dependent adds.)
 __global__ __launch_bounds__(256) void adain_finalize_kernel(const double* __restrict__ part, int nseg,
                                                              const float* __restrict__ gb, int B, int C, int T, float eps,
-                                                             float* __restrict__ a, float* __restrict__ s) {
+                                                             float* __restrict__ a, float* __restrict__ s,
+                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= B * C) return;
   const int b = i / C, c = i % C;
@@ -102,11 +103,16 @@ __global__ __launch_bounds__(256) void adain_finalize_kernel(const double* __res
   const float av = g * rstd;
   a[i] = av;
   s[i] = be - av * (float)mean;
+  if (mean_out) {  // the training graph keeps the statistics for the backward (the same doubles, rounded once)
+    mean_out[i] = (float)mean;
+    rstd_out[i] = rstd;
+  }
 }
 
 int launch_adain_finalize(const double* part, int nseg, const float* gb, int B, int C, int T, float eps, float* a,
-                          float* s, hipStream_t st) {
-  hipLaunchKernelGGL(adain_finalize_kernel, dim3(cdiv(B * C, 4)), dim3(256), 0, st, part, nseg, gb, B, C, T, eps, a, s);
+                          float* s, hipStream_t st, float* mean, float* rstd) {
+  hipLaunchKernelGGL(adain_finalize_kernel, dim3(cdiv(B * C, 4)), dim3(256), 0, st, part, nseg, gb, B, C, T, eps, a, s, mean,
+                     rstd);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -116,7 +122,7 @@ int launch_adain_finalize(const double* part, int nseg, const float* gb, int B, 
 // works on 64 / G channels at a time.  (256 threads with one serial loop per channel took 17-25 us per call.)
 __global__ __launch_bounds__(1024) void grn_finalize_kernel(const double* __restrict__ part, int nseg, int G,
                                                             const float* __restrict__ gamma, int C4,
-                                                            float* __restrict__ scale) {
+                                                            float* __restrict__ scale, float* __restrict__ gx_out) {
   __shared__ float red[16];
   __shared__ float gxs[1024];
   const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -133,6 +139,7 @@ __global__ __launch_bounds__(1024) void grn_finalize_kernel(const double* __rest
     if (gl == 0 && c < C4) {
       const float gx = (float)sqrt(sq);
       gxs[c] = gx;
+      if (gx_out) gx_out[(size_t)b * C4 + c] = gx;  // kept for the backward (grn_bwd_kernel)
       loc += gx;
     }
   }
@@ -147,14 +154,14 @@ __global__ __launch_bounds__(1024) void grn_finalize_kernel(const double* __rest
 }
 
 int launch_grn_finalize(const double* part, int nseg, const float* gamma, int B, int C4, float* scale,
-                        hipStream_t st) {
+                        hipStream_t st, float* gx) {
   if (C4 > 1024) {
     set_error("grn_finalize: 4C = %d > 1024", C4);
     return STY_EINVAL;
   }
   int G = 1;
   while (G < 64 && G < nseg) G <<= 1;
-  hipLaunchKernelGGL(grn_finalize_kernel, dim3(B), dim3(1024), 0, st, part, nseg, G, gamma, C4, scale);
+  hipLaunchKernelGGL(grn_finalize_kernel, dim3(B), dim3(1024), 0, st, part, nseg, G, gamma, C4, scale, gx);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

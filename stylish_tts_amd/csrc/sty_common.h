@@ -361,9 +361,12 @@ int row_stats_nseg(int T);
 int launch_row_stats(const float* x, int rows, int T, double* part, hipStream_t st);
 // AdaIN fold: gb = fc(style) [B][2C] -> a = (1+gamma)*rstd, s = beta - a*mean
 int launch_adain_finalize(const double* part, int nseg, const float* gb, int B, int C, int T, float eps, float* a,
-                          float* s, hipStream_t st);
+                          float* s, hipStream_t st, float* mean = nullptr, float* rstd = nullptr);
+// (mean / rstd [B C], optional: the statistics themselves, kept by the training graph for the backward)
 // GRN: part holds sum of h^2 per (b,ch) -> scale[b][ch] = 1 + gamma[ch]*gx/(mean_ch gx + 1e-6)
-int launch_grn_finalize(const double* part, int nseg, const float* gamma, int B, int C4, float* scale, hipStream_t st);
+// gx [B][C4], optional: the per-channel norms ||h||_2 the scale was made from (kept by the training graph for launch_grn_bwd)
+int launch_grn_finalize(const double* part, int nseg, const float* gamma, int B, int C4, float* scale, hipStream_t st,
+                        float* gx = nullptr);
 // LayerNorm over channels of [B,C,T]; ada=0: y = LN(x)*w[c]+b[c];  ada=1: y = LN(x)*(1+gb[b][c]) + gb[b][C+c]
 int launch_chan_layernorm(const float* x, float* y, int B, int C, int T, float eps, int ada, const float* w,
                           const float* bvec, const float* gb, int relu, const float* out_mask, hipStream_t st);

@@ -81,6 +81,7 @@ struct Trainer {
     g_no_fp32.clear();
     lazy_mask.clear();
     pend_up.clear();
+    pend_row.clear();
     nograd.clear();
     half_.clear();
     g16_ok.clear();
@@ -179,6 +180,7 @@ struct Trainer {
     // an error left the loop before the branch's place: the caller's style stream is joined all the same
     if (br_end) (void)hipStreamWaitEvent(st, br_end, 0);
     while (flush_up && rc == STY_OK && !pend_up.empty()) up_flush(pend_up.begin()->first);
+    while (rc == STY_OK && !pend_row.empty()) row_flush(pend_row.begin()->first);
     side_join();
     if (fc && rc == STY_OK) style_fc_backward();
   }
@@ -486,9 +488,34 @@ struct Trainer {
     chk(launch_pro_bwd(PRO_LRELU, g, C, 0, act, B, C, n, nullptr, nullptr, C, 0, nullptr, nullptr, g, 0, nullptr, nullptr,
                        nullptr, st));
   }
-  // raw: the caller deals with a deferred gate itself; keep_lazy: ... and with a pending masked copy (lazy_mask)
-  float* G(const float* act, size_t n, bool raw = false, bool keep_lazy = false) {
+  // pend_row = activation h -> the row term coef[b][c] * h its gradient buffer is still owed (the GRN term of convnext()):
+  // the activation backward of act() forms it in registers on its way (take_row); anybody else who asks for G(h) first
+  // gets it through G / Gw, which run the plain pass (row_flush).
+  struct PendRow {
+    const float* coef;
+    int rows, T;
+  };
+  std::unordered_map<const float*, PendRow> pend_row;
+  void row_flush(const float* act) {
+    auto it = pend_row.find(act);
+    if (it == pend_row.end()) return;
+    const PendRow p = it->second;
+    pend_row.erase(it);
+    float* g = G(act, (size_t)p.rows * p.T);  // (the entry is erased: no way back here)
+    if (live()) chk(launch_row_scale_add(act, p.coef, 0.f, p.rows, p.T, g, st));
+  }
+  const float* take_row(const float* act) {  // the pending term's coefficients (nullptr: none); the caller applies it
+    auto it = pend_row.find(act);
+    if (it == pend_row.end()) return nullptr;
+    const float* coef = it->second.coef;
+    pend_row.erase(it);
+    return coef;
+  }
+  // raw: the caller deals with a deferred gate itself; keep_lazy: ... and with a pending masked copy (lazy_mask);
+  // keep_row: ... and with a pending row term (pend_row)
+  float* G(const float* act, size_t n, bool raw = false, bool keep_lazy = false, bool keep_row = false) {
     if (!pend_up.empty()) up_flush(act);
+    if (!keep_row && !pend_row.empty()) row_flush(act);
     if (!raw && !ungated.empty()) gate_flush(act);
     if (!keep_lazy && !lazy_mask.empty()) mask_flush(act);
     auto it = gmap.find(act);
@@ -509,6 +536,7 @@ struct Trainer {
   // (acc = 0) and no zero-fill is issued; later writers accumulate
   float* Gw(const float* act, size_t n, int& acc) {
     if (!pend_up.empty()) up_flush(act);
+    if (!pend_row.empty()) row_flush(act);
     if (!ungated.empty()) gate_flush(act);
     if (mask_pending(act)) {  // a second writer: the buffer gets its values now, and the shared twin is no longer its twin
       tw_g.erase(lazy_mask[act].dst);
@@ -789,11 +817,12 @@ struct Trainer {
     if (live()) chk(launch_act_fwd(kind, x, alpha, B, C, Tt, y, st));
     tape.push_back([=]() {
       const int Cin = kind == ACT_GLU ? 2 * C : C;
-      float* gY = G(y, (size_t)B * C * Tt);
+      float* gY = G(y, (size_t)B * C * Tt, false, false, kind != ACT_GLU);
+      const float* row = take_row(y);  // a row term G(y) is still owed (the GRN term): d = gY + row[b][c] * y in the kernel
       int acc = 1;
       float* gX = Gw(x, (size_t)B * Cin * Tt, acc);
       float* dal = kind == ACT_SNAKE ? PG(alpha, C) : nullptr;
-      if (live()) chk(launch_act_bwd(kind, x, gY, alpha, B, C, Tt, gX, acc, dal, st));
+      if (live()) chk(launch_act_bwd(kind, x, gY, alpha, B, C, Tt, gX, acc, dal, st, row ? y : nullptr, row));
     });
     return y;
   }
@@ -887,10 +916,7 @@ struct Trainer {
       if (live()) chk(launch_row_stats(x, B * C, Tt, p2, st));
       part = p2;
     }
-    if (live()) {
-      chk(launch_adain_finalize(part, nseg, gbp(fc), B, C, Tt, 1e-5f, a, s, st));
-      chk(launch_adain_stats(part, nseg, B * C, Tt, 1e-5f, mean, rstd, st));
-    }
+    if (live()) chk(launch_adain_finalize(part, nseg, gbp(fc), B, C, Tt, 1e-5f, a, s, st, mean, rstd));
     const float* gbl = gbp(fc);
     float* dgl = dgbp(fc);
     float* aa = a;
@@ -960,6 +986,7 @@ struct Trainer {
     const size_t n32 = (size_t)B * 32 * Tt, n128 = (size_t)B * 128 * Tt;
     double* part = take<double>((size_t)B * 128 * nt * 2);
     float* scale = take<float>((size_t)B * 128);
+    float* gxn = take<float>((size_t)B * 128);  // ||h||_2 per (b, channel): the GRN backward starts from it
     float* y = take<float>(n32);
     // bf16 mode: the forward keeps the Snake output h as bf16 for the lean backward (convnext_bwd.hip, end of file)
     const bool lean = m->topts.compute_bf16 && Tt % 8 == 0 && getenv("STY_NO_WGRADB") == nullptr &&
@@ -987,7 +1014,7 @@ struct Trainer {
       a.bf16 = m->topts.compute_bf16;
       a.h16 = h16;
       chk(launch_convnext32(a, B, 1, st));
-      chk(launch_grn_finalize(part, nt, c.grn_gamma, B, 128, scale, st));
+      chk(launch_grn_finalize(part, nt, c.grn_gamma, B, 128, scale, st, gxn));
       chk(launch_convnext32(a, B, 2, st));
     }
     if (lean && grad16_stream_on()) g16_ok.insert(y);  // the lean backward reads gY as bf16 when its consumer wrote it so
@@ -1108,7 +1135,7 @@ struct Trainer {
         if (live()) {
           chk(launch_wgrad_cnx(1, h16, gY, B, Tt, pM, 1, st, 1, gy16));
           chk(launch_cnx_m_finish(pM, B, SB, c.w2_raw, scale, ds, frozen ? nullptr : gw2, frozen ? nullptr : gb2, st));
-          chk(launch_grn_bwd(part, nt, c.grn_gamma, ds, B, 128, coef, PG(c.grn_gamma, 128), st));
+          chk(launch_grn_bwd(gxn, nullptr, 0, c.grn_gamma, ds, B, 128, coef, PG(c.grn_gamma, 128), st));
           chk(launch_convnext32_bwd(a, B, 2, st));
           chk(launch_cnx_partial_sum(pgb, B, 64, nt_b, 2, dgl, st));
         }
@@ -1118,7 +1145,7 @@ struct Trainer {
         a1.ntiles = nt;
         chk(launch_convnext32_bwd(a1, B, 1, st));
         chk(launch_cnx_partial_sum(pds, B, 128, nt, 0, ds, st));
-        chk(launch_grn_bwd(part, nt, c.grn_gamma, ds, B, 128, coef, PG(c.grn_gamma, 128), st));
+        chk(launch_grn_bwd(gxn, nullptr, 0, c.grn_gamma, ds, B, 128, coef, PG(c.grn_gamma, 128), st));
         chk(launch_convnext32_bwd(a, B, 2, st));
         chk(launch_cnx_partial_sum(pds, B, 128, nt_b, 1, dal, st));
         chk(launch_cnx_partial_sum(pgb, B, 64, nt_b, 2, dgl, st));
@@ -1191,21 +1218,21 @@ struct Trainer {
     const int nseg = row_stats_nseg(Tt);
     double* part = take<double>((size_t)B * 4 * C * nseg * 2);
     float* scale = take<float>((size_t)B * 4 * C);
+    float* gxn = take<float>((size_t)B * 4 * C);  // ||h||_2 per (b, channel), kept for the GRN backward
     if (live()) {
       chk(launch_row_stats(h, B * 4 * C, Tt, part, st));
-      chk(launch_grn_finalize(part, nseg, c.grn_gamma, B, 4 * C, scale, st));
+      chk(launch_grn_finalize(part, nseg, c.grn_gamma, B, 4 * C, scale, st, gxn));
     }
     const float* gamma = c.grn_gamma;
     tape.push_back([=]() {
       float* dsc = G(scale, (size_t)B * 4 * C);
-      float* gH = G(h, (size_t)B * 4 * C * Tt);
-      const size_t mark = ws.off;
+      G(h, (size_t)B * 4 * C * Tt);  // (the buffer exists: pwconv2's backward wrote it)
+      // coef stays taken (no mark / restore here): it has to outlive this entry, until act()'s entry -- the next one of this
+      // block -- or row_flush has read it; B 4C floats a block, to the end of the backward, counted by the sizing pass
       float* coef = take<float>((size_t)B * 4 * C);
-      if (live()) {
-        chk(launch_grn_bwd(part, nseg, gamma, dsc, B, 4 * C, coef, PG(gamma, 4 * C), st));
-        chk(launch_row_scale_add(h, coef, 0.f, B * 4 * C, Tt, gH, st));
-      }
-      ws.off = mark;
+      if (live()) chk(launch_grn_bwd(gxn, nullptr, 0, gamma, dsc, B, 4 * C, coef, PG(gamma, 4 * C), st));
+      // gH += coef * h is owed, not run: h's producer is act(), whose backward reads gH next and forms the term itself
+      pend_row[h] = PendRow{coef, B * 4 * C, Tt};
     });
     float* y = take<float>((size_t)B * C * Tt);
     ConvArgs b2 = base(c.pw2, h, Tt, y);

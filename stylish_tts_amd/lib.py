@@ -120,6 +120,10 @@ SYMBOLS = {
     "sty_conv1d_bwd_workspace_bytes": (C.c_int, [_I, _I, _I, _I, _I, _SZP]),
     "sty_conv1d_bwd": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
     "sty_partial_sum": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
+    "sty_grn_bwd_workspace_bytes": (C.c_int, [_I, _I, _I, _SZP]),
+    "sty_grn_bwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, C.c_size_t, _P]),
+    "sty_act_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "sty_adain_finalize": (C.c_int, [_I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
     "sty_adamw_step": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                  _I, C.c_float, _P]),
     "sty_adamw_step_scaled": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_double, _P, C.c_float, C.c_float, C.c_float,

@@ -40,6 +40,9 @@ python tools/rocpd_summary.py $O/c5b_trace/*/*_results.db > $O/${tag}_c5-bf16_ke
 python tools/stream_busy.py $O/c3_trace/*/*_results.db 6 > $O/${tag}_c3_streams.txt
 # where the main stream waits inside one timed step (the last steps of a bench run are its single-stream extras: skip 6)
 python tools/step_gaps.py $O/c3_trace/*/*_results.db 6 150 > $O/${tag}_c3_gaps.txt
+# launches of one kernel by call site (the kernel before them on the stream): the ConvNeXt32 and the generic blocks' GRN / activation backward
+python tools/kernel_split.py $O/c3_trace/*/*_results.db grn_bwd_kernel > $O/${tag}_c3_grn_bwd_split.txt
+python tools/kernel_split.py $O/c3_trace/*/*_results.db act_bwd_kernel >> $O/${tag}_c3_grn_bwd_split.txt
 python tools/step_gaps.py $O/c2_trace/*/*_results.db 6 150 > $O/${tag}_c2_gaps.txt
 # the traffic files AND the kernel tables have to be where bench.py looks for them before the bench lines are taken (round 6:
 # the roofline's kernel is the top row of the committed table of the same command)
