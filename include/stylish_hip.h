@@ -401,6 +401,18 @@ int sty_pitch_style_fwd_train(sty_model *m, int B, int T, const float *mel, cons
 int sty_conv1d_workspace_bytes(int Cout, int Cin, int K, size_t *bytes);
 int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float *x, const float *w, const float *bias,
                    float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
+/* The same conv with the fused prologue and output stage of the text encoder's convs: x * in_mask[b,t] in front (in_mask [B,T] or
+ * NULL), then y = relu?(conv + bias) * out_mask (before the residual, or behind it with out_mask_post) + residual; every tensor
+ * fp32, compute_bf16 0 or 1.                                                                                              */
+int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const float *x, const float *w, const float *bias,
+                      const float *in_mask, const float *residual, const float *out_mask, int out_mask_post, int relu,
+                      float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
+/* Which kernel family the dispatch picks for a conv of this shape carrying the operands named in `flags` (host only, nothing is
+ * launched): *kernel = position in the dispatch order's list of families (STY_CONV_*), -1 where the conv is refused.      */
+enum { STY_ROUTE_IN_MASK = 1, STY_ROUTE_RESIDUAL = 2, STY_ROUTE_OUT_MASK = 4, STY_ROUTE_RELU = 8, STY_ROUTE_TWO_BYTE_X = 16,
+       STY_ROUTE_STATS = 32, STY_ROUTE_Y16 = 64, STY_ROUTE_X16 = 128 };
+enum { STY_CONV_STEM2D = 0, STY_CONV_32P, STY_CONV_SC, STY_CONV_K1, STY_CONV_Q, STY_CONV_P16, STY_CONV_TILED };
+int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int compute_bf16, int flags, int *kernel);
 /* Gradients of the same conv on the kernels the training graph uses: dw [Cout,Cin,K] and dbias [Cout] (or NULL) from
  * (x, gy [B,Cout,T]) on the weight-gradient kernels (wgrad.hip), dx [B,Cin,T] (or NULL) on the implicit-GEMM kernel
  * with the flipped weights.  compute_bf16 as in sty_train_opts; 3: bf16 mode with x a bf16 tensor [B,Cin,T] (two-byte

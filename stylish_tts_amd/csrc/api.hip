@@ -2602,6 +2602,92 @@ static PackedConv unit_conv_dims(int Cin, int Cout, int K) {
   pc.CoutP = (int)align_up(Cout, 32);  // the model's padding rule (prepare_conv)
   return pc;
 }
+// the same conv with the fused prologue / output stage the text encoder's convs use (fp32 tensors only)
+int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const float* x, const float* w, const float* bias,
+                      const float* in_mask, const float* residual, const float* out_mask, int out_mask_post, int relu, float* y,
+                      void* workspace, size_t ws_bytes, int compute_bf16, void* stream) {
+  size_t need = 0;
+  int rc = sty_conv1d_workspace_bytes(Cout, Cin, K, &need);
+  if (rc) return rc;
+  if (!x || !w || !y || !workspace || B <= 0 || T <= 0 || dil <= 0 || (K - 1) * dil > 128 || ws_bytes < need ||
+      !(compute_bf16 == 0 || compute_bf16 == 1)) {
+    set_error("sty_conv1d_fwd_ex: bad argument, halo > 128, a compute mode other than 0 / 1 or workspace too small");
+    return STY_EINVAL;
+  }
+  PackedConv pc;
+  pc.Cin = Cin;
+  pc.Cout = Cout;
+  pc.K = K;
+  pc.CinP = (int)align_up(Cin, CI_CHUNK);
+  pc.CoutP = (int)align_up(Cout, 32);  // the model's padding rule (prepare_conv)
+  float* wp = reinterpret_cast<float*>(align_up(reinterpret_cast<size_t>(workspace), 256));
+  float* bp = wp + (size_t)K * pc.CinP * pc.CoutP;
+  STY_HIP(hipMemsetAsync(wp, 0, ((size_t)K * pc.CinP * pc.CoutP + pc.CoutP) * sizeof(float), S(stream)));
+  rc = launch_pack_conv(w, nullptr, nullptr, bias, Cout, Cin, K, wp, bp, pc.CinP, pc.CoutP, S(stream));
+  if (rc) return rc;
+  pc.wp = wp;
+  pc.bias = bias ? bp : nullptr;
+  ConvArgs a;
+  a.x[0] = x;
+  a.xc[0] = Cin;
+  a.nsrc = 1;
+  a.B = B;
+  a.T = T;
+  a.w = pc;
+  a.dil = dil;
+  a.pad = (K - 1) * dil / 2;
+  a.y = y;
+  a.bf16 = compute_bf16;
+  if (in_mask) {
+    a.pro = PRO_MASK;
+    a.mask = in_mask;
+  }
+  a.act = relu ? ACT_RELU : ACT_NONE;
+  a.residual = residual;
+  a.out_mask = out_mask;
+  a.out_mask_post = out_mask ? out_mask_post : 0;
+  return launch_conv1d(a, S(stream));
+}
+// Which kernel family launch_conv1d picks for a conv of this shape (host only, nothing is launched): *kernel = the ConvKernel
+// value, -1 where the conv is refused.  flags: STY_ROUTE_* of stylish_hip.h, operands the conv would carry.
+int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int compute_bf16, int flags, int* kernel) {
+  if (!kernel || B <= 0 || Cin <= 0 || Cout <= 0 || K <= 0 || T <= 0 || dil <= 0) {
+    set_error("sty_conv1d_route: bad argument");
+    return STY_EINVAL;
+  }
+  static_assert(STY_CONV_STEM2D == CONV_STEM2D && STY_CONV_32P == CONV_32P && STY_CONV_SC == CONV_SC && STY_CONV_K1 == CONV_K1 &&
+                    STY_CONV_Q == CONV_Q && STY_CONV_P16 == CONV_P16 && STY_CONV_TILED == CONV_TILED,
+                "stylish_hip.h lists the families in the order of ConvKernel");
+  static float dummy_f[4];
+  static double dummy_d[4];
+  static __bf16 dummy_h[4];
+  ConvArgs a;
+  a.x[0] = dummy_f;
+  a.xc[0] = Cin;
+  a.nsrc = 1;
+  a.B = B;
+  a.T = T;
+  a.w = unit_conv_dims(Cin, Cout, K);
+  a.w.wp = dummy_f;
+  a.dil = dil;
+  a.pad = (K - 1) * dil / 2;
+  a.y = dummy_f;
+  a.bf16 = compute_bf16 != 0;
+  if (flags & STY_ROUTE_IN_MASK) {
+    a.pro = PRO_MASK;
+    a.mask = dummy_f;
+  }
+  if (flags & STY_ROUTE_RESIDUAL) a.residual = dummy_f;
+  if (flags & STY_ROUTE_OUT_MASK) a.out_mask = dummy_f;
+  if (flags & STY_ROUTE_RELU) a.act = ACT_RELU;
+  if (flags & STY_ROUTE_TWO_BYTE_X) a.xh = 1;
+  if (flags & STY_ROUTE_STATS) a.stat_part = dummy_d;
+  if (flags & STY_ROUTE_Y16) a.y16 = dummy_h;
+  if (flags & STY_ROUTE_X16) a.x16 = dummy_h;
+  const ConvRoute r = conv1d_route(a);
+  *kernel = r.refusal == CONV_OK ? (int)r.kernel : -1;
+  return STY_OK;
+}
 int sty_conv1d_bwd_workspace_bytes(int B, int Cin, int Cout, int K, int T, size_t* bytes) {
   if (!bytes || B <= 0 || Cin <= 0 || Cout <= 0 || K <= 0 || T <= 0) {
     set_error("sty_conv1d_bwd_workspace_bytes: bad argument");

@@ -452,11 +452,13 @@ static int launch_tiled(const ConvArgs& a, hipStream_t st) {
 // family reads its switches and thresholds in its predicate).  conv1d_route is their only caller and the only statement of the order.
 bool stem2d_eligible(const ConvArgs& a);   // conv2d.hip
 bool conv32p_eligible(const ConvArgs& a);  // conv32p.hip
+bool convsc_eligible(const ConvArgs& a);   // convsc.hip
 bool convk1_eligible(const ConvArgs& a);   // convk1.hip
 bool convp16_eligible(const ConvArgs& a);  // convp16.hip
 bool convq_eligible(const ConvArgs& a);    // convq.hip
 int launch_stem2d(const ConvArgs& a, hipStream_t st);
 int launch_conv32p(const ConvArgs& a, hipStream_t st);
+int launch_convsc(const ConvArgs& a, hipStream_t st);
 int launch_convk1(const ConvArgs& a, hipStream_t st);
 int launch_convq(const ConvArgs& a, hipStream_t st);
 int launch_convp16(const ConvArgs& a, hipStream_t st);
@@ -471,6 +473,8 @@ ConvRoute conv1d_route(const ConvArgs& a) {
     r.refusal = CONV_NO_TWO_BYTE;
   else if (a.stat_part)
     r.refusal = CONV_NO_STATS;
+  else if (convsc_eligible(a))  // (few columns: in front of the two families that would take these shapes at their thresholds)
+    r.kernel = CONV_SC;
   else if (convk1_eligible(a))
     r.kernel = CONV_K1;
   else if (convp16_eligible(a))
@@ -519,6 +523,7 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
   switch (r.kernel) {
     case CONV_STEM2D: rc = launch_stem2d(a, st); break;
     case CONV_32P: rc = launch_conv32p(a, st); break;
+    case CONV_SC: rc = launch_convsc(a, st); break;
     case CONV_K1: rc = launch_convk1(a, st); break;
     case CONV_Q: rc = launch_convq(a, st); break;
     case CONV_P16: rc = launch_convp16(a, st); break;

@@ -263,6 +263,7 @@ int launch_wgradb16(const ConvArgs& fwd, int nsplit, float* partial, int want_bi
 enum ConvKernel : int {
   CONV_STEM2D,  // conv2d.hip: Conv2d(1 -> C, 3 x 3) of the style encoder's stem, VALU, store-bound
   CONV_32P,     // conv32p.hip: persistent, wave-specialised kernel for the 32 -> 32 channel convs at the 75T rate
+  CONV_SC,      // convsc.hip: few output columns (the text encoder), K = 1 / 3 / 5: 64 x 32 tiles, one stage, fp32 in and out only
   CONV_K1,      // convk1.hip: K = 1 as a plain GEMM (transposing LDS reads)
   CONV_Q,       // convq.hip: convp16's job on bf16 operand twins (ConvArgs::x16), K = 1 / 3: 96 x 256 tiles, wide loads
   CONV_P16,     // convp16.hip: persistent producer / consumer kernel of the bf16 compute mode for Cin >= 64
