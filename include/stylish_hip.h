@@ -43,6 +43,7 @@ const char *sty_last_error(void);
  *       "mel_style_encoder"  = train/models/mel_style_encoder.py:121-152
  *       "text_aligner"       = train/models/text_aligner.py:33-45 (inference only, see sty_aligner_fwd)
  *       "text_aligner_train" = the same module with a training graph (see sty_aligner_fwd_train)
+ *       "rmvpe"              = train/dataprep/rmvpe/model.py:49-86 E2E0 (inference only, see sty_rmvpe_fwd)
  * Dimensions are taken from the bound tensors' shapes (train/config/model.yml defaults are checked).   */
 int sty_model_create(const char *kind, sty_model **out);
 void sty_model_destroy(sty_model *m);
@@ -173,6 +174,36 @@ int sty_forced_align_workspace_bytes(int B, int T, int U, size_t *bytes);
 int sty_forced_align(int B, int T, int V1, int U, const float *log_probs, const int64_t *targets,
                      const int64_t *input_lengths, const int64_t *target_lengths, int blank, int32_t *labels,
                      float *scores, int32_t *status, void *workspace, size_t ws_bytes, void *stream);
+
+/* ---- pitch extraction (train/cli.py:205-243 `pitch --method rmvpe`, train/dataprep/pitch_extractor.py:137-149,
+ *      train/dataprep/rmvpe/; `python -m stylish_tts_amd.pitch`) --------------------------------------------------------
+ * Model kind "rmvpe" = E2E0(n_blocks, 1, (2, 2), 5, inter_layers, 1, en_out_channels) in eval mode (rmvpe/model.py:49-86,
+ * deepunet.py, seq.py), bound by the reference's state_dict keys (unet.encoder.bn.*, unet.encoder.layers.L.conv.J.{conv.0,
+ * conv.1, conv.3, conv.4, shortcut}.*, unet.intermediate.layers.I.conv.J.*, unet.decoder.layers.L.{conv1.0, conv1.1,
+ * conv2.J}.*, cnn.*, fc.0.gru.{weight,bias}_{ih,hh}_l0[_reverse], fc.1.*); n_blocks, inter_layers and en_out_channels are
+ * read from the bound tensors, five encoder / decoder levels, 128 mel bins, one BiGRU layer of 256 and 360 classes are fixed.
+ * Inference only, fp32 operands (pitch values hang on an arg-max): compute_bf16, sty_model_enable_training and
+ * sty_model_bind_grad return STY_EINVAL for this kind.
+ * Front end (rmvpe/inference.py:45-60, rmvpe/spec.py): audio [B,N] at 24 kHz -> torchaudio Resample(24000, 16000,
+ * lowpass_filter_width=128) (sinc_interp_hann, rolloff 0.99: two phases of 391 taps at stride 3, M = ceil(2N/3) samples) ->
+ * MelSpectrogram(128, 16000, 1024, 200, None, 30, 8000): periodic hann, centre / reflect, MAGNITUDE spectrum, librosa
+ * mel(htk=True) with Slaney normalisation, log(clamp(., 1e-5)) -> logmel [B,128,n], n = M / 200 + 1.  torchaudio and librosa
+ * are restated from their documented closed forms: PARITY UNPINNED at this boundary.  The two tables, evaluated in double
+ * and rounded to fp32 once, HOST memory: resample kernel [2][391] (phase, tap), mel basis [128][513].                    */
+void sty_rmvpe_resample_kernel_host(float *out);
+void sty_rmvpe_mel_basis_host(float *out);
+int sty_rmvpe_mel_workspace_bytes(int B, int N, size_t *bytes);
+int sty_rmvpe_mel_fwd(int B, int N, const float *audio, float *logmel, void *workspace, size_t ws_bytes, void *stream);
+/* RMVPE.mel2hidden (rmvpe/inference.py:29-36): logmel [B,128,n] -> salience [B,n,360].  The frame axis is padded by
+ * reflection to the next multiple of 32 and the whole net, the BiGRU included (its backward direction starts at the padded
+ * end), runs on the padded length; the first n frames are kept.  n < 17 cannot be reflected: STY_ESHAPE.                 */
+int sty_rmvpe_workspace_bytes(const sty_model *m, int B, int n, size_t *bytes);
+int sty_rmvpe_fwd(sty_model *m, int B, int n, const float *logmel, float *salience, void *workspace, size_t ws_bytes,
+                  void *stream);
+/* to_local_average_f0 (rmvpe/utils.py:114-131): salience [B,n,360] -> f0 [B,n] in Hz.  Arg-max (lowest index on a tie),
+ * the window [c-4, c+5) clipped to [0, 360), cents = sum s (20 i + 1997.3794084376191) / sum s, f0 = 10 * 2^(cents/1200),
+ * 0 where the row's maximum is < thred.  Viterbi decoding (use_viterbi) is not built.                                   */
+int sty_rmvpe_decode(int B, int n, const float *salience, float thred, float *f0, void *stream);
 
 /* ---- alignment stage, training (train_alignment, train/stage_type.py:268-341; `python -m stylish_tts_amd.train_align`) --
  * Model kind "text_aligner_train": the keys and shapes of "text_aligner", with sty_model_enable_training /

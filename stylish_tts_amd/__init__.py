@@ -9,3 +9,4 @@ from .modules import (DurationPredictor, DurationProcessor, ExportModel, MelStyl
                       PitchEnergyPredictor, PitchStyleEncoder, SpeechPredictor)
 from .align import TextAligner  # noqa: F401,E402
 from .alignment import TrainableTextAligner  # noqa: F401,E402
+from .pitch import RMVPE  # noqa: F401,E402

@@ -567,6 +567,116 @@ struct Builder {
     a.classes = a.out.Cout;
   }
 
+  // ---- RMVPE (train/dataprep/rmvpe/model.py:49-86): n_blocks, inter_layers and en_out_channels from the bound keys / shapes ----
+  void rm_fail(const std::string& key) {
+    if (ok) m->missing = key + " (shape mismatch)";
+    ok = false;
+  }
+  // Conv2d [Cout][Cin][KH][KW] (+ the BatchNorm `bn` behind it, + bias) -> PackedConv in 2-D mode, packed by rmvpe_pack_conv_kernel
+  PackedConv rm_conv2d(const std::string& name, const std::string& bn, bool bias, int Cin, int Cout, int KH) {
+    PackedConv pc;
+    RmvpePackJob j;
+    j.w = ptr(name + ".weight", {Cout, Cin, KH, KH});
+    if (bias) j.bias = ptr(name + ".bias", {Cout});
+    if (!bn.empty()) {
+      j.bn_w = ptr(bn + ".weight", {Cout});
+      j.bn_b = ptr(bn + ".bias", {Cout});
+      j.bn_rm = ptr(bn + ".running_mean", {Cout});
+      j.bn_rv = ptr(bn + ".running_var", {Cout});
+    }
+    pc.Cout = Cout, pc.Cin = KH * Cin, pc.K = KH;
+    pc.CinP = (int)align_up(pc.Cin, CI_CHUNK), pc.CoutP = (int)align_up(Cout, 32);
+    j.wp = m->ab.take<float>((size_t)pc.K * pc.CinP * pc.CoutP);
+    j.bp = m->ab.take<float>(pc.CoutP);
+    j.Cout = Cout, j.Cin = Cin, j.KH = KH, j.KW = KH, j.CinP = pc.CinP, j.CoutP = pc.CoutP;
+    pc.wp = j.wp, pc.bias = j.bp;
+    if (!dry && ok) m->rmv.packs.push_back(j);
+    return pc;
+  }
+  RmvpeBlock rm_block(const std::string& p, int Cin, int Cout) {
+    RmvpeBlock b;
+    b.Cin = Cin, b.Cout = Cout;
+    b.c1 = rm_conv2d(p + ".conv.0", p + ".conv.1", false, Cin, Cout, 3);
+    b.c2 = rm_conv2d(p + ".conv.3", p + ".conv.4", false, Cout, Cout, 3);
+    b.has_sc = Cin != Cout;
+    if (b.has_sc) b.sc = rm_conv2d(p + ".shortcut", "", true, Cin, Cout, 1);
+    return b;
+  }
+  void rmvpe() {
+    RmvpePlan& p = m->rmv;
+    if (!dry) p.packs.clear();
+    const std::string e = "unet.encoder.", im = "unet.intermediate.", d = "unet.decoder.";
+    const Param* w0 = get(e + "layers.0.conv.0.conv.0.weight");
+    if (!w0) return;
+    if (w0->shape.size() != 4 || w0->shape[1] != 1 || w0->shape[0] < 1) return rm_fail(e + "layers.0.conv.0.conv.0.weight");
+    p.C0 = (int)w0->shape[0];
+    p.n_blocks = 0;
+    while (has(e + "layers.0.conv." + std::to_string(p.n_blocks) + ".conv.0.weight")) ++p.n_blocks;
+    p.inter_layers = 0;
+    while (has(im + "layers." + std::to_string(p.inter_layers) + ".conv.0.conv.0.weight")) ++p.inter_layers;
+    if (p.inter_layers < 1) return rm_fail(im + "layers.0.conv.0.conv.0.weight");
+    static const char* bn_part[4] = {"weight", "bias", "running_mean", "running_var"};
+    for (int i = 0; i < 4; ++i) p.in_bn[i] = ptr(e + "bn." + bn_part[i], {1});
+    p.in_ss = m->ab.take<float>(2);
+    int cin = 1, c = p.C0;
+    for (int l = 0; l < RMVPE_LEVELS; ++l) {
+      p.enc[l].clear();
+      for (int j = 0; j < p.n_blocks; ++j)
+        p.enc[l].push_back(rm_block(e + "layers." + std::to_string(l) + ".conv." + std::to_string(j), j ? c : cin, c));
+      cin = c;
+      c *= 2;
+    }
+    // (c = 2 * the deepest encoder width = the intermediate's width)
+    p.inter.clear();
+    for (int i = 0; i < p.inter_layers; ++i)
+      for (int j = 0; j < p.n_blocks; ++j)
+        p.inter.push_back(rm_block(im + "layers." + std::to_string(i) + ".conv." + std::to_string(j), (i || j) ? c : cin, c));
+    for (int i = 0; i < RMVPE_LEVELS; ++i) {
+      const std::string dl = d + "layers." + std::to_string(i);
+      const int co = c / 2;
+      RmvpeUp& u = p.up[i];
+      u.Cin = c, u.Cout = co;
+      RmvpePackJob j;
+      j.w = ptr(dl + ".conv1.0.weight", {c, co, 3, 3});
+      j.bn_w = ptr(dl + ".conv1.1.weight", {co});
+      j.bn_b = ptr(dl + ".conv1.1.bias", {co});
+      j.bn_rm = ptr(dl + ".conv1.1.running_mean", {co});
+      j.bn_rv = ptr(dl + ".conv1.1.running_var", {co});
+      j.wp = m->ab.take<float>((size_t)c * co * 9);
+      j.bp = m->ab.take<float>(co);
+      j.Cout = co, j.Cin = c, j.KH = 3, j.KW = 3, j.deconv = 1;
+      u.wd = j.wp, u.bias = j.bp;
+      if (!dry && ok) p.packs.push_back(j);
+      p.dec[i].clear();
+      for (int k = 0; k < p.n_blocks; ++k) p.dec[i].push_back(rm_block(dl + ".conv2." + std::to_string(k), k ? co : 2 * co, co));
+      c = co;
+    }
+    p.cnn = rm_conv2d("cnn", "", true, p.C0, 3, 3);
+    {  // nn.GRU(384, 256, bidirectional): both directions' W_ih x + b_ih as one K = 1 conv of 1536 rows
+      const int nin = 3 * RMVPE_MELS, H3 = 768;
+      PackedConv pc;
+      pc.Cin = nin, pc.Cout = 2 * H3, pc.K = 1, pc.CinP = (int)align_up(nin, CI_CHUNK), pc.CoutP = (int)align_up(2 * H3, 32);
+      float* wp = m->ab.take<float>((size_t)pc.CinP * pc.CoutP);
+      float* bp = m->ab.take<float>(pc.CoutP);
+      pc.wp = wp, pc.bias = bp;
+      for (int r = 0; r < 2; ++r) {
+        const std::string sfx = r ? "_l0_reverse" : "_l0";
+        RmvpePackJob j;
+        j.w = ptr("fc.0.gru.weight_ih" + sfx, {H3, nin});
+        j.bias = ptr("fc.0.gru.bias_ih" + sfx, {H3});
+        j.wp = wp, j.bp = bp;
+        j.Cout = H3, j.Cin = nin, j.CinP = pc.CinP, j.CoutP = pc.CoutP, j.co_off = r * H3;
+        if (!dry && ok) p.packs.push_back(j);
+        p.whh[r] = ptr("fc.0.gru.weight_hh" + sfx, {H3, 256});
+        p.bhh[r] = ptr("fc.0.gru.bias_hh" + sfx, {H3});
+      }
+      p.gru_ih = pc;
+      p.whhT = m->ab.take<float>((size_t)2 * H3 * 256);
+    }
+    p.head = conv("fc.1");
+    if (ok && (p.head.Cin != 512 || p.head.Cout != RMVPE_CLASSES || p.head.K != 1)) rm_fail("fc.1.weight");
+  }
+
   void build() {
     m->gb_floats_per_batch = 0;
     if (m->kind == "speech_predictor") {
@@ -587,6 +697,8 @@ struct Builder {
       pitch_energy_predictor();
     } else if (m->kind == "text_aligner" || m->kind == "text_aligner_train") {
       text_aligner();
+    } else if (m->kind == "rmvpe") {
+      rmvpe();
     }
   }
 };
@@ -1423,6 +1535,107 @@ static void aligner_forward(Run& r, const float* mel, const int64_t* lengths, in
   }
 }
 
+// RMVPE.mel2hidden (train/dataprep/rmvpe/inference.py:29-36) over E2E0.forward (model.py:82-86): logmel [B][128][n] ->
+// salience [B][n][360].  H is time (reflected to Tp, the next multiple of 32), W the 128 mel bins; every activation is
+// padded-flat [B][C][H][W + 1] (conv2d.hip).  Level l has H = Tp >> l, W = 128 >> l, C0 << l channels.  cat[l] is the decoder's
+// concat input [B][2 C_l][n_l]: the encoder writes its skip into the second half when it produces it (one launch per
+// utterance: the conv's output has no batch stride), the transposed conv writes the first half.
+static void rmvpe_forward(Run& r, int n, const float* logmel, float* sal) {
+  const RmvpePlan& p = r.m->rmv;
+  const int B = r.B, L = RMVPE_LEVELS, Tp = 32 * ((n - 1) / 32 + 1);
+  auto Hl = [&](int l) { return Tp >> l; };
+  auto Wl = [&](int l) { return RMVPE_MELS >> l; };
+  auto Nl = [&](int l) { return (size_t)Hl(l) * (Wl(l) + 1); };
+  auto Cl = [&](int l) { return p.C0 << l; };
+  const float* mk[L + 1];
+  for (int l = 0; l <= L; ++l) {
+    float* m = r.ws.take<float>((size_t)B * Nl(l));
+    if (r.live()) r.chk(launch_flat_mask(B, Hl(l), Wl(l) + 1, Hl(l), Wl(l), m, r.st));
+    mk[l] = m;
+  }
+  float* cat[L];
+  for (int l = 0; l < L; ++l) cat[l] = r.ws.take<float>((size_t)B * 2 * Cl(l) * Nl(l));
+  const size_t big = (size_t)B * (p.C0 > 3 ? p.C0 : 3) * Nl(0);  // (3: cnn's output) the largest activation: C_l n_l shrinks with l, the intermediate is 2 C_4 n_5
+  float* x0 = r.ws.take<float>((size_t)B * Nl(0));
+  float* pp[2] = {r.ws.take<float>(big), r.ws.take<float>(big)};
+  float* hb = r.ws.take<float>(big);
+  float* sb = r.ws.take<float>(big);
+  const int nf = 3 * RMVPE_MELS;
+  float* gin = r.ws.take<float>((size_t)B * nf * Tp);
+  float* xg = r.ws.take<float>((size_t)B * 1536 * Tp);
+  float* hcat = r.ws.take<float>((size_t)B * 512 * Tp);
+  float* logits = r.ws.take<float>((size_t)B * RMVPE_CLASSES * Tp);
+  r.note_peak();
+  if (!r.live()) return;
+  // one conv on level l; Bc = 1 with pre-offset pointers: the launch of one utterance
+  auto conv2d = [&](const PackedConv& w, const float* x, int Cin2d, int l, int Bc, int act, const float* residual, float* y) {
+    if (!r.live()) return;
+    ConvArgs a;
+    a.x[0] = x;
+    a.xc[0] = w.Cin;
+    a.B = Bc;
+    a.T = (int)Nl(l);
+    a.w = w;
+    a.flatW = Wl(l) + 1;
+    a.hpad = a.pad = (w.K - 1) / 2;
+    a.Cin2d = Cin2d;
+    a.act = act;
+    a.residual = residual;
+    a.out_mask = mk[l];
+    a.out_mask_post = 1;
+    a.y = y;
+    r.chk(launch_conv1d(a, r.st));  // fp32 operands: compute_bf16 is refused for the kind
+  };
+  // ConvBlockRes: relu(bn(conv(relu(bn(conv x))))) + (x | conv1x1(x) + b).  skip != nullptr: the output goes to channels
+  // [skip_c0, skip_c0 + Cout) of a buffer with skip_C channels
+  auto block = [&](const RmvpeBlock& k, const float* x, int l, float* y, float* skip, int skip_C, int skip_c0) {
+    const float* res = x;
+    if (k.has_sc) {
+      conv2d(k.sc, x, k.Cin, l, B, ACT_NONE, nullptr, sb);
+      res = sb;
+    }
+    conv2d(k.c1, x, k.Cin, l, B, ACT_RELU, nullptr, hb);
+    if (!skip) return conv2d(k.c2, hb, k.Cout, l, B, ACT_RELU, res, y);
+    const size_t per = (size_t)k.Cout * Nl(l);
+    for (int b = 0; b < B; ++b)
+      conv2d(k.c2, hb + b * per, k.Cout, l, 1, ACT_RELU, res + b * per, skip + ((size_t)b * skip_C + skip_c0) * Nl(l));
+  };
+  r.chk(launch_rmvpe_input(logmel, p.in_ss, B, n, Tp, x0, r.st));
+  const float* cur = x0;
+  int flip = 0;
+  for (int l = 0; l < L && r.live(); ++l) {  // Encoder (deepunet.py:127-133)
+    const int C = Cl(l);
+    for (int j = 0; j < p.n_blocks; ++j) {
+      const bool last = j == p.n_blocks - 1;
+      block(p.enc[l][j], cur, l, pp[flip], last ? cat[l] : nullptr, 2 * C, C);
+      if (!last) cur = pp[flip], flip ^= 1;
+    }
+    for (int b = 0; b < B && r.live(); ++b)  // AvgPool2d(2) of the skip, read where it lies
+      r.chk(launch_avgpool2(cat[l] + ((size_t)b * 2 * C + C) * Nl(l), C, Hl(l), Wl(l), 1.f, pp[flip] + (size_t)b * C * Nl(l + 1), r.st));
+    cur = pp[flip], flip ^= 1;
+  }
+  for (size_t i = 0; i < p.inter.size() && r.live(); ++i) {  // Intermediate (deepunet.py:149-152)
+    block(p.inter[i], cur, L, pp[flip], nullptr, 0, 0);
+    cur = pp[flip], flip ^= 1;
+  }
+  for (int i = 0; i < L && r.live(); ++i) {  // Decoder (deepunet.py:90-95, 167-170)
+    const int l = L - 1 - i, C = Cl(l);
+    r.chk(launch_rmvpe_deconv(cur, p.up[i].wd, p.up[i].bias, B, p.up[i].Cin, C, Hl(l + 1), Wl(l + 1), (size_t)2 * C * Nl(l), cat[l], r.st));
+    cur = cat[l];
+    for (int j = 0; j < p.n_blocks; ++j) {
+      block(p.dec[i][j], cur, l, pp[flip], nullptr, 0, 0);
+      cur = pp[flip], flip ^= 1;
+    }
+  }
+  conv2d(p.cnn, cur, p.C0, 0, B, ACT_NONE, nullptr, hb);  // [B][3][Tp][129]
+  if (!r.live()) return;
+  r.chk(launch_rmvpe_gru_in(hb, B, Tp, gin, r.st));
+  r.conv(r.base(p.gru_ih, gin, Tp, xg));
+  if (r.live()) r.chk(launch_rmvpe_gru(xg, p.whhT, p.bhh[0], p.bhh[1], B, Tp, hcat, r.st));
+  r.conv(r.base(p.head, hcat, Tp, logits));
+  if (r.live()) r.chk(launch_rmvpe_salience(logits, B, Tp, n, sal, r.st));
+}
+
 static int run_style_fc(Run& r, const float* style) {
   sty_model* m = r.m;
   r.gb = r.ws.take<float>(m->gb_floats_per_batch * r.B);
@@ -1491,7 +1704,7 @@ int sty_model_create(const char* kind, sty_model** out) {
   }
   std::string k(kind);
   if (k != "speech_predictor" && k != "vocoder" && k != "mel_style_encoder" && k != "duration_predictor" &&
-      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner" && k != "text_aligner_train") {
+      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner" && k != "text_aligner_train" && k != "rmvpe") {
     set_error("unknown model kind '%s'", kind);
     return STY_EINVAL;
   }
@@ -1602,8 +1815,8 @@ int sty_model_finalize(sty_model* m) {
 
 // the text aligner is an inference-only kind (alignment decisions are arg-max decisions: fp32 operands, no training graph)
 static int refuse_aligner(const sty_model* m, const char* what) {
-  if (m->kind != "text_aligner") return STY_OK;
-  set_error("%s: model kind 'text_aligner' is inference-only and runs fp32 operands", what);
+  if (m->kind != "text_aligner" && m->kind != "rmvpe") return STY_OK;  // (rmvpe: pitch values hang on an arg-max too)
+  set_error("%s: model kind '%s' is inference-only and runs fp32 operands", what, m->kind.c_str());
   return STY_EINVAL;
 }
 
@@ -1994,6 +2207,73 @@ int sty_aligner_fwd(sty_model* m, int B, int T, const float* mel, const int64_t*
   }
   if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
   return aligner_run(m, B, T, mel, mel_lengths, log_probs, workspace, ws_bytes, stream, nullptr);
+}
+// ---- RMVPE pitch extraction (train/dataprep/rmvpe/inference.py) ----
+void sty_rmvpe_resample_kernel_host(float* out) { build_rmvpe_resample_kernel(out); }
+void sty_rmvpe_mel_basis_host(float* out) { build_rmvpe_mel_basis(out); }
+int sty_rmvpe_mel_workspace_bytes(int B, int N, size_t* bytes) {
+  if (!bytes || B <= 0 || N <= 0 || rmvpe_resampled_len(N) <= 512) {
+    set_error("sty_rmvpe_mel_workspace_bytes: bad argument (the reflect padding needs more than 512 samples at 16 kHz)");
+    return STY_EINVAL;
+  }
+  *bytes = rmvpe_mel_workspace_floats(B, N) * sizeof(float);
+  return STY_OK;
+}
+int sty_rmvpe_mel_fwd(int B, int N, const float* audio, float* logmel, void* workspace, size_t ws_bytes, void* stream) {
+  if (!audio || !logmel || !workspace || B <= 0 || N <= 0 || rmvpe_resampled_len(N) <= 512) {
+    set_error("sty_rmvpe_mel_fwd: bad argument (the reflect padding needs more than 512 samples at 16 kHz)");
+    return STY_EINVAL;
+  }
+  if (ws_bytes < rmvpe_mel_workspace_floats(B, N) * sizeof(float)) {
+    set_error("sty_rmvpe_mel_fwd: workspace too small");
+    return STY_ENOMEM;
+  }
+  return launch_rmvpe_mel(B, N, audio, logmel, (float*)workspace, S(stream));
+}
+// the frame axis is reflected to the next multiple of 32: at most 15 frames when n >= 17 (and at most n - 1 above that)
+static int rmvpe_shape_ok(const char* what, const sty_model* m, int B, int n) {
+  if (!m || B <= 0) {
+    set_error("%s: bad argument", what);
+    return STY_EINVAL;
+  }
+  if (n < 17) {
+    set_error("%s: %d frames cannot be reflected to a multiple of 32 (at least 17 are needed)", what, n);
+    return STY_ESHAPE;
+  }
+  return STY_OK;
+}
+static int rmvpe_run(sty_model* m, int B, int n, const float* logmel, float* sal, void* ws, size_t ws_bytes, void* stream,
+                     size_t* need) {
+  Run r(m, B, ws, ws_bytes, stream);
+  rmvpe_forward(r, n, logmel, sal);
+  return r.finish(need, ws, ws_bytes);
+}
+int sty_rmvpe_workspace_bytes(const sty_model* m, int B, int n, size_t* bytes) {
+  int rc = rmvpe_shape_ok("sty_rmvpe_workspace_bytes", m, B, n);
+  if (rc || (rc = model_ready(m, "rmvpe"))) return rc;
+  if (!bytes) {
+    set_error("sty_rmvpe_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  return rmvpe_run(const_cast<sty_model*>(m), B, n, nullptr, nullptr, nullptr, 0, nullptr, bytes);
+}
+int sty_rmvpe_fwd(sty_model* m, int B, int n, const float* logmel, float* salience, void* workspace, size_t ws_bytes,
+                  void* stream) {
+  int rc = rmvpe_shape_ok("sty_rmvpe_fwd", m, B, n);
+  if (rc || (rc = model_ready(m, "rmvpe"))) return rc;
+  if (!logmel || !salience || !workspace) {
+    set_error("sty_rmvpe_fwd: bad argument");
+    return STY_EINVAL;
+  }
+  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  return rmvpe_run(m, B, n, logmel, salience, workspace, ws_bytes, stream, nullptr);
+}
+int sty_rmvpe_decode(int B, int n, const float* salience, float thred, float* f0, void* stream) {
+  if (!salience || !f0 || B <= 0 || n <= 0) {
+    set_error("sty_rmvpe_decode: bad argument");
+    return STY_EINVAL;
+  }
+  return launch_rmvpe_decode(salience, B * n, thred, f0, S(stream));
 }
 // ---- text aligner in the training graph (train_alignment, stage_type.py:268-341): forward, then sty_aligner_bwd ----
 int sty_aligner_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {

@@ -883,6 +883,25 @@ int launch_multispec_single(int B, int N, const float* audio, int n_fft, int hop
   return STY_OK;
 }
 
+// |STFT| alone, plain [B][F][frames] layout (the RMVPE front end, rmvpe.hip: spec.py's magnitude spectrum): the LDS FFT into
+// y [B][2F][frames] (dft_row order), then magphase_kernel without the phase
+int launch_stft_mag(int B, int Ns, const float* audio, int n_fft, int hop, int sample_rate, float* y, float* mag, hipStream_t st) {
+  const FrontTables* t;
+  int rc = get_tables(n_fft, n_fft, 128, sample_rate, st, &t);
+  if (rc) return rc;
+  if (Ns <= n_fft / 2) {
+    set_error("front end: %d samples are too few to reflect-pad a %d-point transform", Ns, n_fft);
+    return STY_ESHAPE;
+  }
+  const int frames = Ns / hop + 1, F = t->F;
+  rc = launch_stft_fft(audio, *t, B, Ns, hop, frames, (size_t)2 * F * frames, (size_t)frames, y, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(magphase_kernel, dim3(cdiv(B * frames, 256), F), dim3(256), 0, st, y, F, frames, (size_t)2 * F * frames,
+                     (size_t)F * frames, (size_t)frames, mag, nullptr, n_fft / 4, B);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
 // =====================================================================================================
 // Acoustic-stage losses on the three-resolution features and their gradient w.r.t. the predicted waveform.
 //   mel          = mean_r ||T_r - P_r||_1 / (||T_r||_1 + 1e-6)           on log1p(mel128(|X|))   (losses.py:17-38)

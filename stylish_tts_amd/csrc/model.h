@@ -199,6 +199,53 @@ int launch_aligner_bn(float* x, int B, int C, int T, const float* scale, const f
 int launch_log_softmax_rows(const float* x, int B, int V, int T, float* out, hipStream_t st);
 int launch_fill_f32(float* x, int n, float v, hipStream_t st);
 
+// RMVPE = E2E0(n_blocks, 1, (2, 2), 5, inter_layers, 1, en_out_channels) in eval mode (train/dataprep/rmvpe/model.py:49-86,
+// deepunet.py, seq.py); rmvpe.hip has the kernels, api.hip the plan
+constexpr int RMVPE_MELS = 128, RMVPE_CLASSES = 360, RMVPE_HOP = 200, RMVPE_LEVELS = 5;
+constexpr float RMVPE_LOG_CLAMP = -11.5129254649702f;  // log(1e-5)
+struct RmvpePackJob {  // one conv whose BatchNorm (if any) is folded while it is packed (rmvpe_pack_conv_kernel)
+  const float *w = nullptr, *bias = nullptr, *bn_w = nullptr, *bn_b = nullptr, *bn_rm = nullptr, *bn_rv = nullptr;
+  float *wp = nullptr, *bp = nullptr;
+  int Cout = 0, Cin = 0, KH = 1, KW = 1, CinP = 0, CoutP = 0, co_off = 0, deconv = 0;
+};
+struct RmvpeBlock {  // ConvBlockRes (deepunet.py:6-41)
+  int Cin = 0, Cout = 0;
+  PackedConv c1, c2, sc;  // 3x3 + BN, 3x3 + BN (2-D mode: Cin = 3 * Cin2d), 1x1 with bias
+  bool has_sc = false;
+};
+struct RmvpeUp {  // ConvTranspose2d + BN of a ResDecoderBlock (deepunet.py:72-84)
+  int Cin = 0, Cout = 0;
+  const float *wd = nullptr, *bias = nullptr;  // [Cin][Cout][9] scaled, [Cout]
+};
+struct RmvpePlan {
+  int n_blocks = 0, inter_layers = 0, C0 = 0;
+  const float* in_bn[4] = {nullptr, nullptr, nullptr, nullptr};  // encoder.bn weight, bias, running_mean, running_var
+  float* in_ss = nullptr;                                        // prepared: scale, shift
+  std::vector<RmvpeBlock> enc[RMVPE_LEVELS], inter, dec[RMVPE_LEVELS];
+  RmvpeUp up[RMVPE_LEVELS];
+  PackedConv cnn, gru_ih, head;  // Conv2d(C0 -> 3), [W_ih forward; W_ih reverse] 384 -> 1536, Linear(512 -> 360)
+  const float *whh[2] = {nullptr, nullptr}, *bhh[2] = {nullptr, nullptr};
+  float* whhT = nullptr;  // prepared: [2][256][768]
+  std::vector<RmvpePackJob> packs;
+};
+inline int rmvpe_resampled_len(int N) { return (int)((2 * (long long)N + 2) / 3); }  // ceil(2 N / 3)
+int rmvpe_mel_frames(int N);
+size_t rmvpe_mel_workspace_floats(int B, int N);
+void build_rmvpe_resample_kernel(float* out);
+void build_rmvpe_mel_basis(float* out);
+int launch_rmvpe_mel(int B, int N, const float* audio, float* logmel, float* ws, hipStream_t st);
+// frontend.hip: |STFT| (periodic hann of n_fft, centre / reflect) of audio [B][Ns] -> mag [B][F][frames]; y: [B][2F][frames] scratch
+int launch_stft_mag(int B, int Ns, const float* audio, int n_fft, int hop, int sample_rate, float* y, float* mag, hipStream_t st);
+int rmvpe_prepare(const RmvpePlan& p, hipStream_t st);
+int launch_rmvpe_input(const float* logmel, const float* ss, int B, int n, int Tp, float* x, hipStream_t st);
+int launch_rmvpe_deconv(const float* x, const float* wd, const float* bias, int B, int Cin, int Cout, int Hi, int Wi, size_t ybs,
+                        float* y, hipStream_t st);
+int launch_rmvpe_gru_in(const float* x, int B, int T, float* y, hipStream_t st);
+int launch_rmvpe_gru(const float* xg, const float* whhT, const float* bhh0, const float* bhh1, int B, int T, float* hout,
+                     hipStream_t st);
+int launch_rmvpe_salience(const float* logits, int B, int T, int n, float* sal, hipStream_t st);
+int launch_rmvpe_decode(const float* sal, int rows, float thred, float* f0, hipStream_t st);
+
 struct Trainer;
 struct StyleResBlk {  // mel_style_encoder.py:69-118
   int Cin = 0, Cout = 0;
@@ -241,6 +288,7 @@ struct sty_model {
   sty::DurationPlan dur;
   sty::PitchEnergyPlan pe;
   sty::AlignerPlan ali;
+  sty::RmvpePlan rmv;
   sty::PackedConv pse_pre;  // PitchStyleEncoder.preconv (mel_style_encoder.py:166)
   float* stft_default = nullptr;  // device [4][33][64]
   // ---- training ----

@@ -436,6 +436,8 @@ int weights_prepare(sty_model* m, hipStream_t st) {
     // (bn_zero is the arena's zero fill)
     if (a.bn_one && (r = launch_fill_f32(a.bn_one, a.hidden, 1.0f, st)) != STY_OK) return r;
   }
+  // RMVPE: the BatchNorm-folding packs, W_hh^T and the input BatchNorm's scale / shift (rmvpe.hip)
+  if (m->kind == "rmvpe" && (r = rmvpe_prepare(m->rmv, st)) != STY_OK) return r;
   // the bf16 fragment buffers the persistent kernels read the packed weights through (bf16 mode)
   if (m->arena && (r = convp16_repack_range(m->arena, m->arena + m->arena_bytes, st)) != STY_OK) return r;
   return STY_OK;

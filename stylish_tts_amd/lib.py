@@ -175,6 +175,13 @@ SYMBOLS = {
     "sty_aligner_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_forced_align_workspace_bytes": (C.c_int, [_I, _I, _I, _SZP]),
     "sty_forced_align": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_rmvpe_resample_kernel_host": (None, [_P]),
+    "sty_rmvpe_mel_basis_host": (None, [_P]),
+    "sty_rmvpe_mel_workspace_bytes": (C.c_int, [_I, _I, _SZP]),
+    "sty_rmvpe_mel_fwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "sty_rmvpe_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
+    "sty_rmvpe_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "sty_rmvpe_decode": (C.c_int, [_I, _I, _P, C.c_float, _P, _P]),
     "sty_aligner_train_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
     "sty_aligner_fwd_train": (C.c_int, [_P, _I, _I, _P, _P, C.c_float, C.c_uint, _P, _P, C.c_size_t, _P]),
     "sty_aligner_bwd": (C.c_int, [_P, _P, _P]),

@@ -336,3 +336,55 @@ def text_aligner_manifest(n_mels=80, tokens=178, hidden_dim=640):
     m["encoder_output_layer.weight"] = [tokens + 1, hidden_dim]
     m["encoder_output_layer.bias"] = [tokens + 1]
     return m
+
+
+def _bn2d(m, name, c):
+    m[name + ".weight"] = [c]
+    m[name + ".bias"] = [c]
+    m[name + ".running_mean"] = [c]
+    m[name + ".running_var"] = [c]
+    m[name + ".num_batches_tracked"] = []
+
+
+def _rmvpe_block(m, p, cin, cout):  # ConvBlockRes, train/dataprep/rmvpe/deepunet.py:6-41
+    m[p + ".conv.0.weight"] = [cout, cin, 3, 3]
+    _bn2d(m, p + ".conv.1", cout)
+    m[p + ".conv.3.weight"] = [cout, cout, 3, 3]
+    _bn2d(m, p + ".conv.4", cout)
+    if cin != cout:
+        m[p + ".shortcut.weight"] = [cout, cin, 1, 1]
+        m[p + ".shortcut.bias"] = [cout]
+
+
+def rmvpe_manifest(n_blocks=4, inter_layers=4, en_out_channels=16):
+    """E2E0(n_blocks, 1, (2, 2), 5, inter_layers, 1, en_out_channels) (train/dataprep/rmvpe/model.py:49-86): DeepUnet0 of five
+    encoder / decoder levels over 128 mel bins (deepunet.py:220-248), Conv2d(en_out_channels, 3, 3 x 3), one bidirectional GRU
+    layer of 256 over 3 * 128 features (seq.py:4-16), Linear(512, 360).  The defaults are RMVPE's own `E2E0(4, 1, (2, 2))`
+    (inference.py:16): 741 keys, 90,423,165 parameters (tests/golden/manifest_rmvpe.json is the reference's own list)."""
+    m = OrderedDict()
+    _bn2d(m, "unet.encoder.bn", 1)
+    cin, c = 1, en_out_channels
+    for l in range(5):
+        for j in range(n_blocks):
+            _rmvpe_block(m, f"unet.encoder.layers.{l}.conv.{j}", cin if j == 0 else c, c)
+        cin, c = c, 2 * c
+    for i in range(inter_layers):
+        for j in range(n_blocks):
+            _rmvpe_block(m, f"unet.intermediate.layers.{i}.conv.{j}", cin if i == 0 and j == 0 else c, c)
+    for i in range(5):
+        co = c // 2
+        m[f"unet.decoder.layers.{i}.conv1.0.weight"] = [c, co, 3, 3]
+        _bn2d(m, f"unet.decoder.layers.{i}.conv1.1", co)
+        for j in range(n_blocks):
+            _rmvpe_block(m, f"unet.decoder.layers.{i}.conv2.{j}", 2 * co if j == 0 else co, co)
+        c = co
+    m["cnn.weight"] = [3, en_out_channels, 3, 3]
+    m["cnn.bias"] = [3]
+    for sfx in ("_l0", "_l0_reverse"):
+        m["fc.0.gru.weight_ih" + sfx] = [768, 384]
+        m["fc.0.gru.weight_hh" + sfx] = [768, 256]
+        m["fc.0.gru.bias_ih" + sfx] = [768]
+        m["fc.0.gru.bias_hh" + sfx] = [768]
+    m["fc.1.weight"] = [360, 512]
+    m["fc.1.bias"] = [360]
+    return m

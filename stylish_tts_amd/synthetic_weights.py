@@ -62,6 +62,10 @@ def fill_tensor(key, shape, seed=0):
         return f32(0.5 * r.standard_normal(shape) / math.sqrt(shape[1]))
     if last in ("weight", "weight_orig"):
         return f32(r.standard_normal(shape) / math.sqrt(_fan_in(shape)))
+    if last.startswith(("weight_ih", "weight_hh")):  # nn.GRU (RMVPE's BiGRU): [3 * hidden, fan_in]
+        return f32(r.standard_normal(shape) / math.sqrt(shape[1]))
+    if last.startswith(("bias_ih", "bias_hh")):
+        return f32(0.1 * r.standard_normal(shape))
     raise KeyError(f"no fill rule for {key} {shape}")
 
 
