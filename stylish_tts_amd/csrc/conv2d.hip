@@ -371,7 +371,7 @@ int launch_pool_fc(const float* x, int B, int C, int n, int count, const float* 
 // workgroup; dwconv2d_s2_bwd_w_sum_kernel adds them up over batch and workgroups in a fixed order.
 // (Two kernels -- dx by input position, the weight gradient by output position with nine strided reads of x per output --
 // moved 1.9 GB for the first ResBlk at ~1.5 TB/s, plus the zero-fill of dx; this one moves 0.96 GB.)
-// gate != nullptr: gy is taken times lrelu'(gate) (0.2 slope), gate laid out as gy (a deferred gate, train.hip `ungated`)
+// gate != nullptr: gy is taken times lrelu'(gate) (0.2 slope), gate laid out as gy (a deferred gate: OWED_GATE in the tape's ledger)
 // Round 4: one thread per 2 x 2 QUAD of input positions (rows 2 qh, 2 qh + 1, columns 2 qw, 2 qw + 1) instead of four
 // consecutive elements with nine parity tests each (the kernel was bound by its ~75 vector instructions per element, not by
 // memory: 1.3 ms per c3 step at 2 TB/s, on the tail of the step).  With stride 2 the parity of an input position selects its
@@ -543,7 +543,7 @@ int launch_dw2d_sn_unpack(const float* g9, const float* w, const float* u, const
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
-// gate != nullptr (laid out as dx): dx = dx * lrelu'(gate) + up(gy) -- a deferred gate (train.hip `ungated`) applied in
+// gate != nullptr (laid out as dx): dx = dx * lrelu'(gate) + up(gy) -- a deferred gate (OWED_GATE in the tape's ledger) applied in
 // the pass that accumulates into dx anyway
 __global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const float* __restrict__ gy, int H, int W, int Ho, int Wo,
                                                            float scale, float* __restrict__ dx,

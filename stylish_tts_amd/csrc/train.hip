@@ -1,573 +1,103 @@
-// Training-mode graphs (SpeechPredictor: text encoder -> expand -> decoder -> vocoder; MelStyleEncoder; vocoder alone)
-// with a tape of backward steps.
+// Training-mode graphs (SpeechPredictor: text encoder -> expand -> decoder -> vocoder; MelStyleEncoder; vocoder alone;
+// the predictors and the aligner) recorded on the tape of tape.h.
 //
 // The forward here is the UNFUSED-epilogue form of the inference plan in api.hip: convs keep their fused input
 // prologues (AdaIN+Snake, GRN scale, ...) but activations / LayerNorms that the backward needs the inputs of are
 // separate ops, nothing is computed in place, and no workspace is recycled, so that every backward step finds its
-// operands.  Each forward op pushes one closure; backward runs them in reverse.  Gradient buffers are zero-filled
-// when first requested and every backward kernel accumulates, which makes fan-out (residual streams) trivial.
-// sty_train_opts selects module.train() behaviour (BatchNorm batch statistics, smoothing, power iteration, dropout,
-// bf16 operands); all zero = the eval-mode graph of the golden gradient fixtures.  Weight gradients run on a second
-// stream (see "side stream" below).
-//
-// Every entry point (trainer_*_forward / _backward, trainer_block_fwd_bwd) follows one protocol.  Forward: open() binds
-// stream, shape and workspace (or the fake base of a sizing pass), the graph's method records ops and tape, the outputs
-// are copied out, and close_forward() reports the size (after a dry backward) or an overflow.  Backward: run_tape()
-// seeds the output gradients, walks the tape in reverse, joins the weight-gradient stream and runs fc(style)'s backward;
-// what a graph does differently is an argument of it.  close_backward() reports an overflow.
-#include <stdlib.h>
+// operands.  Each forward op pushes one closure; backward runs them in reverse (Tape::run_tape).  This file holds the ops
+// (conv, act, layernorm, adain, ...) and the graphs; the tape's mechanics -- the entry-point protocol, the workspace, the
+// gradient buffers and what they are owed (the ledger, grad_ledger.h), the side stream of the weight gradients -- are
+// `struct Tape`.  sty_train_opts selects module.train() behaviour (BatchNorm batch statistics, smoothing, power
+// iteration, dropout, bf16 operands); all zero = the eval-mode graph of the golden gradient fixtures.
 #include <string.h>
 
-#include <map>
-#include <memory>
-#include <unordered_map>
-
-#include "model.h"
+#include "tape.h"
 
 namespace sty {
 
-struct Trainer {
-  sty_model* m = nullptr;
-  hipStream_t st = nullptr;
-  int B = 0, T = 0;
-  Bump ws;
-  int rc = STY_OK;
+struct Trainer : Tape {
   float* gb = nullptr;   // fc(style) outputs of every AdaIN/AdaLN layer
   float* dgb = nullptr;  // their gradients
   const float* style = nullptr;
   float* audio = nullptr;
-  std::vector<std::function<void()>> tape;
-  std::unordered_map<const float*, float*> gmap;
-  std::unordered_set<const float*> nograd;
-  float* scratch_param = nullptr;  // sink for gradients of parameters nobody bound a gradient for
-  size_t scratch_param_n = 0;
   const float* mel_in = nullptr;
-  size_t peak = 0;
-
-  bool dry = false;  // sizing pass: fake base pointer, allocations are tracked but nothing is launched
-  bool live() const { return !dry && ws.base != nullptr && rc == STY_OK; }
-  void chk(int r) {
-    if (rc == STY_OK && r != STY_OK) rc = r;
-  }
-  // ---- the entry-point protocol: open, record the graph, close; backward = seed, tape, join, fc (run_tape) ----
-  // the sizing pass bumps from a fake base that is never dereferenced, under a cap no graph reaches
-  static constexpr size_t kDryBase = size_t(1) << 30, kDryCap = size_t(1) << 46;
-  // what a sizing pass adds to the measured peak
-  static constexpr size_t kSlack = 64 << 20, kSlackStyle = 16 << 20;
-  // the style encoders' sizing pass has no tensors of the caller: these stand in as distinct non-null map keys
-  static inline float kDryMel = 0.f, kDryStyle = 0.f;
-  void open(int B_, int T_, void* ws_, size_t ws_bytes, hipStream_t st_, bool dry_) {
-    st = st_;
-    B = B_;
-    T = T_;
-    rc = STY_OK;
-    ws = Bump();
-    dry = dry_;
-    ws.base = dry ? reinterpret_cast<char*>(kDryBase) : (char*)ws_;
-    ws.cap = dry ? kDryCap : ws_bytes;
-    peak = 0;
-  }
-  // every per-step container and counter; begin() and style_forward() start from here.  ungated is only ever filled by the
-  // 2-D convs of the style encoders, half_ / g16_ok / adain_of / drop_site only by the 1-D graphs: each is empty (zero) on
-  // the path that used to leave it alone.  (se_taps is cleared where it is rebuilt.)
-  void reset_step() {
-    tape.clear();
-    gmap.clear();
-    tw_x[0].clear();
-    tw_x[1].clear();
-    tw_want.clear();
-    tw_g.clear();
-    g_twin_only.clear();
-    g_no_fp32.clear();
-    lazy_mask.clear();
-    pend_up.clear();
-    pend_row.clear();
-    nograd.clear();
-    half_.clear();
-    g16_ok.clear();
-    adain_of.clear();
-    ungated.clear();
-    side_need = 0;
-    wg_sum = 0;
-    drop_site = 0;
-    drop_seed_arg = nullptr;
-    branch_st = nullptr;
-    branch_can_beside = false;
-    branch_lo = branch_hi = branch_join = 0;
-  }
-  // the sizing pass (the entry has run its backward dry by now) reports the peak and drops the tape; the live pass reports
-  // an overflow of the caller's workspace
-  int close_forward(size_t* need, size_t ws_bytes, size_t slack, const char* what) {
-    if (need) {
-      *need = align_up(peak, 256) + slack;
-      tape.clear();
-      return rc;
-    }
-    if (ws.overflow) {
-      set_error("%s workspace too small: need %zu bytes, have %zu", what, peak, ws_bytes);
-      return STY_ENOMEM;
-    }
-    return rc;
-  }
-  int close_backward() {
-    if (ws.overflow) {
-      set_error("training workspace too small in backward: need %zu bytes", peak);
-      return STY_ENOMEM;
-    }
-    return rc;
-  }
-  void copy_f32(float* dst, const float* src, size_t n, const char* what) {  // device to device, on the main stream
-    if (!live()) return;
-    hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) rc = hip_fail(e, what);
-  }
-  // the gradient buffer of a graph output, holding the caller's gradient d (sizing pass: d == nullptr, the buffer alone)
-  float* seed(const float* act, const float* d, size_t n) {
-    float* g = G(act, n);
-    if (d) copy_f32(g, d, n, "seed copy");
-    return g;
-  }
-  // The backward of every graph.  `seeds` calls seed() for each output; the tape runs in reverse and stops at the first
-  // error.  flush_up (the style encoders): pooled shortcut gradients nobody has asked for are up-sampled before the join.
-  // fc (every graph with AdaIN / AdaLN layers): d_style is armed before the tape and fc(style)'s backward runs behind the
-  // join, unless a tape hook has run it (the speech graph); the style encoders have neither.
-  void run_tape(const std::function<void()>& seeds, bool flush_up, bool fc, float* d_style) {
-    side_begin();
-    if (fc) {
-      d_style_out = d_style;
-      fc_bwd_done = false;
-    }
-    seeds();
-    // The prior branch's entries [branch_lo, branch_hi) need nothing but G(lap) / G(pp), which the entry
-    // branch_join (phase_input_conv) writes, and nothing on the main stream needs them before fc(style)'s backward: with a
-    // branch stream they are issued there as soon as branch_join has run, in their own reverse order, and skipped at their place,
-    // where the main stream waits for their end instead.  The sizing pass of a graph that can be given a style stream (the speech
-    // graph: branch_can_beside) always walks the tape in that order (the larger need).
-    const bool br = branch_lo < branch_hi && branch_hi <= branch_join && branch_join < tape.size();
-    const bool br_beside = br && (branch_st || (dry && branch_can_beside));
-    hipEvent_t br_end = nullptr;
-    for (size_t i = tape.size(); i-- > 0 && rc == STY_OK;) {
-      if (br_beside && i >= branch_lo && i < branch_hi) {
-        if (i + 1 == branch_hi && br_end) {
-          hipError_t r = hipStreamWaitEvent(st, br_end, 0);
-          if (r != hipSuccess) rc = hip_fail(r, "prior branch backward join");
-          br_end = nullptr;
-        }
-        continue;
-      }
-      tape[i]();
-      if (rc != STY_OK || !br_beside || i != branch_join) continue;
-      hipStream_t const main_st = st;
-      if (branch_st) {
-        stream_after(branch_st, main_st, "prior branch backward fork");
-        st = branch_st;  // side_push, fresh_copy, the zero-fills of G and every launch of the entries follow
-      }
-      keep_temps = true;
-      for (size_t j = branch_hi; j-- > branch_lo && rc == STY_OK;) tape[j]();
-      keep_temps = false;
-      st = main_st;
-      if (branch_st && live()) {  // (also behind an entry that failed: what it did issue is joined below)
-        const int rc0 = rc;
-        rc = STY_OK;
-        br_end = next_event();
-        if (rc == STY_OK && hipEventRecord(br_end, branch_st) != hipSuccess) {
-          br_end = nullptr;
-          rc = hip_fail(hipGetLastError(), "prior branch backward end");
-        }
-        if (rc0 != STY_OK) rc = rc0;
-      }
-    }
-    // an error left the loop before the branch's place: the caller's style stream is joined all the same
-    if (br_end) (void)hipStreamWaitEvent(st, br_end, 0);
-    while (flush_up && rc == STY_OK && !pend_up.empty()) up_flush(pend_up.begin()->first);
-    while (rc == STY_OK && !pend_row.empty()) row_flush(pend_row.begin()->first);
-    side_join();
-    if (fc && rc == STY_OK) style_fc_backward();
-  }
-
-  // the prior branch of the vocoder graph (see Trainer::forward): where its resblocks run this step (nullptr: the main stream;
-  // kept from the forward for the backward), its tape entries [branch_lo, branch_hi) and the entry of the conv it joins the trunk at
-  hipStream_t branch_st = nullptr;
-  bool branch_can_beside = false;  // the graph takes a style stream (its workspace is sized without one)
-  size_t branch_lo = 0, branch_hi = 0, branch_join = 0;
-
-  // ---- side stream for the weight gradients ----
-  // A weight gradient is a leaf of the backward graph: it reads (x, gY) and nothing reads it before the optimizer.
-  // On the sample_dataset shapes the input-gradient chain is a sequence of kernels too small to fill 256 CUs, so the
-  // weight-gradient kernels (512-1024 workgroups each) run on a second, lower-priority stream and take the idle CUs.
-  // Each launch is handed over at once (one event on the main stream per launch; measured against batches of launches:
-  // c2 step 46.9 ms at 1, 47.5 at 4, 49.0 at 16: the weight gradient then
-  // overlaps the input gradient of its own layer, a kernel of the same size class).  The side stream only ever waits for the main
-  // stream; the main stream never waits for the side stream before the join at the end of the tape, because a
-  // gradient buffer with a side-stream reader is never written again: when G / Gw find such a buffer (it can only
-  // be written again through the residual aliasing below) they hand out a copy instead (copy on write).
-  // The side stream has its own partial-sum buffer (side_partial, sized in the forward for the largest conv): the
-  // main stream recycles its temporaries while the side-stream launches are still pending.
   std::vector<char> fcs_bwd_sent;  // last fc-backward table uploaded to m->fcs_bwd_dev
-  hipStream_t st2 = nullptr;
-  bool side_on = getenv("STY_NO_SIDE_STREAM") == nullptr;
-  std::vector<hipEvent_t> evs;
-  size_t ev_used = 0;
-  std::unordered_set<const float*> side_reads;  // buffers read by a side-stream launch
-  bool side_dirty = false;
-  size_t side_need = 0;  // floats
-  float* side_partial = nullptr;
-  // ---- deferred, grouped reduction of the weight-gradient partial sums (wgrad.hip) ----
-  // Every weight-gradient launch of a backward gets a partial buffer of its own (wg_take, out of one region sized in the
-  // forward: wg_sum), its reduction is recorded instead of launched, and reduce_flush sums everything recorded so far in
-  // one launch on the stream the weight gradients run on -- before a gradient segment is announced and at the end of the
-  // backward -- followed by the few steps that READ a reduced gradient (`after_reduce`: d alpha of the lean ConvNeXt32
-  // backward is a function of dW1).
-  WgReduceDefer* defer = wgrad_defer_create();
-  bool defer_on = getenv("STY_NO_DEFERRED_REDUCE") == nullptr;
-  size_t wg_sum = 0, wg_off = 0;  // floats
-  float* wg_base = nullptr;
-  int flush_site = 0;
-  std::vector<std::function<void(hipStream_t)>> after_reduce;
-  bool deferring() const { return wg_base != nullptr; }
-  float* wg_take(size_t n) {
-    n = (n + 63) & ~size_t(63);
-    float* p = wg_base + wg_off;
-    wg_off += n;
-    if (wg_off > wg_sum && rc == STY_OK) {
-      set_error("training: weight-gradient partial region too small (%zu > %zu floats)", wg_off, wg_sum);
-      rc = STY_ESTATE;
-    }
-    return p;
-  }
-  void wg_need(size_t n) { wg_sum += (n + 63) & ~size_t(63); }
-  struct DeferScope {  // the defer context is current on this thread while a backward issues launches
-    WgReduceDefer* old;
-    explicit DeferScope(Trainer* t) { old = wgrad_defer_set(t->deferring() && t->live() ? t->defer : nullptr); }
-    ~DeferScope() { (void)wgrad_defer_set(old); }
+  // nn.Dropout sites are numbered in execution order; the seed is a train option or (the aligner) an argument of the entry
+  unsigned drop_site = 0;
+  const unsigned* drop_seed_arg = nullptr;
+  unsigned drop_seed_val = 0;
+  // ---- what each graph keeps from its forward for its backward ----
+  const float *in_pitch = nullptr, *in_energy = nullptr, *in_voiced = nullptr;  // decoder
+  float *pe_f0 = nullptr, *pe_n = nullptr, *pe_sx = nullptr;                    // pitch / energy predictor
+  int pe_L = 0;
+  float *du_out = nullptr, *du_dl = nullptr;  // duration predictor
+  int du_L = 0;
+  float* al_logits = nullptr;  // aligner
+  bool al_pending = false;     // a forward whose backward has not run yet
+  float* style_out = nullptr;  // style encoders
+  // parity taps of the style encoder's training graph (sty_style_tap): the stem's output, the four ResBlk outputs and the
+  // head conv's output, as padded-flat images
+  struct SeTap {
+    const float* act;
+    int C, H, W;
   };
-  void reduce_flush(hipStream_t s) {
-    if (!deferring() || !live()) {
-      after_reduce.clear();
-      return;
-    }
-    chk(wgrad_defer_flush(defer, flush_site++, s));
-    WgReduceDefer* cur = wgrad_defer_set(nullptr);  // (what runs now reduces at once, should it reduce at all)
-    if (rc == STY_OK)
-      for (auto& fn : after_reduce) fn(s);
-    (void)wgrad_defer_set(cur);
-    after_reduce.clear();
-  }
-  // ---- bf16 operand twins (ConvArgs::x16 / g16; bf16 compute mode) ----
-  // tw_x[pro]: activation -> its twin bf16(pro(x)) (pro = PRO_NONE, PRO_LRELU), written by the kernel that produced the
-  // activation where that kernel has the output stage for it, by the cast pass (launch_twin_cast) otherwise; kept to the
-  // end of the step (the forward conv reads it, the weight gradient reads it again in the backward).
-  bool twins_env = getenv("STY_NO_TWINS") == nullptr;
-  bool twins_on() const { return twins_env && m->topts.compute_bf16 != 0; }
-  std::unordered_map<const float*, __bf16*> tw_x[2];
-  // gradient twins: tw_want = activations y whose conv will read G(y) as a twin (its weight gradient runs on wgradb16);
-  // tw_g = gradient buffer -> (twin, the [B][n] mask it was multiplied by), registered by the element-wise backward
-  // kernel that writes the buffer LAST (pooling / learned down-sampling backward); the conv's backward takes it when
-  // the mask is its own, and makes the twin with the cast pass otherwise
-  std::unordered_set<const float*> tw_want;
-  std::unordered_map<const float*, std::pair<__bf16*, const float*>> tw_g;
-  static int tw_slot(int pro) { return pro == PRO_LRELU ? 1 : 0; }
-  void twin_register(const float* x, int pro, __bf16* t) { tw_x[tw_slot(pro)][x] = t; }
-  const __bf16* xtwin(const float* x, int pro, int C, int n) {
-    auto& mp = tw_x[tw_slot(pro)];
-    auto it = mp.find(x);
-    if (it != mp.end()) return it->second;
-    __bf16* t = take<__bf16>((size_t)B * C * n);
-    if (live()) chk(launch_twin_cast(x, nullptr, pro, B, C, n, t, st));
-    mp[x] = t;
-    return t;
-  }
-  // Gradient stores nobody loads (style encoder, twins on).  g_twin_only = conv outputs y whose conv reads G(y) through the
-  // bf16 twin alone (conv2d decides with bwd_reads_twin_only when it records the conv); the element-wise backward that is the
-  // one writer of such a gradient then stores the twin and leaves the fp32 tensor out (dwconv2d_s2_bwd: conv1 of a
-  // down-sampling ResBlk).  g_no_fp32 = the buffers left that way: conv2d_bwd refuses one it would have to load.
-  // lazy_mask = activation -> the copy `G(act) = src * mask` its gradient is owed: the shortcut branch's gradient is the
-  // block's output gradient times the output mask, which the twin g16 already holds value for value.  The copy is made by
-  // whoever asks for the fp32 buffer (G / Gw), and never when the one reader takes the twin.
-  std::unordered_set<const float*> g_twin_only, g_no_fp32;
-  struct LazyMask {
-    const float* src;
-    const float* mask;
-    int C, n;
-    float* dst;
-  };
-  std::unordered_map<const float*, LazyMask> lazy_mask;
-  bool mask_pending(const float* act) const { return !lazy_mask.empty() && lazy_mask.count(act) != 0; }
-  void mask_flush(const float* act) {
-    auto it = lazy_mask.find(act);
-    if (it == lazy_mask.end()) return;
-    const LazyMask z = it->second;
-    lazy_mask.erase(it);
-    if (live())
-      chk(launch_pro_bwd(PRO_MASK, z.src, z.C, 0, z.src, B, z.C, z.n, nullptr, nullptr, z.C, 0, nullptr, z.mask, z.dst, 0,
-                         nullptr, nullptr, nullptr, st));
-  }
-  // pend_up = activation x -> the pooled gradient of the shortcut branch that has still to be up-sampled into G(x) (the
-  // backward of pool(x)).  The branch's backward runs BEFORE the main branch's first conv (style_forward records them in that
-  // order); that conv's input-gradient conv then takes the pooled gradient as an output-stage operand (ConvArgs::up_g: gate,
-  // up-sample and twin in its epilogue) where the kernel has the stage, and the element-wise pass (up_apply: what the tape
-  // entry of pool() used to launch) runs behind it otherwise -- or for whoever else asks for G(x) first.
-  struct PendUp {
-    const float* g;     // [BC][H / 2][(W + 1) / 2 + 1]
-    const float* mask;  // [B][n]: the mask of x's producer
-    float scale;
-    int BC, C, H, W, n;
-  };
-  std::unordered_map<const float*, PendUp> pend_up;
-  void up_apply(const float* src, const PendUp& u) {
-    // gs = gs * lrelu'(src) + up(g) in the one pass that accumulates into gs anyway
-    const bool gated = gate_pending(src);
-    if (gated) ungated.erase(src);
-    float* gs = G(src, (size_t)u.BC * u.n);
-    // this pass is the last writer of d loss / d src: it also leaves the bf16 operand twin for src's producer
-    __bf16* g16 = twins_on() && tw_want.count(src) && u.n % 4 == 0 ? take<__bf16>((size_t)u.BC * u.n) : nullptr;
-    if (g16) tw_g[gs] = std::make_pair(g16, u.mask);
-    if (live()) chk(launch_avgpool2_bwd(u.g, u.BC, u.H, u.W, u.scale, gs, gated ? src : nullptr, st, g16, u.mask, u.C));
-  }
-  void up_flush(const float* act) {
-    auto it = pend_up.find(act);
-    if (it == pend_up.end()) return;
-    const PendUp u = it->second;
-    pend_up.erase(it);
-    up_apply(act, u);
-  }
-  ~Trainer() {
-    wgrad_defer_destroy(defer);
-    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    if (d_style_done) (void)hipEventDestroy(d_style_done);
-    if (st2) (void)hipStreamDestroy(st2);
-  }
-  hipEvent_t next_event() {
-    if (ev_used == evs.size()) {
-      hipEvent_t e = nullptr;
-      hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-      if (r != hipSuccess) rc = hip_fail(r, "event");
-      evs.push_back(e);
-    }
-    return evs[ev_used++];
-  }
-  void side_begin() {
-    ev_used = 0;
-    side_reads.clear();
-    side_dirty = false;
-    const bool on = side_on && !single_stream_mode();
-    side_partial = on && side_need ? take<float>(side_need) : nullptr;
-    wg_base = defer_on && wg_sum ? take<float>(wg_sum) : nullptr;
-    wg_off = 0;
-    flush_site = 0;
-    after_reduce.clear();
-    if (on && !st2 && live()) {
-      // (Measured and rejected: hipExtStreamCreateWithCUMask leaving every 2nd / 4th / 8th CU to the main stream, so
-      // that its small kernels need not wait for a resident weight-gradient workgroup to retire -- c2 38.0 -> 62 ms,
-      // c3 120.5 -> 144.5 ms at every mask: masked streams lose far more than the waiting costs.)
-      int least = 0, greatest = 0;
-      (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-      hipError_t r = hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, least);
-      if (r != hipSuccess) rc = hip_fail(r, "side stream");
-    }
-  }
-  bool side_ready() const { return side_partial != nullptr; }  // also in the sizing pass (same allocations)
-  // launch on the side stream, behind the main stream's work so far, what reads gbuf (complete on the main stream at this
-  // point) and nothing the main stream writes later
-  void side_push(const float* gbuf, const std::function<void(hipStream_t)>& fn) {
-    side_reads.insert(gbuf);
-    if (!live() || !st2) return;
-    hipEvent_t e = next_event();
-    if (rc == STY_OK) {
-      hipError_t r = hipEventRecord(e, st);
-      if (r == hipSuccess) r = hipStreamWaitEvent(st2, e, 0);
-      if (r != hipSuccess) rc = hip_fail(r, "side fork");
-    }
-    if (rc == STY_OK) {
-      DeferScope ds(this);
-      fn(st2);
-    }
-    side_dirty = true;
-  }
-  void side_reduce_nowait() {
-    if (side_dirty && st2) reduce_flush(st2);
-  }
-  void side_join() {
-    reduce_flush(side_dirty && st2 ? st2 : st);
-    if (side_dirty && st2) {
-      hipEvent_t e = next_event();
-      hipError_t r = hipEventRecord(e, st2);
-      if (r == hipSuccess) r = hipStreamWaitEvent(st, e, 0);
-      if (r != hipSuccess) rc = hip_fail(r, "side join");
-    }
-    side_reads.clear();
-    side_dirty = false;
-  }
-  // copy on write of a gradient buffer the side stream reads
-  float* side_cow(const float* act, float* g, size_t n) {
-    if (side_reads.empty() || !side_reads.count(g)) return g;
-    return fresh_copy(act, g, n);
-  }
-  float* fresh_copy(const float* act, float* g, size_t n) {
-    float* g2 = take<float>(n);
-    copy_f32(g2, g, n, "grad copy");
-    gmap[act] = g2;
-    return g2;
-  }
-  // the gradient of `act` IS the buffer g (act has exactly one consumer, whose backward produced g in place): no zero-fill,
-  // no accumulate pass.  false if act already has a gradient buffer (another consumer wrote first): the caller adds instead.
-  bool alias_grad(const float* act, float* g) {
-    if (gmap.count(act)) return false;
-    gmap[act] = g;
-    return true;
-  }
-  const float* gbp(const AdaFc& a) const { return gb ? gb + a.off * B : nullptr; }
-  float* dgbp(const AdaFc& a) const { return dgb ? dgb + a.off * B : nullptr; }
-
-  template <typename Tp>
-  Tp* take(size_t n) {
-    Tp* p = ws.take<Tp>(n);
-    peak = ws.off > peak ? ws.off : peak;
-    return p;
-  }
-  // a tape entry gives its temporaries back -- unless it belongs to the prior branch's backward running beside the main stream
-  // (keep_temps): the main stream's later entries would be handed the addresses while the branch's kernels still use them
-  bool keep_temps = false;
-  void release(size_t mark) {
-    if (!keep_temps) ws.off = mark;
-  }
-  // ---- bf16 STORAGE of the 75T-rate activations (bf16 compute mode) ----
-  // What autocast stores: conv outputs live in HBM as bf16 (config/config.yml:9-12, train/train_context.py:97-103).  A tensor
-  // taken with take_act(n, true) IS two bytes per element -- there is no fp32 copy -- and travels through the graph as an
-  // opaque `float*` handle; half_ records which handles are such tensors and every launch site passes the flag of each
-  // operand (ConvArgs::xh / yh / rh, the uh / xh / dh arguments of the element-wise kernels).  Kernels that have no
-  // two-byte form refuse the flag loudly (launch_conv1d, launch_conv1d_wgrad).  Gradient ACCUMULATORS (G / Gw buffers)
-  // stay fp32: they are summed into by several kernels, and the rounding points of the mode stay those of single stores.
-  std::unordered_set<const void*> half_;
-  bool act16_env = getenv("STY_NO_ACT16") == nullptr;
-  bool act16_on() const { return act16_env && m->topts.compute_bf16 != 0; }
-  bool is16(const void* p) const { return p && !half_.empty() && half_.count(p) != 0; }
-  float* take_act(size_t n, bool h) {
-    if (!h) return take<float>(n);
-    float* p = reinterpret_cast<float*>(take<__bf16>((n + 7) & ~size_t(7)));
-    half_.insert(p);
-    return p;
-  }
+  std::vector<SeTap> se_taps;
+  SeTap se_pre2[4] = {};
+  // the harmonic-prior branch of the vocoder graph (branch_st, branch_lo / branch_hi / branch_join are the tape's)
+  struct PriorHead {
+    bool done = false;
+    float* out[2] = {nullptr, nullptr};  // the prior convs' outputs (+ their statistics partials)
+    const double* part[2] = {nullptr, nullptr};
+    float *lap = nullptr, *pp = nullptr;  // the resblocks' outputs
+    hipEvent_t end = nullptr;             // recorded behind them on branch_st
+  } prior_head_;
+  // fc(style)'s backward (style_fc_backward) and the segment hook of the speech graph
+  std::function<void(int)> on_segment;
+  float* d_style_out = nullptr;
+  bool fc_bwd_done = false;
+  hipEvent_t d_style_done = nullptr;
+  // the style encoders' sizing pass has no tensors of the caller: these stand in as distinct non-null ledger keys
+  static inline float kDryMel = 0.f, kDryStyle = 0.f;
   // ---- two-byte GRADIENTS of the 32-channel ConvNeXt chain (round 5; narrowed in round 6) ----
   // In the reference the chain starts at an nn.LayerNorm (phase_norm: fp32 under autocast) and every block returns
   // `residual + x` with an fp32 residual, so the residual STREAM and its gradient gY / gX stay fp32 there (conv_next.py:80-93,
   // generator.py:771-775); what autocast does make bf16 is the depthwise conv's output and hence its gradient gU.  Default
   // (round 6): gU two-byte (its one reader is the depthwise weight-gradient kernel), gY / gX fp32 -- the reference's types.
   // STY_GRAD16_STREAM=1 is the round-5 behaviour (gY / gX two-byte as well: 0.15 ms of a c3 step), a DELIBERATE deviation that
-  // is coarser than the reference; the oracle's round_grad on the stream follows the same switch.  g16_ok holds the
+  // is coarser than the reference; the oracle's round_grad on the stream follows the same switch.  ActRec::grad16 marks the
   // activations whose PRODUCER reads its output gradient as bf16 (a fused lean ConvNeXt32 block, the long-row LayerNorm(32));
   // the consumer that is the first -- in this graph the only -- writer of such an activation's gradient (the next block's fused
-  // input-gradient epilogue, the closing LayerNorm's backward) then takes a bf16 buffer (tagged in half_) and rounds each value
-  // once, where it stores it.  G / Gw refuse such a buffer: nothing accumulates into it.
-  std::unordered_set<const float*> g16_ok;
+  // input-gradient epilogue, the closing LayerNorm's backward) then takes a two-byte buffer (Tape::fresh_grad) and rounds each
+  // value once, where it stores it.  G / Gw refuse such a buffer: nothing accumulates into it.
   bool grad16_env = getenv("STY_NO_GRAD16") == nullptr && getenv("STY_NO_CNX_GX") == nullptr;
   bool grad16_on() const { return grad16_env && act16_on(); }
   bool grad16_stream_env = getenv("STY_GRAD16_STREAM") != nullptr && atoi(getenv("STY_GRAD16_STREAM")) != 0;
   bool grad16_stream_on() const { return grad16_stream_env && grad16_on(); }
-  // the gradient buffer of `act` for a consumer that can read a two-byte one
-  float* G16(const float* act, size_t n) {
-    auto it = gmap.find(act);
-    if (it != gmap.end() && is16(it->second)) return it->second;
-    return G(act, n);
+  bool grad16(const float* act) const {
+    const ActRec* r = ledger.find_act(act);
+    return r && r->grad16;
   }
-  // gradient buffer of an activation (zero-filled on first request)
-  // Deferred LeakyReLU gates (style encoder): `ungated` holds activations a whose gradient buffer still lacks the factor
-  // lrelu'(a) -- the input-gradient conv of a LeakyReLU-prologue conv wrote its raw output there (conv2d_bwd).  The next
-  // element-wise step that touches the buffer anyway applies the factor on its way (avgpool2_bwd accumulating into it,
-  // dwconv2d_s2_bwd reading it); anybody else gets it through G / Gw, which run the plain pass first.
-  std::map<const float*, std::pair<int, int>> ungated;  // activation -> (channels, positions)
-  bool gate_pending(const float* act) const { return !ungated.empty() && ungated.count(act) != 0; }
-  void gate_flush(const float* act) {
-    auto it = ungated.find(act);
-    if (it == ungated.end()) return;
-    const int C = it->second.first, n = it->second.second;
-    ungated.erase(it);
-    auto gi = gmap.find(act);
-    if (gi == gmap.end() || !live()) return;
-    float* g = gi->second;  // in place: one element per thread, read then written
-    chk(launch_pro_bwd(PRO_LRELU, g, C, 0, act, B, C, n, nullptr, nullptr, C, 0, nullptr, nullptr, g, 0, nullptr, nullptr,
-                       nullptr, st));
+
+  ~Trainer() {
+    if (d_style_done) (void)hipEventDestroy(d_style_done);
   }
-  // pend_row = activation h -> the row term coef[b][c] * h its gradient buffer is still owed (the GRN term of convnext()):
-  // the activation backward of act() forms it in registers on its way (take_row); anybody else who asks for G(h) first
-  // gets it through G / Gw, which run the plain pass (row_flush).
-  struct PendRow {
-    const float* coef;
-    int rows, T;
-  };
-  std::unordered_map<const float*, PendRow> pend_row;
-  void row_flush(const float* act) {
-    auto it = pend_row.find(act);
-    if (it == pend_row.end()) return;
-    const PendRow p = it->second;
-    pend_row.erase(it);
-    float* g = G(act, (size_t)p.rows * p.T);  // (the entry is erased: no way back here)
-    if (live()) chk(launch_row_scale_add(act, p.coef, 0.f, p.rows, p.T, g, st));
+  // begin() and style_forward() start from here
+  void reset_step() {
+    Tape::reset_step();
+    drop_site = 0;
+    drop_seed_arg = nullptr;
   }
-  const float* take_row(const float* act) {  // the pending term's coefficients (nullptr: none); the caller applies it
-    auto it = pend_row.find(act);
-    if (it == pend_row.end()) return nullptr;
-    const float* coef = it->second.coef;
-    pend_row.erase(it);
-    return coef;
-  }
-  // raw: the caller deals with a deferred gate itself; keep_lazy: ... and with a pending masked copy (lazy_mask);
-  // keep_row: ... and with a pending row term (pend_row)
-  float* G(const float* act, size_t n, bool raw = false, bool keep_lazy = false, bool keep_row = false) {
-    if (!pend_up.empty()) up_flush(act);
-    if (!keep_row && !pend_row.empty()) row_flush(act);
-    if (!raw && !ungated.empty()) gate_flush(act);
-    if (!keep_lazy && !lazy_mask.empty()) mask_flush(act);
-    auto it = gmap.find(act);
-    if (it != gmap.end() && is16(it->second)) {
-      set_error("a two-byte gradient buffer reached a consumer without a two-byte form");
-      rc = STY_ESTATE;
+  // fc (every graph with AdaIN / AdaLN layers): d_style is armed before the tape and fc(style)'s backward runs behind the
+  // join, unless a tape hook has run it (the speech graph); the style encoders have neither.
+  void run_tape(const std::function<void()>& seeds, bool flush_up, bool fc, float* d_style) {
+    if (fc) {
+      d_style_out = d_style;
+      fc_bwd_done = false;
     }
-    if (it != gmap.end()) return side_cow(act, it->second, n);
-    float* g = take<float>(n);
-    if (live()) {
-      hipError_t e = hipMemsetAsync(g, 0, n * sizeof(float), st);
-      if (e != hipSuccess) rc = hip_fail(e, "grad memset");
-    }
-    gmap[act] = g;
-    return g;
+    Tape::run_tape(seeds, flush_up, fc ? std::function<void()>([this]() { style_fc_backward(); }) : nullptr);
   }
-  // same, for a producer that can either overwrite or accumulate: the first writer of a buffer overwrites it
-  // (acc = 0) and no zero-fill is issued; later writers accumulate
-  float* Gw(const float* act, size_t n, int& acc) {
-    if (!pend_up.empty()) up_flush(act);
-    if (!pend_row.empty()) row_flush(act);
-    if (!ungated.empty()) gate_flush(act);
-    if (mask_pending(act)) {  // a second writer: the buffer gets its values now, and the shared twin is no longer its twin
-      tw_g.erase(lazy_mask[act].dst);
-      mask_flush(act);
-    }
-    auto it = gmap.find(act);
-    if (it != gmap.end() && is16(it->second)) {
-      set_error("a two-byte gradient buffer reached a second writer");
-      rc = STY_ESTATE;
-    }
-    if (it != gmap.end()) {
-      acc = 1;
-      return side_cow(act, it->second, n);
-    }
-    float* g = take<float>(n);
-    gmap[act] = g;
-    acc = 0;
-    return g;
-  }
-  bool wants(const float* act) const { return !nograd.count(act); }
-  // parameter gradient pointer: packed (inside the grad arena) or bound by the caller
-  float* PGpacked(const float* packed) const {
-    if (!packed || !m->garena) return nullptr;
-    return reinterpret_cast<float*>(m->garena + (reinterpret_cast<const char*>(packed) - m->arena));
-  }
-  float* PG(const float* param, size_t n) {
-    auto it = m->pgrad.find(param);
-    if (it != m->pgrad.end()) return it->second;
-    if (n > scratch_param_n) return nullptr;
-    return scratch_param;
-  }
+  const float* gbp(const AdaFc& a) const { return gb ? gb + a.off * B : nullptr; }
+  float* dgbp(const AdaFc& a) const { return dgb ? dgb + a.off * B : nullptr; }
 
   ConvArgs base(const PackedConv& w, const float* x, int Tt, float* y) {
     ConvArgs a;
@@ -644,6 +174,12 @@ struct Trainer {
       if (live()) chk(launch_bias_grad(gY, gmask, B, w.Cout, Tt, shuffle, f.out_scale, PGpacked(w.bias), bs, st));
     }
   }
+  // the instance norm behind f's AdaIN + Snake prologue, when (a, s) came from adain() of this very input and its backward
+  // has not run yet (nullptr otherwise)
+  AdainInfo* adain_to_fuse(const ConvArgs& f) {
+    ActRec* r = ledger.find_act(f.pa);
+    return r && r->has_adain && r->adain.x == f.x[0] && r->adain.s == f.ps && !r->adain.done ? &r->adain : nullptr;
+  }
   void conv_bwd(const ConvArgs& f) {
     const PackedConv& w = f.w;
     const int Tt = f.T;
@@ -654,10 +190,8 @@ struct Trainer {
     // applied after the add, gY itself BECOMES that buffer (this conv is its last reader), no copy, no zero-fill.
     float* gR = nullptr;
     if (f.residual && wants(f.residual)) {
-      if (!gmap.count(f.residual) && !(f.out_mask && f.out_mask_post) && f.shuffle <= 1)
-        gmap[f.residual] = gY;
-      else
-        gR = G(f.residual, ny);
+      const bool can_alias = !(f.out_mask && f.out_mask_post) && f.shuffle <= 1;
+      if (!(can_alias && alias_grad(f.residual, gY))) gR = G(f.residual, ny);
     }
     float* gX[3] = {nullptr, nullptr, nullptr};
     int accX[3] = {1, 1, 1};
@@ -666,14 +200,11 @@ struct Trainer {
     // aliasing of the resblock: G(x) IS the next conv's output gradient, which that conv's weight gradient reads): the kernel
     // reads the old values from there and writes a new buffer -- no copy-on-write pass over 160 MB in front of it
     const float* gX_src = nullptr;
-    if (f.nsrc == 1 && f.pro == PRO_AFFINE_SNAKE && Tt % 8 == 0 && wants(f.x[0]) && !side_reads.empty()) {
-      auto ia = adain_of.find(f.pa);
-      auto ig = gmap.find(f.x[0]);
-      if (ia != adain_of.end() && ia->second.x == f.x[0] && ia->second.s == f.ps && !*ia->second.done && ig != gmap.end() &&
-          side_reads.count(ig->second) && !is16(ig->second) && (ungated.empty() || !ungated.count(f.x[0]))) {
-        gX_src = ig->second;
-        gX[0] = take<float>((size_t)B * f.xc[0] * Tt);
-        gmap[f.x[0]] = gX[0];
+    if (f.nsrc == 1 && f.pro == PRO_AFFINE_SNAKE && Tt % 8 == 0 && wants(f.x[0]) && ledger.any_side_reads()) {
+      const ActRec* rx = ledger.find_act(f.x[0]);
+      if (adain_to_fuse(f) && rx && rx->has_g && ledger.side_read(rx->g) && !is16(rx->g) && !(rx->owed & OWED_GATE)) {
+        gX_src = rx->g;
+        gX[0] = fresh_grad(f.x[0], (size_t)B * f.xc[0] * Tt, false);
         accX[0] = 1;
         any = true;
       }
@@ -688,18 +219,14 @@ struct Trainer {
         if (gX[i] && gX[i] == gX[j]) accX[i] = 1;
     if (side_ready())  // y = conv(x) + x sharing one buffer: the side stream reads gY, the input gradient needs its own
       for (int i = 0; i < f.nsrc; ++i)
-        if (gX[i] && gX[i] == gY) gX[i] = fresh_copy(f.x[i], gY, (size_t)B * f.xc[i] * Tt);
+        if (gX[i] && gX[i] == gY) gX[i] = fresh_copy(ledger.act(f.x[i]), (size_t)B * f.xc[i] * Tt);
     float* dpa = nullptr;
     float* dps = nullptr;
     float* dal = nullptr;
     // AdaIN + Snake prologue whose (a, s) came from adain() of this very input (the resblock convs): the prologue backward,
     // the fold and the instance-norm statistics term run as ONE launch (launch_pro_bwd_adain); adain()'s tape entry then has
     // nothing left to do
-    AdainInfo* fuse = nullptr;
-    if (any && f.pro == PRO_AFFINE_SNAKE && f.nsrc == 1 && Tt % 8 == 0) {
-      auto it = adain_of.find(f.pa);
-      if (it != adain_of.end() && it->second.x == f.x[0] && it->second.s == f.ps && !*it->second.done) fuse = &it->second;
-    }
+    AdainInfo* fuse = any && f.pro == PRO_AFFINE_SNAKE && f.nsrc == 1 && Tt % 8 == 0 ? adain_to_fuse(f) : nullptr;
     if (any && fuse) {
       dal = PG(f.palpha, w.Cin);
     } else if (any) {
@@ -729,22 +256,12 @@ struct Trainer {
       if (it == m->dgrad.end()) {
         set_error("training: no input-gradient weights for a conv (model not finalized for training?)");
         rc = STY_ESTATE;
+        release(mark);
         return;
       }
       // (the input gradient of a conv whose input is a bf16 tensor is stored the same way: d loss / d prologue(x), rounded once)
       const bool u16 = f.xh && f.nsrc == 1 && act16_on();
-      float* U = take_act((size_t)B * w.Cin * Tt, u16);
-      // U is a temporary below the mark: on EVERY way out of this block its two-byte tag goes (the address is handed out again
-      // as soon as the mark is restored, possibly to an fp32 buffer) and the mark comes back
-      struct UGuard {
-        Trainer* t;
-        float* U;
-        size_t mark;
-        ~UGuard() {
-          t->half_.erase(U);
-          t->release(mark);
-        }
-      } u_guard{this, U, mark};
+      float* U = take_act((size_t)B * w.Cin * Tt, u16);  // (a temporary: release(mark) takes its two-byte tag along)
       ConvArgs d;
       d.x[0] = gY;
       d.xc[0] = w.Cout;
@@ -781,23 +298,23 @@ struct Trainer {
       }
       if (live()) chk(launch_conv1d(d, st));
       if (fuse) {
-        *fuse->done = true;
+        fuse->done = true;
         if (live())
           chk(launch_pro_bwd_adain(U, u16, f.x[0], f.xh, B, w.Cin, Tt, f.pa, f.ps, f.palpha, fuse->mean, fuse->rstd, fuse->gbl,
                                    gX[0], is16(gX[0]), accX[0], fuse->dgl, dal, f.bf16 ? 1 : 0, st, gX_src));
-        half_.erase(U);  // (a temporary: the address is handed out again as soon as the mark is restored)
         release(mark);
         return;
       }
       if (gX_src) {
         set_error("training: out-of-place prologue backward planned without the fused kernel");
         rc = STY_ESTATE;
+        release(mark);
         return;
       }
       if (u16 || f.xh) {
-        half_.erase(U);
         set_error("training: bf16-stored conv input without the fused prologue backward");
         rc = STY_ESTATE;
+        release(mark);
         return;
       }
       int c0 = 0;
@@ -817,7 +334,7 @@ struct Trainer {
     if (live()) chk(launch_act_fwd(kind, x, alpha, B, C, Tt, y, st));
     tape.push_back([=]() {
       const int Cin = kind == ACT_GLU ? 2 * C : C;
-      float* gY = G(y, (size_t)B * C * Tt, false, false, kind != ACT_GLU);
+      float* gY = G(y, (size_t)B * C * Tt, kind != ACT_GLU ? OWED_ROW : 0);
       const float* row = take_row(y);  // a row term G(y) is still owed (the GRN term): d = gY + row[b][c] * y in the kernel
       int acc = 1;
       float* gX = Gw(x, (size_t)B * Cin * Tt, acc);
@@ -829,9 +346,6 @@ struct Trainer {
 
   // nn.Dropout(p) with the counter-based hash mask (sty_hash_u), optionally fused with a residual add:
   // y = drop(x) (+ residual).  Sites are numbered in execution order; the backward recomputes the mask.
-  unsigned drop_site = 0;
-  const unsigned* drop_seed_arg = nullptr;  // the seed is an argument of the entry point (the aligner), not a train option
-  unsigned drop_seed_val = 0;
   bool dropout_on() const { return m->topts.dropout_seed != 0; }
   float* dropout(const float* x, float p, int C, int Tt, const float* residual, size_t group = 1) {
     const size_t n = (size_t)B * C * Tt;
@@ -841,9 +355,7 @@ struct Trainer {
     tape.push_back([=]() {
       float* gY = G(y, n);
       if (residual && wants(residual)) {
-        if (!gmap.count(residual)) {
-          gmap[residual] = gY;  // first writer: the output gradient becomes the residual's gradient buffer
-        } else {
+        if (!alias_grad(residual, gY)) {  // (first writer: the output gradient becomes the residual's gradient buffer)
           float* gR = G(residual, n);
           if (live()) chk(launch_row_scale_add(gY, nullptr, 1.0f, 1, (int)n, gR, st));
         }
@@ -868,15 +380,14 @@ struct Trainer {
     float* dgl = fc ? dgbp(*fc) : nullptr;
     if (live()) chk(launch_chan_layernorm(x, y, B, C, Tt, eps, fc ? 1 : 0, w, bvec, gbl, relu, omask, st));
     const bool ln32 = grad16_on() && chan_ln32_eligible(B, C, Tt, relu);
-    if (ln32 && grad16_stream_on()) g16_ok.insert(y);
+    if (ln32 && grad16_stream_on()) ledger.act(y).grad16 = true;
     tape.push_back([=]() {
       const size_t nel = (size_t)B * C * Tt;
       float* gY = ln32 ? G16(y, nel) : G(y, nel);
       int acc = 1, h16 = is16(gY) ? 2 : 0;
       float* gX;
-      if (ln32 && g16_ok.count(x) && !gmap.count(x)) {  // the closing LayerNorm of a two-byte chain: first and only writer
-        gX = take_act(nel, true);
-        gmap[x] = gX;
+      if (ln32 && grad16(x) && !has_grad(x)) {  // the closing LayerNorm of a two-byte chain: first and only writer
+        gX = fresh_grad(x, nel, true);
         acc = 0;
         h16 |= 4;
       } else {
@@ -889,7 +400,7 @@ struct Trainer {
       float* db = fc ? nullptr : PG(bvec, C);
       if (live())
         chk(launch_chan_ln_bwd(x, gY, y, B, C, Tt, eps, fc ? 1 : 0, w, gbl, relu, omask, gX, acc, mu, r, dgl, dw, db, st, h16));
-      ws.off = mark;
+      release(mark);
     });
     return y;
   }
@@ -897,12 +408,6 @@ struct Trainer {
   // AdaIN folded to a per-(b,c) affine (a, s) consumed by the next conv's prologue
   // have_part: the (sum, sum of squares) partials of x were left behind by the conv that produced it (conv32p_kernel,
   // ConvArgs::stat_part) -- no statistics pass over x
-  struct AdainInfo {
-    const float *x, *s, *mean, *rstd, *gbl;
-    float* dgl;
-    std::shared_ptr<bool> done;
-  };
-  std::unordered_map<const float*, AdainInfo> adain_of;  // folded scale a -> the instance norm it came from
   void adain(const float* x, int C, int Tt, const AdaFc& fc, float*& a, float*& s, const double* have_part = nullptr,
              int have_nseg = 0) {
     a = take<float>((size_t)B * C);
@@ -921,14 +426,17 @@ struct Trainer {
     float* dgl = dgbp(fc);
     float* aa = a;
     float* ss = s;
-    auto done = std::make_shared<bool>(false);
-    adain_of[aa] = AdainInfo{x, ss, mean, rstd, gbl, dgl, done};
+    {
+      ActRec& ra = ledger.act(aa);  // the folded scale a -> the instance norm it came from
+      ra.adain = AdainInfo{x, ss, mean, rstd, gbl, dgl, false};
+      ra.has_adain = true;
+    }
     if (!have_part && is16(x)) {
       set_error("training: instance-norm statistics pass over a bf16-stored tensor (the producing conv leaves them behind)");
       rc = STY_ESTATE;
     }
     tape.push_back([=]() {
-      if (*done) return;  // conv_bwd ran the fused prologue + statistics backward (launch_pro_bwd_adain)
+      if (ledger.act(aa).adain.done) return;  // conv_bwd ran the fused prologue + statistics backward (launch_pro_bwd_adain)
       if (is16(x)) {
         set_error("training: AdaIN backward over a bf16-stored tensor outside the fused prologue backward");
         rc = STY_ESTATE;
@@ -968,7 +476,7 @@ struct Trainer {
       const size_t mark = ws.off;
       float* sc = take<float>(dwconv_bwd_scratch_floats(B, C, Tt, K));
       if (live()) chk(launch_dwconv_bwd(x, gY, w, B, C, Tt, K, pad, gX, acc, gw, gb, sc, st));
-      ws.off = mark;
+      release(mark);
     });
     return y;
   }
@@ -1017,7 +525,7 @@ struct Trainer {
       chk(launch_grn_finalize(part, nt, c.grn_gamma, B, 128, scale, st, gxn));
       chk(launch_convnext32(a, B, 2, st));
     }
-    if (lean && grad16_stream_on()) g16_ok.insert(y);  // the lean backward reads gY as bf16 when its consumer wrote it so
+    if (lean && grad16_stream_on()) ledger.act(y).grad16 = true;  // the lean backward reads gY as bf16 when its consumer wrote it so
     const float* gbl = gbp(c.norm);
     float* dgl = dgbp(c.norm);
     {
@@ -1038,24 +546,23 @@ struct Trainer {
       const float* gx_src = nullptr;
       // lean backward, x's gradient not written yet (the chain's ordinary case): the fused kernel writes gX = gY + dwconv^T(gU)
       // itself, out of place, on overlapping tiles (convnext_bwd.hip) -- no dwconv7_bwd_dx pass over gU, gY and gX
-      const bool fuse_gx = !gmap.count(x) && Tt % 4 == 0 && getenv("STY_NO_CNX_GX") == nullptr;
+      const bool fuse_gx = !has_grad(x) && Tt % 4 == 0 && getenv("STY_NO_CNX_GX") == nullptr;
       const bool xn16 = lean && getenv("STY_NO_CNX_XN16") == nullptr;  // xn (an MFMA operand of dW1 only) as bf16
-      // two-byte gX: x's producer reads it as bf16 (g16_ok) and this is its first writer; two-byte gU: its one reader then is
+      // two-byte gX: x's producer reads it as bf16 (grad16) and this is its first writer; two-byte gU: its one reader then is
       // the depthwise weight-gradient kernel
-      const bool gx16 = fuse_gx && lean && grad16_on() && g16_ok.count(x) != 0;
+      const bool gx16 = fuse_gx && lean && grad16_on() && grad16(x);
       const bool gu16 = fuse_gx && lean && grad16_on();
       if (gy16 && !fuse_gx) {
         set_error("convnext32: a two-byte output gradient needs the fused input-gradient path");
         rc = STY_ESTATE;
         return;
       }
-      if (!gmap.count(x)) {
+      if (!has_grad(x)) {
         if (side || fuse_gx) {
-          gX = take_act(n32, gx16);
-          gmap[x] = gX;
+          gX = fresh_grad(x, n32, gx16);
           gx_src = gY;
         } else {
-          gmap[x] = gY;
+          alias_grad(x, gY);
           gX = gY;
         }
       } else {
@@ -1199,7 +706,7 @@ struct Trainer {
         else
           chk(launch_dwconv_bwd(x, gu, dww, B, 32, Tt, 7, 3, gX, 1, gdw, gdb, dsc, st));
       }
-      ws.off = mark;
+      release(mark);
     });
     return y;
   }
@@ -1232,7 +739,7 @@ struct Trainer {
       float* coef = take<float>((size_t)B * 4 * C);
       if (live()) chk(launch_grn_bwd(gxn, nullptr, 0, gamma, dsc, B, 4 * C, coef, PG(gamma, 4 * C), st));
       // gH += coef * h is owed, not run: h's producer is act(), whose backward reads gH next and forms the term itself
-      pend_row[h] = PendRow{coef, B * 4 * C, Tt};
+      ledger.owe(h, OWED_ROW).row = PendRow{coef, B * 4 * C, Tt};
     });
     float* y = take<float>((size_t)B * C * Tt);
     ConvArgs b2 = base(c.pw2, h, Tt, y);
@@ -1318,7 +825,7 @@ struct Trainer {
         d.residual = accX[i] ? gX[i] : nullptr;
         chk(launch_conv1d(d, st));
       }
-      ws.off = mark;
+      release(mark);
     });
   }
   // part_x: the statistics partials of x when the conv that produced x left them behind (ConvArgs::stat_part)
@@ -1407,7 +914,7 @@ struct Trainer {
       if (live())
         chk(launch_attention_bwd(at, gO, gQ, gKV, gKV + (size_t)inner * Tt, at.qbs, at.kbs, at.vbs, at.obs, B, inner / 8,
                                  w2, st));
-      ws.off = mark;
+      release(mark);
     });
     return o;
   }
@@ -1450,7 +957,7 @@ struct Trainer {
       if (live())
         chk(launch_attention_bwd(at, gO, gQ, gK, gV, at.qbs, at.kbs, at.vbs, at.obs, B, Hd / heads, w2, st,
                                  (aq ? 0 : 1) | (ak ? 0 : 2) | (av ? 0 : 4)));
-      ws.off = mark;
+      release(mark);
     });
     return o;
   }
@@ -1467,7 +974,7 @@ struct Trainer {
       chk(launch_length_mask(lengths, B, L, mask, st));
       chk(launch_embedding(tokens, t.emb, B, L, H, t.tokens, esc, x0, st));
     }
-    nograd.insert(mask);
+    no_grad(mask);
     {
       const float* emb = t.emb;
       const int ntok = t.tokens;
@@ -1673,7 +1180,6 @@ struct Trainer {
     return out;
   }
 
-  const float *in_pitch = nullptr, *in_energy = nullptr, *in_voiced = nullptr;
   // Decoder.forward, eval mode (decoder.py:77-90)
   float* decoder(const float* asr, const float* pitch, const float* energy, const float* voiced, int Tt) {
     const DecoderPlan& d = m->dec;
@@ -1708,12 +1214,12 @@ struct Trainer {
         float* g0 = Gw(e0, (size_t)B * Tt, acc);
         if (live()) chk(launch_box_smooth(g, B, Tt, wdt, g0, acc, st));  // symmetric operator = its own transpose
       });
-      if (!wants(e0)) nograd.insert(es);
+      if (!wants(e0)) no_grad(es);
       energy = es;
     }
     float* fnv = take<float>((size_t)B * 3 * Tt);
     if (live()) chk(launch_fnv(pitch, energy, voiced, d.fnv_w, B, Tt, fnv, st));
-    nograd.insert(voiced);
+    no_grad(voiced);
     {
       const float* w34 = d.fnv_w;
       const float* pin = in_pitch;
@@ -1763,8 +1269,6 @@ struct Trainer {
   // PitchEnergyPredictor.forward in the training graph (pitch_energy_predictor.py:62-82; ProsodyEncoder,
   // prosody_encoder.py:63-81: three layers of 2-head attention with partial RoPE on head dimension 96, AdaLN, a 1x1 FFN and
   // a projection back to inter_dim, the style re-attached after every layer; two stacks of four AdaptiveDecoderBlocks)
-  float *pe_f0 = nullptr, *pe_n = nullptr, *pe_sx = nullptr;
-  int pe_L = 0;
   void pitch_energy(const int64_t* tokens, const int64_t* lengths, const float* ali, int L, int Tt) {
     const PitchEnergyPlan& p = m->pe;
     const int D = m->te.proj_m.Cout, S = m->style_dim, HC = D + S, H = p.heads, DH = HC / H;
@@ -1776,7 +1280,7 @@ struct Trainer {
       chk(launch_length_mask(lengths, B, L, mask, st));
       chk(launch_style_expand(style, B, S, L, sx, st));
     }
-    nograd.insert(mask);
+    no_grad(mask);
     pe_sx = sx;  // its gradient, summed over the tokens, joins d_style at the end of the backward
     pe_L = L;
     const float* s0[2] = {enc, sx};
@@ -1877,8 +1381,6 @@ struct Trainer {
 
   // DurationPredictor.forward in the training graph (duration_predictor.py:58-87): cross attention between two AdaLN views
   // of the text encoding, weight-normed depthwise k5 + SiLU + 1x1 with a residual, AdaptiveConvNeXt blocks, class head
-  float *du_out = nullptr, *du_dl = nullptr;
-  int du_L = 0;
   void duration(const int64_t* tokens, const int64_t* lengths, int L) {
     const DurationPlan& d = m->dur;
     const int C = m->te.proj_m.Cout, H = 8;
@@ -1886,7 +1388,7 @@ struct Trainer {
     float* enc = text_encoder(tokens, lengths, L);
     float* mask = take<float>((size_t)B * L);
     if (live()) chk(launch_length_mask(lengths, B, L, mask, st));
-    nograd.insert(mask);
+    no_grad(mask);
     float* qn = layernorm(enc, C, L, 1e-5f, &d.qn, nullptr, nullptr);
     float* kn = layernorm(enc, C, L, 1e-5f, &d.kn, nullptr, nullptr);
     float* q = take<float>(n);
@@ -2019,12 +1521,10 @@ struct Trainer {
       const size_t mark = ws.off;
       float* sums = take<float>(2 * C);
       if (live()) chk(launch_bn_train_bwd(x, gY, one, mean, rstd, B, C, Tt, gX, acc, nullptr, nullptr, sums, st));
-      ws.off = mark;
+      release(mark);
     });
     return y;
   }
-  float* al_logits = nullptr;
-  bool al_pending = false;  // a forward whose backward has not run yet
   void aligner(const float* mel, const int64_t* lengths, int Tt, float drop_p, unsigned drop_seed, float* log_probs) {
     const AlignerPlan& p = m->ali;
     const int H = p.hidden, V = p.classes;
@@ -2035,7 +1535,7 @@ struct Trainer {
     const bool drop = drop_p > 0.f;
     float* mask = take<float>((size_t)B * Tt);
     if (live()) chk(launch_length_mask(lengths, B, Tt, mask, st));
-    nograd.insert(mel);  // layer 0: weight and bias gradient only
+    no_grad(mel);  // layer 0: weight and bias gradient only
     const float* x = mel;
     for (int i = 0; i < 3; ++i) {
       float* y = take<float>(n);
@@ -2072,7 +1572,7 @@ struct Trainer {
   float* expand(const float* enc, const float* ali, int C, int L, int Tt) {
     float* asr = take<float>((size_t)B * C * Tt);
     if (live()) chk(launch_bmm_ct(enc, ali, B, C, L, Tt, asr, st));
-    nograd.insert(ali);
+    no_grad(ali);
     tape.push_back([=]() {
       float* g = G(asr, (size_t)B * C * Tt);
       float* ge = G(enc, (size_t)B * C * L);
@@ -2136,7 +1636,7 @@ struct Trainer {
         float* sums = take<float>(2 * Cb);
         if (live())
           chk(launch_bn_train_bwd(d0, gY, bw, mean, rstd, B, Cb, Tt, gX, acc, PG(bw, Cb), PG(bb, Cb), sums, st));
-        ws.off = mark;
+        release(mark);
       });
     } else {
       if (live()) chk(launch_bn_eval_fwd(d0, c.bn_w, c.bn_b, c.bn_rm, c.bn_rv, 1e-5f, B, 2 * C, Tt, d1, st));
@@ -2150,7 +1650,7 @@ struct Trainer {
           chk(launch_bn_eval_bwd(d0, gY, bw, rm, rv, 1e-5f, B, 2 * C, Tt, tmp, PG(bw, 2 * C), PG(bb, 2 * C), st));
           chk(launch_row_scale_add(tmp, nullptr, 1.0f, B * 2 * C, Tt, gX, st));
         }
-        ws.off = mark;
+        release(mark);
       });
     }
     float* d = act(ACT_SWISH, d1, nullptr, 2 * C, Tt);
@@ -2188,7 +1688,7 @@ struct Trainer {
     a.bf16 = m->topts.compute_bf16;
     if (twins_on() && (pro == PRO_NONE || pro == PRO_LRELU) && w.CinP >= 64 && w.CoutP >= 64 && n % 2 == 0 && wants(x)) {
       a.x16 = xtwin(x, pro, Cin2d, n);
-      tw_want.insert(y);
+      ledger.act(y).reads_twin = true;
     }
     if (twins_on() && y16_act >= 0 && n % 2 == 0 && w.CoutP >= 64) {
       a.y16 = take<__bf16>((size_t)B * w.Cout * n);
@@ -2200,7 +1700,7 @@ struct Trainer {
     wg_need(pn);
     bias_pass_sizing(a);
     if (live()) chk(launch_conv1d(a, st));
-    if (a.x16 && bwd_reads_twin_only(a)) g_twin_only.insert(y);
+    if (a.x16 && bwd_reads_twin_only(a)) ledger.act(y).twin_alone = true;
     tape.push_back([this, a]() { conv2d_bwd(a); });
   }
   // the input-gradient conv of f: the conv of gY (as the twin g16 where there is one) with the transposed weights
@@ -2245,13 +1745,9 @@ struct Trainer {
     // a pooled shortcut gradient waiting for the input's gradient buffer: taken along, as an operand of the input-gradient
     // conv or as the pass behind it
     PendUp up;
-    bool has_up = false;
-    auto pu = pend_up.find(f0.x[0]);
-    if (pu != pend_up.end()) {
-      up = pu->second;
-      has_up = true;
-      pend_up.erase(pu);
-    }
+    ActRec* rx = ledger.find_act(f0.x[0]);
+    bool has_up = rx && ledger.take(*rx, OWED_UP);
+    if (has_up) up = rx->up;
     conv2d_bwd_run(f0, has_up ? &up : nullptr, has_up);
     if (has_up && rc == STY_OK) up_apply(f0.x[0], up);
   }
@@ -2261,24 +1757,23 @@ struct Trainer {
     const PackedConv& w = f.w;
     const int n = f.T;
     const size_t ny = (size_t)B * w.Cout * n, nx = (size_t)B * f.Cin2d * n;
-    float* gY = G(f.y, ny, false, true);
+    float* gY = G(f.y, ny, OWED_MASK);
+    ActRec& ry = ledger.act(f.y);
     bool own_twin = false;
     if (f.x16) {  // the weight gradient and the input gradient read gY * mask as a bf16 twin, rounded once
-      auto tg = tw_g.find(gY);
-      if (tg != tw_g.end() && tg->second.second == f.out_mask) {
-        f.g16 = tg->second.first;  // written by gY's last writer (or, for a shortcut conv, the twin conv2 of the block read)
+      const BufRec* bg = ledger.find_buf(gY);
+      if (bg && bg->g16 && bg->g16_mask == f.out_mask) {
+        f.g16 = static_cast<const __bf16*>(bg->g16);  // written by gY's last writer (or, for a shortcut conv, the twin conv2 of the block read)
         own_twin = true;
       }
     }
-    // the fp32 values of gY: owed as a masked copy (lazy_mask) or left out by the writer (g_no_fp32) -- made now, or refused,
-    // unless every load below goes through the twin
+    // the fp32 values of gY: owed as a masked copy (OWED_MASK) or left out by the writer (BufRec::no_fp32) -- made now, or
+    // refused, unless every load below goes through the twin
     const bool twin_only = own_twin && bwd_reads_twin_only(f);
-    if (twin_only && mask_pending(f.y)) {
-      lazy_mask.erase(f.y);
-      g_no_fp32.insert(gY);
-    }
-    mask_flush(f.y);
-    if (!twin_only && g_no_fp32.count(gY)) {
+    if (twin_only && ledger.take(ry, OWED_MASK)) ledger.buf(gY).no_fp32 = true;
+    mask_flush(f.y, ry);
+    const BufRec* by = ledger.find_buf(gY);
+    if (!twin_only && by && by->no_fp32) {
       set_error("training: a 2-D conv's backward loads an fp32 output gradient its writer left out");
       rc = STY_ESTATE;
       return;
@@ -2292,7 +1787,7 @@ struct Trainer {
     float* gR = (f.residual && wants(f.residual)) ? Gw(f.residual, ny, accR) : nullptr;
     int accX = 1;
     float* gX = wants(f.x[0]) ? Gw(f.x[0], nx, accX) : nullptr;
-    if (side_ready() && gX && gX == gY) gX = fresh_copy(f.x[0], gY, nx);
+    if (side_ready() && gX && gX == gY) gX = fresh_copy(ledger.act(f.x[0]), nx);
     const bool defer_gate = getenv("STY_NO_DEFERRED_GATE") == nullptr;  // A/B switch, read per call (the parity test toggles it)
     // Output stage of the input-gradient conv instead of two element-wise passes: this conv is the first writer of d x, its
     // prologue is the LeakyReLU whose factor would be deferred anyway, the pooled gradient of the shortcut branch is waiting
@@ -2308,7 +1803,7 @@ struct Trainer {
       dup.up_scale = up->scale;
       dup.up_H = up->H;
       if (conv1d_route(dup).up_stage) {
-        if (tw_want.count(f.x[0])) dup.y16 = take<__bf16>(nx);  // (in front of `mark`: kept for x's producer)
+        if (ledger.act(f.x[0]).reads_twin) dup.y16 = take<__bf16>(nx);  // (in front of `mark`: kept for x's producer)
         staged = true;
       }
     }
@@ -2317,9 +1812,9 @@ struct Trainer {
     // gY * mask, exactly as the forward stored y * mask
     if (gR && !accR && f.g16) {
       // first writer of the shortcut's gradient: gR = gY * mask is what g16 holds already.  The twin is registered for the
-      // shortcut's producer and the fp32 copy waits for a reader (lazy_mask)
-      tw_g[gR] = std::make_pair(const_cast<__bf16*>(f.g16), f.out_mask);
-      lazy_mask[f.residual] = LazyMask{gY, f.out_mask, w.Cout, n, gR};
+      // shortcut's producer and the fp32 copy waits for a reader (OWED_MASK)
+      set_grad_twin(gR, f.g16, f.out_mask);
+      ledger.owe(f.residual, OWED_MASK).mask = LazyMask{gY, f.out_mask, w.Cout, n, gR};
     } else if (gR && live()) {
       chk(launch_pro_bwd(PRO_MASK, gY, w.Cout, 0, gY, B, w.Cout, n, nullptr, nullptr, w.Cout, 0, nullptr, f.out_mask,
                          gR, accR, nullptr, nullptr, nullptr, st));
@@ -2333,10 +1828,10 @@ struct Trainer {
         return;
       }
       if (staged) {
-        if (dup.y16) tw_g[gX] = std::make_pair(dup.y16, up->mask);
+        if (dup.y16) set_grad_twin(gX, dup.y16, up->mask);
         if (live()) chk(launch_conv1d(dup, st));
         has_up = false;
-        ws.off = mark;
+        release(mark);
         return;
       }
       float* U = take<float>(nx);
@@ -2344,12 +1839,12 @@ struct Trainer {
       if (gX != gY && (f.pro == PRO_NONE || (f.pro == PRO_LRELU && !accX && defer_gate))) {
         // no pass of its own for the prologue's derivative: the input-gradient conv writes (or, without a prologue,
         // accumulates through its residual operand) the gradient buffer.  LeakyReLU prologue, first writer of the buffer:
-        // the factor lrelu'(x) is left to the next element-wise step that touches the buffer (`ungated`).
+        // the factor lrelu'(x) is left to the next element-wise step that touches the buffer (OWED_GATE).
         d.y = gX;
         d.residual = accX ? gX : nullptr;
         if (live()) chk(launch_conv1d(d, st));
-        if (f.pro == PRO_LRELU) ungated[f.x[0]] = std::make_pair(f.Cin2d, n);
-        ws.off = mark;
+        if (f.pro == PRO_LRELU) ledger.owe(f.x[0], OWED_GATE).gate = PendGate{f.Cin2d, n};
+        release(mark);
         return;
       }
       if (live()) {
@@ -2358,18 +1853,9 @@ struct Trainer {
                            gX, accX, nullptr, nullptr, nullptr, st));
       }
     }
-    ws.off = mark;
+    release(mark);
   }
 
-  float* style_out = nullptr;
-  // parity taps of the style encoder's training graph (sty_style_tap): the stem's output, the four ResBlk outputs and the
-  // head conv's output, as padded-flat images
-  struct SeTap {
-    const float* act;
-    int C, H, W;
-  };
-  std::vector<SeTap> se_taps;
-  SeTap se_pre2[4] = {};
   // pse: PitchStyleEncoder (mel_style_encoder.py:155-205, coarse_multiplier 1): the trunk runs on
   // preconv(cat(mel, pitch, energy)) -- a weight-normed Conv1d(k = 1, padding = 1), so T + 2 frames -- and the backward
   // reaches the preconv's parameters (the three inputs are data: no gradient)
@@ -2395,7 +1881,7 @@ struct Trainer {
         chk(launch_concat(src, cs, 3, B, Tt, cat, st));
         chk(launch_pad_time(cat, B * Cc, Tt, 1, padded, st));
       }
-      nograd.insert(padded);
+      no_grad(padded);
       conv(base(m->pse_pre, padded, Tp, pre));
       mel = pre;
       Tt = Tp;
@@ -2409,7 +1895,7 @@ struct Trainer {
     float* melp = take<float>((size_t)B * H * (W + 1));
     if (live()) chk(launch_pad_cols(mel, (size_t)B * H, W, melp, st));
     if (!pse) {
-      nograd.insert(melp);
+      no_grad(melp);
     } else {  // the padded image is the preconv's output: its gradient goes back without the pad column
       const int Wc = W, Hc = H;
       tape.push_back([this, melp, pre, Hc, Wc]() {
@@ -2447,18 +1933,18 @@ struct Trainer {
         const float* mk_in = mk;  // the mask of the activation being pooled (its producer's output mask)
         tape.push_back([=]() {
           const float* g = nullptr;
-          auto lz = lazy_mask.find(out);
-          if (lz != lazy_mask.end() && lz->second.mask == mko) {
+          ActRec& ro = ledger.act(out);
+          if ((ro.owed & OWED_MASK) && ro.mask.mask == mko) {
             // the pooled tensor is the block's shortcut: its gradient is conv2's output gradient times the mask of the pad
             // column, which the pass below never indexes -- it reads conv2's buffer and the masked copy is not made
-            g = lz->second.src;
-            lazy_mask.erase(lz);
+            g = ro.mask.src;
+            ledger.take(ro, OWED_MASK);
           } else {
             g = G(out, (size_t)BC * no);
           }
           // up-sampled into G(src) by the backward of the conv that reads src (conv2d_bwd), or by up_apply
-          up_flush(src);  // (a second pooling of the same tensor: one at a time)
-          pend_up[src] = PendUp{g, mk_in, scale, BC, Cc, Hc, Wc, n};
+          up_flush(src, ledger.act(src));  // (a second pooling of the same tensor: one at a time)
+          ledger.owe(src, OWED_UP).up = PendUp{g, mk_in, scale, BC, Cc, Hc, Wc, n};
         });
         return out;
       };
@@ -2477,7 +1963,7 @@ struct Trainer {
         }
       };
       // A pooled shortcut is recorded BEHIND conv1, so that the backward has the branch's pooled gradient before conv1's
-      // input-gradient conv runs and can hand it to that conv's output stage (pend_up); the two branches are independent
+      // input-gradient conv runs and can hand it to that conv's output stage (OWED_UP); the two branches are independent
       if (!k.down) shortcut();
       float* h1 = take<float>((size_t)B * k.Cin * n);
       conv2d(k.c1, xin, k.Cin, n, W + 1, h1, 1, 1, PRO_LRELU, 1.f, nullptr, mk, k.down ? -1 : PRO_LRELU);
@@ -2495,23 +1981,23 @@ struct Trainer {
         tape.push_back([=]() {
           // a deferred gate on g(h2) is applied as g is read (the buffer itself stays as it is, and stays marked)
           const bool gated = gate_pending(h2);
-          float* g = G(h2, (size_t)B * Cc * no, gated);
+          float* g = G(h2, (size_t)B * Cc * no, gated ? OWED_GATE : 0);
           int acc = 1;  // (h1 feeds nothing else: this is the first writer of its gradient, no zero-fill, no read)
           float* gx = Gw(h1, (size_t)B * Cc * n, acc);
           // ... and the last: the bf16 operand twin of d loss / d h1 (times conv1's output mask) for conv1's backward
-          __bf16* g16 = twins_on() && !acc && tw_want.count(h1) && n % 4 == 0 ? take<__bf16>((size_t)B * Cc * n) : nullptr;
-          if (g16) tw_g[gx] = std::make_pair(g16, mk1);
+          __bf16* g16 = twins_on() && !acc && ledger.act(h1).reads_twin && n % 4 == 0 ? take<__bf16>((size_t)B * Cc * n) : nullptr;
+          if (g16) set_grad_twin(gx, g16, mk1);
           // ... and where conv1's backward loads the twin alone (and h1 is no parity tap) the fp32 tensor is not stored
           bool tap = false;
           for (const SeTap& tp : se_taps) tap = tap || tp.act == h1;
-          const bool no32 = g16 && !tap && g_twin_only.count(h1) != 0;
-          if (no32) g_no_fp32.insert(gx);
+          const bool no32 = g16 && !tap && ledger.act(h1).twin_alone;
+          if (no32) ledger.buf(gx).no_fp32 = true;
           const size_t mark = ws.off;
           float* sc = take<float>(dwconv2d_s2_bwd_scratch_floats(B, Cc, Hc, Wc));
           if (live())
             chk(launch_dwconv2d_s2_bwd(h1, g, gated ? h2 : nullptr, w9, B, Cc, Hc, Wc, no32 ? nullptr : gx, acc, PGpacked(w9),
                                        PG(dwb, Cc), sc, st, g16, mk1));
-          ws.off = mark;
+          release(mark);
         });
         h = h2;
       }
@@ -2606,14 +2092,6 @@ struct Trainer {
   // an event that orders them after fc(style) and the prior convs; the main stream waits for them in front of
   // phase_input_conv.  No stream of the library's own: a fifth concurrently active stream costs the step more than any overlap
   // returns.  Otherwise (no style stream, single-stream mode, the vocoder alone) everything is issued in place on the main stream.
-  // (branch_st, branch_lo / branch_hi / branch_join: declared with the step state above)
-  struct PriorHead {
-    bool done = false;
-    float* out[2] = {nullptr, nullptr};  // the prior convs' outputs (+ their statistics partials)
-    const double* part[2] = {nullptr, nullptr};
-    float *lap = nullptr, *pp = nullptr;  // the resblocks' outputs
-    hipEvent_t end = nullptr;             // recorded behind them on branch_st
-  } prior_head_;
   void branch_begin(hipStream_t style_stream) {  // per step, before anything of the branch is issued
     prior_head_ = PriorHead();
     branch_lo = branch_hi = branch_join = 0;
@@ -2643,8 +2121,8 @@ struct Trainer {
         chk(launch_source(B, Tt, io.pitch, io.voiced, io.noise, io.seed, v.lin_w, v.lin_b, prior, srcws, st));
       chk(launch_stft64(B, N, prior_used, v.stft_fr, v.stft_fi, hs, hp, st));
     }
-    nograd.insert(hs);
-    nograd.insert(hp);
+    no_grad(hs);
+    no_grad(hp);
     // the prior convs' outputs are the resblocks' inputs: bf16 tensors when the blocks run the two-byte path (the persistent
     // kernel then also leaves the instance-norm statistics of what it stored behind: no statistics pass over a bf16 tensor)
     for (int i = 0; i < 2; ++i) {
@@ -2776,10 +2254,6 @@ struct Trainer {
   // graph places between the text encoder and the decoder (every consumer of style has run its backward by then; the
   // text encoder's backward, still to come, does not touch d_style), or after the tape.  d_style_done is recorded
   // behind it so that a caller can start the style encoder's backward on another stream (sty_speech_d_style_ready).
-  std::function<void(int)> on_segment;
-  float* d_style_out = nullptr;
-  bool fc_bwd_done = false;
-  hipEvent_t d_style_done = nullptr;
   void style_fc_backward() {
     if (fc_bwd_done) return;
     fc_bwd_done = true;
@@ -2832,7 +2306,7 @@ struct Trainer {
   // produced mel (the speech predictor's decoder), or it is copied out to the caller (d_mel; nullptr in the sizing pass)
   enum MelGrad { MEL_GRAD_NONE, MEL_GRAD_INTERNAL, MEL_GRAD_COPY };
   void backward(const float* d_audio, MelGrad mel_grad, float* d_mel, float* d_style) {
-    if (mel_grad == MEL_GRAD_NONE) nograd.insert(mel_in);
+    if (mel_grad == MEL_GRAD_NONE) no_grad(mel_in);
     run_tape([&]() { seed(audio, d_audio, (size_t)B * 300 * T); }, /*flush_up=*/false, /*fc=*/true, d_style);
     if (live() && mel_grad == MEL_GRAD_COPY && d_mel) {
       const size_t n = (size_t)B * m->voc.amp_input_conv.Cin * T;
@@ -2882,8 +2356,8 @@ int trainer_speech_forward(Trainer* t, const sty_speech_io* io, void* ws, size_t
 int trainer_speech_backward(Trainer* t, const float* d_audio, float* d_style, float* d_energy, hipStream_t st,
                             float* d_pitch) {
   t->st = st;
-  if (!d_energy && t->in_energy) t->nograd.insert(t->in_energy);
-  if (!d_pitch && t->in_pitch) t->nograd.insert(t->in_pitch);
+  if (!d_energy && t->in_energy) t->no_grad(t->in_energy);
+  if (!d_pitch && t->in_pitch) t->no_grad(t->in_pitch);
   t->backward(d_audio, Trainer::MEL_GRAD_INTERNAL, nullptr, d_style);
   const size_t n = (size_t)t->B * t->T;
   if (d_pitch && t->in_pitch && t->live()) t->copy_f32(d_pitch, t->G(t->in_pitch, n), n, "d_pitch copy");
@@ -2984,13 +2458,13 @@ int trainer_style_tap(Trainer* t, int i, int grad, float* dst, int* C, int* H, i
   const float* src = tp.act;
   if (grad) {
     t->st = st;
-    t->gate_flush(tp.act);  // (a deferred gate nobody had to apply yet)
-    auto it = t->gmap.find(tp.act);
-    if (it == t->gmap.end()) {
+    ActRec* r = t->ledger.find_act(tp.act);
+    if (r) t->gate_flush(tp.act, *r);  // (a deferred gate nobody had to apply yet)
+    if (!r || !r->has_g) {
       set_error("style tap %d: no gradient (call sty_style_bwd first)", i);
       return STY_ESTATE;
     }
-    src = it->second;
+    src = r->g;
   }
   // padded-flat [B][C][H][W+1] -> [B][C][H][W]
   hipError_t e = hipMemcpy2DAsync(dst, (size_t)tp.W * 4, src, (size_t)(tp.W + 1) * 4, (size_t)tp.W * 4,
@@ -3022,16 +2496,15 @@ int trainer_block_fwd_bwd(Trainer* t, int kind, const void* blk, int B, int C, i
   // backward from gy
   // STY_BLOCK_G16=1 (test aid): the block sits inside a two-byte gradient chain -- its output gradient arrives as bf16 (gy
   // rounded here) and its input's producer takes a bf16 gradient back (converted to fp32 for the caller below)
-  const bool g16 = kind == 0 && getenv("STY_BLOCK_G16") != nullptr && t->grad16_on() && t->g16_ok.count(out) != 0;
+  const bool g16 = kind == 0 && getenv("STY_BLOCK_G16") != nullptr && t->grad16_on() && t->grad16(out);
   t->run_tape(
       [&]() {
         if (!g16) {
           t->seed(out, gy, n);
           return;
         }
-        float* gO16 = t->take_act(n, true);
-        t->gmap[out] = gO16;
-        t->g16_ok.insert(xin);
+        float* gO16 = t->fresh_grad(out, n, true);
+        t->ledger.act(xin).grad16 = true;
         if (t->live() && gy) t->chk(launch_cast_f32_to_16(gy, n, gO16, st));
       },
       /*flush_up=*/false, /*fc=*/true, d_style);
