@@ -490,6 +490,31 @@ int sty_acoustic_loss_fwd_bwd(int B, int N, const float *audio_gt, const float *
                               float w_phase, float *losses, float *d_audio_pred, void *workspace, size_t ws_bytes,
                               void *stream);
 
+/* ---- forward-only loss values for the validation pass (validate_acoustic / _textual / _duration,
+ * train/stage_type.py:376-633; csrc/val_loss.hip) ---------------
+ * The values the three *_fwd_bwd entries above log, without a gradient buffer and with FIXED-ORDER reductions: every
+ * workgroup stores its float64 partial at its own index, one finalize workgroup adds them in index order, no atomics; the
+ * partial count depends on the shape alone.  Two calls on the same buffers give equal bits (a validation loss is compared
+ * against manifest.best_loss across passes).
+ * sty_mel_loss_fwd: the "mel" term alone (MultiResolutionSTFTLoss, train/losses.py:17-38) on the three log1p(mel128|X|)
+ *   tensors sty_acoustic_loss_fwd_bwd compares (the same feature launches; no phase, no backward tensors):
+ *   loss[0] = mean over the three resolutions of sum|t - p| / (sum|t| + 1e-6).  per_item [B][3][2] doubles or NULL: every
+ *   utterance's own (sum|t - p|, sum|t|) per resolution; their sums over B are the sums loss[0] is made of.  N > 1024.
+ * sty_mel_loss_features (host only): where sty_mel_loss_fwd leaves the features in its workspace -- byte offset of
+ *   resolution 0..2, side 0 (target) / 1 (prediction), a float tensor [128][B][frames] -- so that a caller can read what was
+ *   reduced.
+ * sty_pitch_loss_fwd: the value of sty_pitch_loss_fwd_bwd for one [B,T] curve.  workspace: 16 B bytes.
+ * sty_duration_loss_fwd: losses[0..1] as sty_duration_loss_fwd_bwd defines them.  workspace: 16 B bytes.                */
+int sty_mel_loss_workspace_bytes(int B, int N, size_t *bytes);
+int sty_mel_loss_features(int B, int N, int resolution, int side, size_t *offset_bytes, int *frames);
+int sty_mel_loss_fwd(int B, int N, const float *audio_gt, const float *audio_pred, float *loss, double *per_item,
+                     void *workspace, size_t ws_bytes, void *stream);
+int sty_pitch_loss_fwd(int B, int T, const float *target, const float *pred, float *loss, void *workspace,
+                       size_t ws_bytes, void *stream);
+int sty_duration_loss_fwd(int B, int L, int NC, const float *pred, const int64_t *text_lengths, const float *target_dur,
+                          const int64_t *target_class, const float *class_table, const float *ce_weight, float *losses,
+                          void *workspace, size_t ws_bytes, void *stream);
+
 /* ---- adversarial terms of the acoustic stage: spectrogram discriminators ---------------
  * SpecDiscriminator (train/models/discriminator.py:13-68): five weight-normed Conv2d 3x9 / 3x3 with LeakyReLU(0.1),
  * a weight-normed 3x3 score conv after each.  Parameters by reference key: index i = 0..4 is `discriminators.i`,

@@ -4,7 +4,7 @@ Python host layer over libstylish_hip.so (C ABI in include/stylish_hip.h).  Ther
 fallback: importing the library without the built .so, or calling a compute entry point without a HIP
 device, raises.
 """
-from .lib import LIB, StyError, load  # noqa: F401
+from .lib import LIB, StyDeviceError, StyError, load  # noqa: F401
 from .modules import (DurationPredictor, DurationProcessor, ExportModel, MelStyleEncoder, MultiGenerator,  # noqa: F401
                       PitchEnergyPredictor, PitchStyleEncoder, SpeechPredictor)
 from .align import TextAligner  # noqa: F401,E402

@@ -302,6 +302,22 @@ class AcousticTrainer:
         self.audio = audio
         return losses
 
+    @torch.no_grad()
+    def validate(self, *, audio_gt, texts, text_lengths, pitch, durations, noise=None, seed=0, prior_override=None, **_):
+        """validate_acoustic (stage_type.py:376-390): the eval-mode forward (acoustic_forward without the multi-spectrogram:
+        BatchNorm running statistics, no dropout, no smoothing, no power iteration) and the mel loss, forward only ->
+        ({"mel"}, {"audio" [B,1,N], "per_item" [B,3,2] float64}).  Nothing of the trainer changes: no draw from either
+        generator, no optimizer, no parameter or buffer written, the train opts of both models as the next train_batch expects."""
+        from .losses import mel_loss
+        from .validation import eval_opts
+        with eval_opts((self.sp, self.se), self.bf16):
+            step = acoustic_forward(self.sp, self.se, audio_gt=audio_gt, texts=texts, text_lengths=text_lengths, pitch=pitch,
+                                    durations=durations, mean=self.mean, std=self.std, noise=noise, seed=seed,
+                                    prior_override=prior_override)
+        audio = step.pred.audio
+        loss, items = mel_loss(audio_gt, audio.squeeze(1), per_item=True)
+        return {"mel": loss[0]}, {"audio": audio, "per_item": items}
+
     @staticmethod
     def _rank_mean(t):
         import torch.distributed as dist

@@ -1280,6 +1280,9 @@ int launch_acoustic_loss_gan(int B, int N, const float* audio_gt, const float* a
     STY_HIP(hipMemsetAsync(d_pred, 0, (size_t)B * N * sizeof(float), st));
   }
   // features: target (scratch y), prediction (kept y)
+  // (launch_loss_features below is the twin of this loop's STFT / |X| / filter-bank launches for the forward-only mel term of
+  // val_loss.hip, with the resolution table kLossRes: change the two together -- tests/test_validation_gpu.py holds the two
+  // entries' mel values to 1 fp32 ulp of each other)
   for (int r = 0; r < 3; ++r) {
     const FrontTables* t;
     int rc = get_tables(rb[r].n_fft, rb[r].n_fft, 128, 24000, st, &t);
@@ -1367,6 +1370,51 @@ int launch_acoustic_loss_gan(int B, int N, const float* audio_gt, const float* a
     if (rc) return rc;
     rc = launch_frame_bwd(dxt, t->window, B, N, n_fft, rb[r].hop, frames, (size_t)frames, (size_t)B * frames, d_pred, st);
     if (rc) return rc;
+  }
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// Forward half of the loop above for ONE signal and one resolution r, for the forward-only mel term (val_loss.hip): the same
+// launches with the same arguments -- STFT, |X| (no phase), filter bank + log1p -- so that mag [128][B][frames] (batch-folded)
+// holds bit for bit what t_mag / p_mag hold in launch_acoustic_loss_gan.  scratch: loss_features_scratch_floats(B, N).
+static const int kLossRes[3][2] = {{512, 128}, {1024, 256}, {2048, 512}};
+size_t loss_features_scratch_floats(int B, int N) {
+  size_t worst = 0;
+  for (auto& r : kLossRes) {
+    const size_t frames = N / r[1] + 1, F = r[0] / 2 + 1;
+    const size_t t = (size_t)B * frames * ((size_t)r[0] + 2 * F + F) + 1024;  // frames + y + |X|
+    worst = t > worst ? t : worst;
+  }
+  return worst;
+}
+int launch_loss_features(int B, int N, const float* audio, int r, float* mag, float* scratch, hipStream_t st) {
+  const int n_fft = kLossRes[r][0], hop = kLossRes[r][1];
+  const FrontTables* t;
+  int rc = get_tables(n_fft, n_fft, 128, 24000, st, &t);
+  if (rc) return rc;
+  const int frames = N / hop + 1, F = n_fft / 2 + 1;
+  const size_t cols = (size_t)B * frames;
+  float* xt = scratch;
+  float* y = xt + (size_t)B * n_fft * frames;
+  float* fm = y + (size_t)B * 2 * F * frames;
+  if (fft_enabled(n_fft)) {
+    rc = launch_stft_fft(audio, *t, B, N, hop, frames, (size_t)frames, cols, y, st);
+  } else {
+    launch_frame_fold(audio, t->window, B, N, n_fft, hop, frames, (size_t)frames, cols, xt, st);
+    rc = dft_fold_fwd(*t, xt, cols, y, st);
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(magphase_kernel, dim3(cdiv(B * frames, 256), F), dim3(256), 0, st, y, F, frames, (size_t)frames,
+                     (size_t)frames, cols, fm, (float*)nullptr, n_fft / 4, B);
+  if (fb_sparse_enabled()) {
+    hipLaunchKernelGGL(fb_sparse_fwd_kernel<true>, dim3((unsigned)((cols + 255) / 256), 128), dim3(256), 0, st, fm, t->fb.wp,
+                       t->fb.CoutP, t->mband, cols, mag);
+  } else {
+    rc = dense(t->fb, fm, 1, B * frames, mag, st);
+    if (rc) return rc;
+    const size_t n = (size_t)B * 128 * frames;
+    hipLaunchKernelGGL(log1p_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mag, n);
   }
   STY_LAUNCH_CHECK();
   return STY_OK;

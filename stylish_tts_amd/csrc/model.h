@@ -72,6 +72,10 @@ int launch_acoustic_loss_gan(int B, int N, const float* audio_gt, const float* a
                              float* losses_out, float* d_pred, float* ws, const AcousticGan* gan, hipStream_t st);
 int launch_multispec_single(int B, int N, const float* audio, int n_fft, int hop, int sample_rate, float* mag,
                             float* phase, float* fft_mag, float* ws, hipStream_t st);
+// the loss features of one signal at resolution r (0..2), forward only: mag [128][B][N / hop_r + 1] = log1p(mel128 |X|), the
+// tensors the acoustic loss compares (frontend.hip; val_loss.hip reduces them)
+size_t loss_features_scratch_floats(int B, int N);
+int launch_loss_features(int B, int N, const float* audio, int r, float* mag, float* scratch, hipStream_t st);
 
 // bump allocator over a caller-provided workspace (or a dry run that only measures)
 struct Bump {

@@ -68,14 +68,42 @@ def duration_losses(pred, text_lengths, target_dur, target_class, ce_weight, w_d
     return losses, d_pred
 
 
+def duration_loss_values(pred, text_lengths, target_dur, target_class, ce_weight):
+    """-> losses [2] = (duration, duration_ce) on the device, forward only and reduced in a fixed order over the items
+    (sty_duration_loss_fwd); the values duration_losses returns."""
+    lib = L.load()
+    p = pred.detach().contiguous().float()
+    if p.dim() != 3 or p.device.type != "cuda":
+        raise L.StyError(f"duration_loss_values: pred must be [B,L,classes] on a HIP device (got {tuple(p.shape)}, {p.device})")
+    B, Lt, NC = p.shape
+    dev = p.device
+    tl = text_lengths.to(dev, torch.int64).contiguous()
+    td = target_dur.to(dev, torch.float32).contiguous()
+    tc = target_class.to(dev, torch.int64).contiguous()
+    cw = ce_weight.to(dev, torch.float32).contiguous()
+    if tuple(tl.shape) != (B,) or tuple(td.shape) != (B, Lt) or tuple(tc.shape) != (B, Lt) or cw.numel() != NC:
+        raise L.StyError(f"duration_loss_values: lengths {tuple(tl.shape)}, targets {tuple(td.shape)} / {tuple(tc.shape)}, "
+                         f"weights {tuple(cw.shape)} do not fit pred {tuple(p.shape)}")
+    tab = torch.tensor(CLASS_TO_DUR, dtype=torch.float32, device=dev)
+    losses = torch.empty(2, device=dev)
+    ws = torch.empty(16 * B, dtype=torch.uint8, device=dev)
+    L.check(lib.sty_duration_loss_fwd(B, Lt, NC, L.ptr(p), L.ptr(tl), L.ptr(td), L.ptr(tc), L.ptr(tab), L.ptr(cw), L.ptr(losses),
+                                      L.ptr(ws), ws.numel(), _stream(dev)))
+    return losses
+
+
 class DurationTrainer:
     def __init__(self, duration_predictor, duration_style_encoder, dur_disc, duration_weights, lr=1e-4, betas=(0.85, 0.99),
                  eps=1e-9, weight_decay=1e-4, w_gen=1.0, w_duration=8.0, w_ce=8.0, mean=-4.0, std=4.0,
-                 bucket_bytes=25 << 20, train_mode=True, seed=0, dropout=0.2, compute="fp32"):
+                 bucket_bytes=25 << 20, train_mode=True, seed=0, dropout=0.2, compute="fp32", synth_models=None):
         import random
         from .discriminators import DiscriminatorLossHelper
         from .optim import FlatAdamW
         self.dp, self.se = duration_predictor.enable_training(), duration_style_encoder.enable_training()
+        # validate() only: the four models that turn predicted durations into listening samples (none is trained here), a
+        # dict -- or a callable returning one, asked at the first sample -- with the keys pe_style_encoder,
+        # pitch_energy_predictor, speech_predictor, speech_style_encoder
+        self.synth_models = synth_models
         self.dur_disc = dur_disc
         self.ce_weight = torch.sqrt(duration_weights.float())  # DurationLoss (losses.py:433): CrossEntropyLoss(weight=sqrt(w))
         self.w = dict(generator=w_gen, duration=w_duration, duration_ce=w_ce)  # config.yml:73-101
@@ -131,6 +159,63 @@ class DurationTrainer:
         self.disc_helper.track(disc)
         self.duration = duration
         return {"generator": gen[0], "duration_ce": losses[1], "duration": losses[0], "discriminator": disc[0]}
+
+    @torch.no_grad()
+    def validate(self, *, audio_gt, texts, text_lengths, durations, pitch=None, samples=(), noise=None, seed=0,
+                 prior_override=None, **_):
+        """validate_duration (stage_type.py:557-633): the eval-mode forward of the style encoder and the predictor and the two
+        logged losses, forward only -> ({"duration_ce", "duration"}, {"duration" [B,L], "frames" [B] (host ints),
+        "audio": {i: [1,1,N] | StyError}}).  `samples`: the utterances of the batch to synthesise at B = 1 from their PREDICTED
+        durations (stage_type.py:598-622; the reference synthesises all of them and listens to a few -- the logged numbers do not
+        depend on it); an utterance whose synthesis a host-side check refuses holds that StyError instead of audio.  noise /
+        prior_override: {i: tensor} overrides of the vocoder's random draws for utterance i.  Nothing of the trainer changes."""
+        from .validation import eval_opts, or_refusal
+        syn = self._synth() if len(samples) else {}
+        with eval_opts((self.dp, self.se) + tuple(syn.values()), self.bf16):
+            style_mel, _ = calculate_mel(audio_gt, TO_STYLE_MEL, self.mean, self.std)
+            target_dur = durations.long()
+            raw = self.dp(texts, text_lengths, self.se(style_mel.unsqueeze(1)))
+            losses = duration_loss_values(raw, text_lengths, target_dur.float(), dur_to_class(target_dur), self.ce_weight)
+            duration = prediction_to_duration(raw, text_lengths)
+            frames = [int(v) for v in duration.sum(dim=1).round().long().cpu().tolist()]  # the host reads the totals first
+            audio = {}
+            if len(samples):
+                from .acoustic import TO_MEL
+                if pitch is None:
+                    raise L.StyError("DurationTrainer.validate: samples need the batch's pitch (the pitch style encoder's input)")
+                _, _, energy = calculate_mel(audio_gt, TO_MEL, self.mean, self.std, want_energy=True)
+                pe_style = syn["pe_style_encoder"](style_mel, pitch.float().contiguous(), energy)
+                speech_style = syn["speech_style_encoder"](style_mel.unsqueeze(1))
+                lengths = [int(v) for v in text_lengths.cpu().tolist()]
+                for i in samples:
+                    # (a refusal on the host, before a launch, leaves this utterance without a sample; a device error propagates)
+                    audio[i] = or_refusal(lambda i=i: self._synthesize(
+                        syn, texts[i:i + 1], lengths[i], text_lengths[i:i + 1], duration[i:i + 1], frames[i], pe_style[i:i + 1],
+                        speech_style[i:i + 1], (noise or {}).get(i), seed, (prior_override or {}).get(i)))
+        return ({"duration_ce": losses[1], "duration": losses[0]},
+                {"duration": duration, "frames": frames, "audio": audio})
+
+    def _synth(self):
+        syn = self.synth_models() if callable(self.synth_models) else self.synth_models
+        keys = ("pe_style_encoder", "pitch_energy_predictor", "speech_predictor", "speech_style_encoder")
+        if not syn or any(k not in syn for k in keys):
+            raise L.StyError(f"DurationTrainer.validate: samples need synth_models with the keys {keys}")
+        self.synth_models = {k: syn[k] for k in keys}
+        return self.synth_models
+
+    @staticmethod
+    def _synthesize(syn, texts, n, text_lengths, duration, total, pe_style, speech_style, noise, seed, prior_override):
+        """one utterance of n tokens (row [1, L] of the batch): duration_to_alignment -> pitch_energy_predictor -> speech_predictor
+        with voiced = pred_pitch > 20.  As in the reference the alignment is made from the WHOLE row and cut to the n tokens
+        afterwards: its softmax over the text axis counts the padded positions (duration 0) too."""
+        from .acoustic import duration_to_alignment
+        if total <= 1:  # (sty_speech_fwd refuses T <= 1; said here, before the pitch / energy predictor is launched)
+            raise L.StyError(f"the predicted durations round to {total} frame(s): the speech predictor needs more than one")
+        alignment = duration_to_alignment(duration, total)[:, :n, :].contiguous()
+        texts = texts[:, :n].contiguous()
+        pp, pe = syn["pitch_energy_predictor"](texts, text_lengths, alignment, pe_style)
+        return syn["speech_predictor"](texts, text_lengths, alignment, pp, pe, (pp > 20).float(), speech_style, pp, noise=noise,
+                                       seed=seed, prior_override=prior_override).audio
 
     def schedule(self, step, step_limit):
         from .optim import scheduled_lr

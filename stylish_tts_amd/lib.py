@@ -13,7 +13,23 @@ LIB_PATH = os.path.join(HERE, "libstylish_hip.so")
 
 
 class StyError(RuntimeError):
-    pass
+    """A refusal or failure of this package.  `status`: the library's status code when `check` raised it (sty_status), None when
+    a Python-side check did."""
+    status = None
+
+
+class StyDeviceError(StyError):
+    """STY_EHIP: the HIP runtime reported an error (a failed launch, copy or allocation, a sticky device fault, no device).
+    Not a refusal: nothing may be launched behind it, so nobody who skips refused work may catch it as one (`refused_on_host`)."""
+
+
+STY_EHIP = -3  # include/stylish_hip.h sty_status
+
+
+def refused_on_host(e):
+    """True for a StyError that a host-side check raised (a Python shape check, or the library's STY_EINVAL / STY_ESHAPE /
+    STY_ENOMEM / STY_ESTATE); False for a device error and for every other exception."""
+    return isinstance(e, StyError) and not isinstance(e, StyDeviceError) and e.status != STY_EHIP
 
 
 class VocoderIO(C.Structure):
@@ -135,6 +151,11 @@ SYMBOLS = {
     "sty_acoustic_loss_workspace_bytes": (C.c_int, [_I, _I, _SZP]),
     "sty_acoustic_loss_target": (C.c_int, [_I, _I, _P, _P, C.c_size_t, _P]),
     "sty_acoustic_loss_fwd_bwd": (C.c_int, [_I, _I, _P, _P, C.c_float, C.c_float, _P, _P, _P, C.c_size_t, _P]),
+    "sty_mel_loss_workspace_bytes": (C.c_int, [_I, _I, _SZP]),
+    "sty_mel_loss_features": (C.c_int, [_I, _I, _I, _I, _SZP, C.POINTER(C.c_int)]),
+    "sty_mel_loss_fwd": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_pitch_loss_fwd": (C.c_int, [_I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_duration_loss_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_specdisc_workspace_bytes": (C.c_int, [_I, _I, _I, _I, _SZP]),
     "sty_specdisc_forward": (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P, C.c_size_t, _P]),
     "sty_specdisc_losses": (C.c_int, [_P, _I, _I, _I, _P, _P, C.c_float, _P, _P, C.c_float, _P, _P, _I, _P, C.c_size_t,
@@ -248,7 +269,9 @@ def load():
 
 def check(rc):
     if rc != 0:
-        raise StyError(f"libstylish_hip: status {rc}: {LIB.sty_last_error().decode()}")
+        e = (StyDeviceError if rc == STY_EHIP else StyError)(f"libstylish_hip: status {rc}: {LIB.sty_last_error().decode()}")
+        e.status = rc
+        raise e
 
 
 def ptr(t):

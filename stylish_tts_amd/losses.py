@@ -54,6 +54,43 @@ def acoustic_loss(audio_gt, audio_pred, w_mel=5.0, w_phase=8.0, target=None):
     return losses, d
 
 
+def mel_loss(audio_gt, audio_pred, per_item=False, features=False):
+    """The "mel" term alone, forward only, reduced in a fixed order (sty_mel_loss_fwd): audio_gt, audio_pred [B,N] ->
+    loss [1] on the device.  per_item=True: also [B,3,2] float64, every utterance's own (sum|t - p|, sum|t|) per resolution.
+    features=True: also [(target, pred)] x 3, views [128,B,frames] of the log1p-mel tensors that were reduced (they live in the
+    call's workspace).  Returned as (loss[, per_item][, features])."""
+    lib = L.load()
+    dev = audio_pred.device
+    gt = audio_gt.to(torch.float32).contiguous()
+    pr = audio_pred.detach().to(torch.float32).contiguous()
+    if pr.dim() != 2 or gt.shape != pr.shape or gt.device != dev or dev.type != "cuda":
+        raise L.StyError(f"mel_loss: audio_gt {tuple(gt.shape)} on {gt.device} and audio_pred {tuple(pr.shape)} on {dev} must "
+                         "both be [B,N] on one HIP device")
+    B, N = pr.shape
+    need = C.c_size_t()
+    L.check(lib.sty_mel_loss_workspace_bytes(B, N, C.byref(need)))
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, device=dev)
+    items = torch.empty(B, 3, 2, dtype=torch.float64, device=dev) if per_item else None
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    L.check(lib.sty_mel_loss_fwd(B, N, L.ptr(gt), L.ptr(pr), L.ptr(loss), L.ptr(items), L.ptr(ws), ws.numel(), st))
+    out = [loss]
+    if per_item:
+        out.append(items)
+    if features:
+        feats = []
+        for r in range(3):
+            pair = []
+            for side in range(2):
+                off, frames = C.c_size_t(), C.c_int()
+                L.check(lib.sty_mel_loss_features(B, N, r, side, C.byref(off), C.byref(frames)))
+                n = 128 * B * frames.value
+                pair.append(ws[off.value:off.value + 4 * n].view(torch.float32).view(128, B, frames.value))
+            feats.append(tuple(pair))
+        out.append(feats)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def acoustic_gan_loss(audio_gt, audio_pred, mrd, *, w_mel=5.0, w_phase=8.0, w_gen=1.0, disc_scale=1.0, step=(),
                       compute_bf16=False, target=None):
     """acoustic_loss plus the adversarial term of the three spectrogram discriminators `mrd` (SpecDiscriminator shells,

@@ -36,6 +36,20 @@ def pitch_loss(target, pred, weight, d_pred, normalize=True):
     return loss[0]
 
 
+def pitch_loss_value(target, pred):
+    """The value of pitch_loss for one curve, forward only and reduced in a fixed order (sty_pitch_loss_fwd) -> device scalar."""
+    lib = L.load()
+    t, p = target.contiguous().float(), pred.detach().contiguous().float()
+    if p.dim() != 2 or t.shape != p.shape or p.device.type != "cuda" or t.device != p.device:
+        raise L.StyError(f"pitch_loss_value: target {tuple(t.shape)} and pred {tuple(p.shape)} must both be [B,T] on one HIP device")
+    B, T = p.shape
+    loss = torch.empty(1, device=p.device)
+    ws = torch.empty(16 * B, dtype=torch.uint8, device=p.device)
+    L.check(lib.sty_pitch_loss_fwd(B, T, L.ptr(t), L.ptr(p), L.ptr(loss), L.ptr(ws), ws.numel(),
+                                   C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)))
+    return loss[0]
+
+
 class TextualTrainer:
     def __init__(self, pitch_energy_predictor, pe_style_encoder, speech_predictor, speech_style_encoder, pitch_disc,
                  lr=1e-4, betas=(0.85, 0.99), eps=1e-9, weight_decay=1e-4, w_mel=5.0, w_gen=1.0, w_pitch=8.0, w_energy=8.0,
@@ -120,6 +134,27 @@ class TextualTrainer:
         self.disc_helper.track(disc)
         self.pred_pitch, self.pred_energy, self.audio = pp, pe, audio
         return log
+
+    @torch.no_grad()
+    def validate(self, *, audio_gt, texts, text_lengths, pitch, durations, noise=None, seed=0, prior_override=None, **_):
+        """validate_textual (stage_type.py:451-468): the eval-mode forward of all four models -- predicted pitch and energy
+        through the frozen speech predictor -- and the three logged losses, forward only -> ({"mel", "pitch", "energy"},
+        {"audio" [B,1,N], "per_item" [B,3,2] float64}).  Nothing of the trainer changes (no RNG draw, no optimizer, no buffer)."""
+        from .losses import mel_loss
+        from .validation import eval_opts
+        with eval_opts((self.pep, self.pse, self.sp, self.se), self.bf16):
+            mel, _, energy = calculate_mel(audio_gt, TO_MEL, self.mean, self.std, want_energy=True)
+            style_mel, _ = calculate_mel(audio_gt, TO_STYLE_MEL, self.mean, self.std)
+            alignment = duration_to_alignment(durations, mel.shape[2])
+            pitch = pitch.float().contiguous()
+            pe_style = self.pse(style_mel, pitch, energy)
+            pp, pe = self.pep(texts, text_lengths, alignment, pe_style)
+            speech_style = self.se(style_mel.unsqueeze(1))
+            audio = self.sp(texts, text_lengths, alignment, pp, pe, (pp > 20).float(), speech_style, pp, noise=noise, seed=seed,
+                            prior_override=prior_override).audio
+        loss, items = mel_loss(audio_gt, audio.squeeze(1), per_item=True)
+        log = {"mel": loss[0], "pitch": pitch_loss_value(pitch, pp), "energy": pitch_loss_value(energy, pe)}
+        return log, {"audio": audio, "per_item": items}
 
     def schedule(self, step, step_limit):
         from .optim import scheduled_lr

@@ -3,15 +3,20 @@
 the HIP path -> accelerate-layout checkpoints, stage after stage (acoustic -> textual -> duration, stage_type.py:394,472,637).
 
     python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic [--checkpoint DIR] [--reset-stage]
+    python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage S --checkpoint DIR --validate-only
 
 or `stylish_tts_amd.train.train(config_path, model_config_path, out, stage, checkpoint, reset_stage)` -- the reference
 command's arguments in the reference command's order.  What is joined here exists piece by piece elsewhere in this package
-(config.py, data.py, acoustic.py / textual.py / duration.py, optim.py, stage_io.py); this file holds no arithmetic.
+(config.py, data.py, acoustic.py / textual.py / duration.py, optim.py, stage_io.py, validation.py); this file holds no
+arithmetic.  The validation pass (validation.py: the val split through the stage trainer's `validate`, `manifest.best_loss`, the
+reference's "Validation step N: ..." line, listening samples and one JSON line per pass under `<out>/<stage>/eval/`) runs every
+`training.val_interval` / `save_interval` steps and at the natural end of a stage, on rank 0 alone; `--validate-only` loads
+--checkpoint, runs one pass and exits without training or saving.
 The reference's other two commands on the same files: `convert` is below (--convert), `voicepack` is
 stylish_tts_amd/voicepack.py (its consumer, `speak`, is stylish_tts_amd/speak.py); both take the last stage's checkpoint.
 
 What the reference's loop does and this one does NOT (out of scope): the alignment stage (its own command, as in
-the reference: train_align.py), validation audio / tensorboard, the WavLM loss term (third-party weights), the batch-size PROBE
+the reference: train_align.py), validation figures / tensorboard, the WavLM loss term (third-party weights), the batch-size PROBE
 (train/batch_manager.py probe_loop: an out-of-memory search for 24-80 GB cards) -- with 288 GB of HBM every length bin runs at
 `training_plan.<stage>.probe_batch_max` and that table is written to `<stage>_batch_sizes.json` exactly where the probe
 would have left it, so a table the reference probed is used as it is when the file is already there.
@@ -183,16 +188,21 @@ class TrainContext:
                                   w_energy=float(w.energy), **common)
         if stage == "duration":
             from .duration import DurationTrainer
+            # validate_duration's listening samples run the other stages' models (asked for at the first sample only)
+            synth = lambda: {k: self.model(k) for k in ("pe_style_encoder", "pitch_energy_predictor", "speech_predictor",
+                                                        "speech_style_encoder")}
             return DurationTrainer(self.model("duration_predictor"), self.model("duration_style_encoder"), self.model("dur_disc"),
                                    self.duration_weights.to(self.device), w_gen=float(w.generator),
-                                   w_duration=float(w.duration), w_ce=float(w.duration_ce), **common)
+                                   w_duration=float(w.duration), w_ce=float(w.duration_ce), synth_models=synth, **common)
         raise L.StyError(f"{stage} is not a stage of this path (acoustic, textual, duration; the alignment stage is the "
                          "reference's own)")
 
 
 def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage=False, config_path="", model_config_path="",
-                max_steps=None, adversarial=True, device=None, log=_log):
+                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False):
     """train/train.py:76-338.  `max_steps`: stop after that many optimizer steps IN TOTAL (tests; None = the plan's epochs).
+    `validate_only`: load `checkpoint`, run ONE validation pass of `stage` (log line, samples, eval/validation.jsonl; the record
+    is left under `.validation`) and return without a training step or a save.
     Returns the context (models, manifest, the last stage's trainer under `.stage`)."""
     from . import data as D
     from . import stage_io as IO
@@ -242,6 +252,14 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
     else:
         ctx.manifest.current_epoch, ctx.manifest.current_total_step, ctx.manifest.current_step = 1, 0, 0
     ctx.manifest.stage = stage
+    if validate_only:
+        if not checkpoint:
+            raise L.StyError("validate_only needs a checkpoint")
+        from .validation import rank_validates
+        ctx.validation = None  # (ranks other than 0: the pass and its files are rank 0's alone, here as in the loop)
+        if rank_validates(ctx.rank, ctx.world):
+            ctx.validation = _validation_pass(ctx, ctx.stage, log).run(ctx.stage.trainer, ctx.manifest, config.loss_weight)
+        return ctx
     total = 0
     while True:
         st = ctx.stage
@@ -262,10 +280,26 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
     return ctx
 
 
+def _validation_pass(ctx, st, log):
+    from .validation import ValidationPass
+    return ValidationPass(ctx.config, ctx.model_config, st.name, st.out_dir, st.batch_sizes.get_batch_size, ctx.device, log=log)
+
+
 def _train_loop(ctx, st, fast_forward, max_steps, total, D, IO, log):
-    """train_val_loop (train/train.py:341-442) without the validation pass: epochs over the length-bin sampler, the cosine
-    schedule driven by the manifest's step, a checkpoint every save_interval steps and `checkpoint_final` at the end."""
+    """train_val_loop (train/train.py:341-442): epochs over the length-bin sampler, the cosine schedule driven by the manifest's
+    step, a validation pass every val_interval / save_interval steps (before the save) and at the natural end of the stage, a
+    checkpoint every save_interval steps and `checkpoint_final` at the end."""
+    from .validation import rank_validates, should_validate
     m, cfg = ctx.manifest, ctx.config.training
+    val = [None, None]  # the stage's ValidationPass (built at the first pass), the total step it last ran at
+
+    def validate():  # rank 0 alone, no collective: the other ranks wait in their next step's gradient exchange
+        if not rank_validates(ctx.rank, ctx.world) or val[1] == m.current_total_step:
+            return
+        val[0] = val[0] or _validation_pass(ctx, st, log)
+        val[0].run(st.trainer, m, ctx.config.loss_weight)
+        val[1] = m.current_total_step
+
     m.steps_per_epoch = st.batch_sizes.get_steps(ctx.time_bins)  # Stage.get_steps (stage.py:95-106)
     step_limit = max(1, m.steps_per_epoch * st.max_epoch)
     # every rank takes every world-th batch of the same shuffled order (the reference gets this split from accelerate's
@@ -296,14 +330,18 @@ def _train_loop(ctx, st, fast_forward, max_steps, total, D, IO, log):
                 first = float(vals.reshape(-1)[0])
                 running = first if running is None else 0.9 * running + 0.1 * first
                 log(f"{st.name} epoch {m.current_epoch} step {m.current_step}/{m.steps_per_epoch}: first logged loss {first:.4f}")
+            if should_validate(num, cfg.val_interval, cfg.save_interval):
+                validate()
             if num % int(cfg.save_interval) == 0:
                 save("checkpoint", True)
-            if max_steps is not None and total >= max_steps:
+            if max_steps is not None and total >= max_steps:  # (a test hook: this exit adds no validation pass)
                 save("checkpoint_final", False)
                 return total
         m.current_epoch += 1
         m.current_step = 0
         m.training_log.append(f"Completed 1 epoch of {st.name} training")
+    if should_validate(0, cfg.val_interval, cfg.save_interval, stage_end=True):
+        validate()
     save("checkpoint_final", False)
     return total
 
@@ -349,11 +387,14 @@ def main(argv=None):
     ap.add_argument("--reset-stage", dest="reset_stage", action="store_true")
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--convert", action="store_true", help="export the inference graph of --checkpoint instead of training")
+    ap.add_argument("--validate-only", dest="validate_only", action="store_true",
+                    help="one validation pass of --stage on --checkpoint: the log line, the samples and the JSON line; no training")
     a = ap.parse_args(argv)
     if a.convert:
         convert(a.config_path, a.model_config_path, a.out, a.checkpoint)
         return
-    train(a.config_path, a.model_config_path, a.out, a.stage, a.checkpoint, a.reset_stage, max_steps=a.max_steps)
+    train(a.config_path, a.model_config_path, a.out, a.stage, a.checkpoint, a.reset_stage, max_steps=a.max_steps,
+          validate_only=a.validate_only)
 
 
 if __name__ == "__main__":
