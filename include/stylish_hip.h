@@ -439,9 +439,11 @@ int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const flo
                       const float *in_mask, const float *residual, const float *out_mask, int out_mask_post, int relu,
                       float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
 /* Which kernel family the dispatch picks for a conv of this shape carrying the operands named in `flags` (host only, nothing is
- * launched): *kernel = position in the dispatch order's list of families (STY_CONV_*), -1 where the conv is refused.      */
+ * launched): *kernel = position in the dispatch order's list of families (STY_CONV_*), -1 where the conv is refused.
+ * STY_ROUTE_FLAT_IMAGE: the conv is a 3-row 2-D conv in flat-image mode (the discriminators' layout): Cin = 3 * the image's
+ * channels, T = rows * row pitch (the pitch itself does not enter the choice).                                            */
 enum { STY_ROUTE_IN_MASK = 1, STY_ROUTE_RESIDUAL = 2, STY_ROUTE_OUT_MASK = 4, STY_ROUTE_RELU = 8, STY_ROUTE_TWO_BYTE_X = 16,
-       STY_ROUTE_STATS = 32, STY_ROUTE_Y16 = 64, STY_ROUTE_X16 = 128 };
+       STY_ROUTE_STATS = 32, STY_ROUTE_Y16 = 64, STY_ROUTE_X16 = 128, STY_ROUTE_FLAT_IMAGE = 256 };
 enum { STY_CONV_STEM2D = 0, STY_CONV_32P, STY_CONV_SC, STY_CONV_K1, STY_CONV_Q, STY_CONV_P16, STY_CONV_TILED };
 int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int compute_bf16, int flags, int *kernel);
 /* Gradients of the same conv on the kernels the training graph uses: dw [Cout,Cin,K] and dbias [Cout] (or NULL) from

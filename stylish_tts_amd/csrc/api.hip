@@ -2964,6 +2964,15 @@ int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int comput
   if (flags & STY_ROUTE_STATS) a.stat_part = dummy_d;
   if (flags & STY_ROUTE_Y16) a.y16 = dummy_h;
   if (flags & STY_ROUTE_X16) a.x16 = dummy_h;
+  if (flags & STY_ROUTE_FLAT_IMAGE) {
+    if (Cin % 3) {
+      set_error("sty_conv1d_route: flat-image mode needs Cin = 3 * image channels");
+      return STY_EINVAL;
+    }
+    a.flatW = 4;  // (no family's predicate reads the pitch's value)
+    a.hpad = 1;
+    a.Cin2d = Cin / 3;
+  }
   const ConvRoute r = conv1d_route(a);
   *kernel = r.refusal == CONV_OK ? (int)r.kernel : -1;
   return STY_OK;

@@ -20,7 +20,8 @@
 //   * the 32 -> 1 score convs and their backward are bandwidth-bound VALU kernels (a 32x padded MFMA tile would cost
 //     more than the main convs);
 //   * the losses need the median of (real - gen) scores over up to 10 M elements: an 8-bit x 4 pass radix select on the
-//     device (no sort, no host round trip), the gradient goes to the selected element as torch.median's does.
+//     device (no sort, no host round trip); the median's gradient is divided evenly among the elements equal to it, as
+//     torch.median's is (one element when there is no tie).
 //
 // Forward activations are computed once for target and prediction and serve both the generator-side backward (input
 // gradient) and the discriminator-side backward (weight gradients): stage.py:104-147 evaluates the two losses with the
@@ -65,34 +66,48 @@ __global__ __launch_bounds__(256) void sd_pack_kernel(const float* __restrict__ 
 
 // gradient of the packed weights -> (dg, dv, db) of the weight_norm parametrization, added to the caller's buffers:
 //   dg = <dW, v> / ||v||,   dv = (g / ||v||) (dW - v <dW, v> / ||v||^2).  gd: double-precision packed gradient (score convs)
+// The two sums and the projection are taken in double: dv is the difference of two terms of the size of dW, and where the
+// row holds one element (dim_in 1, K 1) it is structurally zero -- in fp32 the difference left 1e-7 |dW| there, more than the
+// absolute floor of the gradient gates (tests/test_disc_edges.py, the K = 1 case).  32 or 64 workgroups of <= 1344 elements.
+__device__ __forceinline__ double sd_block_sum_d(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
 __global__ __launch_bounds__(256) void sd_unpack_kernel(const float* __restrict__ gwp, const double* __restrict__ gd,
                                                         const float* __restrict__ gbp, const double* __restrict__ gbd,
                                                         const float* __restrict__ g, const float* __restrict__ v,
                                                         int form, int Cin, int KH, int KW, int CinP, int CoutP,
                                                         float scale, float* __restrict__ dg, float* __restrict__ dv,
                                                         float* __restrict__ db) {
-  __shared__ float red[256];
+  __shared__ double red[256];
   const int co = blockIdx.x, n = Cin * KH * KW;
-  float svv = 0.f, sgv = 0.f;
+  double svv = 0.0, sgv = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
     const int kw = i % KW, kh = (i / KW) % KH, ci = i / (KW * KH);
     const size_t o = sd_off(form, co, ci, kh, kw, CinP, CoutP);
-    const float d = gd ? (float)gd[o] : gwp[o];
-    const float vv = v[(size_t)co * n + i];
-    svv = fmaf(vv, vv, svv);
-    sgv = fmaf(d, vv, sgv);
+    const double d = gd ? gd[o] : (double)gwp[o];
+    const double vv = (double)v[(size_t)co * n + i];
+    svv = fma(vv, vv, svv);
+    sgv = fma(d, vv, sgv);
   }
-  svv = sd_block_sum(svv, red);
-  sgv = sd_block_sum(sgv, red);
-  const float nrm = sqrtf(svv), gg = g[co];
+  svv = sd_block_sum_d(svv, red);
+  sgv = sd_block_sum_d(sgv, red);
+  const double nrm = sqrt(svv), gg = (double)g[co];
   for (int i = threadIdx.x; i < n; i += 256) {
     const int kw = i % KW, kh = (i / KW) % KH, ci = i / (KW * KH);
     const size_t o = sd_off(form, co, ci, kh, kw, CinP, CoutP);
-    const float d = gd ? (float)gd[o] : gwp[o];
-    dv[(size_t)co * n + i] += scale * (gg / nrm) * (d - v[(size_t)co * n + i] * sgv / svv);
+    const double d = gd ? gd[o] : (double)gwp[o];
+    dv[(size_t)co * n + i] += (float)((double)scale * (gg / nrm) * (d - (double)v[(size_t)co * n + i] * (sgv / svv)));
   }
   if (threadIdx.x == 0) {
-    dg[co] += scale * sgv / nrm;
+    dg[co] += (float)((double)scale * sgv / nrm);
     db[co] += scale * (gbd ? (float)gbd[co] : gbp[co]);
   }
 }

@@ -25,11 +25,14 @@ __device__ __forceinline__ float sd_block_sum(float v, float* red) {
 //   generator (losses.py:346-373):     mean((1 - g)^2) + min(tau, mean_{g < r + m} ((g - r) - m)^2),  m = median(g - r)
 //   discriminator (losses.py:245-290): mean((1 - r)^2) + mean(g^2) + min(tau, sum_{r < g + m} ((r - g) - m)^2 / (count + 1e-9)),
 //                                      m = median(r - g)
-// SelState: radix-select state; sums[0..5] = S_a, S_b, count, S_rel, S_lin, unused
+// The median enters rel through every selected element, so d rel / d m = -2 * S_lin / count flows back to the score maps
+// through torch.median's backward.  For the full reduction that is evenly_distribute_backward: the gradient is divided
+// equally among ALL elements equal to the median (-0.0 == +0.0 counts as equal, as in torch), not put on one of them.
+// SelState: radix-select state; sums[0..5] = S_a, S_b, count, S_rel, S_lin, ties (elements equal to the median; sums of
+// whole numbers, exact as doubles)
 // ---------------------------------------------------------------------------------------------------------------
 struct SdSel {
   unsigned prefix, kth, hist[256];
-  int jmed;
   float m;
   double sums[6];
 };
@@ -46,7 +49,6 @@ __global__ void sd_sel_init_kernel(SdSel* s, unsigned kth) {
   if (t == 0) {
     s->prefix = 0;
     s->kth = kth;
-    s->jmed = 0x7fffffff;
     s->m = 0.f;
     for (int i = 0; i < 6; ++i) s->sums[i] = 0.0;
   }
@@ -83,13 +85,12 @@ __global__ void sd_sel_pick_kernel(SdSel* s, int pass) {
   for (int i = 0; i < 256; ++i) s->hist[i] = 0;
   if (pass == 3) s->m = sd_unkey(s->prefix);
 }
-// sums + the index of the median element (the first one holding the median value)
+// sums + the number of elements holding the median value
 __global__ __launch_bounds__(256) void sd_loss_sums_kernel(const float* __restrict__ r, const float* __restrict__ g, int gen,
                                                            size_t n, SdSel* s) {
   __shared__ float red[256];
   const float m = s->m;
-  float sa = 0.f, sb = 0.f, cnt = 0.f, srel = 0.f, slin = 0.f;
-  int jm = 0x7fffffff;
+  float sa = 0.f, sb = 0.f, cnt = 0.f, srel = 0.f, slin = 0.f, ties = 0.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float rv = r[i], gv = g[i];
     const float d = gen ? gv - rv : rv - gv;
@@ -105,14 +106,13 @@ __global__ __launch_bounds__(256) void sd_loss_sums_kernel(const float* __restri
       srel = fmaf(d - m, d - m, srel);
       slin += d - m;
     }
-    if (d == m && (int)i < jm) jm = (int)i;
+    if (d == m) ties += 1.f;
   }
-  float v[5] = {sa, sb, cnt, srel, slin};
-  for (int t = 0; t < 5; ++t) {
+  float v[6] = {sa, sb, cnt, srel, slin, ties};
+  for (int t = 0; t < 6; ++t) {
     const float x = sd_block_sum(v[t], red);
     if (threadIdx.x == 0 && x != 0.f) atomicAdd(&s->sums[t], (double)x);
   }
-  if (jm != 0x7fffffff) atomicMin(&s->jmed, jm);
 }
 // loss value (added to out[0], the part without the relativistic term to out[1]) and the score gradients times `scale`
 __global__ __launch_bounds__(256) void sd_loss_grad_kernel(const float* __restrict__ r, const float* __restrict__ g, int gen,
@@ -126,12 +126,12 @@ __global__ __launch_bounds__(256) void sd_loss_grad_kernel(const float* __restri
   const bool act = SD_TAU - rel > 0.f;  // relu(tau - rel) passes the gradient
   const float inv_n = 1.f / (float)n, inv_c = (float)(1.0 / den);
   const float gm = -2.f * (float)s->sums[4] * inv_c;  // d rel / d m
+  const float gm_each = gm / (float)s->sums[5];       // ... split evenly among the elements equal to m (>= 1 of them)
   if (blockIdx.x == 0 && threadIdx.x == 0 && out) {
     const float plain = (float)((s->sums[0] + s->sums[1]) / (double)n);
     atomicAdd(&out[0], plain + (SD_TAU - fmaxf(SD_TAU - rel, 0.f)));
     atomicAdd(&out[1], plain);
   }
-  const int jmed = s->jmed;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const float rv = r[i], gv = g[i];
     const float d = gen ? gv - rv : rv - gv;
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void sd_loss_grad_kernel(const float* __restri
     float t = 0.f;  // d (relativistic term) / d d_i
     if (act) {
       if (in) t = 2.f * (d - m) * inv_c;
-      if ((int)i == jmed) t += gm;
+      if (d == m) t += gm_each;
     }
     if (gen) {
       gg[i] = scale * (-2.f * (1.f - gv) * inv_n + t);

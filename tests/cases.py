@@ -62,6 +62,114 @@ MEL_FRONT_CASES = [
 ]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Discriminator shapes (csrc/disc.hip, csrc/cfdisc.hip, csrc/disc_common.h), derived from the kernels as they stand.  Every case
+# keeps >= 16 elements in its smallest score map (the selected set of the relativistic term stays non-empty); the smallest map's
+# element count B * H * Wl[3] (spectrogram), B * t * 16 (waveform), B * T (sequences) is the number in brackets.
+#
+# Spectrogram discriminator, (B, H, W).  SdRun::geometry: widths Wl = W, ceil(W/2), ceil(./2), ceil(./2), same; row pitches
+# Wp[3] = align4(Wl[3] + 4), Wp[0] = 8 Wp[3], halved per level.  sd_l0_kernel and sd_score4_kernel<4> own 4 columns per thread and
+# 1024 per workgroup in x; sd_score4_kernel<4> owns RH = 4 rows per thread (grid.y = ceil(H / 4)); its loads row[-1] (w0 > 0) and
+# row[4] stay inside the row because Wp[i] >= Wl[i] + 4 at every level.  In fp32 mode every conv, input-gradient conv included, is
+# conv1d_mfma_kernel in flat-image mode (the bf16-only families refuse it): <1,4,1,2> for the 32-wide outputs, <2,2,1,1> for the
+# 64-wide input gradients of levels 1-3 (profiles/disc_edges_table.txt lists the family per conv).
+DISC_SPEC_CASES = [
+    (2, 2, 32),    # [16] Wl 32/16/8/4, pitches 64/32/16/8: the largest width on Wp[0] = 64; level 3 has exactly the 4 zero columns of
+                   # the 3x9 window's reach (Wl[3] % 4 == 0); even at every halving; H < RH: one row group, rows 2, 3 of it empty, and
+                   # no row has both neighbours
+    (1, 4, 25),    # [16] Wl 25/13/7/4: the smallest width with Wl[3] = 4 (again 4 zero columns), odd at the first three halvings;
+                   # H = RH: one exactly full row group
+    (3, 7, 33),    # [105] Wl 33/17/9/5, pitches 96/48/24/12: the first Wp[3] = 12 (three float4 groups per row at level 3, pitches no
+                   # power of two); H = 7: the second row group holds 3 rows; two batch borders
+    (4, 1, 40),    # [20] H = 1: every kh != 1 tap and every +-Wp shift of the flat-image convs leaves the slab; Wl 40/20/10/5
+    (2, 6, 9),     # [24] Wl 9/5/3/2, pitches 64/32/16/8: a single tile at every level, 6 pad columns at level 3; H = 6: second row
+                   # group with 2 rows
+    (1, 3, 1024),  # [384] Wp[0] = 1056: the second sd_l0 workgroup (blockIdx.x = 1) writes pad columns only; the level-0 sd_score4
+                   # workgroup is exactly full (256 threads x 4 columns) and there is no second one
+    (2, 3, 1025),  # [774] Wl 1025/513/257/129, Wp[0] = 1088: one valid column in the second workgroup of sd_l0 and of the level-0
+                   # sd_score4 (one live thread with one valid column)
+]
+# compute_bf16 mode, same gates as test_spec_discriminator_bf16_mode.  (3, 7, 33) and (2, 3, 1025) stay below convp16_kernel's
+# threshold (48 tiles of 128 flat positions) at every level, so their convs run conv1d_mfma_kernel<.., true> followed by
+# sd_post_kernel; no case above reaches convp16_kernel's flat-image mode with its LeakyReLU + column-split output stage.
+# (4, 45, 25) is the smallest shape of the table's kind that does: level 1 has 45 * 32 = 1440 flat positions, 12 tiles x B = 48,
+# so the level-1 conv and its input gradient run convp16_kernel while levels 2-4 (24 / 12 / 12 tiles) stay on the tiled kernel.
+DISC_SPEC_BF16_CASES = [(3, 7, 33), (2, 3, 1025), (4, 45, 25)]
+DISC_SPEC_TIED = (3, 9, 25)  # rows 0 and 1 of pred equal target: two thirds of every real - gen map are +0.0, the median is 0
+
+# Waveform discriminator, (B, N).  CfRun::geometry: t = (N - 1024) // 512 + 1 windows of 1024 samples every 512, the tail is
+# dropped; level-l tensors are [B][C][t * P_l], P = 1280/320/80/40/20 with L = 1024/256/64/32/16 valid positions.  cf_fold_kernel
+# adds the (at most two) windows w1 - 1, w1 = n // 512 that cover sample n and must leave the dropped tail at exactly zero.
+DISC_WAVE_CASES = [
+    (1, 1024),  # [16] one window, no tail; the level-4 tensors are 20 positions per row, far below any conv tile
+    (2, 1535),  # [32] one window and the longest dropped tail (511 samples): d_pred[:, 1024:] stays exactly zero
+    (1, 1536),  # [32] the first two-window length; samples 512 .. 1023 lie in both windows
+    (3, 2047),  # [96] two windows + a 511-sample tail, three rows
+    (2, 2560),  # [128] four windows, no tail
+    (1, 3583),  # [80] five windows (odd count) + a 511-sample tail
+]
+
+# Pitch / duration discriminators, (name, dim_in, K, B, T); name "pitch" / "dur": the fixture's weights, "seeded": disc_seq_params.
+# pd_score_kernel / pd_gz_kernel own 64 columns per workgroup; K = 21 and K = 5 take pd_score_wgrad_kernel<K>, every other odd
+# K <= 31 takes pd_score_wgrad_generic_kernel.  The dense convs are conv1d_mfma_kernel<2,2,1,1> (64 couts x 64 columns; <1,4,1,2>
+# for the input gradient of layer 0, whose packed Cout is 32).
+DISC_SEQ_CASES = [
+    ("pitch", 2, 21, 2, 63), ("pitch", 2, 21, 2, 64), ("pitch", 2, 21, 2, 65),  # [126 ..] one column below / on / above a workgroup
+    ("dur", 1, 5, 2, 63), ("dur", 1, 5, 2, 64), ("dur", 1, 5, 2, 65),
+    ("pitch", 2, 21, 4, 7),    # [28] T < K // 2 = 10: every tap row is clipped on both sides, taps 0 .. 3 and 17 .. 20 never land
+    ("dur", 1, 5, 8, 2),       # [16] T = K // 2: the duration discriminator sees token counts
+    ("seeded", 3, 7, 3, 65),   # [195] K = 7: the generic score weight-gradient kernel; one column into the second workgroup
+    ("seeded", 1, 1, 4, 5),    # [20] K = 1: pad 0, the generic kernel with a single tap
+]
+DISC_SEQ_TIED = ("dur", 1, 5, 3, 64)  # rows 0 and 1 of pred equal target
+
+
+def disc_spec_inputs(B, H, W, tied=False):
+    """magnitude-like target and prediction [B, 1, H, W] (the recipe of test_discriminators.py); tied: rows 0, 1 of pred = target.
+    The noise of 0.6 puts the level-0 relativistic term of the fixture's weights at 0.02 .. 0.037, below tau = 0.04 at every level
+    of every case (its gradient is live, test_disc_oracle.py asserts it) and large enough for the choice of the median to show in
+    the loss VALUES; at the 0.4 of test_discriminators.py the upper median would move them by less than two gates."""
+    g = torch.Generator().manual_seed(B * 1000 + W + 7 * H)
+    t = torch.rand(B, 1, H, W, generator=g) ** 2 * 3
+    q = (t + (0.1 if tied else 0.6) * torch.randn(B, 1, H, W, generator=g)).abs()
+    if tied:
+        q[:2] = t[:2]
+    return t, q
+
+
+def disc_wave_inputs(B, N):
+    """(the seed's + 1: with N + B alone the cases (2, 2560) and (1, 3583) hold a unit of the ReLU behind last.0 whose
+    pre-activation is 3e-7, inside the fp32 rounding of that tensor (2e-6) -- at such a kink the gradient is whatever side the
+    rounding falls on, and there is nothing to compare; test_disc_oracle.py asserts the margin of every case)"""
+    g = torch.Generator().manual_seed(N + B + 1)
+    t = 0.3 * torch.randn(B, N, generator=g)
+    return t, t + 0.1 * torch.randn(B, N, generator=g)
+
+
+def disc_seq_inputs(dim_in, B, T, tied=False):
+    g = torch.Generator().manual_seed(9 + 100 * T + B)
+    t = torch.randn(B, dim_in, T, generator=g) * 2
+    q = t + (0.1 if tied else 0.5) * torch.randn(t.shape, generator=g)
+    if tied:
+        q[:2] = t[:2]
+    return t, q
+
+
+def disc_seq_params(dim_in, K, seed=31):
+    """PitchDiscriminator state_dict for a tap count the fixtures do not hold: original1 normal, original0 = the row norm times
+    (1 + 0.1 normal), small biases."""
+    g = torch.Generator().manual_seed(seed + 1000 * K + dim_in)
+    p = {}
+    for name, shapes in (("discriminators", [(64, dim_in, K)] + [(64, 64, K)] * 4), ("out", [(1, 64, K)] * 5)):
+        for i, s in enumerate(shapes):
+            v = torch.randn(s, generator=g) / (s[1] * s[2]) ** 0.5
+            p[f"{name}.{i}.parametrizations.weight.original1"] = v
+            p[f"{name}.{i}.parametrizations.weight.original0"] = (
+                v.flatten(1).norm(dim=1) * (1 + 0.1 * torch.randn(s[0], generator=g))).view(-1, 1, 1)
+            p[f"{name}.{i}.bias"] = 0.05 * torch.randn(s[0], generator=g)
+    return p
+
+
 def make_ragged(L, lengths, T=None, seed=21):
     """A ragged text batch: valid tokens randint(1, 170); texts_a has id 0 on the padded positions, texts_b ids drawn from
     RAGGED_PAD_IDS.  With T: integer durations, 1 on every valid token plus a multinomial split of the remaining T - len

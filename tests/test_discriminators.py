@@ -10,13 +10,9 @@ import pytest
 import torch
 from safetensors.torch import load_file
 
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _fixture():
-    fx = load_file(os.path.join(G, "disc_small.safetensors"))
-    params = {k[2:]: v for k, v in fx.items() if k.startswith("w.")}
-    return fx, params
+from tests.disc_checks import (G, cf_check as _cf_check, cf_fixture as _cf_fixture, check_against_oracle as _check_against_oracle,
+                               hip_cf_model as _cf_model, hip_spec_model as _hip_model, pd_check as _pd_check,
+                               pd_fixture as _pd_fixture, spec_fixture as _fixture)
 
 
 def test_spec_discriminator_manifest_equals_reference_state_dict():
@@ -52,14 +48,6 @@ def test_discriminator_oracle_matches_reference_classes():
             assert (pp[k].grad - ref).abs().max().item() <= 2e-5 * max(ref.abs().max().item(), 1e-3), k
 
 
-def _hip_model(params, dev):
-    from stylish_tts_amd.discriminators import SpecDiscriminator
-    m = SpecDiscriminator().to(dev)
-    missing = m.load_state_dict(params, strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return m
-
-
 @pytest.mark.gpu
 def test_spec_discriminator_hip_vs_reference_fixture():
     """HIP SpecDiscriminator.forward, GeneratorLossHelper and DiscriminatorLossHelper against the values the reference's
@@ -90,48 +78,6 @@ def test_spec_discriminator_hip_vs_reference_fixture():
         # gradients: the oracle (pinned to the reference's gradients on this very fixture by the CPU test above) fed with
         # the HIP score maps -- see _check_against_oracle for why not the fixture's gradient tensors directly
         _check_against_oracle(m, params, fx[f"c{case}.target"], fx[f"c{case}.pred"], dev, 2e-5, 2e-4)
-
-
-def _check_against_oracle(m, params, t, q0, dev, tol_x, tol_w, tol_loss=2e-5):
-    """The relativistic term puts a large share of its gradient on ONE score element (the median of real - gen, as
-    torch.median's backward does), so score maps that differ in the last bit can move that spike to another element.
-    The comparison is therefore made in two exact halves: (1) the loss kernels against the oracle's loss functions ON
-    THE HIP SCORE MAPS (same inputs bit for bit -> same median element): values here, gradients through (2);
-    (2) the network backward against the oracle network's backward fed with those score gradients."""
-    from oracle import discriminator as od
-    B, _, H, W = t.shape
-    td, qd = t.to(dev), q0.to(dev)
-    rs_h = [x.cpu().clone().requires_grad_(True) for x in m(td)[0]]
-    gs_h = [x.cpu().clone().requires_grad_(True) for x in m(qd)[0]]
-    gl = od.generator_loss_helper(rs_h, gs_h)
-    g_gen = torch.autograd.grad(gl, gs_h)
-    dl = od.discriminator_loss_helper(rs_h, gs_h)
-    g_dr = torch.autograd.grad(dl, rs_h, retain_graph=True)
-    g_dg = torch.autograd.grad(dl, gs_h)
-    # oracle network, score gradients injected
-    q = q0.clone().requires_grad_(True)
-    pp = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    so_t, so_q = od.spec_discriminator(pp, t), od.spec_discriminator(pp, q)
-    for a_, b_ in zip(so_t + so_q, rs_h + gs_h):  # the HIP score maps themselves
-        assert (a_ - b_).abs().max().item() <= tol_x * max(a_.abs().max().item(), 0.1)
-    dq, = torch.autograd.grad(so_q, q, grad_outputs=list(g_gen), retain_graph=True)
-    keys = sorted(pp)
-    dw = torch.autograd.grad(so_t + so_q, [pp[k] for k in keys], grad_outputs=list(g_dr) + list(g_dg))
-    for p_ in m.parameters():
-        p_.grad = None
-    d_pred = torch.zeros(B, H, W, device=dev)
-    gen, disc = m.losses(td, qd, gen_scale=2.0, d_pred=d_pred, disc_scale=3.0)
-    assert abs(gen[0].item() - gl.item()) <= tol_loss * gl.item(), (gen[0].item(), gl.item())
-    assert abs(disc[0].item() - dl.item()) <= tol_loss * dl.item(), (disc[0].item(), dl.item())
-    err = (d_pred.cpu() - 2.0 * dq[:, 0]).abs().max().item()
-    assert err <= tol_w * 2.0 * dq.abs().max().item(), ("d_pred", err, dq.abs().max().item())
-    got = dict(m.named_parameters())
-    for k, ref in zip(keys, dw):
-        ref = 3.0 * ref
-        err = (got[k].grad.cpu() - ref).abs().max().item()
-        lim = tol_w * (5.0 if k.endswith("original0") else 1.0) * max(ref.abs().max().item(), 1e-3)
-        assert err <= lim, (k, err, ref.abs().max().item())
-    return gen, disc, d_pred
 
 
 @pytest.mark.gpu
@@ -170,11 +116,14 @@ def test_spec_discriminator_bf16_mode():
 
 
 @pytest.mark.gpu
-def test_acoustic_loss_with_adversarial_term_composes_the_pinned_pieces():
+@pytest.mark.parametrize("B,N", [(2, 9600), (3, 4096)])
+def test_acoustic_loss_with_adversarial_term_composes_the_pinned_pieces(B, N):
     """sty_acoustic_gan_loss_fwd_bwd = the acoustic losses + the "mrd" generator term + the discriminator side, all from
     one pass.  Checked against the separately pinned pieces: mel / phase losses and their seed (sty_acoustic_loss_fwd_bwd),
     the three discriminators on MultiSpectrogram's |X| (sty_specdisc_losses), and the oracle's STFT (torch.stft) for the
-    vector-Jacobian product that carries d loss / d |X| back to the waveform."""
+    vector-Jacobian product that carries d loss / d |X| back to the waveform.  (3, 4096): the three spectrogram widths are
+    33 / 17 / 9 and B = 3, so the batch-folded [H][B][W] input strides of sd_l0_kernel, sd_x27_kernel and sd_fold27_kernel run at
+    odd widths and a batch other than 2."""
     from oracle import frontend as of
     from stylish_tts_amd.frontend import MultiSpectrogram
     from stylish_tts_amd.losses import acoustic_gan_loss, acoustic_loss
@@ -186,7 +135,6 @@ def test_acoustic_loss_with_adversarial_term_composes_the_pinned_pieces():
         p = {k: (v * (1.0 + 0.1 * torch.randn(v.shape, generator=g)) if k.endswith("original1") else v.clone())
              for k, v in params.items()}
         mrd.append(_hip_model(p, dev))
-    B, N = 2, 9600
     gt = 0.3 * torch.randn(B, N, generator=g)
     pr = gt + 0.1 * torch.randn(B, N, generator=g)
     gtd, prd = gt.to(dev), pr.to(dev)
@@ -223,12 +171,6 @@ def test_acoustic_loss_with_adversarial_term_composes_the_pinned_pieces():
     assert err <= 2e-4 * vjp.abs().max().item() + 1e-6 * d0.abs().max().item(), (err, vjp.abs().max().item())
 
 
-def _cf_fixture():
-    fx = load_file(os.path.join(G, "cfdisc_small.safetensors"))
-    params = {k[2:]: v for k, v in fx.items() if k.startswith("w.")}
-    return fx, params
-
-
 def test_context_free_discriminator_oracle_and_manifest_match_reference():
     """oracle.context_free_discriminator vs the reference's ContextFreeDiscriminator in training mode: score maps, both
     helpers' losses and gradients; the shell's key table equals the reference state_dict."""
@@ -254,48 +196,6 @@ def test_context_free_discriminator_oracle_and_manifest_match_reference():
             # (a bias in front of a BatchNorm has a structurally zero gradient: |ref| ~ 1e-8 of rounding noise on both sides,
             # whose size depends on the host's conv kernels -- the floor keeps such a tensor from being compared to itself)
             assert (pp[k].grad - ref).abs().max().item() <= 1e-4 * max(ref.abs().max().item(), 1e-3), k
-
-
-def _cf_model(params, dev):
-    from stylish_tts_amd.discriminators import ContextFreeDiscriminator
-    m = ContextFreeDiscriminator()
-    m.load_state_dict(params, strict=True)
-    return m.to(dev)
-
-
-def _cf_check(m, params, t, q0, dev, tol_x, tol_w):
-    """same two-part scheme as _check_against_oracle (the relativistic term's median spike)"""
-    from oracle import discriminator as od
-    B, N = t.shape
-    td, qd = t.to(dev), q0.to(dev)
-    rs_h = m(td)[0][0].cpu().clone().requires_grad_(True)
-    gs_h = m(qd)[0][0].cpu().clone().requires_grad_(True)
-    gl = od.generator_loss_helper([rs_h], [gs_h])
-    g_gen, = torch.autograd.grad(gl, gs_h)
-    dl = od.discriminator_loss_helper([rs_h], [gs_h])
-    g_dr, = torch.autograd.grad(dl, rs_h, retain_graph=True)
-    g_dg, = torch.autograd.grad(dl, gs_h)
-    q = q0.clone().requires_grad_(True)
-    keys = sorted(k for k, v in params.items() if v.is_floating_point() and "running" not in k)
-    pp = {k: (v.clone().requires_grad_(True) if k in keys else v) for k, v in params.items()}
-    so_t, so_q = od.context_free_discriminator(pp, t), od.context_free_discriminator(pp, q)
-    for a_, b_ in ((so_t, rs_h), (so_q, gs_h)):
-        assert (a_ - b_).abs().max().item() <= tol_x * max(a_.abs().max().item(), 0.1), (a_ - b_).abs().max().item()
-    dq, = torch.autograd.grad(so_q, q, grad_outputs=g_gen, retain_graph=True)
-    dw = torch.autograd.grad([so_t, so_q], [pp[k] for k in keys], grad_outputs=[g_dr, g_dg])
-    for p_ in m.parameters():
-        p_.grad = None
-    d_pred = torch.zeros(B, N, device=dev)
-    gen, disc = m.losses(td, qd, gen_scale=2.0, d_pred=d_pred, disc_scale=3.0)
-    assert abs(gen[0].item() - gl.item()) <= 5e-5 * gl.item(), (gen[0].item(), gl.item())
-    assert abs(disc[0].item() - dl.item()) <= 5e-5 * dl.item(), (disc[0].item(), dl.item())
-    err = (d_pred.cpu() - 2.0 * dq).abs().max().item()
-    assert err <= tol_w * 2.0 * dq.abs().max().item(), ("d_pred", err, dq.abs().max().item())
-    got = dict(m.named_parameters())
-    for k, ref in zip(keys, dw):
-        ref = 3.0 * ref
-        err = (got[k].grad.cpu() - ref).abs().max().item()
-        assert err <= tol_w * max(ref.abs().max().item(), 1e-3), (k, err, ref.abs().max().item())
 
 
 @pytest.mark.gpu
@@ -335,12 +235,6 @@ def test_context_free_discriminator_hip_vs_oracle_other_shapes(B, N):
     _cf_check(_cf_model(params, dev), params, t, q, dev, 2e-5, 5e-4)
 
 
-def _pd_fixture(name):
-    fx = load_file(os.path.join(G, "pdisc_small.safetensors"))
-    params = {k[len(name) + 3:]: v for k, v in fx.items() if k.startswith(name + ".w.")}
-    return {k[len(name) + 1:]: v for k, v in fx.items() if k.startswith(name + ".") and ".w." not in k[:len(name) + 3]}, params
-
-
 @pytest.mark.parametrize("name", ["pitch", "dur"])
 def test_pitch_discriminator_oracle_matches_reference(name):
     from oracle import discriminator as od
@@ -367,7 +261,6 @@ def test_pitch_discriminator_oracle_matches_reference(name):
 def test_pitch_discriminator_hip(name, dim_in, kernel):
     """HIP PitchDiscriminator (pitch_disc / dur_disc configurations): score maps and both loss values against the
     reference fixture, gradients through the pinned oracle (two-part scheme), then a longer odd-length sequence."""
-    from oracle import discriminator as od
     from stylish_tts_amd.discriminators import PitchDiscriminator
     dev = torch.device("cuda:0")
     fx, params = _pd_fixture(name)
@@ -379,39 +272,16 @@ def test_pitch_discriminator_hip(name, dim_in, kernel):
     tl = torch.randn(4, dim_in, 517, generator=g) * 2
     cases.append((tl, tl + 0.5 * torch.randn(tl.shape, generator=g), False))
     for t, q0, pinned in cases:
-        td, qd = t.to(dev), q0.to(dev)
-        rs_h = [x.cpu().clone().requires_grad_(True) for x in m(td)[0]]
-        gs_h = [x.cpu().clone().requires_grad_(True) for x in m(qd)[0]]
         if pinned:
+            rs_h = [x.cpu() for x in m(t.to(dev))[0]]
+            gs_h = [x.cpu() for x in m(q0.to(dev))[0]]
             for i in range(5):
                 assert (rs_h[i] - fx[f"real_score{i}"]).abs().max().item() <= 2e-5 * max(fx[f"real_score{i}"].abs().max().item(), 0.1)
                 assert (gs_h[i] - fx[f"gen_score{i}"]).abs().max().item() <= 2e-5 * max(fx[f"gen_score{i}"].abs().max().item(), 0.1)
-        gl = od.generator_loss_helper(rs_h, gs_h)
-        g_gen = torch.autograd.grad(gl, gs_h)
-        dl = od.discriminator_loss_helper(rs_h, gs_h)
-        g_dr = torch.autograd.grad(dl, rs_h, retain_graph=True)
-        g_dg = torch.autograd.grad(dl, gs_h)
-        q = q0.clone().requires_grad_(True)
-        keys = sorted(params)
-        pp = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-        so_t, so_q = od.pitch_discriminator(pp, t), od.pitch_discriminator(pp, q)
-        dq, = torch.autograd.grad(so_q, q, grad_outputs=list(g_gen), retain_graph=True)
-        dw = torch.autograd.grad(so_t + so_q, [pp[k] for k in keys], grad_outputs=list(g_dr) + list(g_dg))
-        for p_ in m.parameters():
-            p_.grad = None
-        d_pred = torch.zeros_like(qd)
-        gen, disc = m.losses(td, qd, gen_scale=2.0, d_pred=d_pred, disc_scale=3.0)
-        assert abs(gen[0].item() - gl.item()) <= 2e-5 * gl.item() and abs(disc[0].item() - dl.item()) <= 2e-5 * dl.item()
+        gen, disc, _ = _pd_check(m, params, t, q0, dev, check_scores=False)  # (tests/disc_checks.py: the former loop body)
         if pinned:
             assert abs(gen[0].item() - fx["gen_loss"].item()) <= 5e-5 * fx["gen_loss"].item()
             assert abs(disc[0].item() - fx["disc_loss"].item()) <= 5e-5 * fx["disc_loss"].item()
-        err = (d_pred.cpu() - 2.0 * dq).abs().max().item()
-        assert err <= 2e-4 * 2.0 * dq.abs().max().item(), ("d_pred", err)
-        got = dict(m.named_parameters())
-        for k, ref in zip(keys, dw):
-            ref = 3.0 * ref
-            err = (got[k].grad.cpu() - ref).abs().max().item()
-            assert err <= (1e-3 if k.endswith("original0") else 2e-4) * max(ref.abs().max().item(), 1e-3), (k, err)
 
 
 def test_discriminator_shells_load_reference_state_dicts_and_refuse_the_cpu():
