@@ -661,6 +661,16 @@ int sty_prof_only(const char *family);
  * durations measured that way are free of the stretch from sharing the chip with another stream.  The workspace must
  * have been sized in the same mode it is used in (call before sty_*_train_workspace_bytes).                        */
 int sty_set_single_stream(int on);
+/* Deterministic mode (process-wide, default 0): 1 = every sum whose result depends on the order in which atomics arrive
+ * (parameter gradients summed over the batch, d style, the embedding scatter, the style head, the double-precision loss
+ * and BatchNorm sums of the losses and discriminators) takes a fixed-order path: partial slots and an in-order sum.  Two
+ * runs of a training step on the same inputs then give the same bits.  The mode is latched by each sty_*_fwd_train call
+ * (by the call itself where forward and backward are one call): a backward runs in the mode of its forward, whatever the
+ * switch says by then.  sty_*_workspace_bytes return the figure of the current mode (mode 1 adds the slots); a training
+ * forward given less than its mode needs returns STY_ENOMEM before anything is launched.  Mode 0 launches exactly what the
+ * library launched before the switch existed.  Nothing is claimed about the order of a gradient exchange between ranks. */
+int sty_set_deterministic(int on);
+int sty_get_deterministic(void);
 int sty_prof_report(sty_prof_row *rows, int cap);
 
 #ifdef __cplusplus

@@ -72,8 +72,12 @@ class AcousticTrainer:
 
     def __init__(self, speech_predictor, style_encoder, lr=1e-4, betas=(0.85, 0.99), eps=1e-9, weight_decay=1e-4,
                  w_mel=5.0, w_phase=8.0, mean=-4.0, std=4.0, bucket_bytes=25 << 20, train_mode=True, seed=0,
-                 text_dropout=0.2, compute="fp32", mrd=None, w_gen=1.0, disc=None, shared_seed=1):
+                 text_dropout=0.2, compute="fp32", mrd=None, w_gen=1.0, disc=None, shared_seed=1, deterministic=False):
         import random
+        # deterministic=True switches the process-wide deterministic mode on (lib.set_deterministic) before anything is sized;
+        # False leaves the switch as it is (STY_DETERMINISTIC=1 or an earlier call may have set it)
+        if deterministic:
+            L.set_deterministic(True)
         from .optim import FlatAdamW
         self.train_mode = train_mode
         self.text_dropout = text_dropout  # model.yml text_encoder.dropout
@@ -165,6 +169,13 @@ class AcousticTrainer:
         """second torch stream for the style encoder (STY_NO_SE_STREAM=1: everything on the current stream)"""
         import os
         if os.environ.get("STY_NO_SE_STREAM") or getattr(self, "single_stream", False):
+            return None
+        # Deterministic mode: no second torch stream (the style encoder runs in line and the predictor is given no style
+        # stream, so its prior branch is issued in place too).  Measured reason: with it the bf16 step at the benchmark's size
+        # (B 32, T 520) does not repeat -- from the second step on the FORWARD's losses differ between two runs by 1e-4, the
+        # parameters in front of it being equal bit for bit -- and without it three of three steps repeat; fp32 repeats either
+        # way.  No atomic is involved (DESIGN.md section 4.23 has the record); the weight-gradient stream stays on.
+        if L.get_deterministic():
             return None
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(device=device)

@@ -168,8 +168,12 @@ class AlignmentTrainer:
 
     def __init__(self, aligner, lr=1e-4, betas=(0.85, 0.99), eps=1e-9, weight_decay=1e-4, w_align=1.0, mean=-4.0, std=4.0,
                  dropout=0.1, seed=0, hop_length=300, n_fft=ALIGNER_MEL["n_fft"], win_length=ALIGNER_MEL["win_length"],
-                 bucket_bytes=25 << 20, log=print):
+                 bucket_bytes=25 << 20, log=print, deterministic=False):
         import random
+        # deterministic=True switches the process-wide deterministic mode on (lib.set_deterministic) before anything is sized;
+        # False leaves the switch as it is (STY_DETERMINISTIC=1 or an earlier call may have set it)
+        if deterministic:
+            L.set_deterministic(True)
         from .frontend import MelSpec
         from .optim import FlatAdamW
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <cxxabi.h>
 
+#include <functional>
 #include <map>
 #include <string>
 
@@ -37,6 +38,8 @@ struct ProfEntry {
 thread_local const void* g_last_kernel = nullptr;
 static bool g_single_stream = false;  // sty_set_single_stream
 bool single_stream_mode() { return g_single_stream; }
+static bool g_deterministic = false;  // sty_set_deterministic
+bool deterministic_mode() { return g_deterministic; }
 static bool g_prof_on = false;
 static std::string g_prof_only;  // non-empty: only launches of this family are timed (sty_prof_only)
 static std::vector<ProfEntry> g_prof;
@@ -1658,6 +1661,11 @@ int sty_set_single_stream(int on) {
   sty::g_single_stream = on != 0;
   return STY_OK;
 }
+int sty_set_deterministic(int on) {
+  sty::g_deterministic = on != 0;
+  return STY_OK;
+}
+int sty_get_deterministic(void) { return sty::g_deterministic ? 1 : 0; }
 int sty_prof_only(const char* family) {
   g_prof_only = family ? family : "";
   return STY_OK;
@@ -1878,6 +1886,21 @@ static int finish_bwd(sty_model* m, hipStream_t st, int seg = -1) {
   return STY_OK;
 }
 
+// Deterministic mode: the partial slots of its fixed-order sums are part of a training graph's workspace figure, and the
+// backward takes them long after the forward has launched.  A *_fwd_train entry therefore sizes its graph for the mode first
+// (the sizing pass: host code only) and refuses a smaller workspace here, before anything is launched.
+static int det_ws_check(const char* what, size_t ws_bytes, const std::function<int(size_t*)>& size_of) {
+  if (!deterministic_mode()) return STY_OK;
+  size_t need = 0;
+  const int rc = size_of(&need);
+  if (rc) return rc;
+  if (ws_bytes < need) {
+    set_error("%s: workspace too small for the deterministic mode: need %zu bytes, have %zu", what, need, ws_bytes);
+    return STY_ENOMEM;
+  }
+  return STY_OK;
+}
+
 int sty_speech_train_workspace_bytes(sty_model* m, int B, int L, int T, size_t* bytes) {
   int rc = train_ready(m, STY_EINVAL, "speech_predictor");
   if (rc) return rc;
@@ -1914,6 +1937,7 @@ int sty_speech_fwd_train(sty_model* m, const sty_speech_io* io, void* workspace,
     set_error("sty_speech_fwd_train: bad argument");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_speech_fwd_train", ws_bytes, [&](size_t* n) { return sty_speech_train_workspace_bytes(m, io->B, io->L, io->T, n); }))) return rc;
   if (m->train_prepared) {  // done by sty_speech_prepare_train since the last optimizer step
     if ((rc = prepared_consume(m, stream))) return rc;
   } else if ((rc = sty_model_prepare(m, stream))) {
@@ -2008,6 +2032,7 @@ int sty_vocoder_fwd_train(sty_model* m, const sty_vocoder_io* io, void* workspac
     set_error("sty_vocoder_fwd_train: bad argument");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_vocoder_fwd_train", ws_bytes, [&](size_t* n) { return sty_vocoder_train_workspace_bytes(m, io->B, io->T, n); }))) return rc;
   if ((rc = sty_model_prepare(m, stream))) return rc;  // parameters change every step
   m->prepared = false;
   return trainer_vocoder_forward(m->trainer, io, workspace, ws_bytes, S(stream), nullptr);
@@ -2299,6 +2324,7 @@ int sty_aligner_fwd_train(sty_model* m, int B, int T, const float* mel, const in
     set_error("sty_aligner_fwd_train: compute_bf16 is refused for the text aligner");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_aligner_fwd_train", ws_bytes, [&](size_t* n) { return sty_aligner_train_workspace_bytes(m, B, T, n); }))) return rc;
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
   return trainer_aligner_forward(m->trainer, B, T, mel, mel_lengths, drop_p, drop_seed, log_probs, workspace, ws_bytes,
@@ -2341,6 +2367,7 @@ int sty_duration_fwd_train(sty_model* m, int B, int L, const int64_t* texts, con
     set_error("sty_duration_fwd_train: bad argument");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_duration_fwd_train", ws_bytes, [&](size_t* n) { return sty_duration_train_workspace_bytes(m, B, L, n); }))) return rc;
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
   return trainer_duration_forward(m->trainer, B, L, texts, text_lengths, style, out, workspace, ws_bytes, S(stream), nullptr);
@@ -2376,6 +2403,7 @@ int sty_pitch_energy_fwd_train(sty_model* m, int B, int L, int T, const int64_t*
     set_error("sty_pitch_energy_fwd_train: bad argument");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_pitch_energy_fwd_train", ws_bytes, [&](size_t* n) { return sty_pitch_energy_train_workspace_bytes(m, B, L, T, n); }))) return rc;
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
   return trainer_pitch_energy_forward(m->trainer, B, L, T, texts, text_lengths, alignment, style, pitch, energy, workspace,
@@ -2548,6 +2576,7 @@ int sty_block_fwd_bwd(sty_model* m, const char* kind, const char* prefix, int B,
   int k = 0;
   const void* blk = nullptr;
   if ((rc = find_block(m, kind, prefix, C, &k, &blk))) return rc;
+  if ((rc = det_ws_check("sty_block_fwd_bwd", ws_bytes, [&](size_t* n) { return sty_block_train_workspace_bytes(m, kind, prefix, B, C, T, n); }))) return rc;
   if ((rc = sty_model_prepare(m, stream))) return rc;
   m->prepared = false;
   rc = trainer_block_fwd_bwd(m->trainer, k, blk, B, C, T, x, style, gy, y, gx, d_style, workspace, ws_bytes, S(stream),
@@ -2769,6 +2798,7 @@ int sty_style_fwd_train(sty_model* m, int B, int T, const float* mel, float* sty
     set_error("sty_style_fwd_train: bad argument (T >= 40 frames)");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_style_fwd_train", ws_bytes, [&](size_t* n) { return sty_style_train_workspace_bytes(m, B, T, n); }))) return rc;
   if ((rc = style_train_prepare(m, stream))) return rc;
   return trainer_style_forward(m->trainer, B, T, mel, style, workspace, ws_bytes, S(stream), nullptr);
 }
@@ -2790,6 +2820,7 @@ int sty_pitch_style_fwd_train(sty_model* m, int B, int T, const float* mel, cons
     set_error("sty_pitch_style_fwd_train: bad argument (T >= 40 frames)");
     return STY_EINVAL;
   }
+  if ((rc = det_ws_check("sty_pitch_style_fwd_train", ws_bytes, [&](size_t* n) { return sty_pitch_style_train_workspace_bytes(m, B, T, n); }))) return rc;
   if ((rc = style_train_prepare(m, stream))) return rc;
   return trainer_style_forward(m->trainer, B, T, mel, style, workspace, ws_bytes, S(stream), nullptr, pitch, energy);
 }
@@ -3113,6 +3144,16 @@ int sty_grn_bwd(int B, int C4, int T, const float* h, const float* ds, const flo
   int rc = launch_row_stats(h, B * C4, T, part, st);
   if (rc) return rc;
   if ((rc = launch_grn_finalize(part, nseg, gamma, B, C4, scale, st, gx))) return rc;
+  if (deterministic_mode() && B > 1) {
+    // deterministic mode: one launch per utterance; the adds into dgamma then meet in stream order (this unit entry has no
+    // room for slots in the workspace its callers size)
+    for (int b = 0; b < B; ++b) {
+      const size_t o = (size_t)b * C4;
+      if ((rc = launch_grn_bwd(from_gx ? gx + o : nullptr, part + o * nseg * 2, nseg, gamma, ds + o, 1, C4, coef + o, dgamma, st)))
+        return rc;
+    }
+    return STY_OK;
+  }
   return launch_grn_bwd(from_gx ? gx : nullptr, part, nseg, gamma, ds, B, C4, coef, dgamma, st);
 }
 int sty_act_bwd(int kind, int B, int C, int T, const float* x, float* dy, const float* alpha, const float* h,
@@ -3126,6 +3167,16 @@ int sty_act_bwd(int kind, int B, int C, int T, const float* x, float* dy, const 
     const int rc = launch_row_scale_add(h, coef, 0.f, B * C, T, dy, st);
     if (rc) return rc;
     h = coef = nullptr;
+  }
+  if (deterministic_mode() && kind == ACT_SNAKE && dalpha && B > 1) {
+    // deterministic mode: one launch per utterance, so that the rows' adds into d alpha meet in stream order
+    for (int b = 0; b < B; ++b) {
+      const size_t o = (size_t)b * C * T;
+      const int rc = launch_act_bwd(kind, x + o, dy + o, alpha, 1, C, T, dx + o, accumulate, dalpha, st, h ? h + o : nullptr,
+                                    coef ? coef + (size_t)b * C : nullptr);
+      if (rc) return rc;
+    }
+    return STY_OK;
   }
   return launch_act_bwd(kind, x, dy, alpha, B, C, T, dx, accumulate, dalpha, st, h, coef);
 }

@@ -36,6 +36,10 @@ __device__ __forceinline__ void block_sum(double (&v)[N], double (*red)[4]) {
 // mode = ConvPro.  One workgroup per (b, c) row.  u is [B][Cu][T] with this tensor's channels starting at cu0
 // (the dgrad conv of a channel-concatenated input produces one tensor for all sources).
 // mode | 0x100 (bf16 compute mode): the Snake derivative takes the hardware sine / cosine (sty_sincos_hw)
+// DET (deterministic mode, here and in every kernel below that takes it): the batch-summed parameter gradient is not added with
+// an atomic; the row's sum is stored to slot [b][channel] of the caller's partial buffer (passed in the gradient's place) and
+// summed over b in index order by the caller (Tape::det_sum)
+template <bool DET>
 __global__ __launch_bounds__(256) void pro_bwd_kernel(int mode_, const float* __restrict__ u, int Cu, int cu0,
                                                       const float* __restrict__ x, int C, int T,
                                                       const float* __restrict__ pa, const float* __restrict__ ps,
@@ -129,19 +133,28 @@ __global__ __launch_bounds__(256) void pro_bwd_kernel(int mode_, const float* __
   if (threadIdx.x == 0) {
     if (dpa) dpa[(size_t)b * pC + pc0 + c] = (float)acc[0];
     if (dps) dps[(size_t)b * pC + pc0 + c] = (float)acc[1];
-    if (dalpha && mode == PRO_AFFINE_SNAKE) atomicAdd(&dalpha[pc0 + c], (float)acc[2]);
+    if (dalpha && mode == PRO_AFFINE_SNAKE) {
+      if (DET)
+        dalpha[(size_t)b * pC + pc0 + c] = (float)acc[2];
+      else
+        atomicAdd(&dalpha[pc0 + c], (float)acc[2]);
+    }
   }
 }
 
 int launch_pro_bwd(int mode, const float* u, int Cu, int cu0, const float* x, int B, int C, int T, const float* pa,
                    const float* ps, int pC, int pc0, const float* alpha, const float* mask, float* dx, int accumulate,
-                   float* dpa, float* dps, float* dalpha, hipStream_t st) {
+                   float* dpa, float* dps, float* dalpha, hipStream_t st, bool det) {
   char detail[40];
   snprintf(detail, sizeof(detail), "m%d C%d T%d acc%d", mode & 0xff, C, T, accumulate);
   const double n = (double)B * C * T;
   ProfScope prof("pro_bwd_kernel", 0.0, 4.0 * n * (accumulate ? 4.0 : 3.0), st, detail);
-  hipLaunchKernelGGL(pro_bwd_kernel, dim3(C, B), dim3(256), 0, st, mode, u, Cu, cu0, x, C, T, pa, ps, pC, pc0, alpha,
-                     mask, dx, accumulate, dpa, dps, dalpha);
+  if (det)
+    hipLaunchKernelGGL(pro_bwd_kernel<true>, dim3(C, B), dim3(256), 0, st, mode, u, Cu, cu0, x, C, T, pa, ps, pC, pc0, alpha,
+                       mask, dx, accumulate, dpa, dps, dalpha);
+  else
+    hipLaunchKernelGGL(pro_bwd_kernel<false>, dim3(C, B), dim3(256), 0, st, mode, u, Cu, cu0, x, C, T, pa, ps, pC, pc0, alpha,
+                       mask, dx, accumulate, dpa, dps, dalpha);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -172,6 +185,7 @@ __device__ __forceinline__ void st8_any(void* p, size_t i8, bool h, const float 
     reinterpret_cast<float4*>(p)[2 * i8 + 1] = make_float4(v[4], v[5], v[6], v[7]);
   }
 }
+template <bool DET>
 __global__ __launch_bounds__(256) void pro_bwd_adain_kernel(const void* __restrict__ u, int uh, const void* __restrict__ x, int xh,
                                                             int C, int T, const float* __restrict__ pa,
                                                             const float* __restrict__ ps, const float* __restrict__ alpha,
@@ -253,7 +267,12 @@ __global__ __launch_bounds__(256) void pro_bwd_adain_kernel(const void* __restri
     const float k1 = -dr * r * r * r / (float)T;
     cc[1] = k1;
     cc[0] = dmu / (float)T - k1 * mu;
-    if (dalpha) atomicAdd(&dalpha[c], (float)acc[2]);
+    if (dalpha) {
+      if (DET)
+        dalpha[row] = (float)acc[2];
+      else
+        atomicAdd(&dalpha[c], (float)acc[2]);
+    }
   }
   __syncthreads();
   const float c0 = cc[0], c1 = cc[1];
@@ -276,7 +295,7 @@ __global__ __launch_bounds__(256) void pro_bwd_adain_kernel(const void* __restri
 }
 int launch_pro_bwd_adain(const void* u, int uh, const void* x, int xh, int B, int C, int T, const float* pa, const float* ps,
                          const float* alpha, const float* mean, const float* rstd, const float* gb, void* dx, int dh,
-                         int accumulate, float* dgb, float* dalpha, int hw, hipStream_t st, const void* dsrc) {
+                         int accumulate, float* dgb, float* dalpha, int hw, hipStream_t st, const void* dsrc, bool det) {
   if (T % 8 != 0 || ((((size_t)u | (size_t)x | (size_t)dx | (size_t)dsrc) & 15) != 0)) {
     set_error("pro_bwd_adain: T %% 8 != 0 or unaligned rows");
     return STY_EINVAL;
@@ -286,8 +305,12 @@ int launch_pro_bwd_adain(const void* u, int uh, const void* x, int xh, int B, in
   const double n = (double)B * C * T;
   ProfScope prof("pro_bwd_adain_kernel", 0.0, n * (2.0 * ((uh ? 2 : 4) + (xh ? 2 : 4)) + (accumulate ? 2.0 : 1.0) * (dh ? 2 : 4)), st,
                  detail);
-  hipLaunchKernelGGL(pro_bwd_adain_kernel, dim3(C, B), dim3(256), 0, st, u, uh, x, xh, C, T, pa, ps, alpha, mean, rstd, gb, dx,
-                     dh, accumulate, dgb, dalpha, hw, dsrc);
+  if (det)
+    hipLaunchKernelGGL(pro_bwd_adain_kernel<true>, dim3(C, B), dim3(256), 0, st, u, uh, x, xh, C, T, pa, ps, alpha, mean, rstd, gb,
+                       dx, dh, accumulate, dgb, dalpha, hw, dsrc);
+  else
+    hipLaunchKernelGGL(pro_bwd_adain_kernel<false>, dim3(C, B), dim3(256), 0, st, u, uh, x, xh, C, T, pa, ps, alpha, mean, rstd, gb,
+                       dx, dh, accumulate, dgb, dalpha, hw, dsrc);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -528,6 +551,7 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_dx_kernel(const float* __rest
   }
 }
 // per (b,c) row: dA = sum_t g xhat, dB = sum_t g  ->  dgb (ada) or atomics into dw/db (affine)
+template <bool DET>
 __global__ __launch_bounds__(256) void chan_ln_bwd_param_kernel(const float* __restrict__ x,
                                                                 const float* __restrict__ dy,
                                                                 const float* __restrict__ y,
@@ -553,6 +577,9 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_param_kernel(const float* __r
     if (ada) {
       dgb[(size_t)b * 2 * C + c] += (float)acc[0];
       dgb[(size_t)b * 2 * C + C + c] += (float)acc[1];
+    } else if (DET) {
+      dw[(size_t)b * C + c] = (float)acc[0];
+      db[(size_t)b * C + c] = (float)acc[1];
     } else {
       atomicAdd(&dw[c], (float)acc[0]);
       atomicAdd(&db[c], (float)acc[1]);
@@ -565,15 +592,18 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_param_kernel(const float* __r
 // twice through its three workgroup-wide combines (237 us per launch at c3's size = 2 TB/s) and the parameter gradients took a
 // second kernel over x and dy.  Here the per-channel sums over time (sum g xh, sum g) are reduced across each 32-lane half with
 // DPP adds, across the workgroup with LDS atomics and leave as ONE partial row per workgroup; chan_ln32_param_sum_kernel adds
-// the rows in a fixed order (deterministic; the general path's one atomic per (b, c) row is not).
+// the rows in a fixed order (the general path's one atomic per (b, c) row is not).  The LDS atomics of the eight half-waves
+// arrive in any order and a float sum of eight terms depends on it: with DET every half-wave stores its sums to a slot of its
+// own and the slots are added in index order.
 // h16 bits: 1 = x, 2 = dy, 4 = dx are bf16 tensors (the two ends of a two-byte ConvNeXt32 chain; dx then without accumulate)
+template <bool DET>
 __global__ __launch_bounds__(256) void chan_ln32_bwd_kernel(const void* __restrict__ x, const void* __restrict__ dy, int T,
                                                             float eps, int ada, const float* __restrict__ w,
                                                             const float* __restrict__ gb, const float* __restrict__ out_mask,
                                                             void* __restrict__ dx, int accumulate, float* __restrict__ part,
                                                             int h16) {
   __shared__ float A_s[32];
-  __shared__ float red[64];
+  __shared__ float red[DET ? 8 * 64 : 64];
   const int tid = threadIdx.x, b = blockIdx.y;
   const int t = blockIdx.x * 256 + tid;
   const bool in = t < T;
@@ -628,12 +658,26 @@ __global__ __launch_bounds__(256) void chan_ln32_bwd_kernel(const void* __restri
     const float a0 = sty_half_sum_to_lane31(gv[c] * xv[c]);
     const float a1 = sty_half_sum_to_lane31(gv[c]);
     if ((tid & 31) == 31) {
-      atomicAdd(&red[c], a0);
-      atomicAdd(&red[32 + c], a1);
+      if (DET) {
+        red[(tid >> 5) * 64 + c] = a0;
+        red[(tid >> 5) * 64 + 32 + c] = a1;
+      } else {
+        atomicAdd(&red[c], a0);
+        atomicAdd(&red[32 + c], a1);
+      }
     }
   }
   __syncthreads();
-  if (tid < 64) part[((size_t)b * gridDim.x + blockIdx.x) * 64 + tid] = red[tid];
+  if (DET) {
+    if (tid < 64) {
+      float s = red[tid];
+#pragma unroll
+      for (int k = 1; k < 8; ++k) s += red[k * 64 + tid];
+      part[((size_t)b * gridDim.x + blockIdx.x) * 64 + tid] = s;
+    }
+  } else if (tid < 64) {
+    part[((size_t)b * gridDim.x + blockIdx.x) * 64 + tid] = red[tid];
+  }
 }
 // out: ada ? dgb[b][0..31 | 32..63] += sum over the row's workgroups : dw[c] / db[c] += sum over (b, workgroup); fixed order
 __global__ __launch_bounds__(64) void chan_ln32_param_sum_kernel(const float* __restrict__ part, int B, int nblk, int ada,
@@ -674,7 +718,7 @@ bool chan_ln32_eligible(int B, int C, int T, int relu) {
 }
 int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, int C, int T, float eps, int ada,
                        const float* w, const float* gb, int relu, const float* out_mask, float* dx, int accumulate,
-                       float* mu_tmp, float* r_tmp, float* dgb, float* dw, float* db, hipStream_t st, int h16) {
+                       float* mu_tmp, float* r_tmp, float* dgb, float* dw, float* db, hipStream_t st, int h16, bool det) {
   const bool no32 = getenv("STY_NO_LN32_BWD") != nullptr;  // (read per call: the A/B test toggles it)
   if (C == 32 && !relu && (size_t)B * T >= 65536 && !no32) {  // the 75T-rate LayerNorms: one thread per column (above)
     const int nblk = cdiv(T, 256);                           // partial rows live in mu_tmp (B T floats >= 64 B nblk)
@@ -682,8 +726,12 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
       set_error("chan_ln_bwd: a two-byte dx cannot be accumulated into");
       return STY_EINVAL;
     }
-    hipLaunchKernelGGL(chan_ln32_bwd_kernel, dim3(nblk, B), dim3(256), 0, st, x, dy, T, eps, ada, w, gb, out_mask, dx, accumulate,
-                       mu_tmp, h16);
+    if (det)
+      hipLaunchKernelGGL(chan_ln32_bwd_kernel<true>, dim3(nblk, B), dim3(256), 0, st, x, dy, T, eps, ada, w, gb, out_mask, dx,
+                         accumulate, mu_tmp, h16);
+    else
+      hipLaunchKernelGGL(chan_ln32_bwd_kernel<false>, dim3(nblk, B), dim3(256), 0, st, x, dy, T, eps, ada, w, gb, out_mask, dx,
+                         accumulate, mu_tmp, h16);
     hipLaunchKernelGGL(chan_ln32_param_sum_kernel, dim3(ada ? B * 64 : 64), dim3(64), 0, st, mu_tmp, B, nblk, ada, dgb, dw, db);
     STY_LAUNCH_CHECK();
     return STY_OK;
@@ -701,8 +749,12 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
   else
     hipLaunchKernelGGL(chan_ln_bwd_dx_kernel<16>, dim3(cdiv(T, 16), B), dim3(256), 0, st, x, dy, y, C, T, eps, ada, w, gb,
                        relu, out_mask, dx, accumulate, mu_tmp, r_tmp);
-  hipLaunchKernelGGL(chan_ln_bwd_param_kernel, dim3(C, B), dim3(256), 0, st, x, dy, y, mu_tmp, r_tmp, C, T, ada, relu,
-                     out_mask, dgb, dw, db);
+  if (det)
+    hipLaunchKernelGGL(chan_ln_bwd_param_kernel<true>, dim3(C, B), dim3(256), 0, st, x, dy, y, mu_tmp, r_tmp, C, T, ada, relu,
+                       out_mask, dgb, dw, db);
+  else
+    hipLaunchKernelGGL(chan_ln_bwd_param_kernel<false>, dim3(C, B), dim3(256), 0, st, x, dy, y, mu_tmp, r_tmp, C, T, ada, relu,
+                       out_mask, dgb, dw, db);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -713,6 +765,7 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
 // gx[b][c] = ||h||_2 as the forward's grn_finalize_kernel kept it.  (Rebuilding it here from the forward's double partials --
 // a wave walking 32 channels of 150 segments one after the other on the ConvNeXt32 blocks -- was 40-50 us of latency per
 // launch on the backward's chain; that form stays behind gx == nullptr for the unit entry's comparison only.)
+template <bool DET>
 __global__ __launch_bounds__(256) void grn_bwd_kernel(const float* __restrict__ gx, const double* __restrict__ part, int nseg,
                                                       const float* __restrict__ gamma,
                                                       const float* __restrict__ ds, int C4,
@@ -750,7 +803,10 @@ __global__ __launch_bounds__(256) void grn_bwd_kernel(const float* __restrict__ 
   for (int c = threadIdx.x; c < C4; c += 256) {
     const float dnx = ds[(size_t)b * C4 + c] * gamma[c];
     d2[0] += (double)dnx * gxs[c];
-    atomicAdd(&dgamma[c], ds[(size_t)b * C4 + c] * (gxs[c] / m));
+    if (DET)
+      dgamma[(size_t)b * C4 + c] = ds[(size_t)b * C4 + c] * (gxs[c] / m);
+    else
+      atomicAdd(&dgamma[c], ds[(size_t)b * C4 + c] * (gxs[c] / m));
   }
   __syncthreads();
   block_sum<1>(d2, red);
@@ -763,7 +819,7 @@ __global__ __launch_bounds__(256) void grn_bwd_kernel(const float* __restrict__ 
   }
 }
 int launch_grn_bwd(const float* gx, const double* part, int nseg, const float* gamma, const float* ds, int B, int C4,
-                   float* coef, float* dgamma, hipStream_t st) {
+                   float* coef, float* dgamma, hipStream_t st, bool det) {
   if (C4 > 1024) {
     set_error("grn_bwd: 4C > 1024");
     return STY_EINVAL;
@@ -773,7 +829,10 @@ int launch_grn_bwd(const float* gx, const double* part, int nseg, const float* g
     return STY_EINVAL;
   }
   ProfScope prof("grn_bwd_kernel", 0.0, 4.0 * B * C4 * 4, st, gx ? "gx" : "part");
-  hipLaunchKernelGGL(grn_bwd_kernel, dim3(B), dim3(256), 0, st, gx, part, nseg, gamma, ds, C4, coef, dgamma);
+  if (det)
+    hipLaunchKernelGGL(grn_bwd_kernel<true>, dim3(B), dim3(256), 0, st, gx, part, nseg, gamma, ds, C4, coef, dgamma);
+  else
+    hipLaunchKernelGGL(grn_bwd_kernel<false>, dim3(B), dim3(256), 0, st, gx, part, nseg, gamma, ds, C4, coef, dgamma);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -842,6 +901,7 @@ int launch_act_fwd(int kind, const float* x, const float* alpha, int B, int C, i
 // h, coef (optional; not for GLU): a row term the output gradient is still owed, d = dy + coef[b][c] * h (the GRN term of the
 // ConvNeXt block, h = the activation's own output as the forward stored it) -- formed in registers here as the fma that
 // row_scale_add4_kernel compiles to, instead of a pass of its own that reads h and dy and writes dy for this kernel to read
+template <bool DET>
 __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __restrict__ x,
                                                       const float* __restrict__ dy, const float* __restrict__ alpha,
                                                       int C, int T, float* __restrict__ dx, int accumulate,
@@ -934,17 +994,25 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int kind, const float* __r
   }
   if (kind == ACT_SNAKE && dalpha) {
     block_sum<1>(acc, red);
-    if (threadIdx.x == 0) atomicAdd(&dalpha[c], (float)acc[0]);
+    if (threadIdx.x == 0) {
+      if (DET)
+        dalpha[(size_t)b * C + c] = (float)acc[0];
+      else
+        atomicAdd(&dalpha[c], (float)acc[0]);
+    }
   }
 }
 int launch_act_bwd(int kind, const float* x, const float* dy, const float* alpha, int B, int C, int T, float* dx,
-                   int accumulate, float* dalpha, hipStream_t st, const float* h, const float* coef) {
+                   int accumulate, float* dalpha, hipStream_t st, const float* h, const float* coef, bool det) {
   if (h && (kind == ACT_GLU || !coef)) {
     set_error("act_bwd: a row term needs its coefficients and a one-to-one activation");
     return STY_EINVAL;
   }
   ProfScope prof("act_bwd_kernel", 0.0, 4.0 * B * C * T * (3.0 + (accumulate ? 1 : 0) + (h ? 1 : 0)), st, h ? "row term" : nullptr);
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(C, B), dim3(256), 0, st, kind, x, dy, alpha, C, T, dx, accumulate, dalpha, h, coef);
+  if (det)
+    hipLaunchKernelGGL(act_bwd_kernel<true>, dim3(C, B), dim3(256), 0, st, kind, x, dy, alpha, C, T, dx, accumulate, dalpha, h, coef);
+  else
+    hipLaunchKernelGGL(act_bwd_kernel<false>, dim3(C, B), dim3(256), 0, st, kind, x, dy, alpha, C, T, dx, accumulate, dalpha, h, coef);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -1518,6 +1586,9 @@ int launch_partial_sum(int dw_form, const float* part, int C, int K, int nblk, f
 // grid (layer, slice): every slice takes a strided share of the layer's three loops (one workgroup per layer took
 // 0.68 ms for the ~80 AdaIN / AdaLN projections of the predictor)
 constexpr int SFC_SLICES = 8;
+// DET: the share of (layer, slice) for d style goes to slot [layer * SFC_SLICES + slice] of a [slots][B][style_dim] partial
+// buffer (passed as dstyle; every slot is written for every b) and the caller sums the slots in index order
+template <bool DET>
 __global__ __launch_bounds__(256) void style_fc_bwd_kernel(const StyleFcBwdDesc* __restrict__ descs, int style_dim,
                                                            const float* __restrict__ style,
                                                            const float* __restrict__ dgb_base, int B,
@@ -1568,19 +1639,48 @@ __global__ __launch_bounds__(256) void style_fc_bwd_kernel(const StyleFcBwdDesc*
           acc3 = fmaf(g[7], w[7], acc3);
         }
         for (; j < d.n; j += SFC_SLICES) acc0 = fmaf(gr[j], wr[(size_t)j * style_dim], acc0);
-        atomicAdd(&dstyle[(size_t)b * style_dim + lane], (acc0 + acc1) + (acc2 + acc3));
+        if (DET)
+          dstyle[(((size_t)blockIdx.x * SFC_SLICES + blockIdx.y) * B + b) * style_dim + lane] = (acc0 + acc1) + (acc2 + acc3);
+        else
+          atomicAdd(&dstyle[(size_t)b * style_dim + lane], (acc0 + acc1) + (acc2 + acc3));
       }
     }
   }
 }
+int style_fc_bwd_slots(int nlayers) { return nlayers * SFC_SLICES; }
 int launch_style_fc_bwd(const void* descs_dev, int nlayers, int B, int style_dim, const float* style,
-                        const float* dgb_base, float* dstyle, hipStream_t st) {
+                        const float* dgb_base, float* dstyle, hipStream_t st, bool det) {
   if (style_dim > 64) {
     set_error("style_fc_bwd: style_dim %d > 64", style_dim);
     return STY_EINVAL;
   }
-  hipLaunchKernelGGL(style_fc_bwd_kernel, dim3(nlayers, SFC_SLICES, 4), dim3(256), 0, st, (const StyleFcBwdDesc*)descs_dev, style_dim,
-                     style, dgb_base, B, dstyle);
+  if (det)
+    hipLaunchKernelGGL(style_fc_bwd_kernel<true>, dim3(nlayers, SFC_SLICES, 4), dim3(256), 0, st, (const StyleFcBwdDesc*)descs_dev,
+                       style_dim, style, dgb_base, B, dstyle);
+  else
+    hipLaunchKernelGGL(style_fc_bwd_kernel<false>, dim3(nlayers, SFC_SLICES, 4), dim3(256), 0, st, (const StyleFcBwdDesc*)descs_dev,
+                       style_dim, style, dgb_base, B, dstyle);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---- deterministic mode: the fixed-order sum of double partials (loss sums, BatchNorm sums, score-conv gradients) ----
+// One wave per output element: lane l adds slots l, l + 64, ... in that order, the 64 lane sums meet in the butterfly of
+// wave_sum -- the same additions in the same order on every run, whatever the slots' writers did.
+__global__ __launch_bounds__(64) void det_sum64_kernel(const double* __restrict__ part, int nslots, size_t stride,
+                                                       double* __restrict__ out) {
+  const size_t i = blockIdx.x;
+  double s = 0.0;
+  for (int k = threadIdx.x; k < nslots; k += 64) s += part[(size_t)k * stride + i];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) out[i] += s;
+}
+int launch_det_sum64(const double* part, int nslots, size_t n, size_t stride, double* out, hipStream_t st) {
+  if (nslots <= 0 || n == 0 || n > stride) {
+    set_error("det_sum64: bad slot layout");
+    return STY_EINVAL;
+  }
+  hipLaunchKernelGGL(det_sum64_kernel, dim3((unsigned)n), dim3(64), 0, st, part, nslots, stride, out);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

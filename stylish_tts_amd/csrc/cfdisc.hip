@@ -56,6 +56,9 @@ __global__ void cf_mask_kernel(int T, int P, int L, float* __restrict__ m) {
   if (i < T) m[(size_t)b * T + i] = (i % P) < L ? 1.f : 0.f;
 }
 // per-channel sums of z and z^2 (doubles): acc[c], acc[C + c]
+// DET (deterministic mode, also in cf_bn_bwd_sums4_kernel): acc is a partial buffer of gridDim.x slots of 2C doubles, one per
+// blockIdx.x; launch_det_sum64 adds the slots in index order
+template <bool DET>
 __global__ __launch_bounds__(256) void cf_bn_sums_kernel(const float* __restrict__ z, int B, int C, int T,
                                                          double* __restrict__ acc) {
   __shared__ float red[256];
@@ -72,8 +75,13 @@ __global__ __launch_bounds__(256) void cf_bn_sums_kernel(const float* __restrict
   s1 = sd_block_sum(s1, red);
   s2 = sd_block_sum(s2, red);
   if (threadIdx.x == 0) {
-    atomicAdd(&acc[c], (double)s1);
-    atomicAdd(&acc[C + c], (double)s2);
+    if (DET) {
+      acc[(size_t)blockIdx.x * 2 * C + c] = (double)s1;
+      acc[(size_t)blockIdx.x * 2 * C + C + c] = (double)s2;
+    } else {
+      atomicAdd(&acc[c], (double)s1);
+      atomicAdd(&acc[C + c], (double)s2);
+    }
   }
 }
 // mean / rstd from the sums, running statistics (momentum; unbiased variance as torch), stats[c] = mean, stats[C+c] = rstd
@@ -136,6 +144,7 @@ __global__ void cf_bn_gelu4_kernel(const float* __restrict__ z, const float* __r
 }
 // backward, four positions per thread.  Pass 1: du = da * gelu'(u) on the valid positions; acc[c] += sum du,
 // acc[C + c] += sum du * xhat.  Pass 2: dz = gamma * rstd * (du - mean(du) - xhat * mean(du * xhat)), 0 in the gaps.
+template <bool DET>
 __global__ __launch_bounds__(256) void cf_bn_bwd_sums4_kernel(const float* __restrict__ z, const float* __restrict__ da,
                                                               const float* __restrict__ stats,
                                                               const float* __restrict__ gamma,
@@ -166,8 +175,13 @@ __global__ __launch_bounds__(256) void cf_bn_bwd_sums4_kernel(const float* __res
   s1 = sd_block_sum(s1, red);
   s2 = sd_block_sum(s2, red);
   if (threadIdx.x == 0) {
-    atomicAdd(&acc[c], (double)s1);
-    atomicAdd(&acc[C + c], (double)s2);
+    if (DET) {
+      acc[(size_t)blockIdx.x * 2 * C + c] = (double)s1;
+      acc[(size_t)blockIdx.x * 2 * C + C + c] = (double)s2;
+    } else {
+      atomicAdd(&acc[c], (double)s1);
+      atomicAdd(&acc[C + c], (double)s2);
+    }
   }
 }
 __global__ void cf_bn_bwd_dx4_kernel(const float* __restrict__ z, const float* __restrict__ da,
@@ -404,10 +418,16 @@ struct CfRun : DiscBase {
     double* acc = take<double>(2 * C);
     ac.stats[k] = take<float>(2 * C);
     ac.A[k] = take<float>((size_t)B * C * Tt);
+    const int gx = cdiv(Tt, 2048) < 64 ? cdiv(Tt, 2048) : 64;
+    double* part = det ? take<double>((size_t)gx * 2 * C) : nullptr;
     if (!live()) return;
     hipchk(hipMemsetAsync(acc, 0, 2 * C * sizeof(double), st), "cfdisc memset");
-    hipLaunchKernelGGL(cf_bn_sums_kernel, dim3(cdiv(Tt, 2048) < 64 ? cdiv(Tt, 2048) : 64, C), dim3(256), 0, st, ac.Z[k], B, C,
-                       Tt, acc);
+    if (det) {
+      hipLaunchKernelGGL(cf_bn_sums_kernel<true>, dim3(gx, C), dim3(256), 0, st, ac.Z[k], B, C, Tt, part);
+      chk(launch_det_sum64(part, gx, 2 * C, 2 * C, acc, st));
+    } else {
+      hipLaunchKernelGGL(cf_bn_sums_kernel<false>, dim3(gx, C), dim3(256), 0, st, ac.Z[k], B, C, Tt, acc);
+    }
     hipLaunchKernelGGL(cf_bn_finish_kernel, dim3(cdiv(C, 64)), dim3(64), 0, st, acc, C, (double)B * t * CF_L[l], 1e-5f,
                        update_running ? momentum : 0.f, prm->bn_rm[k], prm->bn_rv[k], ac.stats[k]);
     hipLaunchKernelGGL(cf_bn_gelu4_kernel, dim3(cdiv(Tt, 1024), C, B), dim3(256), 0, st, ac.Z[k], ac.stats[k], prm->bn_w[k],
@@ -475,10 +495,18 @@ struct CfRun : DiscBase {
     const int C = CF_BN_C[k];
     double* acc = take<double>(2 * C);
     float* dz = take<float>((size_t)B * C * Tt);
+    const int gx = cdiv(Tt, 4096) < 64 ? cdiv(Tt, 4096) : 64;
+    double* part = det ? take<double>((size_t)gx * 2 * C) : nullptr;
     if (!live()) return dz;
     hipchk(hipMemsetAsync(acc, 0, 2 * C * sizeof(double), st), "cfdisc memset");
-    hipLaunchKernelGGL(cf_bn_bwd_sums4_kernel, dim3(cdiv(Tt, 4096) < 64 ? cdiv(Tt, 4096) : 64, C), dim3(256), 0, st, ac.Z[k], da,
-                       ac.stats[k], prm->bn_w[k], prm->bn_b[k], mask[l], B, C, Tt, split, acc);
+    if (det) {
+      hipLaunchKernelGGL(cf_bn_bwd_sums4_kernel<true>, dim3(gx, C), dim3(256), 0, st, ac.Z[k], da, ac.stats[k], prm->bn_w[k],
+                         prm->bn_b[k], mask[l], B, C, Tt, split, part);
+      chk(launch_det_sum64(part, gx, 2 * C, 2 * C, acc, st));
+    } else {
+      hipLaunchKernelGGL(cf_bn_bwd_sums4_kernel<false>, dim3(gx, C), dim3(256), 0, st, ac.Z[k], da, ac.stats[k], prm->bn_w[k],
+                         prm->bn_b[k], mask[l], B, C, Tt, split, acc);
+    }
     hipLaunchKernelGGL(cf_bn_bwd_dx4_kernel, dim3(cdiv(Tt, 1024), C, B), dim3(256), 0, st, ac.Z[k], da, ac.stats[k], prm->bn_w[k],
                        prm->bn_b[k], mask[l], acc, (double)B * t * CF_L[l], C, Tt, split, dz);
     if (gr)

@@ -627,6 +627,9 @@ int launch_avgpool2_bwd(const float* gy, int BC, int H, int W, float scale, floa
 }
 // pool + LeakyReLU + Linear backward: gs [B][S] -> dW (+=), db (+=), dx[b][c][:] += (W^T gs)[c] lrelu'(mean)/count
 // (every position: the head conv's backward masks its output gradient to the valid region)
+// DET: the activated means a[b][c] go to the caller's [B][C] buffer (passed as dW) and pool_fc_outer_kernel forms
+// dW[j][c] += sum_b g[b][j] a[b][c], db[j] += sum_b g[b][j] with b in index order
+template <bool DET>
 __global__ __launch_bounds__(256) void pool_fc_bwd_kernel(const float* __restrict__ x, int B, int C, int n,
                                                           float inv_count, const float* __restrict__ W, int S,
                                                           const float* __restrict__ gs, float* __restrict__ dW,
@@ -649,14 +652,38 @@ __global__ __launch_bounds__(256) void pool_fc_bwd_kernel(const float* __restric
   float* d = dx + ((size_t)b * C + c) * n;
   for (int i = lane; i < n; i += 64) d[i] = accumulate ? d[i] + gp : gp;
   const float a = pooled > 0.f ? pooled : 0.2f * pooled;
+  if (DET) {
+    if (lane == 0) dW[(size_t)b * C + c] = a;
+    return;
+  }
   for (int j = lane; j < S; j += 64) {
     atomicAdd(&dW[(size_t)j * C + c], g[j] * a);
     if (c == 0) atomicAdd(&db[j], g[j]);
   }
 }
+__global__ __launch_bounds__(256) void pool_fc_outer_kernel(const float* __restrict__ a, const float* __restrict__ gs, int B, int C,
+                                                            int S, float* __restrict__ dW, float* __restrict__ db) {
+  const int c = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+  if (c >= C) return;
+  float w = 0.f, bsum = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float g = gs[(size_t)b * S + j];
+    w += g * a[(size_t)b * C + c];  // (the atomic form's term: a product, then the add)
+    bsum += g;
+  }
+  dW[(size_t)j * C + c] += w;
+  if (c == 0) db[j] += bsum;
+}
 int launch_pool_fc_bwd(const float* x, int B, int C, int n, int count, const float* W, int S, const float* gs,
-                       float* dW, float* db, float* dx, int accumulate, hipStream_t st) {
-  hipLaunchKernelGGL(pool_fc_bwd_kernel, dim3(cdiv(C, 4), B), dim3(256), 0, st, x, B, C, n, 1.0f / (float)count, W, S, gs,
+                       float* dW, float* db, float* dx, int accumulate, hipStream_t st, float* det_a) {
+  if (det_a) {
+    hipLaunchKernelGGL(pool_fc_bwd_kernel<true>, dim3(cdiv(C, 4), B), dim3(256), 0, st, x, B, C, n, 1.0f / (float)count, W, S, gs,
+                       det_a, db, dx, accumulate);
+    hipLaunchKernelGGL(pool_fc_outer_kernel, dim3(cdiv(C, 256), S), dim3(256), 0, st, det_a, gs, B, C, S, dW, db);
+    STY_LAUNCH_CHECK();
+    return STY_OK;
+  }
+  hipLaunchKernelGGL(pool_fc_bwd_kernel<false>, dim3(cdiv(C, 4), B), dim3(256), 0, st, x, B, C, n, 1.0f / (float)count, W, S, gs,
                      dW, db, dx, accumulate);
   STY_LAUNCH_CHECK();
   return STY_OK;

@@ -310,6 +310,10 @@ __global__ __launch_bounds__(256) void sd_gz4_kernel(const float* __restrict__ g
 }
 
 // score conv weight gradient: acc[c*9 + t] += sum a[c][h + dh - 1][w + dw - 1] gs[h][w]; acc[288] += sum gs  (doubles)
+// DET (deterministic mode): acc is a partial buffer of [B * gridDim.x] slots of SD_SACC doubles, one per (b, blockIdx.x); the
+// 32 channel workgroups of a slot write its 289 entries, launch_det_sum64 adds the slots in index order
+constexpr int SD_SACC = 296;
+template <bool DET>
 __global__ __launch_bounds__(256) void sd_score_wgrad_kernel(const float* __restrict__ a, const float* __restrict__ gs,
                                                              int H, int W, int Wp, double* __restrict__ acc) {
   // One thread: four activations of channel c (one float4) against the 3 x 6 score gradients they met in the forward,
@@ -358,7 +362,10 @@ __global__ __launch_bounds__(256) void sd_score_wgrad_kernel(const float* __rest
   if (threadIdx.x < 9 || (threadIdx.x == 9 && c == 0)) {
     const int t = threadIdx.x;
     const float r = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-    atomicAdd(&acc[t == 9 ? 288 : c * 9 + t], (double)r);
+    if (DET)
+      acc[((size_t)b * gridDim.x + blockIdx.x) * SD_SACC + (t == 9 ? 288 : c * 9 + t)] = (double)r;
+    else
+      atomicAdd(&acc[t == 9 ? 288 : c * 9 + t], (double)r);
   }
 }
 
@@ -522,9 +529,15 @@ struct SdRun : DiscBase {
       }
       const ConvArgs f = conv_args(i, in, nullptr);
       if (gwp) {
-        if (live())
-          hipLaunchKernelGGL(sd_score_wgrad_kernel, dim3(min(64, cdiv(n[i] / 4, 256)), 32, B), dim3(256), 0, st, ac.a[i],
-                             gs[i], H, Wl[i], Wp[i], sacc[i]);
+        const int gx = min(64, cdiv(n[i] / 4, 256));
+        double* part = det ? take<double>((size_t)B * gx * SD_SACC) : nullptr;
+        if (live() && det) {
+          hipLaunchKernelGGL(sd_score_wgrad_kernel<true>, dim3(gx, 32, B), dim3(256), 0, st, ac.a[i], gs[i], H, Wl[i], Wp[i], part);
+          chk(launch_det_sum64(part, B * gx, 289, SD_SACC, sacc[i], st));
+        } else if (live()) {
+          hipLaunchKernelGGL(sd_score_wgrad_kernel<false>, dim3(gx, 32, B), dim3(256), 0, st, ac.a[i], gs[i], H, Wl[i], Wp[i],
+                             sacc[i]);
+        }
         float* partial = take<float>(wgrad_partial_floats(f.w, B, n[i]));
         bool bias_done = false;
         if (live()) chk(launch_conv1d_wgrad(f, gz, nullptr, 1.f, gwp[i], partial, gbp[i], &bias_done, st));
@@ -616,7 +629,9 @@ __global__ void pd_gz_kernel(const float* __restrict__ gs, const float* __restri
 // stride 256 and keeps the K tap sums of its positions; the 256 partial sums of a tap are added in a fixed order (a tree over
 // thread indices), so the result does not depend on scheduling.  (Until the end of round 6: one THREAD per entry looping over
 // all B x T positions -- 2.0 ms per launch at c3, ten launches per `train_textual` step: 20 of its 101 ms.)
-template <int KT>
+// DET (deterministic mode): acc is a partial buffer of PD_SLICES slots of (PD_C * KT + 1) doubles, one per blockIdx.y
+constexpr int PD_SLICES = 8;
+template <int KT, bool DET>
 __global__ __launch_bounds__(256) void pd_score_wgrad_kernel(const float* __restrict__ a, const float* __restrict__ gs, int B, int T,
                                                             double* __restrict__ acc) {
   __shared__ double red[256];
@@ -654,7 +669,12 @@ __global__ __launch_bounds__(256) void pd_score_wgrad_kernel(const float* __rest
       if (tid < o) red[tid] += red[tid + o];
       __syncthreads();
     }
-    if (tid == 0) atomicAdd(&acc[(c == PD_C ? PD_C * KT : c * KT) + k], red[0]);
+    if (tid == 0) {
+      if (DET)
+        acc[(size_t)blockIdx.y * (PD_C * KT + 1) + (c == PD_C ? PD_C * KT : c * KT) + k] = red[0];
+      else
+        atomicAdd(&acc[(c == PD_C ? PD_C * KT : c * KT) + k], red[0]);
+    }
     __syncthreads();
   }
 }
@@ -680,13 +700,25 @@ __global__ void pd_score_wgrad_generic_kernel(const float* __restrict__ a, const
   }
   acc[i] += s;
 }
-static void launch_pd_score_wgrad(const float* a, const float* gs, int B, int T, int K, double* acc, hipStream_t st) {
+// doubles of partial slots the deterministic form needs (0: the generic kernel sums in a fixed order as it is)
+static size_t pd_score_wgrad_slots(int K) { return K == 21 || K == 5 ? (size_t)PD_SLICES * (PD_C * K + 1) : 0; }
+static int launch_pd_score_wgrad(const float* a, const float* gs, int B, int T, int K, double* acc, hipStream_t st,
+                                 double* part = nullptr) {
+  if (part && K == 21) {
+    hipLaunchKernelGGL((pd_score_wgrad_kernel<21, true>), dim3(PD_C + 1, PD_SLICES), dim3(256), 0, st, a, gs, B, T, part);
+    return launch_det_sum64(part, PD_SLICES, PD_C * 21 + 1, PD_C * 21 + 1, acc, st);
+  }
+  if (part && K == 5) {
+    hipLaunchKernelGGL((pd_score_wgrad_kernel<5, true>), dim3(PD_C + 1, PD_SLICES), dim3(256), 0, st, a, gs, B, T, part);
+    return launch_det_sum64(part, PD_SLICES, PD_C * 5 + 1, PD_C * 5 + 1, acc, st);
+  }
   if (K == 21)
-    hipLaunchKernelGGL(pd_score_wgrad_kernel<21>, dim3(PD_C + 1, 8), dim3(256), 0, st, a, gs, B, T, acc);
+    hipLaunchKernelGGL((pd_score_wgrad_kernel<21, false>), dim3(PD_C + 1, PD_SLICES), dim3(256), 0, st, a, gs, B, T, acc);
   else if (K == 5)
-    hipLaunchKernelGGL(pd_score_wgrad_kernel<5>, dim3(PD_C + 1, 8), dim3(256), 0, st, a, gs, B, T, acc);
+    hipLaunchKernelGGL((pd_score_wgrad_kernel<5, false>), dim3(PD_C + 1, PD_SLICES), dim3(256), 0, st, a, gs, B, T, acc);
   else
     hipLaunchKernelGGL(pd_score_wgrad_generic_kernel, dim3(cdiv(PD_C * K + 1, 64)), dim3(64), 0, st, a, gs, B, T, K, acc);
+  return STY_OK;
 }
 
 struct PdRun : DiscBase {
@@ -763,8 +795,9 @@ struct PdRun : DiscBase {
         hipLaunchKernelGGL(pd_gz_kernel, dim3(cdiv(T, 64), PD_C, B), dim3(64), 0, st, gs[i], sw[i], ac.a[i], dnext, T, K, gz);
       const ConvArgs f = conv_args(i, i == 0 ? ac.x : ac.a[i - 1], nullptr);
       if (gwp) {
-        if (live())
-          launch_pd_score_wgrad(ac.a[i], gs[i], B, T, K, sacc[i], st);
+        const size_t nslot = det ? pd_score_wgrad_slots(K) : 0;
+        double* part = nslot ? take<double>(nslot) : nullptr;
+        if (live()) chk(launch_pd_score_wgrad(ac.a[i], gs[i], B, T, K, sacc[i], st, part));
         float* partial = take<float>(wgrad_partial_floats(f.w, B, T));
         bool done = false;
         if (live()) chk(launch_conv1d_wgrad(f, gz, nullptr, 1.f, gwp[i], partial, gbp[i], &done, st));

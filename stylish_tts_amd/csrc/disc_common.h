@@ -114,7 +114,39 @@ __global__ __launch_bounds__(256) void sd_loss_sums_kernel(const float* __restri
     if (threadIdx.x == 0 && x != 0.f) atomicAdd(&s->sums[t], (double)x);
   }
 }
+// deterministic mode: the same sums, every workgroup's six to slot blockIdx.x of `part` ([gridDim.x][6] doubles);
+// launch_det_sum64 adds the slots to s->sums in a fixed order (the double atomics' order moves the last digit otherwise)
+__global__ __launch_bounds__(256) void sd_loss_sums_det_kernel(const float* __restrict__ r, const float* __restrict__ g, int gen,
+                                                               size_t n, const SdSel* s, double* __restrict__ part) {
+  __shared__ float red[256];
+  const float m = s->m;
+  float sa = 0.f, sb = 0.f, cnt = 0.f, srel = 0.f, slin = 0.f, ties = 0.f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float rv = r[i], gv = g[i];
+    const float d = gen ? gv - rv : rv - gv;
+    const bool in = gen ? (gv < rv + m) : (rv < gv + m);
+    if (gen) {
+      sa = fmaf(1.f - gv, 1.f - gv, sa);
+    } else {
+      sa = fmaf(1.f - rv, 1.f - rv, sa);
+      sb = fmaf(gv, gv, sb);
+    }
+    if (in) {
+      cnt += 1.f;
+      srel = fmaf(d - m, d - m, srel);
+      slin += d - m;
+    }
+    if (d == m) ties += 1.f;
+  }
+  float v[6] = {sa, sb, cnt, srel, slin, ties};
+  for (int t = 0; t < 6; ++t) {
+    const float x = sd_block_sum(v[t], red);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.x * 6 + t] = (double)x;
+  }
+}
 // loss value (added to out[0], the part without the relativistic term to out[1]) and the score gradients times `scale`
+// (out[0], out[1]: one thread of one workgroup per launch adds to them and the launches of a run follow each other on one
+// stream, so the float atomics below meet in stream order: nothing for the deterministic mode to do here)
 __global__ __launch_bounds__(256) void sd_loss_grad_kernel(const float* __restrict__ r, const float* __restrict__ g, int gen,
                                                            size_t n, const SdSel* __restrict__ s, float scale,
                                                            float* __restrict__ out, float* __restrict__ gr,
@@ -161,6 +193,7 @@ struct DiscBase {
   hipStream_t st;
   int rc = STY_OK;
   size_t hwm = 0;
+  const bool det = deterministic_mode();  // latched for the run: every entry is one call, forward and backward
   bool live() const { return ws.base != nullptr && rc == STY_OK; }
   void chk(int r) {
     if (r && rc == STY_OK) rc = r;
@@ -181,15 +214,21 @@ struct DiscBase {
   // loss of one score-map pair; gen: generator form.  out[0] += loss, out[1] += loss without the relativistic term
   void loss_pair(const float* r, const float* g, size_t ne, int gen, float scale, float* out, float* gr, float* gg) {
     SdSel* sel = take<SdSel>(1);
-    if (!live()) return;
     size_t nblk = (ne + 2047) / 2048;
     const int nb = (int)(nblk < 1024 ? nblk : 1024);
+    double* part = det ? take<double>((size_t)nb * 6) : nullptr;
+    if (!live()) return;
     hipLaunchKernelGGL(sd_sel_init_kernel, dim3(1), dim3(256), 0, st, sel, (unsigned)((ne - 1) / 2));
     for (int p = 0; p < 4; ++p) {
       hipLaunchKernelGGL(sd_sel_hist_kernel, dim3(nb), dim3(256), 0, st, r, g, gen, ne, p, sel);
       hipLaunchKernelGGL(sd_sel_pick_kernel, dim3(1), dim3(64), 0, st, sel, p);
     }
-    hipLaunchKernelGGL(sd_loss_sums_kernel, dim3(nb), dim3(256), 0, st, r, g, gen, ne, sel);
+    if (det) {
+      hipLaunchKernelGGL(sd_loss_sums_det_kernel, dim3(nb), dim3(256), 0, st, r, g, gen, ne, sel, part);
+      chk(launch_det_sum64(part, nb, 6, 6, sel->sums, st));
+    } else {
+      hipLaunchKernelGGL(sd_loss_sums_kernel, dim3(nb), dim3(256), 0, st, r, g, gen, ne, sel);
+    }
     hipLaunchKernelGGL(sd_loss_grad_kernel, dim3(nb), dim3(256), 0, st, r, g, gen, ne, sel, scale, out, gr, gg);
   }
 };

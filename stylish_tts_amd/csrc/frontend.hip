@@ -920,6 +920,11 @@ struct ResBufs {  // per resolution, all [B][.][frames]
 __device__ __forceinline__ float aw_res(float x) { return x - 6.28318530717958647692f * rintf(x / 6.28318530717958647692f); }
 
 // sums[r*5 + {0: sum|T-P|, 1: sum|T|, 2: sum aw0 W, 3: sum aw1 W, 4: sum aw2 W}]  (double atomics)
+// DET (deterministic mode): `sums` is the resolution's partial buffer, [LOSS_SUM_BLOCKS][5] doubles, one slot per workgroup;
+// launch_det_sum64 adds the slots in index order.  These sums scale the backward seed: their last bit reaches every gradient.
+constexpr int LOSS_SUM_BLOCKS = 1024;
+constexpr size_t LOSS_DET_FLOATS = (size_t)3 * LOSS_SUM_BLOCKS * 5 * 2;  // the three resolutions' slots, as floats of workspace
+template <bool DET>
 __global__ __launch_bounds__(256) void loss_sums_kernel(ResBufs rb, int r, int B, double* __restrict__ sums) {
   __shared__ double red[5][4];
   __shared__ float wtab[1025];  // the frequency weights, once per workgroup (a double-precision exp per ELEMENT, ten
@@ -969,8 +974,13 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(ResBufs rb, int r, int B
     if (lane == 0) red[k][wave] = v;
   }
   __syncthreads();
-  if (threadIdx.x < 5) atomicAdd(&sums[r * 5 + threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] +
-                                                                 red[threadIdx.x][2] + red[threadIdx.x][3]);
+  if (threadIdx.x < 5) {
+    const double v = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    if (DET)
+      sums[(size_t)blockIdx.x * 5 + threadIdx.x] = v;
+    else
+      atomicAdd(&sums[r * 5 + threadIdx.x], v);
+  }
 }
 
 // losses[0] = mel, losses[1] = multi_phase (device scalars)
@@ -1196,7 +1206,9 @@ static int launch_frame_bwd(const float* dxt, const float* w, int B, int N, int 
   return STY_OK;
 }
 
-size_t acoustic_loss_workspace_floats(int B, int N) {
+// the default mode's figure; the deterministic mode's partial slots (LOSS_DET_FLOATS) lie behind it, so the layout in front
+// of them -- which sty_acoustic_loss_target fills ahead of the step -- is the same in both modes
+static size_t acoustic_loss_base_floats(int B, int N) {
   size_t tot = 64;
   const int res[3][2] = {{512, 128}, {1024, 256}, {2048, 512}};
   size_t tmp = 0;
@@ -1207,6 +1219,11 @@ size_t acoustic_loss_workspace_floats(int B, int N) {
     tmp = t > tmp ? t : tmp;
   }
   return tot + tmp + 4096;
+}
+// where the slots start: behind the default mode's figure, rounded up to 64 floats (they are doubles)
+static size_t acoustic_loss_det_offset_floats(int B, int N) { return (acoustic_loss_base_floats(B, N) + 63) / 64 * 64; }
+size_t acoustic_loss_workspace_floats(int B, int N) {
+  return deterministic_mode() ? acoustic_loss_det_offset_floats(B, N) + LOSS_DET_FLOATS : acoustic_loss_base_floats(B, N);
 }
 
 // (Measured and rejected: the three resolutions on three streams.  With six streams in the process the whole c2 step
@@ -1254,6 +1271,10 @@ int launch_acoustic_loss_gan(int B, int N, const float* audio_gt, const float* a
     return q;
   };
   double* sums = reinterpret_cast<double*>(take(32));
+  // deterministic mode, latched here for the call (forward and backward are one call; the entry points have checked the
+  // workspace against acoustic_loss_workspace_floats of the mode)
+  const bool det = deterministic_mode();
+  double* det_part = det ? reinterpret_cast<double*>(ws + acoustic_loss_det_offset_floats(B, N)) : nullptr;
   LossDims hdims;
   for (int r = 0; r < 3; ++r) {
     const int frames = N / res[r][1] + 1, F = res[r][0] / 2 + 1;
@@ -1319,7 +1340,14 @@ int launch_acoustic_loss_gan(int B, int N, const float* audio_gt, const float* a
       }
     }
     if (target_only) continue;
-    hipLaunchKernelGGL(loss_sums_kernel, dim3(1024), dim3(256), 0, st, rb[r], r, B, sums);
+    if (det) {
+      double* part = det_part + (size_t)r * LOSS_SUM_BLOCKS * 5;
+      hipLaunchKernelGGL(loss_sums_kernel<true>, dim3(LOSS_SUM_BLOCKS), dim3(256), 0, st, rb[r], r, B, part);
+      rc = launch_det_sum64(part, LOSS_SUM_BLOCKS, 5, 5, sums + r * 5, st);
+      if (rc) return rc;
+    } else {
+      hipLaunchKernelGGL(loss_sums_kernel<false>, dim3(LOSS_SUM_BLOCKS), dim3(256), 0, st, rb[r], r, B, sums);
+    }
     if (gan) {  // target |X| (scratch) and predicted |X| are both live here, in the batch-folded layout [F][B][frames]
       STY_HIP(hipMemsetAsync(d_gan[r], 0, (size_t)B * F * frames * sizeof(float), st));
       rc = specdisc_run(gan->p[r], B, F, frames, (size_t)frames, (size_t)B * frames, tfft, rb[r].p_fft, nullptr, nullptr,

@@ -261,8 +261,30 @@ __global__ void embedding_bwd_kernel(const int64_t* __restrict__ tok, const floa
   if (t < 0 || t >= ntok) t = 0;
   atomicAdd(&demb[(size_t)t * H + c], g[((size_t)b * H + c) * L + l] * scale);
 }
+// deterministic mode: one workgroup per (token id, slice of 64 channels) walks the B L token ids in index order and adds the
+// matching columns of g in that order -- a repeated token's rows meet in a fixed order, and nothing is scattered
+__global__ __launch_bounds__(64) void embedding_bwd_det_kernel(const int64_t* __restrict__ tok, const float* __restrict__ g, int B,
+                                                               int L, int H, int ntok, float scale, float* __restrict__ demb) {
+  const int id = blockIdx.x, c = blockIdx.y * 64 + threadIdx.x;
+  float acc = 0.f;
+  bool any = false;
+  for (int i = 0; i < B * L; ++i) {
+    int64_t t = tok[i];
+    if (t < 0 || t >= ntok) t = 0;
+    if (t != id) continue;  // (uniform over the workgroup)
+    any = true;
+    const int b = i / L, l = i - b * L;
+    if (c < H) acc += g[((size_t)b * H + c) * L + l] * scale;
+  }
+  if (any && c < H) demb[(size_t)id * H + c] += acc;
+}
 int launch_embedding_bwd(const int64_t* tokens, const float* g, int B, int L, int H, int ntok, float scale, float* demb,
-                         hipStream_t st) {
+                         hipStream_t st, bool det) {
+  if (det) {
+    hipLaunchKernelGGL(embedding_bwd_det_kernel, dim3(ntok, cdiv(H, 64)), dim3(64), 0, st, tokens, g, B, L, H, ntok, scale, demb);
+    STY_LAUNCH_CHECK();
+    return STY_OK;
+  }
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3(cdiv(L, 64), H, B), dim3(64), 0, st, tokens, g, L, H, ntok, scale, demb);
   STY_LAUNCH_CHECK();
   return STY_OK;
@@ -371,6 +393,10 @@ int launch_slice_add(const float* src, int Csrc, int c0, int B, int C, int T, fl
   return STY_OK;
 }
 // fnv (three weight-normed 1->1 k3 convs): gradients of the inputs and of the effective weights w34 [3][4]
+// DET: the slice's twelve sums go to slot blockIdx.y of a [FNV_SLICES][12] partial buffer (passed as dw34)
+constexpr int FNV_SLICES = 16;
+int fnv_bwd_slices() { return FNV_SLICES; }
+template <bool DET>
 __global__ __launch_bounds__(256) void fnv_bwd_kernel(const float* __restrict__ p, const float* __restrict__ e,
                                                       const float* __restrict__ v, const float* __restrict__ w34,
                                                       const float* __restrict__ g, int B, int T,
@@ -409,11 +435,21 @@ __global__ __launch_bounds__(256) void fnv_bwd_kernel(const float* __restrict__ 
       for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x < 4) atomicAdd(&dw34[i * 4 + threadIdx.x], red[threadIdx.x][0]);
+  if (threadIdx.x < 4) {
+    if (DET)
+      dw34[blockIdx.y * 12 + i * 4 + threadIdx.x] = red[threadIdx.x][0];
+    else
+      atomicAdd(&dw34[i * 4 + threadIdx.x], red[threadIdx.x][0]);
+  }
 }
 int launch_fnv_bwd(const float* pitch, const float* energy, const float* voiced, const float* w34, const float* g, int B,
-                   int T, float* dw34, float* dp, float* de, float* dv, hipStream_t st) {
-  hipLaunchKernelGGL(fnv_bwd_kernel, dim3(3, 16), dim3(256), 0, st, pitch, energy, voiced, w34, g, B, T, dw34, dp, de, dv);
+                   int T, float* dw34, float* dp, float* de, float* dv, hipStream_t st, bool det) {
+  if (det)
+    hipLaunchKernelGGL(fnv_bwd_kernel<true>, dim3(3, FNV_SLICES), dim3(256), 0, st, pitch, energy, voiced, w34, g, B, T, dw34, dp, de,
+                       dv);
+  else
+    hipLaunchKernelGGL(fnv_bwd_kernel<false>, dim3(3, FNV_SLICES), dim3(256), 0, st, pitch, energy, voiced, w34, g, B, T, dw34, dp, de,
+                       dv);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

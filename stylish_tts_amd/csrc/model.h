@@ -327,14 +327,15 @@ inline ConvRoute plan_route(const sty_model* m, ConvArgs a) {
 }
 int launch_pro_bwd(int mode, const float* u, int Cu, int cu0, const float* x, int B, int C, int T, const float* pa,
                    const float* ps, int pC, int pc0, const float* alpha, const float* mask, float* dx, int accumulate,
-                   float* dpa, float* dps, float* dalpha, hipStream_t st);
+                   float* dpa, float* dps, float* dalpha, hipStream_t st, bool det = false);
 int launch_adain_fold_bwd(const float* da, const float* ds, const float* mean, const float* rstd, const float* gb, int B,
                           int C, int T, float* dgb, float* c0, float* c1, hipStream_t st);
 int launch_row_axpb(const float* x, const float* c0, const float* c1, int rows, int T, float* dx, hipStream_t st);
 // AdaIN + Snake prologue backward with the instance-norm statistics term in ONE launch (bwd.hip); u / x / dx fp32 or bf16 tensors
 int launch_pro_bwd_adain(const void* u, int uh, const void* x, int xh, int B, int C, int T, const float* pa, const float* ps,
                          const float* alpha, const float* mean, const float* rstd, const float* gb, void* dx, int dh,
-                         int accumulate, float* dgb, float* dalpha, int hw, hipStream_t st, const void* dsrc = nullptr);
+                         int accumulate, float* dgb, float* dalpha, int hw, hipStream_t st, const void* dsrc = nullptr,
+                         bool det = false);
 // plain casts between an fp32 tensor and a two-byte one (test aids of the block entry point)
 int launch_cast_f32_to_16(const float* x, size_t n, void* y16, hipStream_t st);
 int launch_cast_16_to_f32(const void* x16, size_t n, float* y, hipStream_t st);
@@ -342,15 +343,17 @@ bool chan_ln32_eligible(int B, int C, int T, int relu);  // the one-thread-per-c
 // h16 bits: 1 = x, 2 = dy, 4 = dx are bf16 tensors
 int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, int C, int T, float eps, int ada,
                        const float* w, const float* gb, int relu, const float* out_mask, float* dx, int accumulate,
-                       float* mu_tmp, float* r_tmp, float* dgb, float* dw, float* db, hipStream_t st, int h16 = 0);
+                       float* mu_tmp, float* r_tmp, float* dgb, float* dw, float* db, hipStream_t st, int h16 = 0,
+                       bool det = false);
 // gx [B][C4]: the forward's per-channel norms (launch_grn_finalize).  gx == nullptr (the unit entry's comparison only): they
 // are rebuilt from the forward's partials (part, nseg)
 int launch_grn_bwd(const float* gx, const double* part, int nseg, const float* gamma, const float* ds, int B, int C4,
-                   float* coef, float* dgamma, hipStream_t st);
+                   float* coef, float* dgamma, hipStream_t st, bool det = false);
 int launch_act_fwd(int kind, const float* x, const float* alpha, int B, int C, int T, float* y, hipStream_t st);
 // h, coef [B][C] (optional): the output gradient is dy + coef[b][c] * h, formed in the kernel (the GRN term)
 int launch_act_bwd(int kind, const float* x, const float* dy, const float* alpha, int B, int C, int T, float* dx,
-                   int accumulate, float* dalpha, hipStream_t st, const float* h = nullptr, const float* coef = nullptr);
+                   int accumulate, float* dalpha, hipStream_t st, const float* h = nullptr, const float* coef = nullptr,
+                   bool det = false);
 int launch_row_scale_add(const float* src, const float* coef, float k, int rows, int T, float* dst, hipStream_t st);
 int launch_dwconv_fwd(const float* x, const float* w, const float* bias, int B, int C, int T, int K, int pad, float* y,
                       hipStream_t st);
@@ -367,7 +370,8 @@ int launch_partial_sum(int dw_form, const float* part, int C, int K, int nblk, f
 int launch_bias_grad(const float* g, const float* mask, int B, int C, int T, int shuffle, float scale, float* db,
                      float* scratch, hipStream_t st);
 int launch_style_fc_bwd(const void* descs_dev, int nlayers, int B, int style_dim, const float* style,
-                        const float* dgb_base, float* dstyle, hipStream_t st);
+                        const float* dgb_base, float* dstyle, hipStream_t st, bool det = false);
+int style_fc_bwd_slots(int nlayers);  // det: dstyle is a [slots][B][style_dim] partial buffer
 int launch_istft64_bwd(int B, int F, const float* audio, const float* daudio, const float* logamp, const float* real,
                        const float* imag, const float* bbr, const float* bbi, float* dlogamp, float* dreal,
                        float* dimag, hipStream_t st);
@@ -381,6 +385,10 @@ void wgrad_defer_destroy(WgReduceDefer* d);
 WgReduceDefer* wgrad_defer_set(WgReduceDefer* d);  // returns the previous one (nullptr = immediate reductions)
 size_t wgrad_defer_pending(const WgReduceDefer* d);
 int wgrad_defer_flush(WgReduceDefer* d, int site, hipStream_t st);
+// gwp[i] (+ gbias behind `plane`) += sum over k < nslices of partial[k * stride + i], the slices in a fixed order; recorded
+// while a WgReduceDefer is current, launched on `st` otherwise
+void launch_wgrad_reduce_planes(const float* partial, int nslices, size_t plane, size_t stride, int nb, float* gwp,
+                                float* gbias, hipStream_t st);
 int launch_attention_bwd(const AttnArgs& a, const float* dO, float* dQ, float* dK, float* dV, size_t dqbs, size_t dkbs,
                          size_t dvbs, size_t dobs, int B, int DH, float* ws, hipStream_t st, int overwrite = 0);
 bool attention_bwd_can_overwrite(const AttnArgs& a, int DH);
@@ -389,11 +397,12 @@ size_t attention_bwd_ws_floats(int B, int H, int T);
 int launch_rope_signed(float* q, float* k, int B, int H, int DH, int L, int d, const float* theta4, float sgn,
                        hipStream_t st);
 int launch_embedding_bwd(const int64_t* tokens, const float* g, int B, int L, int H, int ntok, float scale, float* demb,
-                         hipStream_t st);
+                         hipStream_t st, bool det = false);
 int launch_bmm_ct_bwd(const float* g, const float* ali, int B, int C, int L, int T, float* denc, hipStream_t st);
 int launch_slice_add(const float* src, int Csrc, int c0, int B, int C, int T, float* dst, hipStream_t st);
 int launch_fnv_bwd(const float* pitch, const float* energy, const float* voiced, const float* w34, const float* g, int B,
-                   int T, float* dw34, float* dp, float* de, float* dv, hipStream_t st);
+                   int T, float* dw34, float* dp, float* de, float* dv, hipStream_t st, bool det = false);
+int fnv_bwd_slices();  // det: dw34 is a [slices][12] partial buffer
 int launch_fnv_unpack(const float* dw34, const float* g0, const float* v0, const float* g1, const float* v1,
                       const float* g2, const float* v2, float* dg0, float* dv0, float* db0, float* dg1, float* dv1,
                       float* db1, float* dg2, float* dv2, float* db2, hipStream_t st);
@@ -410,7 +419,7 @@ int launch_dw2d_sn_unpack(const float* g9, const float* w, const float* u, const
 int launch_avgpool2_bwd(const float* gy, int BC, int H, int W, float scale, float* dx, const float* gate, hipStream_t st,
                         __bf16* dx16 = nullptr, const float* mask16 = nullptr, int C = 0);
 int launch_pool_fc_bwd(const float* x, int B, int C, int n, int count, const float* W, int S, const float* gs,
-                       float* dW, float* db, float* dx, int accumulate, hipStream_t st);
+                       float* dW, float* db, float* dx, int accumulate, hipStream_t st, float* det_a = nullptr);
 int launch_bn_train_fwd(const float* x, const float* w, const float* b, float* rm, float* rv, float eps, float momentum,
                         int B, int C, int T, float* y, float* mean, float* rstd, double* part, hipStream_t st);
 int launch_bn_train_bwd(const float* x, const float* dy, const float* w, const float* mean, const float* rstd, int B,
@@ -448,6 +457,13 @@ int trainer_block_fwd_bwd(Trainer* t, int kind, const void* blk, int B, int C, i
                           size_t* need);
 void trainer_set_segment_hook(Trainer* t, std::function<void(int)> fn);  // called once segment 0's gradients are final
 bool single_stream_mode();  // sty_set_single_stream: no internal side streams (measurement aid)
+// sty_set_deterministic: sums whose result depends on the arrival order of atomics take a fixed-order path.  A launcher's
+// `det` argument (default false: the atomic form) says that the gradient pointer it is given in the parameter's place is a
+// partial buffer with one slot per writer -- [B][C] for the per-(b, c) rows -- which the caller sums in index order.  Every
+// entry that runs a forward latches the mode; its backward follows the forward's.
+bool deterministic_mode();
+// out[i] += sum over k < nslots of part[k * stride + i], i < n: the slots in a fixed order, in double
+int launch_det_sum64(const double* part, int nslots, size_t n, size_t stride, double* out, hipStream_t st);
 int trainer_wait_d_style(Trainer* t, hipStream_t stream);
 void* trainer_branch_stream(Trainer* t);  // where the prior branch of the last speech forward ran and its backward will (nullptr: in place)
 int trainer_pitch_energy_forward(Trainer* t, int B, int L, int T, const int64_t* texts, const int64_t* lengths,

@@ -217,6 +217,38 @@ __global__ void pitch_loss_sums_kernel(const float* __restrict__ tg, const float
     atomicAdd(&acc[1], c);
   }
 }
+// deterministic mode (also duration_loss_sums_det_kernel): ONE workgroup walks the nb = B utterances in index order and adds
+// their sums in that order -- B rows of a few hundred values, no slots and no second launch
+__global__ void pitch_loss_sums_det_kernel(const float* __restrict__ tg, const float* __restrict__ pr, int T,
+                                           double* __restrict__ acc, int nb) {
+  __shared__ float r0[64], r1[64];
+  double ta = 0.0, tc = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    float s0 = 0.f, s1 = 0.f;
+    for (int t = threadIdx.x; t < T; t += 64) {
+      const size_t o = (size_t)b * T + t;
+      s0 += sl1(pr[o] - tg[o]);
+      if (t + 1 < T) s1 += sl1((pr[o + 1] - pr[o]) - (tg[o + 1] - tg[o]));
+    }
+    r0[threadIdx.x] = s0;
+    r1[threadIdx.x] = s1;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double a = 0.0, c = 0.0;
+      for (int i = 0; i < 64; ++i) {
+        a += r0[i];
+        c += r1[i];
+      }
+      ta += a;
+      tc += c;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {  // (the caller zeroed acc)
+    acc[0] = ta;
+    acc[1] = tc;
+  }
+}
 // loss[0] = value; d_pred += k * d loss / d pred with k = weight / (loss + 1e-9) (LossLog.backwards_loss) or weight
 __global__ void pitch_loss_grad_kernel(const float* __restrict__ tg, const float* __restrict__ pr, int B, int T,
                                        const double* __restrict__ acc, float weight, int normalize, float* __restrict__ loss,
@@ -236,7 +268,10 @@ __global__ void pitch_loss_grad_kernel(const float* __restrict__ tg, const float
 int launch_pitch_loss(const float* target, const float* pred, int B, int T, float weight, int normalize, float* loss,
                       float* d_pred, double* acc, hipStream_t st) {
   STY_HIP(hipMemsetAsync(acc, 0, 2 * sizeof(double), st));
-  hipLaunchKernelGGL(pitch_loss_sums_kernel, dim3(B), dim3(64), 0, st, target, pred, T, acc);
+  if (deterministic_mode())
+    hipLaunchKernelGGL(pitch_loss_sums_det_kernel, dim3(1), dim3(64), 0, st, target, pred, T, acc, B);
+  else
+    hipLaunchKernelGGL(pitch_loss_sums_kernel, dim3(B), dim3(64), 0, st, target, pred, T, acc);
   hipLaunchKernelGGL(pitch_loss_grad_kernel, dim3(cdiv(T, 64), B), dim3(64), 0, st, target, pred, B, T, acc, weight, normalize,
                      loss, d_pred);
   STY_LAUNCH_CHECK();
@@ -302,6 +337,46 @@ __global__ void duration_loss_sums_kernel(const float* __restrict__ pred, const 
     itemW[b] = (float)w;
     atomicAdd(&acc[0], a / ((double)len * B));
     atomicAdd(&acc[1], c / (w * B));
+  }
+}
+// deterministic mode: see pitch_loss_sums_det_kernel
+__global__ void duration_loss_sums_det_kernel(const float* __restrict__ pred, const int64_t* __restrict__ lengths,
+                                              const float* __restrict__ tgt, const int64_t* __restrict__ cls,
+                                              const float* __restrict__ tab, const float* __restrict__ cw, int B, int L, int NC,
+                                              double* __restrict__ acc, float* __restrict__ itemW) {
+  __shared__ float r0[64], r1[64], r2[64];
+  double ta = 0.0, tc = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const int len = (int)lengths[b];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int l = threadIdx.x; l < len; l += 64) {
+      float p[32], S, E;
+      dur_softmax(pred + ((size_t)b * L + l) * NC, NC, p, tab, S, E);
+      s0 += sl1(E / (S + 1e-9f) - tgt[(size_t)b * L + l]);
+      const int y = (int)cls[(size_t)b * L + l];
+      s1 -= cw[y] * logf(fmaxf(p[y], 1e-38f));
+      s2 += cw[y];
+    }
+    r0[threadIdx.x] = s0;
+    r1[threadIdx.x] = s1;
+    r2[threadIdx.x] = s2;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double a = 0.0, c = 0.0, w = 0.0;
+      for (int i = 0; i < 64; ++i) {
+        a += r0[i];
+        c += r1[i];
+        w += r2[i];
+      }
+      itemW[b] = (float)w;
+      ta += a / ((double)len * B);
+      tc += c / (w * B);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {  // (the caller zeroed acc)
+    acc[0] = ta;
+    acc[1] = tc;
   }
 }
 // d_pred [B][L][NC] = d (w_dur dur / dur.detach + w_ce ce / ce.detach) / d pred + extra[b][l] * d duration / d pred
@@ -370,8 +445,12 @@ extern "C" int sty_duration_loss_fwd_bwd(int B, int L, int NC, const float* pred
   double* acc = static_cast<double*>(workspace);
   float* itemW = reinterpret_cast<float*>(acc + 2);
   STY_HIP(hipMemsetAsync(acc, 0, 2 * sizeof(double), st));
-  hipLaunchKernelGGL(sty::duration_loss_sums_kernel, dim3(B), dim3(64), 0, st, pred, text_lengths, target_dur, target_class,
-                     class_table, ce_weight, B, L, NC, acc, itemW);
+  if (sty::deterministic_mode())
+    hipLaunchKernelGGL(sty::duration_loss_sums_det_kernel, dim3(1), dim3(64), 0, st, pred, text_lengths, target_dur, target_class,
+                       class_table, ce_weight, B, L, NC, acc, itemW);
+  else
+    hipLaunchKernelGGL(sty::duration_loss_sums_kernel, dim3(B), dim3(64), 0, st, pred, text_lengths, target_dur, target_class,
+                       class_table, ce_weight, B, L, NC, acc, itemW);
   hipLaunchKernelGGL(sty::duration_loss_grad_kernel, dim3(sty::cdiv(L, 64), B), dim3(64), 0, st, pred, text_lengths, target_dur,
                      target_class, class_table, ce_weight, d_duration_extra, B, L, NC, acc, itemW, w_duration, w_ce, losses,
                      d_pred);

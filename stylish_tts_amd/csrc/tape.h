@@ -32,6 +32,9 @@ struct Tape {
   int rc = STY_OK;
   size_t peak = 0;
   bool dry = false;  // sizing pass: fake base pointer, allocations are tracked but nothing is launched
+  // deterministic mode (sty_set_deterministic), latched by open(): the forward, its sizing pass and the backward of that
+  // forward all see this value, whatever the switch says by the time the backward runs
+  bool det = false;
   std::vector<std::function<void()>> tape;
   GradLedger ledger;
   float* scratch_param = nullptr;  // sink for gradients of parameters nobody bound a gradient for
@@ -86,6 +89,7 @@ struct Tape {
     rc = STY_OK;
     ws = Bump();
     dry = dry_;
+    det = deterministic_mode();
     ws.base = dry ? reinterpret_cast<char*>(kDryBase) : (char*)ws_;
     ws.cap = dry ? kDryCap : ws_bytes;
     peak = 0;
@@ -303,6 +307,9 @@ struct Tape {
       after_reduce.clear();
       return;
     }
+    // deterministic mode: the partial slots summed here (det_sum) were written on the main stream, after the side stream's
+    // last wait for it
+    if (det && s != st) stream_after(s, st, "deterministic partials");
     chk(wgrad_defer_flush(defer, flush_site++, s));
     WgReduceDefer* cur = wgrad_defer_set(nullptr);  // (what runs now reduces at once, should it reduce at all)
     if (rc == STY_OK)
@@ -311,6 +318,29 @@ struct Tape {
     after_reduce.clear();
   }
 
+  // ---- deterministic mode: batch-summed parameter gradients without atomics ----
+  // det_slots: a [slots][n] partial buffer for a launcher's `det` form, or nullptr (default mode / no gradient wanted).  It has
+  // to outlive the entry that takes it (the grouped reduction reads it at the next flush), so an entry takes it BEFORE its
+  // mark; the sizing pass walks the same code, so the workspace figure of the mode includes every such buffer.
+  // det_sum: out[i] += sum_k part[k][i], k in index order -- recorded into the grouped reduction of the weight gradients
+  // where one is deferring (no launch of its own; jobs onto one destination go to consecutive rounds in recording order),
+  // launched at once on the main stream otherwise or when `now` (somebody reads `out` before the next flush).
+  // (a gradient nobody bound goes to the scratch sink: it keeps the atomic form -- its values are never read, and reduce jobs
+  // onto the one sink would all overlap, each in a round and a launch of its own)
+  float* det_slots(const float* grad, size_t slots, size_t n) {
+    return det && grad && grad != scratch_param ? take<float>(slots * n) : nullptr;
+  }
+  void det_sum(const float* part, size_t slots, size_t n, float* out, bool now = false) {
+    if (!part || !live()) return;
+    if (now) {
+      WgReduceDefer* cur = wgrad_defer_set(nullptr);
+      launch_wgrad_reduce_planes(part, (int)slots, n, n, 0, out, nullptr, st);
+      (void)wgrad_defer_set(cur);
+    } else {
+      DeferScope ds(this);
+      launch_wgrad_reduce_planes(part, (int)slots, n, n, 0, out, nullptr, st);
+    }
+  }
   // ---- workspace ----
   template <typename Tp>
   Tp* take(size_t n) {

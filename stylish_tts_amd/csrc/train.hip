@@ -223,6 +223,7 @@ struct Trainer : Tape {
     float* dpa = nullptr;
     float* dps = nullptr;
     float* dal = nullptr;
+    float* dal_part = nullptr;  // deterministic mode: [B][Cin] slots for the Snake d alpha rows
     // AdaIN + Snake prologue whose (a, s) came from adain() of this very input (the resblock convs): the prologue backward,
     // the fold and the instance-norm statistics term run as ONE launch (launch_pro_bwd_adain); adain()'s tape entry then has
     // nothing left to do
@@ -239,6 +240,11 @@ struct Trainer : Tape {
         dpa = Gw(f.pa, (size_t)B * w.Cin, dummy);
       }
       if (f.pro == PRO_AFFINE_SNAKE) dal = PG(f.palpha, w.Cin);
+    }
+    dal_part = det_slots(dal, B, w.Cin);
+    if (dal_part && !fuse && live()) {  // (a source nobody wants the gradient of leaves its slots unwritten)
+      hipError_t e = hipMemsetAsync(dal_part, 0, (size_t)B * w.Cin * sizeof(float), st);
+      if (e != hipSuccess) rc = hip_fail(e, "d alpha slots memset");
     }
     const size_t mark = ws.off;
     // y = ((acc + bias) * out_scale * mask_pre + residual) * mask_post: the conv core always sees gY * mask
@@ -301,7 +307,9 @@ struct Trainer : Tape {
         fuse->done = true;
         if (live())
           chk(launch_pro_bwd_adain(U, u16, f.x[0], f.xh, B, w.Cin, Tt, f.pa, f.ps, f.palpha, fuse->mean, fuse->rstd, fuse->gbl,
-                                   gX[0], is16(gX[0]), accX[0], fuse->dgl, dal, f.bf16 ? 1 : 0, st, gX_src));
+                                   gX[0], is16(gX[0]), accX[0], fuse->dgl, dal_part ? dal_part : dal, f.bf16 ? 1 : 0, st, gX_src,
+                                   dal_part != nullptr));
+        det_sum(dal_part, B, w.Cin, dal);
         release(mark);
         return;
       }
@@ -321,9 +329,10 @@ struct Trainer : Tape {
       for (int i = 0; i < f.nsrc; ++i) {
         if (gX[i] && live())
           chk(launch_pro_bwd(f.pro | (f.bf16 ? 0x100 : 0), U, w.Cin, c0, f.x[i], B, f.xc[i], Tt, f.pa, f.ps, w.Cin, c0, f.palpha, f.mask, gX[i],
-                             accX[i], dpa, dps, dal, st));
+                             accX[i], dpa, dps, dal_part ? dal_part : dal, st, dal_part != nullptr));
         c0 += f.xc[i];
       }
+      det_sum(dal_part, B, w.Cin, dal);
     }
     release(mark);
   }
@@ -339,7 +348,11 @@ struct Trainer : Tape {
       int acc = 1;
       float* gX = Gw(x, (size_t)B * Cin * Tt, acc);
       float* dal = kind == ACT_SNAKE ? PG(alpha, C) : nullptr;
-      if (live()) chk(launch_act_bwd(kind, x, gY, alpha, B, C, Tt, gX, acc, dal, st, row ? y : nullptr, row));
+      float* dal_part = det_slots(dal, B, C);
+      if (live())
+        chk(launch_act_bwd(kind, x, gY, alpha, B, C, Tt, gX, acc, dal_part ? dal_part : dal, st, row ? y : nullptr, row,
+                           dal_part != nullptr));
+      det_sum(dal_part, B, C, dal);
     });
     return y;
   }
@@ -393,13 +406,22 @@ struct Trainer : Tape {
       } else {
         gX = Gw(x, nel, acc);
       }
+      float* dw = fc ? nullptr : PG(w, C);
+      float* db = fc ? nullptr : PG(bvec, C);
+      // deterministic mode: the general kernel's per-(b, c) rows go to [B][C] slots (the long-row C = 32 kernel sums its
+      // workgroup rows in a fixed order in both modes and takes no slots)
+      const bool e32 = chan_ln32_eligible(B, C, Tt, relu);
+      const bool slots = det && dw && db && !e32;
+      float* dw_part = slots ? take<float>((size_t)B * C) : nullptr;
+      float* db_part = slots ? take<float>((size_t)B * C) : nullptr;
       const size_t mark = ws.off;
       float* mu = take<float>((size_t)B * Tt);
       float* r = take<float>((size_t)B * Tt);
-      float* dw = fc ? nullptr : PG(w, C);
-      float* db = fc ? nullptr : PG(bvec, C);
       if (live())
-        chk(launch_chan_ln_bwd(x, gY, y, B, C, Tt, eps, fc ? 1 : 0, w, gbl, relu, omask, gX, acc, mu, r, dgl, dw, db, st, h16));
+        chk(launch_chan_ln_bwd(x, gY, y, B, C, Tt, eps, fc ? 1 : 0, w, gbl, relu, omask, gX, acc, mu, r, dgl,
+                               slots ? dw_part : dw, slots ? db_part : db, st, h16, e32 ? det : slots));
+      det_sum(dw_part, B, C, dw);
+      det_sum(db_part, B, C, db);
       release(mark);
     });
     return y;
@@ -581,6 +603,8 @@ struct Trainer : Tape {
       float* xn_p = side ? take<float>(xn16 ? n32 / 2 : n32) : nullptr;
       float* gu_p = side ? take<float>(gu16 ? n32 / 2 : n32) : nullptr;
       float* dsc_p = side ? take<float>(dwconv_bwd_scratch_floats(B, 32, Tt, 7)) : nullptr;
+      float* dgam = PG(c.grn_gamma, 128);
+      float* dgam_part = det_slots(dgam, B, 128);  // deterministic mode: the GRN d gamma rows, one slot per utterance
       const size_t mark = ws.off;
       double* pds = take<double>((size_t)B * 128 * nt_b);
       double* pgb = take<double>((size_t)B * 64 * nt_b);
@@ -642,7 +666,8 @@ struct Trainer : Tape {
         if (live()) {
           chk(launch_wgrad_cnx(1, h16, gY, B, Tt, pM, 1, st, 1, gy16));
           chk(launch_cnx_m_finish(pM, B, SB, c.w2_raw, scale, ds, frozen ? nullptr : gw2, frozen ? nullptr : gb2, st));
-          chk(launch_grn_bwd(gxn, nullptr, 0, c.grn_gamma, ds, B, 128, coef, PG(c.grn_gamma, 128), st));
+          chk(launch_grn_bwd(gxn, nullptr, 0, c.grn_gamma, ds, B, 128, coef, dgam_part ? dgam_part : dgam, st, dgam_part != nullptr));
+          det_sum(dgam_part, B, 128, dgam);
           chk(launch_convnext32_bwd(a, B, 2, st));
           chk(launch_cnx_partial_sum(pgb, B, 64, nt_b, 2, dgl, st));
         }
@@ -652,7 +677,8 @@ struct Trainer : Tape {
         a1.ntiles = nt;
         chk(launch_convnext32_bwd(a1, B, 1, st));
         chk(launch_cnx_partial_sum(pds, B, 128, nt, 0, ds, st));
-        chk(launch_grn_bwd(gxn, nullptr, 0, c.grn_gamma, ds, B, 128, coef, PG(c.grn_gamma, 128), st));
+        chk(launch_grn_bwd(gxn, nullptr, 0, c.grn_gamma, ds, B, 128, coef, dgam_part ? dgam_part : dgam, st, dgam_part != nullptr));
+        det_sum(dgam_part, B, 128, dgam);
         chk(launch_convnext32_bwd(a, B, 2, st));
         chk(launch_cnx_partial_sum(pds, B, 128, nt_b, 1, dal, st));
         chk(launch_cnx_partial_sum(pgb, B, 64, nt_b, 2, dgl, st));
@@ -737,7 +763,10 @@ struct Trainer : Tape {
       // coef stays taken (no mark / restore here): it has to outlive this entry, until act()'s entry -- the next one of this
       // block -- or row_flush has read it; B 4C floats a block, to the end of the backward, counted by the sizing pass
       float* coef = take<float>((size_t)B * 4 * C);
-      if (live()) chk(launch_grn_bwd(gxn, nullptr, 0, gamma, dsc, B, 4 * C, coef, PG(gamma, 4 * C), st));
+      float* dgam = PG(gamma, 4 * C);
+      float* dgam_part = det_slots(dgam, B, 4 * C);
+      if (live()) chk(launch_grn_bwd(gxn, nullptr, 0, gamma, dsc, B, 4 * C, coef, dgam_part ? dgam_part : dgam, st, dgam_part != nullptr));
+      det_sum(dgam_part, B, 4 * C, dgam);
       // gH += coef * h is owed, not run: h's producer is act(), whose backward reads gH next and forms the term itself
       ledger.owe(h, OWED_ROW).row = PendRow{coef, B * 4 * C, Tt};
     });
@@ -980,7 +1009,7 @@ struct Trainer : Tape {
       const int ntok = t.tokens;
       tape.push_back([=]() {
         float* g = G(x0, n);
-        if (live()) chk(launch_embedding_bwd(tokens, g, B, L, H, ntok, esc, PG(emb, (size_t)ntok * H), st));
+        if (live()) chk(launch_embedding_bwd(tokens, g, B, L, H, ntok, esc, PG(emb, (size_t)ntok * H), st, det));
       });
     }
     const float* h = x0;
@@ -1227,7 +1256,12 @@ struct Trainer : Tape {
         float* g = G(fnv, (size_t)B * 3 * Tt);
         float* de = wants(energy) ? G(energy, (size_t)B * Tt) : nullptr;
         float* dp = wants(pin) ? G(pitch, (size_t)B * Tt) : nullptr;  // (pitch == pin unless it was smoothed)
-        if (live()) chk(launch_fnv_bwd(pitch, energy, voiced, w34, g, B, Tt, PGpacked(w34), dp, de, nullptr, st));
+        float* dw34 = PGpacked(w34);
+        float* dw34_part = det_slots(dw34, fnv_bwd_slices(), 12);
+        if (live())
+          chk(launch_fnv_bwd(pitch, energy, voiced, w34, g, B, Tt, dw34_part ? dw34_part : dw34, dp, de, nullptr, st,
+                             dw34_part != nullptr));
+        det_sum(dw34_part, fnv_bwd_slices(), 12, dw34);
       });
     }
     const float* s1[2] = {asr, fnv};
@@ -2043,7 +2077,8 @@ struct Trainer : Tape {
       float* gs = G(style_dst, (size_t)B * S);
       int acc = 1;
       float* gx = Gw(hd, (size_t)B * Cc * n, acc);
-      if (live()) chk(launch_pool_fc_bwd(hd, B, Cc, n, cnt, fw, S, gs, PG(fw, (size_t)S * Cc), PG(fb, S), gx, acc, st));
+      float* det_a = det ? take<float>((size_t)B * Cc) : nullptr;  // deterministic mode: the activated means a[b][c]
+      if (live()) chk(launch_pool_fc_bwd(hd, B, Cc, n, cnt, fw, S, gs, PG(fw, (size_t)S * Cc), PG(fb, S), gx, acc, st, det_a));
     });
   }
   void style_backward(const float* d_style) {
@@ -2258,6 +2293,10 @@ struct Trainer : Tape {
     if (fc_bwd_done) return;
     fc_bwd_done = true;
     float* d_style = d_style_out;
+    // deterministic mode: every (layer, slice) workgroup's share of d style in a slot of its own.  (The sizing pass has no
+    // d_style of the caller and takes the slots all the same.)
+    const size_t ds_slots = (size_t)style_fc_bwd_slots((int)m->fcs.size());
+    float* ds_part = det && !m->fcs.empty() && (d_style || dry) ? take<float>(ds_slots * B * m->style_dim) : nullptr;
     if (live() && !m->fcs.empty()) {
       if (d_style) {
         hipError_t e = hipMemsetAsync(d_style, 0, (size_t)B * m->style_dim * sizeof(float), st);
@@ -2287,7 +2326,10 @@ struct Trainer : Tape {
           if (e != hipSuccess) rc = hip_fail(e, "fc bwd table copy");
           fcs_bwd_sent.assign(reinterpret_cast<const char*>(hb.data()), reinterpret_cast<const char*>(hb.data()) + nb);
         }
-        chk(launch_style_fc_bwd(m->fcs_bwd_dev, (int)hb.size(), B, m->style_dim, style, dgb, d_style, st));
+        chk(launch_style_fc_bwd(m->fcs_bwd_dev, (int)hb.size(), B, m->style_dim, style, dgb, ds_part ? ds_part : d_style, st,
+                                ds_part != nullptr));
+        // (d_style is the next thing anybody reads: summed at once, behind the kernel on this stream)
+        det_sum(ds_part, ds_slots, (size_t)B * m->style_dim, d_style, /*now=*/true);
       }
     }
     if (live()) {

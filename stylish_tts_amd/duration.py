@@ -95,8 +95,13 @@ def duration_loss_values(pred, text_lengths, target_dur, target_class, ce_weight
 class DurationTrainer:
     def __init__(self, duration_predictor, duration_style_encoder, dur_disc, duration_weights, lr=1e-4, betas=(0.85, 0.99),
                  eps=1e-9, weight_decay=1e-4, w_gen=1.0, w_duration=8.0, w_ce=8.0, mean=-4.0, std=4.0,
-                 bucket_bytes=25 << 20, train_mode=True, seed=0, dropout=0.2, compute="fp32", synth_models=None):
+                 bucket_bytes=25 << 20, train_mode=True, seed=0, dropout=0.2, compute="fp32", synth_models=None,
+                 deterministic=False):
         import random
+        # deterministic=True switches the process-wide deterministic mode on (lib.set_deterministic) before anything is sized;
+        # False leaves the switch as it is (STY_DETERMINISTIC=1 or an earlier call may have set it)
+        if deterministic:
+            L.set_deterministic(True)
         from .discriminators import DiscriminatorLossHelper
         from .optim import FlatAdamW
         self.dp, self.se = duration_predictor.enable_training(), duration_style_encoder.enable_training()

@@ -212,6 +212,8 @@ SYMBOLS = {
     "sty_prof_enable": (C.c_int, [_I]),
     "sty_prof_only": (C.c_int, [C.c_char_p]),
     "sty_set_single_stream": (C.c_int, [_I]),
+    "sty_set_deterministic": (C.c_int, [_I]),
+    "sty_get_deterministic": (C.c_int, []),
     "sty_prof_report": (C.c_int, [_P, _I]),
 }
 
@@ -264,7 +266,20 @@ def load():
         fn.restype = res
         fn.argtypes = args
     LIB = lib
+    # STY_DETERMINISTIC=1: the deterministic mode for a whole process (read once, here), e.g. an unchanged benchmark command
+    if os.environ.get("STY_DETERMINISTIC", "0") not in ("", "0"):
+        lib.sty_set_deterministic(1)
     return lib
+
+
+def set_deterministic(on):
+    """The process-wide deterministic mode (sty_set_deterministic): fixed-order sums, training steps that repeat to the bit.
+    Each training forward latches the mode; workspaces are sized per call for the mode in force."""
+    check(load().sty_set_deterministic(1 if on else 0))
+
+
+def get_deterministic():
+    return bool(load().sty_get_deterministic())
 
 
 def check(rc):

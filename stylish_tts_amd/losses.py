@@ -15,6 +15,16 @@ class LossTarget:
         self.ws, self.shape = ws, tuple(shape)
 
 
+def _target_ws(target, need):
+    """The workspace of a LossTarget, grown when the call needs more than the target was sized for (the deterministic mode switched
+    on in between: its partial slots lie BEHIND the layout the target side filled, so the features are copied as they are)."""
+    if target.ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=target.ws.device)
+        ws[:target.ws.numel()].copy_(target.ws)
+        target.ws = ws
+    return target.ws
+
+
 def acoustic_loss_target(audio_gt):
     lib = L.load()
     gt = audio_gt.to(torch.float32).contiguous()
@@ -47,7 +57,7 @@ def acoustic_loss(audio_gt, audio_pred, w_mel=5.0, w_phase=8.0, target=None):
     L.check(lib.sty_acoustic_loss_workspace_bytes(B, N, C.byref(need)))
     if target is not None and target.shape != tuple(gt.shape):
         raise L.StyError(f"acoustic_loss: target features are for {target.shape}, audio_gt is {tuple(gt.shape)}")
-    ws = target.ws if target is not None else torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws = _target_ws(target, need.value) if target is not None else torch.empty(need.value, dtype=torch.uint8, device=dev)
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     L.check(lib.sty_acoustic_loss_fwd_bwd(B, N, None if target is not None else L.ptr(gt), L.ptr(pr), float(w_mel),
                                           float(w_phase), L.ptr(losses), L.ptr(d), L.ptr(ws), ws.numel(), st))
@@ -117,7 +127,7 @@ def acoustic_gan_loss(audio_gt, audio_pred, mrd, *, w_mel=5.0, w_phase=8.0, w_ge
     L.check(lib.sty_acoustic_gan_workspace_bytes(B, N, int(mask != 0), C.byref(need_g)))
     if target is not None and target.shape != tuple(gt.shape):
         raise L.StyError(f"acoustic_gan_loss: target features are for {target.shape}, audio_gt is {tuple(gt.shape)}")
-    ws = target.ws if target is not None else torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws = _target_ws(target, need.value) if target is not None else torch.empty(need.value, dtype=torch.uint8, device=dev)
     wsg = torch.empty(need_g.value, dtype=torch.uint8, device=dev)
     params = (L.SpecDiscPtrs * 3)(*[m._ptrs() for m in mrd])
     grads = (L.SpecDiscPtrs * 3)(*[m._ptrs(grads=True) if (mask >> i) & 1 else L.SpecDiscPtrs() for i, m in enumerate(mrd)])

@@ -54,8 +54,12 @@ class TextualTrainer:
     def __init__(self, pitch_energy_predictor, pe_style_encoder, speech_predictor, speech_style_encoder, pitch_disc,
                  lr=1e-4, betas=(0.85, 0.99), eps=1e-9, weight_decay=1e-4, w_mel=5.0, w_gen=1.0, w_pitch=8.0, w_energy=8.0,
                  mean=-4.0, std=4.0, bucket_bytes=25 << 20, train_mode=True, seed=0, dropout=0.2, compute="fp32",
-                 block_dropout=0.2):
+                 block_dropout=0.2, deterministic=False):
         import random
+        # deterministic=True switches the process-wide deterministic mode on (lib.set_deterministic) before anything is sized;
+        # False leaves the switch as it is (STY_DETERMINISTIC=1 or an earlier call may have set it)
+        if deterministic:
+            L.set_deterministic(True)
         from .discriminators import DiscriminatorLossHelper
         from .optim import FlatAdamW
         self.pep, self.pse = pitch_energy_predictor.enable_training(), pe_style_encoder.enable_training()

@@ -114,12 +114,13 @@ class TrainContext:
     """train/train_context.py:72-183 for this path: configs, dataset, models under the reference's keys, manifest,
     normalization."""
 
-    def __init__(self, config, model_config, base_out_dir, device, adversarial=True, log=_log):
+    def __init__(self, config, model_config, base_out_dir, device, adversarial=True, log=_log, deterministic=False):
         from . import data as D
         from . import dist
         from . import stage_io as IO
         self.config, self.model_config, self.base_out_dir, self.device, self.log = config, model_config, base_out_dir, device, log
         self.adversarial = adversarial
+        self.deterministic = bool(deterministic)  # handed to every stage's trainer
         self.rank, self.world = dist.init() if "WORLD_SIZE" in os.environ else (0, 1)
         mp = config.training.mixed_precision
         if mp not in ("no", "bf16"):
@@ -172,7 +173,7 @@ class TrainContext:
     def make_trainer(self, stage, lr):
         w = self.config.loss_weight
         norm = dict(mean=self.normalization.mel_log_mean, std=self.normalization.mel_log_std)
-        common = dict(lr=lr, seed=self.rank, compute=self.compute, **norm)
+        common = dict(lr=lr, seed=self.rank, compute=self.compute, deterministic=self.deterministic, **norm)
         if stage == "acoustic":
             from .acoustic import AcousticTrainer
             adv = dict(mrd=[self.model(f"mrd{i}") for i in range(3)], disc=self.model("disc"),
@@ -199,13 +200,16 @@ class TrainContext:
 
 
 def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage=False, config_path="", model_config_path="",
-                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False):
-    """train/train.py:76-338.  `max_steps`: stop after that many optimizer steps IN TOTAL (tests; None = the plan's epochs).
+                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False, deterministic=False):
+    """train/train.py:76-338.  `deterministic`: the library's deterministic mode for the run (fixed-order sums: two runs from one
+    seed give the same bits on one rank; the order of the gradient exchange between ranks is the backend's).  `max_steps`: stop after that many optimizer steps IN TOTAL (tests; None = the plan's epochs).
     `validate_only`: load `checkpoint`, run ONE validation pass of `stage` (log line, samples, eval/validation.jsonl; the record
     is left under `.validation`) and return without a training step or a save.
     Returns the context (models, manifest, the last stage's trainer under `.stage`)."""
     from . import data as D
     from . import stage_io as IO
+    if deterministic:  # first of all: nothing is sized, loaded or normalised in the other mode
+        L.set_deterministic(True)
     random.seed(1)  # train/train.py:87-88
     check_supported(model_config)
     if stage not in NEXT_STAGE:
@@ -216,7 +220,7 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
         raise L.StyError("no HIP device: there is no CPU training path in this package")
     device = torch.device(device or f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}")
     torch.cuda.set_device(device)
-    ctx = TrainContext(config, model_config, out_dir, device, adversarial=adversarial, log=log)
+    ctx = TrainContext(config, model_config, out_dir, device, adversarial=adversarial, log=log, deterministic=deterministic)
 
     def enter(name):
         st = _Stage(name, ctx)
@@ -387,6 +391,8 @@ def main(argv=None):
     ap.add_argument("--reset-stage", dest="reset_stage", action="store_true")
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--convert", action="store_true", help="export the inference graph of --checkpoint instead of training")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="fixed-order sums: a seed reproduces the run to the bit (STY_DETERMINISTIC=1 does the same)")
     ap.add_argument("--validate-only", dest="validate_only", action="store_true",
                     help="one validation pass of --stage on --checkpoint: the log line, the samples and the JSON line; no training")
     a = ap.parse_args(argv)
@@ -394,7 +400,7 @@ def main(argv=None):
         convert(a.config_path, a.model_config_path, a.out, a.checkpoint)
         return
     train(a.config_path, a.model_config_path, a.out, a.stage, a.checkpoint, a.reset_stage, max_steps=a.max_steps,
-          validate_only=a.validate_only)
+          validate_only=a.validate_only, deterministic=a.deterministic)
 
 
 if __name__ == "__main__":

@@ -47,14 +47,16 @@ def _dataset(lines, config, model_config):
 
 
 def train_align_model(config, model_config, out_dir, checkpoint="", reset_stage=False, config_path="", model_config_path="",
-                      max_steps=None, device=None, log=_log):
-    """train_model (train/train.py:76-338) for the alignment stage.  `max_steps`: stop after that many optimizer steps of the
+                      max_steps=None, device=None, log=_log, deterministic=False):
+    """train_model (train/train.py:76-338) for the alignment stage.  `deterministic`: the library's deterministic mode.  `max_steps`: stop after that many optimizer steps of the
     training split (tests; None = the plan's epochs).  Returns the context (.trainer, .manifest, .aligner)."""
     from safetensors.torch import save_file
     from . import data as D
     from . import stage_io as IO
     from .align import ALIGNER_MEL
     from .alignment import AlignmentTrainer, TrainableTextAligner
+    if deterministic:  # first of all: nothing is sized, loaded or normalised in the other mode
+        L.set_deterministic(True)
     random.seed(1)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise L.StyError("train-align runs in one process: the label priors' all-gather over ranks is not built")
@@ -108,7 +110,7 @@ def train_align_model(config, model_config, out_dir, checkpoint="", reset_stage=
         ctx.aligner, lr=lr, w_align=float(config.loss_weight.get("align_loss", 1.0)), mean=ctx.normalization.mel_log_mean,
         std=ctx.normalization.mel_log_std, dropout=float(ta.get("dropout", 0.1)), seed=0,
         hop_length=model_config.hop_length * model_config.coarse_multiplier, n_fft=int(ta.get("n_fft", ALIGNER_MEL["n_fft"])),
-        win_length=int(ta.get("win_length", ALIGNER_MEL["win_length"])), log=log)
+        win_length=int(ta.get("win_length", ALIGNER_MEL["win_length"])), log=log, deterministic=deterministic)
     fast_forward = 0
     if checkpoint:
         st = tr.checkpoint_state()
@@ -223,8 +225,11 @@ def main(argv=None):
     ap.add_argument("--checkpoint", default="")
     ap.add_argument("--reset-stage", dest="reset_stage", action="store_true")
     ap.add_argument("--max-steps", type=int, default=None)
+    ap.add_argument("--deterministic", action="store_true",
+                    help="fixed-order sums: a seed reproduces the run to the bit (STY_DETERMINISTIC=1 does the same)")
     a = ap.parse_args(argv)
-    train_align(a.config_path, a.model_config_path, a.out, a.checkpoint, a.reset_stage, max_steps=a.max_steps)
+    train_align(a.config_path, a.model_config_path, a.out, a.checkpoint, a.reset_stage, max_steps=a.max_steps,
+                deterministic=a.deterministic)
 
 
 if __name__ == "__main__":
