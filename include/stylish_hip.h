@@ -44,6 +44,7 @@ const char *sty_last_error(void);
  *       "text_aligner"       = train/models/text_aligner.py:33-45 (inference only, see sty_aligner_fwd)
  *       "text_aligner_train" = the same module with a training graph (see sty_aligner_fwd_train)
  *       "rmvpe"              = train/dataprep/rmvpe/model.py:49-86 E2E0 (inference only, see sty_rmvpe_fwd)
+ *       "wavlm"              = transformers WavLMModel in eval mode (forward only, see sty_wavlm_fwd)
  * Dimensions are taken from the bound tensors' shapes (train/config/model.yml defaults are checked).   */
 int sty_model_create(const char *kind, sty_model **out);
 void sty_model_destroy(sty_model *m);
@@ -516,6 +517,39 @@ int sty_pitch_loss_fwd(int B, int T, const float *target, const float *pred, flo
 int sty_duration_loss_fwd(int B, int L, int NC, const float *pred, const int64_t *text_lengths, const float *target_dur,
                           const int64_t *target_class, const float *class_table, const float *ce_weight, float *losses,
                           void *workspace, size_t ws_bytes, void *stream);
+
+/* ---- slm loss value (WavLMLoss, train/losses.py:376-394; csrc/wavlm.hip; stylish_tts_amd/slm.py) -----------------------
+ * Model kind "wavlm" = transformers' WavLMModel in eval mode (no dropout, SpecAugment or LayerDrop), bound by the keys of
+ * WavLMModel.state_dict() without masked_spec_embed: feature_extractor.conv_layers.I.conv.weight, ...0.layer_norm.*,
+ * feature_projection.{layer_norm, projection}.*, encoder.pos_conv_embed.conv.{bias, parametrizations.weight.original0/1},
+ * encoder.layer_norm.*, encoder.layers.L.{attention.{q,k,v,out}_proj, attention.gru_rel_pos_linear, layer_norm,
+ * feed_forward.{intermediate_dense, output_dense}, final_layer_norm}.*, ...attention.gru_rel_pos_const and
+ * encoder.layers.0.attention.rel_attn_embed.weight.  Widths, depths, heads, kernels, groups and num_buckets are read from
+ * the bound shapes; what no shape shows (the conv strides, max_bucket_distance, layer_norm_eps) comes from
+ * sty_wavlm_set_config, called before sty_model_finalize.  Built: feat_extract_norm "group", do_stable_layer_norm false,
+ * conv_bias false, exact GELU.  Forward only, fp32 operands on the fp32 matrix cores: compute_bf16,
+ * sty_model_enable_training and sty_model_bind_grad return STY_EINVAL for this kind.
+ * Resampler: torchaudio.transforms.Resample(orig, new) with its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff
+ * 0.99) restated from the documented closed form -- torchaudio is no dependency: PARITY UNPINNED at this boundary.  The rates are
+ * reduced by their gcd (24000 -> 16000 is 3 -> 2: two phases of 23 taps at stride 3); sty_slm_resample_len = ceil(N new /
+ * orig).  sty_slm_resample_kernel_host: the table [new][2 width + orig], width = ceil(6 orig / (0.99 min(orig, new))) in
+ * reduced rates, HOST memory, evaluated in double and rounded once; returns the number of floats (out may be NULL).
+ * sty_wavlm_frames: frames T of N16 samples, floor((n - k) / s) + 1 per conv layer; no frame left: STY_ESHAPE.
+ * sty_wavlm_fwd: audio16 [B,N16] -> hidden [layers + 1, B, T, hidden_size]: [0] = the encoder's input after the positional
+ * conv and LayerNorm, [i] = the output of layer i (the tuple output_hidden_states=True returns).
+ * sty_wavlm_rel_buckets_host: _relative_positions_bucket of the distances -(T - 1) .. T - 1 (HOST memory).
+ * sty_slm_loss_fwd: loss[0] = mean |a - b| over n floats, float64 partials added in index order (two calls, equal bits). */
+int sty_wavlm_set_config(sty_model *m, int n_conv, const int *conv_stride, int max_bucket_distance, float layer_norm_eps);
+int sty_slm_resample_len(int N, int orig, int new_rate);
+int sty_slm_resample_kernel_host(int orig, int new_rate, float *out);
+int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float *audio, float *out, void *stream);
+int sty_wavlm_frames(const sty_model *m, int N16, int *T);
+int sty_wavlm_workspace_bytes(const sty_model *m, int B, int N16, size_t *bytes);
+int sty_wavlm_fwd(sty_model *m, int B, int N16, const float *audio16, float *hidden, void *workspace, size_t ws_bytes,
+                  void *stream);
+int sty_wavlm_rel_buckets_host(int T, int num_buckets, int max_distance, int32_t *out);
+int sty_slm_loss_workspace_bytes(size_t n, size_t *bytes);
+int sty_slm_loss_fwd(size_t n, const float *a, const float *b, float *loss, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---- adversarial terms of the acoustic stage: spectrogram discriminators ---------------
  * SpecDiscriminator (train/models/discriminator.py:13-68): five weight-normed Conv2d 3x9 / 3x3 with LeakyReLU(0.1),

@@ -313,6 +313,8 @@ class AcousticTrainer:
         self.audio = audio
         return losses
 
+    slm = None  # a slm.WavLMLoss on the trainer's device (train(..., slm_path=...)): validate then also returns the slm value
+
     @torch.no_grad()
     def validate(self, *, audio_gt, texts, text_lengths, pitch, durations, noise=None, seed=0, prior_override=None, **_):
         """validate_acoustic (stage_type.py:376-390): the eval-mode forward (acoustic_forward without the multi-spectrogram:
@@ -327,7 +329,13 @@ class AcousticTrainer:
                                     prior_override=prior_override)
         audio = step.pred.audio
         loss, items = mel_loss(audio_gt, audio.squeeze(1), per_item=True)
-        return {"mel": loss[0]}, {"audio": audio, "per_item": items}
+        extra = {"audio": audio, "per_item": items}
+        if self.slm is not None:
+            # `train --slm`: the batch's slm value beside the log, never in it (validation.py).  A host-side refusal of the slm
+            # path (no frame left, a shape) comes back as a value: it must not cost the batch its numbers
+            from .validation import or_refusal
+            extra["slm"] = or_refusal(lambda: self.slm(audio_gt, audio))
+        return {"mel": loss[0]}, extra
 
     @staticmethod
     def _rank_mean(t):

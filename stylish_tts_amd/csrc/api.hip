@@ -6,9 +6,12 @@
 #include <stdlib.h>
 #include <cxxabi.h>
 
+#include <algorithm>
 #include <functional>
 #include <map>
+#include <mutex>
 #include <string>
+#include <tuple>
 
 #include "model.h"
 
@@ -680,6 +683,115 @@ struct Builder {
     if (ok && (p.head.Cin != 512 || p.head.Cout != RMVPE_CLASSES || p.head.K != 1)) rm_fail("fc.1.weight");
   }
 
+  // ---- WavLM (transformers' WavLMModel): widths, depths, heads, kernels, groups and num_buckets from the bound shapes; the
+  //      strides, max_bucket_distance and layer_norm_eps from sty_wavlm_set_config ----
+  void wavlm() {
+    WavlmPlan& p = m->wav;
+    if (!dry) p.packs.clear();
+    p.layers.clear();
+    p.pos.clear();
+    if (p.n_conv < 2) {
+      if (ok) m->missing = "the conv strides (sty_wavlm_set_config was not called)";
+      ok = false;
+      return;
+    }
+    const std::string fe = "feature_extractor.conv_layers.";
+    int cin = 1;
+    for (int i = 0; i < p.n_conv; ++i) {
+      const std::string key = fe + std::to_string(i) + ".conv.weight";
+      const Param* w = get(key);
+      if (!w) return;
+      if (w->shape.size() != 3 || w->shape[1] != cin || w->shape[2] < 1) return rm_fail(key);
+      const int C = (int)w->shape[0], k = (int)w->shape[2], s = p.stride[i];
+      p.dim[i] = C, p.kern[i] = k;
+      if (i == 0) {
+        p.conv0_w = w->p;
+        p.gn_w = ptr(fe + "0.layer_norm.weight", {C});
+        p.gn_b = ptr(fe + "0.layer_norm.bias", {C});
+      } else {
+        PackedConv pc;
+        pc.Cin = s * cin, pc.Cout = C, pc.K = cdiv(k, s);
+        pc.CinP = (int)align_up(pc.Cin, CI_CHUNK), pc.CoutP = (int)align_up(C, 32);
+        WavlmPackJob j;
+        j.w = w->p;
+        j.wp = m->ab.take<float>((size_t)pc.K * pc.CinP * pc.CoutP);
+        j.Cout = C, j.Cin = cin, j.K = k, j.s = s, j.CinP = pc.CinP, j.CoutP = pc.CoutP;
+        pc.wp = j.wp;
+        p.conv[i] = pc;
+        if (!dry && ok) p.packs.push_back(j);
+      }
+      cin = C;
+    }
+    p.fp_ln_w = ptr("feature_projection.layer_norm.weight", {cin});
+    p.fp_ln_b = ptr("feature_projection.layer_norm.bias", {cin});
+    p.proj = conv("feature_projection.projection");
+    if (!ok) return;
+    if (p.proj.Cin != cin || p.proj.K != 1) return rm_fail("feature_projection.projection.weight");
+    const int H = p.hidden = p.proj.Cout;
+    {
+      const std::string pc_ = "encoder.pos_conv_embed.conv.";
+      const Param* v = get(pc_ + "parametrizations.weight.original1");
+      if (!v) return;
+      if (v->shape.size() != 3 || v->shape[0] != H || v->shape[1] < 1 || H % v->shape[1]) return rm_fail(pc_ + "parametrizations.weight.original1");
+      const int Cg = (int)v->shape[1], K = (int)v->shape[2];
+      p.pos_k = K, p.pos_groups = H / Cg, p.pos_v = v->p;
+      if (K - 1 > 128) return rm_fail(pc_ + "parametrizations.weight.original1 (more than 129 taps)");
+      const float* g = ptr(pc_ + "parametrizations.weight.original0", {1, 1, K});
+      const float* bias = ptr(pc_ + "bias", {H});
+      p.pos_nrm = m->ab.take<float>(K);
+      for (int gi = 0; gi < p.pos_groups; ++gi) {
+        PackedConv pc;
+        pc.Cin = pc.Cout = Cg, pc.K = K;
+        pc.CinP = (int)align_up(Cg, CI_CHUNK), pc.CoutP = (int)align_up(Cg, 32);
+        WavlmPackJob j;
+        j.w = v->p, j.g = g, j.nrm = p.pos_nrm, j.bias = bias;
+        j.wp = m->ab.take<float>((size_t)K * pc.CinP * pc.CoutP);
+        j.bp = m->ab.take<float>(pc.CoutP);
+        j.Cout = Cg, j.Cin = Cg, j.K = K, j.s = 1, j.CinP = pc.CinP, j.CoutP = pc.CoutP, j.co0 = gi * Cg;
+        pc.wp = j.wp, pc.bias = j.bp;
+        p.pos.push_back(pc);
+        if (!dry && ok) p.packs.push_back(j);
+      }
+    }
+    p.enc_ln_w = ptr("encoder.layer_norm.weight", {H});
+    p.enc_ln_b = ptr("encoder.layer_norm.bias", {H});
+    const Param* emb = get("encoder.layers.0.attention.rel_attn_embed.weight");
+    if (!emb) return;
+    if (emb->shape.size() != 2 || emb->shape[0] < 4 || emb->shape[1] < 1 || H % emb->shape[1]) return rm_fail("encoder.layers.0.attention.rel_attn_embed.weight");
+    p.num_buckets = (int)emb->shape[0], p.heads = (int)emb->shape[1], p.rel_embed = emb->p;
+    if (p.max_distance <= p.num_buckets / 4) {  // (the bucket function divides by log(max_distance / (num_buckets / 4)))
+      if (ok) m->missing = "max_bucket_distance " + std::to_string(p.max_distance) + " must exceed num_buckets / 4 = " + std::to_string(p.num_buckets / 4) + " (shape mismatch)";
+      ok = false;
+      return;
+    }
+    const int DH = H / p.heads;
+    for (int l = 0; has("encoder.layers." + std::to_string(l) + ".attention.q_proj.weight"); ++l) {
+      const std::string pl = "encoder.layers." + std::to_string(l) + ".";
+      WavlmLayer y;
+      y.q = conv(pl + "attention.q_proj");
+      y.k = conv(pl + "attention.k_proj");
+      y.v = conv(pl + "attention.v_proj");
+      y.o = conv(pl + "attention.out_proj");
+      y.gate_w = ptr(pl + "attention.gru_rel_pos_linear.weight", {8, DH});
+      y.gate_b = ptr(pl + "attention.gru_rel_pos_linear.bias", {8});
+      y.gate_c = ptr(pl + "attention.gru_rel_pos_const", {1, p.heads, 1, 1});
+      y.ln1_w = ptr(pl + "layer_norm.weight", {H});
+      y.ln1_b = ptr(pl + "layer_norm.bias", {H});
+      y.f1 = conv(pl + "feed_forward.intermediate_dense");
+      y.f2 = conv(pl + "feed_forward.output_dense");
+      y.ln2_w = ptr(pl + "final_layer_norm.weight", {H});
+      y.ln2_b = ptr(pl + "final_layer_norm.bias", {H});
+      if (ok && (y.q.Cin != H || y.q.Cout != H || y.k.Cout != H || y.v.Cout != H || y.o.Cout != H || y.f1.Cin != H || y.f2.Cout != H ||
+                 y.f2.Cin != y.f1.Cout))
+        return rm_fail(pl + "attention.q_proj.weight");
+      p.layers.push_back(y);
+    }
+    if (ok && p.layers.empty()) {
+      m->missing = "encoder.layers.0.attention.q_proj.weight";
+      ok = false;
+    }
+  }
+
   void build() {
     m->gb_floats_per_batch = 0;
     if (m->kind == "speech_predictor") {
@@ -702,6 +814,8 @@ struct Builder {
       text_aligner();
     } else if (m->kind == "rmvpe") {
       rmvpe();
+    } else if (m->kind == "wavlm") {
+      wavlm();
     }
   }
 };
@@ -1639,6 +1753,140 @@ static void rmvpe_forward(Run& r, int n, const float* logmel, float* sal) {
   if (r.live()) r.chk(launch_rmvpe_salience(logits, B, Tp, n, sal, r.st));
 }
 
+// frames after conv layer i of N16 samples: floor((n - k) / s) + 1; 0 when a layer is left without a frame
+static int wavlm_frames_at(const WavlmPlan& p, int N16, int layer) {
+  long long n = N16;
+  for (int i = 0; i <= layer; ++i) {
+    if (n < p.kern[i]) return 0;
+    n = (n - p.kern[i]) / p.stride[i] + 1;
+  }
+  return (int)n;
+}
+// WavLMModel.forward(output_hidden_states=True) in eval mode (modeling_wavlm.py): audio16 [B][N16] -> hidden [layers + 1][B][T][H].
+// Every activation is channel-major [B][C][T]; wavlm.hip says what each of its kernels does.
+static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden) {
+  sty_model* m = r.m;
+  const WavlmPlan& p = m->wav;
+  const int B = r.B, nc = p.n_conv, H = p.hidden, NH = p.heads, DH = H / NH;
+  int Tl[WAVLM_MAX_CONV], Tp[WAVLM_MAX_CONV] = {0};
+  size_t max_out = 0, max_stage = 0;
+  for (int i = 0; i < nc; ++i) {
+    Tl[i] = wavlm_frames_at(p, N16, i);
+    max_out = std::max(max_out, (size_t)B * p.dim[i] * Tl[i]);
+    if (i) {
+      Tp[i] = Tl[i] + p.conv[i].K - 1;  // columns of the staged view the conv reads
+      max_stage = std::max(max_stage, (size_t)B * p.conv[i].Cin * Tp[i]);
+    }
+  }
+  const int T = Tl[nc - 1], Cl = p.dim[nc - 1];
+  max_stage = std::max(max_stage, (size_t)B * Cl * T);
+  const size_t n = (size_t)B * H * T;
+  float* x = r.ws.take<float>(n);
+  {  // ---- feature encoder and projection ----
+    Run::Scope sc(r);
+    float* out = r.ws.take<float>(max_out);
+    float* stg = r.ws.take<float>(max_stage);
+    const int nt = wavlm_conv0_ntiles(Tl[0]);
+    double* part = r.ws.take<double>((size_t)B * p.dim[0] * nt * 2);
+    float* ga = r.ws.take<float>((size_t)B * p.dim[0]);
+    float* gs = r.ws.take<float>((size_t)B * p.dim[0]);
+    if (r.live()) {
+      r.chk(launch_wavlm_conv0(audio, p.conv0_w, B, N16, p.dim[0], p.kern[0], p.stride[0], Tl[0], out, part, r.st));
+      r.chk(launch_wavlm_gn_finalize(part, nt, p.gn_w, p.gn_b, B * p.dim[0], p.dim[0], Tl[0], 1e-5f, ga, gs, r.st));
+    }
+    for (int i = 1; i < nc && r.live(); ++i) {
+      r.chk(launch_wavlm_stage(out, i == 1 ? ga : nullptr, gs, B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], stg, r.st));
+      ConvArgs a = r.base(p.conv[i], stg, Tl[i], out);
+      a.pad = 0;
+      a.Tin = Tp[i] != Tl[i] ? Tp[i] : 0;
+      a.act = ACT_GELU;
+      r.conv(a);
+    }
+    if (r.live()) {
+      r.chk(launch_chan_layernorm(out, stg, B, Cl, T, p.ln_eps, 0, p.fp_ln_w, p.fp_ln_b, nullptr, 0, nullptr, r.st));
+      r.conv(r.base(p.proj, stg, T, x));
+    }
+  }
+  // ---- encoder ----
+  const int G = p.pos_groups, Cg = H / G, FF = p.layers[0].f1.Cout;
+  float* xa = r.ws.take<float>(n);
+  float* xb = r.ws.take<float>(n);
+  float* q = r.ws.take<float>(n);
+  float* k = r.ws.take<float>(n);
+  float* v = r.ws.take<float>(n);
+  float* o = r.ws.take<float>(n);
+  float* big = r.ws.take<float>((size_t)B * FF * T);
+  float* gate = r.ws.take<float>((size_t)B * NH * T);
+  float* tab = r.ws.take<float>((size_t)NH * (2 * T - 1));
+  r.note_peak();
+  if (!r.live()) return;
+  {  // x + GELU(pos_conv(x)) in the group-major layout (q, k as scratch), then the LayerNorm
+    r.chk(launch_wavlm_group_perm(x, B, G, Cg, T, 1, q, r.st));
+    for (int g = 0; g < G && r.live(); ++g) {
+      const size_t off = (size_t)g * B * Cg * T;
+      ConvArgs a = r.base(p.pos[g], q + off, T, k + off);
+      a.pad = p.pos_k / 2;
+      a.act = ACT_GELU;
+      a.residual = q + off;
+      r.conv(a);
+    }
+    if (!r.live()) return;
+    r.chk(launch_wavlm_group_perm(k, B, G, Cg, T, 0, xa, r.st));
+    r.chk(launch_chan_layernorm(xa, x, B, H, T, p.ln_eps, 0, p.enc_ln_w, p.enc_ln_b, nullptr, 0, nullptr, r.st));
+    r.chk(launch_wavlm_transpose_out(x, B, H, T, hidden, r.st));
+  }
+  {  // the position bias table of this frame count, shared by every layer.  The bucket table is one per model: sized for the
+     // largest frame count seen (at least 2 048 frames, 41 s), so a validation split of many lengths allocates once
+    if (T > m->wav_bucket_T) {
+      const int Tm = std::max(T, 2048);
+      std::vector<int32_t> host(2 * Tm - 1);
+      wavlm_rel_buckets(Tm, p.num_buckets, p.max_distance, host.data());
+      int32_t* dev = nullptr;
+      if (hipMalloc((void**)&dev, host.size() * sizeof(int32_t)) != hipSuccess ||
+          hipMemcpy(dev, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {  // (pageable: complete on return)
+        if (dev) (void)hipFree(dev);
+        set_error("wavlm: the bucket table of %d frames could not be placed on the device", Tm);
+        r.rc = STY_EHIP;
+        return;
+      }
+      if (m->wav_bucket_dev) (void)hipFree(m->wav_bucket_dev);  // (hipFree waits for the launches that still read it)
+      m->wav_bucket_dev = dev;
+      m->wav_bucket_T = Tm;
+    }
+    r.chk(launch_wavlm_rel_table(p.rel_embed, m->wav_bucket_dev + (m->wav_bucket_T - T), NH, T, tab, r.st));
+  }
+  for (size_t l = 0; l < p.layers.size() && r.live(); ++l) {
+    const WavlmLayer& y = p.layers[l];
+    r.chk(launch_wavlm_gate(x, y.gate_w, y.gate_b, y.gate_c, B, NH, DH, T, gate, r.st));
+    r.conv(r.base(y.q, x, T, q));
+    r.conv(r.base(y.k, x, T, k));
+    r.conv(r.base(y.v, x, T, v));
+    if (!r.live()) return;
+    AttnArgs at;
+    at.q = q, at.k = k, at.v = v, at.o = o;
+    at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * T;
+    at.T = T, at.H = NH;
+    at.scale = 1.0f / sqrtf((float)DH);
+    at.lengths = nullptr;
+    at.rel_tab = tab, at.rel_gate = gate;
+    r.chk(launch_attention(at, B, DH, r.st));
+    ConvArgs ao = r.base(y.o, o, T, xa);
+    ao.residual = x;
+    r.conv(ao);
+    if (!r.live()) return;
+    r.chk(launch_chan_layernorm(xa, xb, B, H, T, p.ln_eps, 0, y.ln1_w, y.ln1_b, nullptr, 0, nullptr, r.st));
+    ConvArgs f1 = r.base(y.f1, xb, T, big);
+    f1.act = ACT_GELU;
+    r.conv(f1);
+    ConvArgs f2 = r.base(y.f2, big, T, xa);
+    f2.residual = xb;
+    r.conv(f2);
+    if (!r.live()) return;
+    r.chk(launch_chan_layernorm(xa, x, B, H, T, p.ln_eps, 0, y.ln2_w, y.ln2_b, nullptr, 0, nullptr, r.st));
+    r.chk(launch_wavlm_transpose_out(x, B, H, T, hidden + (l + 1) * n, r.st));
+  }
+}
+
 static int run_style_fc(Run& r, const float* style) {
   sty_model* m = r.m;
   r.gb = r.ws.take<float>(m->gb_floats_per_batch * r.B);
@@ -1712,7 +1960,7 @@ int sty_model_create(const char* kind, sty_model** out) {
   }
   std::string k(kind);
   if (k != "speech_predictor" && k != "vocoder" && k != "mel_style_encoder" && k != "duration_predictor" &&
-      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner" && k != "text_aligner_train" && k != "rmvpe") {
+      k != "pitch_energy_predictor" && k != "pitch_style_encoder" && k != "text_aligner" && k != "text_aligner_train" && k != "rmvpe" && k != "wavlm") {
     set_error("unknown model kind '%s'", kind);
     return STY_EINVAL;
   }
@@ -1732,6 +1980,7 @@ void sty_model_destroy(sty_model* m) {
   if (m->stft_default) (void)hipFree(m->stft_default);
   if (m->garena) (void)hipFree(m->garena);
   if (m->fcs_bwd_dev) (void)hipFree(m->fcs_bwd_dev);
+  if (m->wav_bucket_dev) (void)hipFree(m->wav_bucket_dev);
   m->wt.free();
   if (m->trainer) trainer_destroy(m->trainer);
   delete m;
@@ -1769,6 +2018,9 @@ int sty_model_finalize(sty_model* m) {
   }
   m->requested.clear();
   m->jobs.clear();
+  if (m->wav_bucket_dev) (void)hipFree(m->wav_bucket_dev);  // (it depends on num_buckets and max_bucket_distance)
+  m->wav_bucket_dev = nullptr;
+  m->wav_bucket_T = 0;
   m->wt.free();
   m->fcs.clear();
   m->missing.clear();
@@ -1823,7 +2075,8 @@ int sty_model_finalize(sty_model* m) {
 
 // the text aligner is an inference-only kind (alignment decisions are arg-max decisions: fp32 operands, no training graph)
 static int refuse_aligner(const sty_model* m, const char* what) {
-  if (m->kind != "text_aligner" && m->kind != "rmvpe") return STY_OK;  // (rmvpe: pitch values hang on an arg-max too)
+  // (rmvpe: pitch values hang on an arg-max too; wavlm: a frozen network whose forward alone is built)
+  if (m->kind != "text_aligner" && m->kind != "rmvpe" && m->kind != "wavlm") return STY_OK;
   set_error("%s: model kind '%s' is inference-only and runs fp32 operands", what, m->kind.c_str());
   return STY_EINVAL;
 }
@@ -2299,6 +2552,140 @@ int sty_rmvpe_decode(int B, int n, const float* salience, float thred, float* f0
     return STY_EINVAL;
   }
   return launch_rmvpe_decode(salience, B * n, thred, f0, S(stream));
+}
+// ---- slm loss value: resampler, WavLM forward, mean |a - b| (train/losses.py:376-394; wavlm.hip) ----
+static int gcd_(int a, int b) { return b ? gcd_(b, a % b) : a; }
+static bool resample_rates_ok(int orig, int nw) { return orig > 0 && nw > 0 && orig / gcd_(orig, nw) <= 1024 && nw / gcd_(orig, nw) <= 1024; }
+int sty_wavlm_set_config(sty_model* m, int n_conv, const int* conv_stride, int max_bucket_distance, float layer_norm_eps) {
+  if (!m || m->kind != "wavlm" || !conv_stride || n_conv < 2 || n_conv > WAVLM_MAX_CONV || max_bucket_distance < 2 || !(layer_norm_eps > 0.f)) {
+    set_error("sty_wavlm_set_config: bad argument (kind 'wavlm', 2 to %d conv layers)", WAVLM_MAX_CONV);
+    return STY_EINVAL;
+  }
+  for (int i = 0; i < n_conv; ++i)
+    if (conv_stride[i] < 1 || conv_stride[i] > 16) {
+      set_error("sty_wavlm_set_config: conv stride %d of layer %d (1 to 16 are built)", conv_stride[i], i);
+      return STY_EINVAL;
+    }
+  WavlmPlan& p = m->wav;
+  p.n_conv = n_conv;
+  for (int i = 0; i < n_conv; ++i) p.stride[i] = conv_stride[i];
+  p.max_distance = max_bucket_distance;
+  p.ln_eps = layer_norm_eps;
+  m->finalized = false;
+  return STY_OK;
+}
+int sty_slm_resample_len(int N, int orig, int new_rate) {
+  if (N <= 0 || !resample_rates_ok(orig, new_rate)) return -1;
+  const int g = gcd_(orig, new_rate);
+  return (int)(((long long)N * (new_rate / g) + orig / g - 1) / (orig / g));
+}
+int sty_slm_resample_kernel_host(int orig, int new_rate, float* out) {
+  if (!resample_rates_ok(orig, new_rate)) return -1;
+  const int g = gcd_(orig, new_rate), o = orig / g, n = new_rate / g;
+  if (out) build_resample_kernel(o, n, 6.0, out);
+  return n * (2 * resample_width(o, n, 6.0) + o);
+}
+int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float* audio, float* out, void* stream) {
+  if (!audio || !out || B <= 0 || N <= 0 || !resample_rates_ok(orig, new_rate)) {
+    set_error("sty_slm_resample_fwd: bad argument");
+    return STY_EINVAL;
+  }
+  const int g = gcd_(orig, new_rate), o = orig / g, n = new_rate / g, width = resample_width(o, n, 6.0);
+  const size_t floats = (size_t)n * (2 * width + o);
+  if (floats * sizeof(float) > 48 * 1024) {
+    set_error("sty_slm_resample_fwd: %d -> %d needs a table of %zu taps (more than the kernel keeps)", orig, new_rate, floats);
+    return STY_EINVAL;
+  }
+  // device tables by (device, reduced rate pair), built on first use under a lock; a table is cached only once it is filled
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int>, float*> tables;
+  int device = 0;
+  STY_HIP(hipGetDevice(&device));
+  float* dev = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    float*& slot = tables[std::make_tuple(device, o, n)];
+    if (!slot) {
+      std::vector<float> host(floats);
+      build_resample_kernel(o, n, 6.0, host.data());
+      float* fresh = nullptr;
+      STY_HIP(hipMalloc((void**)&fresh, floats * sizeof(float)));
+      const hipError_t e = hipMemcpy(fresh, host.data(), floats * sizeof(float), hipMemcpyHostToDevice);  // (pageable: complete on return)
+      if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        return hip_fail(e, "hipMemcpy of the resample table");
+      }
+      slot = fresh;
+    }
+    dev = slot;
+  }
+  return launch_resample_fir(audio, dev, B, N, sty_slm_resample_len(N, orig, new_rate), o, n, width, out, S(stream));
+}
+int sty_wavlm_frames(const sty_model* m, int N16, int* T) {
+  int rc = model_ready(m, "wavlm");
+  if (rc) return rc;
+  if (!T || N16 <= 0) {
+    set_error("sty_wavlm_frames: bad argument");
+    return STY_EINVAL;
+  }
+  *T = wavlm_frames_at(m->wav, N16, m->wav.n_conv - 1);
+  if (*T < 1) {
+    set_error("wavlm: %d samples leave no frame behind the feature encoder", N16);
+    return STY_ESHAPE;
+  }
+  return STY_OK;
+}
+static int wavlm_run(sty_model* m, int B, int N16, const float* audio, float* hidden, void* ws, size_t ws_bytes, void* stream,
+                     size_t* need) {
+  Run r(m, B, ws, ws_bytes, stream);
+  wavlm_forward(r, N16, audio, hidden);
+  return r.finish(need, ws, ws_bytes);
+}
+int sty_wavlm_workspace_bytes(const sty_model* m, int B, int N16, size_t* bytes) {
+  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
+  if (rc) return rc;
+  if (!bytes || B <= 0) {
+    set_error("sty_wavlm_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  return wavlm_run(const_cast<sty_model*>(m), B, N16, nullptr, nullptr, nullptr, 0, nullptr, bytes);
+}
+int sty_wavlm_fwd(sty_model* m, int B, int N16, const float* audio16, float* hidden, void* workspace, size_t ws_bytes, void* stream) {
+  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
+  if (rc) return rc;
+  if (!audio16 || !hidden || !workspace || B <= 0) {
+    set_error("sty_wavlm_fwd: bad argument");
+    return STY_EINVAL;
+  }
+  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  return wavlm_run(m, B, N16, audio16, hidden, workspace, ws_bytes, stream, nullptr);
+}
+int sty_wavlm_rel_buckets_host(int T, int num_buckets, int max_distance, int32_t* out) {
+  if (T < 1 || num_buckets < 4 || max_distance < 2 || !out || max_distance <= num_buckets / 4) {
+    set_error("sty_wavlm_rel_buckets_host: bad argument");
+    return STY_EINVAL;
+  }
+  wavlm_rel_buckets(T, num_buckets, max_distance, out);
+  return STY_OK;
+}
+int sty_slm_loss_workspace_bytes(size_t n, size_t* bytes) {
+  if (!bytes || n == 0) {
+    set_error("sty_slm_loss_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  *bytes = (size_t)slm_loss_groups(n) * sizeof(double);
+  return STY_OK;
+}
+int sty_slm_loss_fwd(size_t n, const float* a, const float* b, float* loss, void* workspace, size_t ws_bytes, void* stream) {
+  if (!a || !b || !loss || !workspace || n == 0 || ((uintptr_t)workspace & 7)) {
+    set_error("sty_slm_loss_fwd: bad argument");
+    return STY_EINVAL;
+  }
+  if (ws_bytes < (size_t)slm_loss_groups(n) * sizeof(double)) {
+    set_error("sty_slm_loss_fwd: workspace too small");
+    return STY_ENOMEM;
+  }
+  return launch_slm_loss(n, a, b, loss, (double*)workspace, S(stream));
 }
 // ---- text aligner in the training graph (train_alignment, stage_type.py:268-341): forward, then sty_aligner_bwd ----
 int sty_aligner_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {

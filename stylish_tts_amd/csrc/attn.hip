@@ -1,6 +1,8 @@
 // Fused softmax attention on channel-major tensors with the fp32 matrix cores.
 //   vocoder conformer: 8 heads x 64, no mask, no positional encoding (conformer.py:111-144)
 //   text encoder:      8 heads x 16, additive -1e4 mask, partial RoPE on 8 dims (text_encoder.py:234-280)
+//   WavLM (slm loss):  12 heads x 64, additive bias gate[b][h][i] * table[h][j - i] indexed in the kernel (REL): the
+//                      [B H, T, T] tensor the class materialises is never written
 // q/k/v/o are [B, H*DH, T] (what the 1x1-conv projections produce and consume), so
 //   S^T[j][i] = sum_d K[d][j] Q[d][i]   A = K tile (LDS), B = Q fragment (registers, lanes along queries)
 //   O^T[d][i] = sum_j V[d][j] P^T[j][i] A = V tile (LDS, lanes along d), B = P^T straight from the S^T accumulator
@@ -11,7 +13,7 @@
 namespace sty {
 
 
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool REL = false>
 __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   constexpr int DP = DH < 32 ? 32 : DH;  // V rows padded to a multiple of 32
   constexpr int LS = 33;
@@ -38,6 +40,13 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
   float m_run = -3.0e38f, l_run = 0.f;
   const bool q_pad = a.lengths && qi >= len;
+  // REL: this query's gate and the row of the [H][2T - 1] table; column j - qi + T - 1 is in range for every j, qi < T
+  float rel_g = 0.f;
+  const float* rel_row = nullptr;
+  if constexpr (REL) {
+    rel_g = qi < T ? a.rel_gate[((size_t)b * a.H + h) * T + qi] : 0.f;
+    rel_row = a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 - (qi < T ? qi : T - 1));  // (tail lanes: kept inside the table, never read)
+  }
 
   for (int j0 = 0; j0 < T; j0 += 32) {
     __syncthreads();
@@ -64,6 +73,9 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
       const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
       float x = s[r];
       if (a.lengths && (q_pad || j >= len)) x += -1e4f;
+      if constexpr (REL) {
+        if (j < T && qi < T) x = fmaf(rel_g, rel_row[j], x);
+      }
       if (j >= T) x = -INFINITY;
       s[r] = x;
       mx = fmaxf(mx, x);
@@ -119,7 +131,16 @@ int launch_attention(const AttnArgs& a, int B, int DH, hipStream_t st) {
   if (attention16_eligible(a, DH)) return launch_attention16(a, B, st);
   dim3 grid(cdiv(a.T, 128), a.H, B);
   const bool drop = a.drop_p > 0.f;
-  if (DH == 64 && !drop)
+  if (a.rel_tab || a.rel_gate) {  // the gated relative position bias (WavLM)
+    if (!a.rel_tab || !a.rel_gate || drop || a.lengths || (DH != 64 && DH != 16)) {
+      set_error("attention: the relative-bias variant takes a table and a gate, head dim 64 or 16, no mask and no dropout (head dim %d)", DH);
+      return STY_EINVAL;
+    }
+    if (DH == 64)
+      hipLaunchKernelGGL((attn_kernel<64, false, true>), grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((attn_kernel<16, false, true>), grid, dim3(256), 0, st, a);
+  } else if (DH == 64 && !drop)
     hipLaunchKernelGGL((attn_kernel<64, false>), grid, dim3(256), 0, st, a);
   else if (DH == 16 && !drop)
     hipLaunchKernelGGL((attn_kernel<16, false>), grid, dim3(256), 0, st, a);

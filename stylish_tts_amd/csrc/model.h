@@ -1,5 +1,8 @@
 // Host-side model object: parameters bound by reference state_dict key, prepared-weight arena, forward plans.
 #pragma once
+#include <math.h>
+
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -250,6 +253,62 @@ int launch_rmvpe_gru(const float* xg, const float* whhT, const float* bhh0, cons
 int launch_rmvpe_salience(const float* logits, int B, int T, int n, float* sal, hipStream_t st);
 int launch_rmvpe_decode(const float* sal, int rows, float thred, float* f0, hipStream_t st);
 
+// FIR resampler of torchaudio's sinc_interp_hann form in rates reduced by their gcd (rmvpe.hip): `nw` phases of 2 width + orig
+// taps at stride orig, y[b][nw q + p] = sum_j taps[p][j] x[b][orig q + j - width], zero outside [0, N)
+inline int resample_width(int orig, int nw, double lpw) {
+  const double base = (double)(orig < nw ? orig : nw) * 0.99;
+  return (int)ceil(lpw * orig / base);
+}
+void build_resample_kernel(int orig, int nw, double lpw, float* out);
+int launch_resample_fir(const float* x, const float* taps, int B, int N, int M, int orig, int nw, int width, float* y, hipStream_t st);
+
+// WavLM = transformers' WavLMModel in eval mode (wavlm.hip has the kernels, api.hip the plan, weights.hip the packs)
+constexpr int WAVLM_MAX_CONV = 8;
+struct WavlmPackJob {  // wp[(kk / s) CinP + (kk % s) Cin + ci][co] = w[co0 + co][ci][kk] * (g ? g[kk] / nrm[kk] : 1); bp[co] = bias[co0 + co]
+  const float *w = nullptr, *g = nullptr, *nrm = nullptr, *bias = nullptr;
+  float *wp = nullptr, *bp = nullptr;
+  int Cout = 0, Cin = 0, K = 1, s = 1, CinP = 0, CoutP = 0, co0 = 0;
+};
+struct WavlmLayer {
+  PackedConv q, k, v, o, f1, f2;
+  const float *gate_w = nullptr, *gate_b = nullptr, *gate_c = nullptr;  // gru_rel_pos_linear [8][DH], [8]; gru_rel_pos_const [H]
+  const float *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
+};
+struct WavlmPlan {
+  // sty_wavlm_set_config
+  int n_conv = 0, stride[WAVLM_MAX_CONV] = {0}, max_distance = 800;
+  float ln_eps = 1e-5f;
+  // from the bound shapes
+  int dim[WAVLM_MAX_CONV] = {0}, kern[WAVLM_MAX_CONV] = {0};
+  int hidden = 0, heads = 0, pos_k = 0, pos_groups = 0, num_buckets = 0;
+  const float *conv0_w = nullptr, *gn_w = nullptr, *gn_b = nullptr;
+  PackedConv conv[WAVLM_MAX_CONV];  // i >= 1: the stride-s conv as a stride-1 conv of ceil(k / s) taps over s C phase-major channels
+  const float *fp_ln_w = nullptr, *fp_ln_b = nullptr, *enc_ln_w = nullptr, *enc_ln_b = nullptr, *rel_embed = nullptr;
+  PackedConv proj;
+  const float* pos_v = nullptr;
+  float* pos_nrm = nullptr;        // prepared: ||v[:, :, k]|| per tap
+  std::vector<PackedConv> pos;     // one per group
+  std::vector<WavlmLayer> layers;
+  std::vector<WavlmPackJob> packs;
+};
+int wavlm_prepare(const WavlmPlan& p, hipStream_t st);  // weights.hip
+int launch_wavlm_conv0(const float* x, const float* w, int B, int N, int C, int K, int S, int T, float* y, double* part, hipStream_t st);
+int wavlm_conv0_ntiles(int T);
+int launch_wavlm_gn_finalize(const double* part, int ntiles, const float* w, const float* b, int BC, int C, int T, float eps, float* a,
+                             float* s, hipStream_t st);
+// x [B][C][Tin] -> y [B][S C][Tp], y[b][p C + c][t] = f(x[b][c][S t + p]) (0 past Tin); f = GELU(a[b][c] x + s[b][c]) with a set, else x
+int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st);
+// [B][G Cg][T] <-> [G][B][Cg][T]
+int launch_wavlm_group_perm(const float* x, int B, int G, int Cg, int T, int to_groups, float* y, hipStream_t st);
+// bucket: the entry of distance -(T - 1) (the caller offsets a larger table)
+int launch_wavlm_rel_table(const float* embed, const int32_t* bucket, int H, int T, float* tab, hipStream_t st);
+int launch_wavlm_gate(const float* x, const float* w, const float* b, const float* c, int B, int H, int DH, int T, float* gate,
+                      hipStream_t st);
+int launch_wavlm_transpose_out(const float* x, int B, int C, int T, float* y, hipStream_t st);  // [B][C][T] -> [B][T][C]
+void wavlm_rel_buckets(int T, int num_buckets, int max_distance, int32_t* out);
+int slm_loss_groups(size_t n);
+int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st);
+
 struct Trainer;
 struct StyleResBlk {  // mel_style_encoder.py:69-118
   int Cin = 0, Cout = 0;
@@ -293,6 +352,11 @@ struct sty_model {
   sty::PitchEnergyPlan pe;
   sty::AlignerPlan ali;
   sty::RmvpePlan rmv;
+  sty::WavlmPlan wav;
+  // device bucket table of the distances -(wav_bucket_T - 1) .. wav_bucket_T - 1: a bucket depends on the distance alone, so one
+  // table sized for the largest frame count seen serves every smaller one at an offset
+  int32_t* wav_bucket_dev = nullptr;
+  int wav_bucket_T = 0;
   sty::PackedConv pse_pre;  // PitchStyleEncoder.preconv (mel_style_encoder.py:166)
   float* stft_default = nullptr;  // device [4][33][64]
   // ---- training ----

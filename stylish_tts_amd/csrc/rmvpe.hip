@@ -2,10 +2,10 @@
 // utils.py:114-131, spec.py): everything of the pitch command that is not a dense conv on launch_conv1d.
 //
 // (1) Front end.  torchaudio Resample(24000, 16000, lowpass_filter_width=128), sinc_interp_hann, rolloff 0.99: the ratio
-//     reduces to 3 -> 2, so the output is two interleaved phases of a 391-tap FIR at stride 3 (rmvpe_resample_kernel, taps in
-//     LDS); the 1024-point |STFT| runs on the LDS FFT of frontend.hip, the 128 x 513 mel basis (librosa mel(htk=True), Slaney
+//     reduces to 3 -> 2, so the output is two interleaved phases of a 391-tap FIR at stride 3 (resample_fir_kernel, taps in
+//     LDS; the slm loss shares it with 23 taps); the 1024-point |STFT| runs on the LDS FFT of frontend.hip, the 128 x 513 mel basis (librosa mel(htk=True), Slaney
 //     normalised) is a K = 1 conv, rmvpe_logmel_kernel takes log(clamp(., 1e-5)).  Both tables are closed forms evaluated in
-//     double on the host and rounded to fp32 once (build_rmvpe_resample_kernel, build_rmvpe_mel_basis).  torchaudio and librosa
+//     double on the host and rounded to fp32 once (build_resample_kernel, build_rmvpe_mel_basis).  torchaudio and librosa
 //     are absent: PARITY UNPINNED at this boundary, as the other front end is.
 // (2) Weight side.  Every BatchNorm behind a bias-free conv is folded into the packed weights and the bias
 //     (rmvpe_pack_conv_kernel: Conv2d [Cout][Cin][KH][KW] -> the flat 2-D order wp[kw][kh Cin + ci][co], also the GRU's two
@@ -36,20 +36,23 @@ namespace sty {
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int RS_WIDTH = 194;             // ceil(128 * 3 / 1.98)
 constexpr int RS_TAPS = 2 * RS_WIDTH + 3;  // 391
-// out [2][391]: phase p, tap j' = j - 194
-void build_rmvpe_resample_kernel(float* out) {
-  const double base = 2.0 * 0.99, lpw = 128.0, pi = 3.14159265358979323846;
-  for (int p = 0; p < 2; ++p)
-    for (int j = 0; j < RS_TAPS; ++j) {
-      double t = (-(double)p / 2.0 + (double)(j - RS_WIDTH) / 3.0) * base;
+// out [nw][2 width + orig]: phase p, tap j' = j - width (torchaudio _get_sinc_resample_kernel, sinc_interp_hann, rolloff 0.99)
+void build_resample_kernel(int orig, int nw, double lpw, float* out) {
+  const double base = (double)(orig < nw ? orig : nw) * 0.99, pi = 3.14159265358979323846;
+  const int width = resample_width(orig, nw, lpw), taps = 2 * width + orig;
+  for (int p = 0; p < nw; ++p)
+    for (int j = 0; j < taps; ++j) {
+      double t = (-(double)p / (double)nw + (double)(j - width) / (double)orig) * base;
       t = t < -lpw ? -lpw : (t > lpw ? lpw : t);
       const double c = cos(t * pi / lpw / 2.0);
       const double window = c * c;
       t *= pi;
       const double sinc = t == 0.0 ? 1.0 : sin(t) / t;
-      out[p * RS_TAPS + j] = (float)(sinc * window * (base / 3.0));
+      out[p * taps + j] = (float)(sinc * window * (base / (double)orig));
     }
 }
+// out [2][391]: the pitch front end's table, lowpass_filter_width = 128
+void build_rmvpe_resample_kernel(float* out) { build_resample_kernel(3, 2, 128.0, out); }
 // out [128][513]: librosa.filters.mel(sr=16000, n_fft=1024, n_mels=128, fmin=30, fmax=8000, htk=True), norm="slaney"
 void build_rmvpe_mel_basis(float* out) {
   const int n_mels = RMVPE_MELS, F = 513;
@@ -72,21 +75,31 @@ void build_rmvpe_mel_basis(float* out) {
 // ---------------------------------------------------------------------------------------------------------------------
 // front end
 // ---------------------------------------------------------------------------------------------------------------------
-// y[b][2 q + p] = sum_j k[p][j] x[b][3 q + j - 194], zero outside [0, N); M = ceil(2 N / 3) outputs per row
-__global__ __launch_bounds__(256) void rmvpe_resample_kernel(const float* __restrict__ x, const float* __restrict__ taps, int N,
-                                                             int M, float* __restrict__ y) {
-  __shared__ float k[2 * RS_TAPS];
-  for (int i = threadIdx.x; i < 2 * RS_TAPS; i += 256) k[i] = taps[i];
+// y[b][nw q + p] = sum_j k[p][j] x[b][orig q + j - width], zero outside [0, N); M = ceil(nw N / orig) outputs per row; the
+// nw (2 width + orig) taps in LDS (the pitch front end: 2 x 391; the slm loss: 2 x 23)
+__global__ __launch_bounds__(256) void resample_fir_kernel(const float* __restrict__ x, const float* __restrict__ taps, int N,
+                                                           int M, int orig, int nw, int width, float* __restrict__ y) {
+  extern __shared__ float k[];
+  const int nt = 2 * width + orig;
+  for (int i = threadIdx.x; i < nw * nt; i += 256) k[i] = taps[i];
   __syncthreads();
   const int m = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
   if (m >= M) return;
-  const int q = m >> 1, p = m & 1;
+  const int q = m / nw, p = m - q * nw;
   const float* xb = x + (size_t)b * N;
-  const int i0 = 3 * q - RS_WIDTH;
-  const int j0 = i0 < 0 ? -i0 : 0, j1 = i0 + RS_TAPS > N ? N - i0 : RS_TAPS;
+  const int i0 = orig * q - width;
+  const int j0 = i0 < 0 ? -i0 : 0, j1 = i0 + nt > N ? N - i0 : nt;
   float acc = 0.f;
-  for (int j = j0; j < j1; ++j) acc = fmaf(k[p * RS_TAPS + j], xb[i0 + j], acc);
+  for (int j = j0; j < j1; ++j) acc = fmaf(k[p * nt + j], xb[i0 + j], acc);
   y[(size_t)b * M + m] = acc;
+}
+int launch_resample_fir(const float* x, const float* taps, int B, int N, int M, int orig, int nw, int width, float* y, hipStream_t st) {
+  const int nt = 2 * width + orig;
+  ProfScope prof("resample_fir_kernel", 2.0 * nt * B * M, 4.0 * B * ((double)N + M), st);
+  hipLaunchKernelGGL(resample_fir_kernel, dim3(cdiv(M, 256), B), dim3(256), (size_t)nw * nt * sizeof(float), st, x, taps, N, M, orig, nw,
+                     width, y);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
 }
 // in place: log(clamp(x, 1e-5)); the clamped value is the constant, so that silence is one bit pattern
 __global__ __launch_bounds__(256) void rmvpe_logmel_kernel(float* __restrict__ x, size_t n) {
@@ -132,11 +145,7 @@ int launch_rmvpe_mel(int B, int N, const float* audio, float* logmel, float* ws,
   float* res = ws;
   float* y = res + (size_t)B * align_up(M, 64);
   float* mag = y + (size_t)B * 2 * F * n;
-  {
-    ProfScope prof("rmvpe_resample_kernel", 2.0 * RS_TAPS * B * M, 4.0 * B * ((double)N + M), st);
-    hipLaunchKernelGGL(rmvpe_resample_kernel, dim3(cdiv(M, 256), B), dim3(256), 0, st, audio, g_resample_taps, N, M, res);
-    STY_LAUNCH_CHECK();
-  }
+  if ((rc = launch_resample_fir(audio, g_resample_taps, B, N, M, 3, 2, RS_WIDTH, res, st)) != STY_OK) return rc;
   if ((rc = launch_stft_mag(B, M, res, 1024, RMVPE_HOP, 16000, y, mag, st)) != STY_OK) return rc;
   ConvArgs a;
   a.x[0] = mag;

@@ -486,6 +486,10 @@ struct AttnArgs {
   unsigned drop_seed = 0, drop_site = 0;
   float* lse = nullptr;  // optional [B][H][T]: log-sum-exp of every score row, kept for the MFMA backward
   int bf16 = 0;          // bf16 compute mode: the contractions on v_mfma_f32_32x32x16_bf16 (attn16.hip; 8 x 64 heads, no mask)
+  // gated relative position bias (WavLM): logit (i, j) += rel_gate[b][h][i] * rel_tab[h][j - i + T - 1]; rel_tab [H][2T - 1],
+  // rel_gate [B][H][T]; both or neither (head dims 64 and 16, no dropout)
+  const float* rel_tab = nullptr;
+  const float* rel_gate = nullptr;
 };
 // attn16.hip: the conformer's attention in the bf16 compute mode
 bool attention16_eligible(const AttnArgs& a, int DH);

@@ -1,0 +1,283 @@
+// WavLM forward for the slm loss value (WavLMLoss, train/losses.py:376-394; transformers' modeling_wavlm.py in eval mode):
+// everything of it that is not a dense conv on launch_conv1d, an attention launch (attn.hip, the gated relative-bias variant)
+// or a channel LayerNorm (norms.hip).  api.hip has the plan (wavlm_forward), weights.hip the packs.
+//
+// (1) Feature encoder, layer 0 (Conv1d(1, C, k, stride s), bias-free; k = 10, s = 5 at full size): bandwidth work.
+//     wavlm_conv0_kernel writes the conv's output [B][C][T0] and, from the same registers, the float64 (sum, sum of squares)
+//     partial of every (b, c, 256-frame tile): GroupNorm(C, C) is a per-(b, c) norm over the whole time axis, up to 20 799 frames
+//     at the c3 wave size.  wavlm_gn_finalize_kernel adds the tiles in index order and folds the affine into (a, s).
+// (2) Layers 1 .. n - 1 (stride s, k taps, C -> C'): a stride-s conv over C channels is a stride-1 conv of ceil(k / s) taps over
+//     the s C channels of the input read s frames at a time.  wavlm_stage_kernel writes that view, phase-major
+//     (y[p C + c][t] = x[c][s t + p]), applying layer 0's norm and GELU on the way for layer 1 (one pass, not three); the conv
+//     itself is launch_conv1d on the fp32 matrix cores with the weights packed for the view (weights.hip) and GELU in its
+//     epilogue.
+// (3) Positional conv (grouped, k even): wavlm_group_perm_kernel turns [B][G Cg][T] into [G][B][Cg][T], one dense conv per group
+//     writes x + GELU(conv(x)) in that layout (the last output frame of the even kernel is never computed), the inverse
+//     permutation leads into the LayerNorm.
+// (4) Attention glue: wavlm_rel_table_kernel (rel_attn_embed through the host bucket table -> [H][2T - 1], once per call),
+//     wavlm_gate_kernel (gru_rel_pos_linear on the layer INPUT's head slice -> [B][H][T]).
+// (5) wavlm_transpose_out_kernel: [B][C][T] -> the [B][T][C] hidden state the loss reads.
+// (6) slm_loss kernels: mean |a - b| with float64 partials at fixed indices, added in index order (val_loss.hip's discipline).
+#include <math.h>
+
+#include "model.h"
+
+namespace sty {
+namespace {
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
+constexpr int C0_CG = 8;      // channels per workgroup of wavlm_conv0_kernel
+constexpr int C0_MAXK = 16;   // most taps of layer 0
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
+// feature encoder, layer 0 + GroupNorm sums
+// ---------------------------------------------------------------------------------------------------------------------
+int wavlm_conv0_ntiles(int T) { return cdiv(T, 256); }
+// x [B][N], w [C][K] -> y[b][c][t] = sum_k w[c][k] x[b][S t + k] (S t + k < N by T's definition);
+// part[((b C + c) ntiles + tile) 2 + {0, 1}] = sum, sum of squares of the tile's frames
+__global__ __launch_bounds__(256) void wavlm_conv0_kernel(const float* __restrict__ x, const float* __restrict__ w, int N, int C, int K,
+                                                          int S, int T, float* __restrict__ y, double* __restrict__ part) {
+  __shared__ double red[2][C0_CG][4];
+  const int t = blockIdx.x * 256 + threadIdx.x, c0 = blockIdx.y * C0_CG, b = blockIdx.z;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool in = t < T;
+  float xv[C0_MAXK];
+  const float* xb = x + (size_t)b * N + (size_t)S * (in ? t : 0);
+#pragma unroll
+  for (int k = 0; k < C0_MAXK; ++k) xv[k] = (in && k < K) ? xb[k] : 0.f;
+#pragma unroll
+  for (int cc = 0; cc < C0_CG; ++cc) {
+    const int c = c0 + cc;
+    if (c >= C) break;  // (uniform)
+    const float* wc = w + (size_t)c * K;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < C0_MAXK; ++k)
+      if (k < K) acc = fmaf(wc[k], xv[k], acc);
+    if (in) y[((size_t)b * C + c) * T + t] = acc;
+    const double v = in ? (double)acc : 0.0;
+    const double s1 = wave_sum(v), s2 = wave_sum(v * v);
+    if (lane == 0) {
+      red[0][cc][wave] = s1;
+      red[1][cc][wave] = s2;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * C0_CG) {
+    const int cc = threadIdx.x >> 1, k = threadIdx.x & 1;
+    if (c0 + cc < C)
+      part[(((size_t)b * C + c0 + cc) * gridDim.x + blockIdx.x) * 2 + k] =
+          ((red[k][cc][0] + red[k][cc][1]) + red[k][cc][2]) + red[k][cc][3];
+  }
+}
+int launch_wavlm_conv0(const float* x, const float* w, int B, int N, int C, int K, int S, int T, float* y, double* part, hipStream_t st) {
+  if (K > C0_MAXK) {
+    set_error("wavlm: the first feature conv has %d taps (at most %d are built)", K, C0_MAXK);
+    return STY_EINVAL;
+  }
+  ProfScope prof("wavlm_conv0_kernel", 2.0 * K * B * C * T, 4.0 * B * ((double)N + (double)C * T), st);
+  hipLaunchKernelGGL(wavlm_conv0_kernel, dim3(wavlm_conv0_ntiles(T), cdiv(C, C0_CG), B), dim3(256), 0, st, x, w, N, C, K, S, T, y, part);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+// GroupNorm(C, C): per row (b, c) mean and biased variance over T frames from the tile partials, added in index order;
+// a = w[c] rstd, s = b[c] - a mean
+__global__ __launch_bounds__(256) void wavlm_gn_finalize_kernel(const double* __restrict__ part, int ntiles, const float* __restrict__ w,
+                                                                const float* __restrict__ bv, int BC, int C, int T, float eps,
+                                                                float* __restrict__ a, float* __restrict__ s) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= BC) return;
+  const double* p = part + (size_t)row * ntiles * 2;
+  double s1 = 0.0, s2 = 0.0;
+  for (int i = 0; i < ntiles; ++i) {
+    s1 += p[2 * i];
+    s2 += p[2 * i + 1];
+  }
+  const double mean = s1 / T;
+  double var = s2 / T - mean * mean;
+  var = var < 0.0 ? 0.0 : var;
+  const int c = row % C;
+  const double av = (double)w[c] / sqrt(var + (double)eps);
+  a[row] = (float)av;
+  s[row] = (float)((double)bv[c] - av * mean);
+}
+int launch_wavlm_gn_finalize(const double* part, int ntiles, const float* w, const float* b, int BC, int C, int T, float eps, float* a,
+                             float* s, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_gn_finalize_kernel, dim3(cdiv(BC, 256)), dim3(256), 0, st, part, ntiles, w, b, BC, C, T, eps, a, s);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the s-frames-at-a-time view of a strided conv's input
+// ---------------------------------------------------------------------------------------------------------------------
+template <bool NORM>
+__global__ __launch_bounds__(256) void wavlm_stage_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                          const float* __restrict__ s, int C, int Tin, int S, int Tp,
+                                                          float* __restrict__ y) {
+  const int t = blockIdx.x * 256 + threadIdx.x, pc = blockIdx.y, b = blockIdx.z;
+  if (t >= Tp) return;
+  const int p = pc / C, c = pc - p * C;
+  const long long ts = (long long)S * t + p;
+  float v = 0.f;
+  if (ts < Tin) {
+    v = x[((size_t)b * C + c) * Tin + ts];
+    if constexpr (NORM) v = gelu_erf(fmaf(v, a[(size_t)b * C + c], s[(size_t)b * C + c]));
+  }
+  y[((size_t)b * S * C + pc) * Tp + t] = v;
+}
+int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st) {
+  const dim3 grid(cdiv(Tp, 256), S * C, B);
+  ProfScope prof("wavlm_stage_kernel", 0.0, 8.0 * B * S * (double)C * Tp, st);
+  if (a)
+    hipLaunchKernelGGL(wavlm_stage_kernel<true>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
+  else
+    hipLaunchKernelGGL(wavlm_stage_kernel<false>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// positional conv: group-major layout
+// ---------------------------------------------------------------------------------------------------------------------
+// to_groups: y[g][b][c][t] = x[b][g Cg + c][t]; otherwise the inverse
+__global__ __launch_bounds__(256) void wavlm_group_perm_kernel(const float* __restrict__ x, int B, int G, int Cg, int T, int to_groups,
+                                                               float* __restrict__ y) {
+  const int t = blockIdx.x * 256 + threadIdx.x, gc = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  const int g = gc / Cg, c = gc - g * Cg;
+  const size_t flat = ((size_t)b * G * Cg + gc) * T + t, grp = (((size_t)g * B + b) * Cg + c) * T + t;
+  if (to_groups)
+    y[grp] = x[flat];
+  else
+    y[flat] = x[grp];
+}
+int launch_wavlm_group_perm(const float* x, int B, int G, int Cg, int T, int to_groups, float* y, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_group_perm_kernel, dim3(cdiv(T, 256), G * Cg, B), dim3(256), 0, st, x, B, G, Cg, T, to_groups, y);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// attention glue
+// ---------------------------------------------------------------------------------------------------------------------
+// _relative_positions_bucket (modeling_wavlm.py) of the distances d = j - i in -(T - 1) .. T - 1, in the class's order of
+// operations; out[d + T - 1].  (fp32 and float64 arithmetic agree on every distance 0 .. 2047 for (320, 800) and (32, 64);
+// tests/golden/slm_small.json holds the class's own tables)
+void wavlm_rel_buckets(int T, int num_buckets, int max_distance, int32_t* out) {
+  const int nb = num_buckets / 2, max_exact = nb / 2;
+  for (int d = -(T - 1); d <= T - 1; ++d) {
+    int bucket = d > 0 ? nb : 0;
+    const int n = d < 0 ? -d : d;
+    if (n < max_exact) {
+      bucket += n;
+    } else {
+      float v = logf((float)n / (float)max_exact);
+      v = v / (float)log((double)max_distance / (double)max_exact);
+      v = v * (float)(nb - max_exact);
+      int large = (int)((float)max_exact + v);
+      if (large > nb - 1) large = nb - 1;
+      bucket += large;
+    }
+    out[d + T - 1] = bucket;
+  }
+}
+// tab[h][d] = embed[bucket[d]][h], d < 2T - 1
+__global__ __launch_bounds__(256) void wavlm_rel_table_kernel(const float* __restrict__ embed, const int32_t* __restrict__ bucket, int H,
+                                                              int n, float* __restrict__ tab) {
+  const int d = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
+  if (d >= n) return;
+  tab[(size_t)h * n + d] = embed[(size_t)bucket[d] * H + h];
+}
+int launch_wavlm_rel_table(const float* embed, const int32_t* bucket, int H, int T, float* tab, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_rel_table_kernel, dim3(cdiv(2 * T - 1, 256), H), dim3(256), 0, st, embed, bucket, H, 2 * T - 1, tab);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+// x [B][H DH][T] -> gate[b][h][t] = ga (gb const[h] - 1) + 2 with (ga, gb) = sigmoid of the two sums of four of
+// Linear(DH, 8)(x[b][h DH .. (h + 1) DH][t])
+__global__ __launch_bounds__(256) void wavlm_gate_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                         const float* __restrict__ bv, const float* __restrict__ cst, int H, int DH,
+                                                         int T, float* __restrict__ gate) {
+  const int t = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  const float* xp = x + ((size_t)b * H + h) * DH * T + t;
+  float r[8];
+#pragma unroll
+  for (int o = 0; o < 8; ++o) r[o] = 0.f;
+  for (int d = 0; d < DH; ++d) {
+    const float v = xp[(size_t)d * T];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) r[o] = fmaf(w[o * DH + d], v, r[o]);
+  }
+#pragma unroll
+  for (int o = 0; o < 8; ++o) r[o] += bv[o];
+  const float sa = ((r[0] + r[1]) + r[2]) + r[3], sb = ((r[4] + r[5]) + r[6]) + r[7];
+  const float ga = 1.0f / (1.0f + expf(-sa)), gb = 1.0f / (1.0f + expf(-sb));
+  gate[((size_t)b * H + h) * T + t] = fmaf(ga, fmaf(gb, cst[h], -1.0f), 2.0f);
+}
+int launch_wavlm_gate(const float* x, const float* w, const float* b, const float* c, int B, int H, int DH, int T, float* gate,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_gate_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, st, x, w, b, c, H, DH, T, gate);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// [B][C][T] -> [B][T][C] through a 32 x 33 LDS tile
+__global__ __launch_bounds__(256) void wavlm_transpose_out_kernel(const float* __restrict__ x, int C, int T, float* __restrict__ y) {
+  __shared__ float tile[32][33];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32, b = blockIdx.z;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int c = c0 + r, t = t0 + tx;
+    tile[r][tx] = (c < C && t < T) ? x[((size_t)b * C + c) * T + t] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int t = t0 + r, c = c0 + tx;
+    if (t < T && c < C) y[((size_t)b * T + t) * C + c] = tile[tx][r];
+  }
+}
+int launch_wavlm_transpose_out(const float* x, int B, int C, int T, float* y, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_transpose_out_kernel, dim3(cdiv(T, 32), cdiv(C, 32), B), dim3(256), 0, st, x, C, T, y);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// slm loss: mean |a - b|
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SLM_G_MAX = 1024, SLM_PER_WG = 8192;
+int slm_loss_groups(size_t n) {
+  const size_t g = (n + SLM_PER_WG - 1) / SLM_PER_WG;
+  return g < 1 ? 1 : (g < (size_t)SLM_G_MAX ? (int)g : SLM_G_MAX);
+}
+__global__ __launch_bounds__(256) void slm_loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
+                                                               double* __restrict__ part) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc += (double)fabsf(a[i] - b[i]);
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+__global__ void slm_loss_finalize_kernel(const double* __restrict__ part, int G, size_t n, float* __restrict__ loss) {
+  double s = 0.0;
+  for (int g = 0; g < G; ++g) s += part[g];
+  loss[0] = (float)(s / (double)n);
+}
+int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st) {
+  const int G = slm_loss_groups(n);
+  ProfScope prof("slm_loss_partial_kernel", 2.0 * n, 8.0 * n, st);
+  hipLaunchKernelGGL(slm_loss_partial_kernel, dim3(G), dim3(256), 0, st, a, b, n, part);
+  hipLaunchKernelGGL(slm_loss_finalize_kernel, dim3(1), dim3(1), 0, st, part, G, n, loss);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+}  // namespace sty

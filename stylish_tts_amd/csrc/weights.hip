@@ -396,6 +396,46 @@ int weights_sn_power_iter(sty_model* m, hipStream_t st) {
   return launch_sn_prep_table(m->wt.sn_prep, m->wt.sn_wtu, true, false, st);  // every layer in four launches
 }
 
+// ---- WavLM (kind "wavlm", forward only: nothing to un-pack) ----
+// nrm[k] = || v[:, :, k] || over the n = Cout Cin rows of v [n][K] (weight-norm dim = 2 of the positional conv): one workgroup
+// per tap, float64 partials added in a fixed order
+__global__ __launch_bounds__(256) void wavlm_tap_norm_kernel(const float* __restrict__ v, int n, int K, float* __restrict__ nrm) {
+  __shared__ double red[256];
+  const int k = blockIdx.x;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double x = (double)v[(size_t)i * K + k];
+    acc += x * x;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) nrm[k] = (float)sqrt(red[0]);
+}
+// one workgroup per output channel of the job (WavlmPackJob, model.h)
+__global__ __launch_bounds__(256) void wavlm_pack_kernel(WavlmPackJob j) {
+  const int co = blockIdx.x, n = j.Cin * j.K;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int ci = i / j.K, kk = i - ci * j.K;
+    const int kp = kk / j.s, p = kk - kp * j.s;
+    float v = j.w[(size_t)(j.co0 + co) * n + i];
+    if (j.g) v *= j.g[kk] / j.nrm[kk];
+    j.wp[((size_t)kp * j.CinP + (size_t)p * j.Cin + ci) * j.CoutP + co] = v;
+  }
+  if (threadIdx.x == 0 && j.bp) j.bp[co] = j.bias ? j.bias[j.co0 + co] : 0.f;
+}
+int wavlm_prepare(const WavlmPlan& p, hipStream_t st) {
+  if (p.pos_nrm)
+    hipLaunchKernelGGL(wavlm_tap_norm_kernel, dim3(p.pos_k), dim3(256), 0, st, p.pos_v, p.hidden * (p.hidden / p.pos_groups), p.pos_k,
+                       p.pos_nrm);
+  for (const WavlmPackJob& j : p.packs) hipLaunchKernelGGL(wavlm_pack_kernel, dim3(j.Cout), dim3(256), 0, st, j);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
 int weights_prepare(sty_model* m, hipStream_t st) {
   int r = tables_ready(m);
   if (r != STY_OK) return r;
@@ -438,6 +478,8 @@ int weights_prepare(sty_model* m, hipStream_t st) {
   }
   // RMVPE: the BatchNorm-folding packs, W_hh^T and the input BatchNorm's scale / shift (rmvpe.hip)
   if (m->kind == "rmvpe" && (r = rmvpe_prepare(m->rmv, st)) != STY_OK) return r;
+  // WavLM: the strided feature convs packed for their s-frames-at-a-time view, the positional conv's weight norm folded per group
+  if (m->kind == "wavlm" && (r = wavlm_prepare(m->wav, st)) != STY_OK) return r;
   // the bf16 fragment buffers the persistent kernels read the packed weights through (bf16 mode)
   if (m->arena && (r = convp16_repack_range(m->arena, m->arena + m->arena_bytes, st)) != STY_OK) return r;
   return STY_OK;

@@ -203,6 +203,16 @@ SYMBOLS = {
     "sty_rmvpe_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
     "sty_rmvpe_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "sty_rmvpe_decode": (C.c_int, [_I, _I, _P, C.c_float, _P, _P]),
+    "sty_wavlm_set_config": (C.c_int, [_P, _I, _P, _I, C.c_float]),
+    "sty_slm_resample_len": (C.c_int, [_I, _I, _I]),
+    "sty_slm_resample_kernel_host": (C.c_int, [_I, _I, _P]),
+    "sty_slm_resample_fwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P]),
+    "sty_wavlm_frames": (C.c_int, [_P, _I, _P]),
+    "sty_wavlm_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
+    "sty_wavlm_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "sty_wavlm_rel_buckets_host": (C.c_int, [_I, _I, _I, _P]),
+    "sty_slm_loss_workspace_bytes": (C.c_int, [C.c_size_t, _SZP]),
+    "sty_slm_loss_fwd": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_aligner_train_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
     "sty_aligner_fwd_train": (C.c_int, [_P, _I, _I, _P, _P, C.c_float, C.c_uint, _P, _P, C.c_size_t, _P]),
     "sty_aligner_bwd": (C.c_int, [_P, _P, _P]),

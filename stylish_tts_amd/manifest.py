@@ -388,3 +388,62 @@ def rmvpe_manifest(n_blocks=4, inter_layers=4, en_out_channels=16):
     m["fc.1.weight"] = [360, 512]
     m["fc.1.bias"] = [360]
     return m
+
+
+WAVLM_DEFAULT_CFG = dict(
+    hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
+    conv_dim=(512, 512, 512, 512, 512, 512, 512), conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2),
+    num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16, num_buckets=320, max_bucket_distance=800,
+    layer_norm_eps=1e-5, feat_extract_norm="group", feat_extract_activation="gelu", hidden_act="gelu",
+    do_stable_layer_norm=False, conv_bias=False,
+)
+
+
+def wavlm_manifest(**cfg):
+    """transformers' WavLMModel(WavLMConfig(**cfg)).state_dict() without masked_spec_embed (eval mode never reads it), for the
+    configurations slm.check_wavlm_config accepts: group norm on the first feature conv, bias-free feature convs, post-LN layers.
+    The defaults are the class's own (what microsoft/wavlm-base-plus is): 247 keys, 94,381,168 parameters with
+    masked_spec_embed's 768 left out (tests/golden/manifest_wavlm.json is the class's own list)."""
+    c = dict(WAVLM_DEFAULT_CFG)
+    unknown = sorted(set(cfg) - set(c))
+    if unknown:
+        raise TypeError(f"wavlm_manifest: unknown config field(s) {unknown}")
+    c.update(cfg)
+    H, heads = c["hidden_size"], c["num_attention_heads"]
+    m = OrderedDict()
+    cin = 1
+    for i, (dim, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
+        m[f"feature_extractor.conv_layers.{i}.conv.weight"] = [dim, cin, k]
+        if i == 0:
+            m["feature_extractor.conv_layers.0.layer_norm.weight"] = [dim]
+            m["feature_extractor.conv_layers.0.layer_norm.bias"] = [dim]
+        cin = dim
+    m["feature_projection.layer_norm.weight"] = [cin]
+    m["feature_projection.layer_norm.bias"] = [cin]
+    m["feature_projection.projection.weight"] = [H, cin]
+    m["feature_projection.projection.bias"] = [H]
+    K, G = c["num_conv_pos_embeddings"], c["num_conv_pos_embedding_groups"]
+    m["encoder.pos_conv_embed.conv.bias"] = [H]
+    m["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = [1, 1, K]  # weight_norm(dim=2)
+    m["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = [H, H // G, K]
+    m["encoder.layer_norm.weight"] = [H]
+    m["encoder.layer_norm.bias"] = [H]
+    for l in range(c["num_hidden_layers"]):
+        p = f"encoder.layers.{l}."
+        for name in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            m[p + f"attention.{name}.weight"] = [H, H]
+            m[p + f"attention.{name}.bias"] = [H]
+        m[p + "attention.gru_rel_pos_const"] = [1, heads, 1, 1]
+        m[p + "attention.gru_rel_pos_linear.weight"] = [8, H // heads]
+        m[p + "attention.gru_rel_pos_linear.bias"] = [8]
+        if l == 0:
+            m[p + "attention.rel_attn_embed.weight"] = [c["num_buckets"], heads]
+        m[p + "layer_norm.weight"] = [H]
+        m[p + "layer_norm.bias"] = [H]
+        m[p + "feed_forward.intermediate_dense.weight"] = [c["intermediate_size"], H]
+        m[p + "feed_forward.intermediate_dense.bias"] = [c["intermediate_size"]]
+        m[p + "feed_forward.output_dense.weight"] = [H, c["intermediate_size"]]
+        m[p + "feed_forward.output_dense.bias"] = [H]
+        m[p + "final_layer_norm.weight"] = [H]
+        m[p + "final_layer_norm.bias"] = [H]
+    return m

@@ -1,0 +1,232 @@
+"""The slm loss value on the HIP path: `WavLMLoss` (train/losses.py:376-394), the last term of the reference's acoustic step
+(`step.slm_loss()`, train/stage_type.py:221-225, 363).  Both waves are resampled `model_sr` -> `slm_sr`, both go through a frozen
+WavLM (`microsoft/wavlm-base-plus` in the reference's model.yml), and the loss is the L1 distance between the stacks of all
+hidden states (13 at full depth); the trainer weights it with `loss_weight.slm`.
+
+What is built is the VALUE: the network's forward in HIP (csrc/wavlm.hip) and its first user, the validation pass
+(`train --slm DIR`).  The gradient with respect to the predicted wave, the term inside `AcousticTrainer.train_batch` and a bf16
+operand mode are not built: `WavLMLoss.forward` raises in grad mode when the prediction requires a gradient.
+
+Nothing is downloaded.  `model` is a local directory in the hub snapshot layout: `config.json` plus `model.safetensors`, or
+`pytorch_model.bin` read with `torch.load(weights_only=True)`.  The `transformers` package is not imported: `config.json` is read
+as JSON and the network is this package's own.  State-dict keys are those of `WavLMModel.state_dict()` without
+`masked_spec_embed` (eval mode never reads it); for the positional conv both spellings of the weight norm load
+(`...conv.parametrizations.weight.original0/1` and the older `...conv.weight_g/weight_v` hub files carry); a leading `wavlm.` is
+stripped; strict otherwise.
+
+The resampler restates `torchaudio.transforms.Resample(model_sr, slm_sr)` with its defaults (sinc_interp_hann,
+lowpass_filter_width 6, rolloff 0.99) from the documented closed form; torchaudio is not a dependency of this package: PARITY
+UNPINNED at that boundary (tests/slm_cases.py has the float64 restatement the kernel is held to).  No test uses trained WavLM
+weights: the network is held to the class's own CPU runs on key-filled weights (tests/golden/slm_*); that the value on real
+speech is right is not shown by a test.
+"""
+import ctypes as C
+import json
+import os.path as osp
+
+import torch
+
+from . import lib as L
+from .manifest import WAVLM_DEFAULT_CFG, wavlm_manifest
+from .modules import _HipModule, _f32
+
+# config.json fields whose every other value is refused by name (what wavlm-base-plus is by the class defaults)
+SUPPORTED = dict(feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False, feat_extract_activation="gelu",
+                 hidden_act="gelu")
+_SHAPE_FIELDS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "conv_dim", "conv_kernel",
+                 "conv_stride", "num_conv_pos_embeddings", "num_conv_pos_embedding_groups", "num_buckets", "max_bucket_distance",
+                 "layer_norm_eps")
+_WN_OLD = {"weight_g": "parametrizations.weight.original0", "weight_v": "parametrizations.weight.original1"}
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def check_wavlm_config(cfg):
+    """config.json (a dict) -> the fields wavlm_manifest takes, the class defaults where the file is silent.  A value this path
+    does not build is refused by name, as config.check_supported does for model.yml."""
+    for name, want in SUPPORTED.items():
+        got = cfg.get(name, want)
+        if got != want:
+            raise L.StyError(f"WavLM config: {name}={got!r} is not built (only {name}={want!r})")
+    out = {k: cfg.get(k, WAVLM_DEFAULT_CFG[k]) for k in _SHAPE_FIELDS}
+    for k in ("conv_dim", "conv_kernel", "conv_stride"):
+        out[k] = tuple(int(v) for v in out[k])
+    n = len(out["conv_dim"])
+    if not (2 <= n <= 8) or len(out["conv_kernel"]) != n or len(out["conv_stride"]) != n:
+        raise L.StyError(f"WavLM config: conv_dim / conv_kernel / conv_stride must have the same length, 2 to 8 (got {n})")
+    if out["conv_kernel"][0] > 16:
+        raise L.StyError(f"WavLM config: conv_kernel[0]={out['conv_kernel'][0]} is not built (at most 16 taps)")
+    if out["num_conv_pos_embeddings"] % 2 or out["num_conv_pos_embeddings"] > 128:
+        raise L.StyError(f"WavLM config: num_conv_pos_embeddings={out['num_conv_pos_embeddings']} is not built (even, at most 128)")
+    H, heads, G = out["hidden_size"], out["num_attention_heads"], out["num_conv_pos_embedding_groups"]
+    if H % heads or H // heads not in (16, 64):
+        raise L.StyError(f"WavLM config: hidden_size={H} with num_attention_heads={heads} is not built (head dim 16 or 64)")
+    if H % G:
+        raise L.StyError(f"WavLM config: num_conv_pos_embedding_groups={G} does not divide hidden_size={H}")
+    if out["num_buckets"] < 4 or out["max_bucket_distance"] <= out["num_buckets"] // 4:
+        raise L.StyError(f"WavLM config: num_buckets={out['num_buckets']} / max_bucket_distance={out['max_bucket_distance']} "
+                         "is not built")
+    return out
+
+
+def wavlm_frames(n16, cfg=None):
+    """frames of `n16` samples at the slm rate: floor((n - k) / s) + 1 per feature conv; 0 when a layer is left without one"""
+    c = cfg or WAVLM_DEFAULT_CFG
+    n = int(n16)
+    for k, s in zip(c["conv_kernel"], c["conv_stride"]):
+        if n < k:
+            return 0
+        n = (n - k) // s + 1
+    return n
+
+
+def normalize_state_dict(state):
+    """a hub-layout state dict -> the keys of wavlm_manifest: `wavlm.` stripped, the old weight-norm spelling renamed,
+    masked_spec_embed dropped"""
+    out = {}
+    for k, v in state.items():
+        if k.startswith("wavlm."):
+            k = k[len("wavlm."):]
+        if k == "masked_spec_embed":
+            continue
+        head, _, last = k.rpartition(".")
+        if last in _WN_OLD and head.endswith("pos_conv_embed.conv"):
+            k = f"{head}.{_WN_OLD[last]}"
+        out[k] = v
+    return out
+
+
+class WavLM(_HipModule):
+    """transformers' WavLMModel in eval mode with its state_dict keys (manifest.wavlm_manifest).  forward(audio16 [B, N16]) ->
+    hidden states [layers + 1, B, T, hidden_size]: what `WavLMModel(x, output_hidden_states=True).hidden_states` stacks to."""
+    KIND = "wavlm"
+
+    def __init__(self, **cfg):
+        super().__init__()
+        self.cfg = check_wavlm_config(cfg)
+        self._build(wavlm_manifest(**{k: v for k, v in self.cfg.items() if k != "layer_norm_eps"}))
+
+    def enable_training(self):
+        raise L.StyError("WavLM: forward only (the network is frozen; its backward is not built)")
+
+    def set_train_opts(self, **kw):
+        if kw.get("compute_bf16"):
+            raise L.StyError("WavLM: compute_bf16 is refused: the kind runs fp32 operands (the bf16 mode is not built)")
+        return super().set_train_opts(**kw)
+
+    def _ensure(self, device):
+        if self._handle is None and torch.device(device).type == "cuda":
+            lib = L.load()
+            h = C.c_void_p()
+            L.check(lib.sty_model_create(self.KIND.encode(), C.byref(h)))
+            stride = (C.c_int * len(self.cfg["conv_stride"]))(*self.cfg["conv_stride"])
+            L.check(lib.sty_wavlm_set_config(h, len(self.cfg["conv_stride"]), stride, int(self.cfg["max_bucket_distance"]),
+                                             float(self.cfg["layer_norm_eps"])))
+            self._handle = h
+        return super()._ensure(device)
+
+    def forward(self, audio16):
+        if torch.is_grad_enabled() and audio16.requires_grad:
+            raise L.StyError("WavLM: backward is not built")
+        if audio16.dim() != 2 or not audio16.is_cuda:
+            raise L.StyError(f"WavLM: audio must be [B, N] on a HIP device (got {tuple(audio16.shape)} on {audio16.device}); "
+                             "there is no CPU path")
+        B, n16 = audio16.shape
+        T = wavlm_frames(n16, self.cfg)
+        if T < 1:
+            raise L.StyError(f"WavLM: {n16} samples leave no frame behind the feature encoder")
+        dev = audio16.device
+        lib = self._ensure(dev)
+        x = _f32(audio16.detach(), dev)
+        out = torch.empty(self.cfg["num_hidden_layers"] + 1, B, T, self.cfg["hidden_size"], dtype=torch.float32, device=dev)
+        need = C.c_size_t()
+        L.check(lib.sty_wavlm_workspace_bytes(self._handle, B, n16, C.byref(need)))
+        ws = self._workspace(need.value, dev)
+        L.check(lib.sty_wavlm_fwd(self._handle, B, n16, L.ptr(x), L.ptr(out), L.ptr(ws), ws.numel(), _stream(dev)))
+        return out
+
+
+def resample(audio, orig, new):
+    """torchaudio.transforms.Resample(orig, new) with its defaults, restated (PARITY UNPINNED): [B, N] -> [B, ceil(N new / orig)]"""
+    if audio.dim() != 2 or not audio.is_cuda:
+        raise L.StyError(f"slm.resample: audio must be [B, N] on a HIP device (got {tuple(audio.shape)} on {audio.device})")
+    lib = L.load()
+    B, N = audio.shape
+    M = lib.sty_slm_resample_len(N, int(orig), int(new))
+    if M < 1:
+        raise L.StyError(f"slm.resample: {orig} -> {new} on {N} samples is not built")
+    x = _f32(audio.detach(), audio.device)
+    out = torch.empty(B, M, dtype=torch.float32, device=audio.device)
+    L.check(lib.sty_slm_resample_fwd(B, N, int(orig), int(new), L.ptr(x), L.ptr(out), _stream(audio.device)))
+    return out
+
+
+def l1_mean(a, b):
+    """mean |a - b| of two equally shaped fp32 device tensors, float64 partials in a fixed order: the same inputs, the same bits"""
+    if a.shape != b.shape or not a.is_cuda:
+        raise L.StyError(f"slm.l1_mean: shapes {tuple(a.shape)} and {tuple(b.shape)} on {a.device}")
+    lib = L.load()
+    a, b = _f32(a, a.device), _f32(b, a.device)
+    need = C.c_size_t()
+    L.check(lib.sty_slm_loss_workspace_bytes(a.numel(), C.byref(need)))
+    ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=a.device)
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    L.check(lib.sty_slm_loss_fwd(a.numel(), L.ptr(a), L.ptr(b), L.ptr(loss), L.ptr(ws), ws.numel() * 8, _stream(a.device)))
+    return loss[0]
+
+
+def load_snapshot(model):
+    """(config dict, normalised state dict) of a local hub-layout directory; anything else raises"""
+    if not isinstance(model, (str, bytes)) and not hasattr(model, "__fspath__") or not osp.isdir(model):
+        raise L.StyError(f"WavLMLoss: {model!r} is not an existing directory.  Nothing is downloaded: pass the local snapshot "
+                         "directory of the WavLM model (config.json + model.safetensors or pytorch_model.bin) with --slm")
+    cfg_path = osp.join(model, "config.json")
+    if not osp.isfile(cfg_path):
+        raise L.StyError(f"WavLMLoss: {cfg_path} not found (--slm takes a hub snapshot directory)")
+    with open(cfg_path, encoding="utf-8") as f:
+        cfg = json.load(f)
+    st, pt = osp.join(model, "model.safetensors"), osp.join(model, "pytorch_model.bin")
+    if osp.isfile(st):
+        from safetensors.torch import load_file
+        state = load_file(st)
+    elif osp.isfile(pt):
+        state = torch.load(pt, map_location="cpu", weights_only=True)
+    else:
+        raise L.StyError(f"WavLMLoss: neither model.safetensors nor pytorch_model.bin in {model} (--slm)")
+    return cfg, normalize_state_dict(state)
+
+
+class WavLMLoss(torch.nn.Module):
+    """WavLMLoss(model, model_sr, slm_sr=16000) (train/losses.py:376-394): the reference's constructor; `model` is a local
+    snapshot directory.  forward(wav [B, N], y_rec [B, 1, N] or [B, N]) -> scalar, under torch.no_grad()."""
+
+    def __init__(self, model, model_sr, slm_sr=16000):
+        super().__init__()
+        cfg, state = load_snapshot(model)
+        self.wavlm = WavLM(**{k: v for k, v in cfg.items() if k in SUPPORTED or k in _SHAPE_FIELDS})
+        self.wavlm.load_state_dict(state, strict=True)
+        self.wavlm.eval()
+        for p in self.wavlm.parameters():
+            p.requires_grad_(False)
+        self.model_sr, self.slm_sr = int(model_sr), int(slm_sr)
+
+    def hidden_states(self, wav):
+        """[B, N] at model_sr -> [layers + 1, B, T, H]"""
+        return self.wavlm(resample(wav, self.model_sr, self.slm_sr))
+
+    def forward(self, wav, y_rec):
+        if torch.is_grad_enabled() and y_rec.requires_grad:
+            raise L.StyError("WavLMLoss: backward is not built")
+        if y_rec.dim() == 3 and y_rec.shape[1] == 1:
+            y_rec = y_rec[:, 0]
+        if wav.dim() != 2 or y_rec.dim() != 2:
+            raise L.StyError(f"WavLMLoss: wav must be [B, N] and y_rec [B, 1, N] or [B, N] (got {tuple(wav.shape)}, "
+                             f"{tuple(y_rec.shape)})")
+        if wav.shape != y_rec.shape:
+            raise L.StyError(f"WavLMLoss: unequal lengths {tuple(wav.shape)} and {tuple(y_rec.shape)}")
+        with torch.no_grad():
+            # (the ground-truth stack is kept; the second forward reuses the network's workspace)
+            ref = self.hidden_states(wav)
+            return l1_mean(ref, self.hidden_states(y_rec))

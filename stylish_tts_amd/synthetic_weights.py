@@ -40,6 +40,10 @@ def fill_tensor(key, shape, seed=0):
         return f32(r.uniform(0.5, 1.5, shape))
     if last == "running_mean":
         return f32(0.1 * r.standard_normal(shape))
+    if last == "gru_rel_pos_const":  # WavLM's per-head constant of the gated position bias (the class starts it at 1)
+        return f32(1.0 + 0.3 * r.standard_normal(shape))
+    if key.endswith("rel_attn_embed.weight"):  # WavLM's bucket -> per-head bias table
+        return f32(r.standard_normal(shape))
     if last == "original0":  # weight-norm gain g
         return f32(r.uniform(0.7, 1.3, shape))
     if last == "original1":  # weight-norm direction v

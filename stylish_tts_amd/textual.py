@@ -139,6 +139,8 @@ class TextualTrainer:
         self.pred_pitch, self.pred_energy, self.audio = pp, pe, audio
         return log
 
+    slm = None  # a slm.WavLMLoss on the trainer's device (train(..., slm_path=...)): validate then also returns the slm value
+
     @torch.no_grad()
     def validate(self, *, audio_gt, texts, text_lengths, pitch, durations, noise=None, seed=0, prior_override=None, **_):
         """validate_textual (stage_type.py:451-468): the eval-mode forward of all four models -- predicted pitch and energy
@@ -158,7 +160,13 @@ class TextualTrainer:
                             prior_override=prior_override).audio
         loss, items = mel_loss(audio_gt, audio.squeeze(1), per_item=True)
         log = {"mel": loss[0], "pitch": pitch_loss_value(pitch, pp), "energy": pitch_loss_value(energy, pe)}
-        return log, {"audio": audio, "per_item": items}
+        extra = {"audio": audio, "per_item": items}
+        if self.slm is not None:
+            # `train --slm`: the batch's slm value beside the log, never in it (validation.py).  A host-side refusal of the slm
+            # path (no frame left, a shape) comes back as a value: it must not cost the batch its numbers
+            from .validation import or_refusal
+            extra["slm"] = or_refusal(lambda: self.slm(audio_gt, audio))
+        return log, extra
 
     def schedule(self, step, step_limit):
         from .optim import scheduled_lr

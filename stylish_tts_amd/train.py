@@ -3,7 +3,7 @@
 the HIP path -> accelerate-layout checkpoints, stage after stage (acoustic -> textual -> duration, stage_type.py:394,472,637).
 
     python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic [--checkpoint DIR] [--reset-stage]
-    python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage S --checkpoint DIR --validate-only
+    python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage S --checkpoint DIR --validate-only [--slm DIR]
 
 or `stylish_tts_amd.train.train(config_path, model_config_path, out, stage, checkpoint, reset_stage)` -- the reference
 command's arguments in the reference command's order.  What is joined here exists piece by piece elsewhere in this package
@@ -16,7 +16,8 @@ The reference's other two commands on the same files: `convert` is below (--conv
 stylish_tts_amd/voicepack.py (its consumer, `speak`, is stylish_tts_amd/speak.py); both take the last stage's checkpoint.
 
 What the reference's loop does and this one does NOT (out of scope): the alignment stage (its own command, as in
-the reference: train_align.py), validation figures / tensorboard, the WavLM loss term (third-party weights), the batch-size PROBE
+the reference: train_align.py), validation figures / tensorboard, the WavLM loss term INSIDE the training step (slm.py has its value: `--slm DIR` logs it in the
+validation pass; its backward is not built), the batch-size PROBE
 (train/batch_manager.py probe_loop: an out-of-memory search for 24-80 GB cards) -- with 288 GB of HBM every length bin runs at
 `training_plan.<stage>.probe_batch_max` and that table is written to `<stage>_batch_sizes.json` exactly where the probe
 would have left it, so a table the reference probed is used as it is when the file is already there.
@@ -121,6 +122,7 @@ class TrainContext:
         self.config, self.model_config, self.base_out_dir, self.device, self.log = config, model_config, base_out_dir, device, log
         self.adversarial = adversarial
         self.deterministic = bool(deterministic)  # handed to every stage's trainer
+        self.slm = None  # slm.WavLMLoss on the device (train_model(slm_path=...), rank 0): the validation pass hands it to the trainer
         self.rank, self.world = dist.init() if "WORLD_SIZE" in os.environ else (0, 1)
         mp = config.training.mixed_precision
         if mp not in ("no", "bf16"):
@@ -200,14 +202,21 @@ class TrainContext:
 
 
 def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage=False, config_path="", model_config_path="",
-                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False, deterministic=False):
+                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False, deterministic=False, slm_path=None):
     """train/train.py:76-338.  `deterministic`: the library's deterministic mode for the run (fixed-order sums: two runs from one
     seed give the same bits on one rank; the order of the gradient exchange between ranks is the backend's).  `max_steps`: stop after that many optimizer steps IN TOTAL (tests; None = the plan's epochs).
     `validate_only`: load `checkpoint`, run ONE validation pass of `stage` (log line, samples, eval/validation.jsonl; the record
     is left under `.validation`) and return without a training step or a save.
+    `slm_path`: the local snapshot directory of the WavLM model (slm.py; nothing is downloaded, and model.yml's `slm.model` is
+    never picked up by itself): the validation passes of the acoustic and the textual stage then also log the slm value
+    (WavLMLoss of `model_config.sample_rate` -> `model_config.slm.sr`) and write it as the record's "slm"; metrics, total and
+    best_loss do not see it.
     Returns the context (models, manifest, the last stage's trainer under `.stage`)."""
     from . import data as D
     from . import stage_io as IO
+    if slm_path is not None and not osp.isdir(slm_path):  # (before anything is loaded; slm.load_snapshot says the same)
+        raise L.StyError(f"--slm {slm_path!r} is not an existing directory.  Nothing is downloaded: pass the local snapshot "
+                         "directory of the WavLM model (config.json + model.safetensors or pytorch_model.bin)")
     if deterministic:  # first of all: nothing is sized, loaded or normalised in the other mode
         L.set_deterministic(True)
     random.seed(1)  # train/train.py:87-88
@@ -221,6 +230,13 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
     device = torch.device(device or f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}")
     torch.cuda.set_device(device)
     ctx = TrainContext(config, model_config, out_dir, device, adversarial=adversarial, log=log, deterministic=deterministic)
+    if slm_path is not None and stage == "duration":  # (the last stage: no later stage would use the network either)
+        log("--slm has no effect on the duration stage (its validation synthesises row by row): the WavLM model is not loaded")
+    elif slm_path is not None and ctx.rank == 0:  # (validation runs on rank 0 alone, and so does this)
+        from .slm import WavLMLoss
+        slm_cfg = model_config.get("slm") or {}
+        ctx.slm = WavLMLoss(slm_path, int(model_config.sample_rate), int(slm_cfg.get("sr", 16000))).to(device)
+        log(f"slm: WavLM from {slm_path} ({ctx.slm.model_sr} -> {ctx.slm.slm_sr} Hz): validation also logs the slm value")
 
     def enter(name):
         st = _Stage(name, ctx)
@@ -286,6 +302,8 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
 
 def _validation_pass(ctx, st, log):
     from .validation import ValidationPass
+    if ctx.slm is not None and st.name in ("acoustic", "textual"):  # (the duration stage synthesises row by row)
+        st.trainer.slm = ctx.slm
     return ValidationPass(ctx.config, ctx.model_config, st.name, st.out_dir, st.batch_sizes.get_batch_size, ctx.device, log=log)
 
 
@@ -395,12 +413,15 @@ def main(argv=None):
                     help="fixed-order sums: a seed reproduces the run to the bit (STY_DETERMINISTIC=1 does the same)")
     ap.add_argument("--validate-only", dest="validate_only", action="store_true",
                     help="one validation pass of --stage on --checkpoint: the log line, the samples and the JSON line; no training")
+    ap.add_argument("--slm", dest="slm_path", default=None, metavar="DIR",
+                    help="local snapshot directory of the WavLM model (config.json + model.safetensors / pytorch_model.bin): the "
+                         "validation passes of the acoustic and textual stage also log the slm value; nothing is downloaded")
     a = ap.parse_args(argv)
     if a.convert:
         convert(a.config_path, a.model_config_path, a.out, a.checkpoint)
         return
     train(a.config_path, a.model_config_path, a.out, a.stage, a.checkpoint, a.reset_stage, max_steps=a.max_steps,
-          validate_only=a.validate_only, deterministic=a.deterministic)
+          validate_only=a.validate_only, deterministic=a.deterministic, slm_path=a.slm_path)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,8 @@ the reference's log line, listening samples as wav files.
     pass_ = ValidationPass(config, model_config, stage, out_dir, batch_size_of, device, log=log)   # val split + length-bin
                                                                     # sampler at the stage's batch sizes; no device touched
     record = pass_.run(trainer, manifest, loss_weight)              # {"step", "stage", "total", "metrics", "best_before",
-                                                                    #  "batches", "skipped", "samples"}
+                                                                    #  "batches", "skipped", "samples"} (+ "slm" with
+                                                                    #  `train --slm`: trainer.slm is set)
 
 What the reference also draws and this does not: mel / attention figures and tensorboard scalars (neither matplotlib's figure
 path nor tensorboard is part of this package's dependencies); the record goes to `<out>/<stage>/eval/validation.jsonl` instead.
@@ -221,13 +222,19 @@ class ValidationPass:
         from .data import to_step_inputs
         step = int(manifest.current_total_step)
         sr = int(self.model_config.sample_rate)
-        samples = []
+        samples, slm_logs = [], []
 
         def validate(batch, wanted):
             kw = to_step_inputs(batch, self.device)
             if self.stage == "duration":
                 kw["samples"] = [i for i, _ in wanted]
-            return trainer.validate(**kw)
+            out, extra = trainer.validate(**kw)
+            value = extra.get("slm")  # (`train --slm`, acoustic and textual stage)
+            if isinstance(value, Exception):  # refused on the host: this batch has no slm value; its metrics stand
+                self.log(f"validation batch: slm value skipped: {value}")
+            elif value is not None:
+                slm_logs.append({"slm": float(value)})
+            return out, extra
 
         def on_sample(i, j, path, batch, extra):
             entry = {"sample": j, "path": path}
@@ -260,6 +267,13 @@ class ValidationPass:
         record = {"step": step, "stage": self.stage, "total": finite_or_none(total),
                   "metrics": {k: finite_or_none(v) for k, v in metrics.items()}, "best_before": finite_or_none(best_before),
                   "batches": len(logs), "skipped": skipped, "samples": samples}
+        if slm_logs:
+            # The slm value (slm.WavLMLoss, unweighted; the reference's training log shows this term, its validation does not
+            # compute it): combined over the batches as the metrics are, one line of its own and one top-level field.  metrics,
+            # total, best_before and manifest.best_loss above never see it: best_loss decides which checkpoint is best.
+            slm_value = combine(slm_logs)["slm"]
+            self.log(f"Validation step {step}: slm: {slm_value:.3f}")
+            record["slm"] = finite_or_none(slm_value)
         os.makedirs(self.eval_dir, exist_ok=True)
         with open(osp.join(self.eval_dir, "validation.jsonl"), "a", encoding="utf-8") as f:
             f.write(record_line(record) + "\n")

@@ -1,0 +1,119 @@
+"""One WavLMLoss.forward (stylish_tts_amd/slm.py: two resamplings, two WavLM forwards, the L1 reduction) at the c3 wave size:
+B = 32 x 156 000 samples at 24 kHz, full width (the class defaults, 12 layers), key-filled weights, fp32 operands.  ms per call from
+device events around blocks of calls after a warm-up; then one profiled call for the per-family split (sty_prof_report).
+Dense work by the issue's count: 87 GFLOP per utterance and forward, 5.6 TFLOP per call; the fp32 matrix-core figure it is set
+against is 157.3 TFLOP/s (v_mfma_f32_32x32x2_f32).  python tools/slm_bench.py [B]"""
+import json
+import os
+import statistics
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+
+from stylish_tts_amd import lib as L
+from stylish_tts_amd import slm
+from stylish_tts_amd.manifest import WAVLM_DEFAULT_CFG, wavlm_manifest
+from stylish_tts_amd.synthetic_weights import fill_state_dict
+
+DEV = "cuda:0"
+N = 300 * 520  # bench.py WORKLOADS["c3"]: 6.5 s at 24 kHz
+BLOCK, ROUNDS = 2, 5
+PEAK_FP32_MFMA = 157.3e12
+
+
+def dense_flops(n16, cfg=WAVLM_DEFAULT_CFG):
+    """multiply-adds x 2 of the dense contractions of one forward of one utterance"""
+    n, cin, fl = n16, 1, 0.0
+    for dim, k, s in zip(cfg["conv_dim"], cfg["conv_kernel"], cfg["conv_stride"]):
+        n = (n - k) // s + 1
+        fl += 2.0 * dim * cin * k * n
+        cin = dim
+    H, FF, T = cfg["hidden_size"], cfg["intermediate_size"], n
+    fl += 2.0 * H * cin * T + 2.0 * H * (H // cfg["num_conv_pos_embedding_groups"]) * cfg["num_conv_pos_embeddings"] * T
+    fl += cfg["num_hidden_layers"] * (4 * 2.0 * H * H * T + 2 * 2.0 * H * FF * T + 2 * 2.0 * H * T * T)
+    return fl, T
+
+
+def main():
+    assert torch.cuda.is_available(), "needs a HIP device"
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+    with tempfile.TemporaryDirectory() as d:
+        from safetensors.torch import save_file
+        json.dump({}, open(os.path.join(d, "config.json"), "w"))  # the class defaults
+        save_file(fill_state_dict(wavlm_manifest(), 23), os.path.join(d, "model.safetensors"))
+        loss = slm.WavLMLoss(d, 24000, 16000).to(DEV)
+    g = torch.Generator().manual_seed(3)
+    gt = (0.3 * torch.randn(B, N, generator=g)).to(DEV)
+    pr = gt + (0.03 * torch.randn(B, N, generator=g)).to(DEV)
+    with torch.no_grad():
+        for _ in range(2):  # warm-up: code objects, tables, the workspace, the packed weights
+            v = loss(gt, pr)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(ROUNDS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(BLOCK):
+                loss(gt, pr)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / BLOCK)
+        fl, T = dense_flops((2 * N + 2) // 3)
+        total = 2 * B * fl
+        med = statistics.median(ms)
+        print(f"WavLMLoss.forward B={B} N={N} (T={T}): value {v.item():.6f}; median {med:.2f} ms per call (min {min(ms):.2f}, max {max(ms):.2f}, "
+              f"{ROUNDS} blocks of {BLOCK})")
+        print(f"dense work {total / 1e12:.2f} TFLOP per call ({fl / 1e9:.1f} GFLOP per utterance and forward): {total / med / 1e9:.1f} TFLOP/s achieved, "
+              f"{100 * total / (med * 1e-3) / PEAK_FP32_MFMA:.1f} % of the fp32 matrix-core figure ({PEAK_FP32_MFMA / 1e12:.1f} TFLOP/s)")
+        lib = L.load()
+        L.check(lib.sty_prof_enable(1))
+        loss(gt, pr)
+        torch.cuda.synchronize()
+        rows = sorted(L.prof_report(cap=256), key=lambda r: -r["ms"])
+        L.check(lib.sty_prof_enable(0))
+        tot = sum(r["ms"] for r in rows)
+        print(f"per-family split of one call under the in-situ timers ({tot:.2f} ms in timed launches; untimed glue kernels are not in it):")
+        for r in rows:
+            tf = r["flops"] / (r["ms"] * 1e-3) / 1e12 if r["ms"] > 0 else 0.0
+            print(f"  {r['name']:44s} {r['launches']:5d} launches {r['ms']:9.3f} ms {100 * r['ms'] / tot:5.1f} %  {tf:6.1f} TFLOP/s")
+    validate_only_pass()
+
+
+def validate_only_pass():
+    """one --validate-only pass of the small set-up (the 8-utterance sample dataset, batch 2, an untrained acoustic checkpoint)
+    without and with --slm on a full-width key-filled snapshot: wall seconds of the second of two passes each"""
+    import time
+    from safetensors.torch import save_file
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from make_sample_dataset import make
+    from stylish_tts_amd import train as T
+    from tests.test_boundary import _default_config_yaml, _default_model_yaml
+    with tempfile.TemporaryDirectory() as d:
+        make(os.path.join(d, "data"), 8, 11)
+        cfg, mdl, snap = os.path.join(d, "config.yml"), os.path.join(d, "model.yml"), os.path.join(d, "wavlm")
+        open(cfg, "w").write(_default_config_yaml(os.path.join(d, "data"), acoustic=dict(epochs=1)))
+        open(mdl, "w").write(_default_model_yaml())
+        os.makedirs(snap)
+        json.dump({}, open(os.path.join(snap, "config.json"), "w"))
+        save_file(fill_state_dict(wavlm_manifest(), 23), os.path.join(snap, "model.safetensors"))
+        quiet = lambda s: None
+        T.train(cfg, mdl, os.path.join(d, "out"), "acoustic", max_steps=1, log=quiet)
+        final = os.path.join(d, "out", "acoustic", "checkpoint_final")
+        for label, kw in (("without --slm", {}), ("with --slm", dict(slm_path=snap))):
+            secs = []
+            for i in range(2):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ctx = T.train(cfg, mdl, os.path.join(d, f"v_{len(kw)}_{i}"), "acoustic", checkpoint=final, validate_only=True, log=quiet, **kw)
+                torch.cuda.synchronize()
+                secs.append(time.perf_counter() - t0)
+            rec = ctx.validation
+            print(f"--validate-only, acoustic, {rec['batches']} batches of the sample val split, {label}: {secs[1]:.2f} s (first pass {secs[0]:.2f} s; "
+                  f"model loading included)  total {rec['total']:.6f}  slm {rec.get('slm')}")
+
+
+if __name__ == "__main__":
+    main()
