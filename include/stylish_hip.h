@@ -464,8 +464,9 @@ int sty_partial_sum(int dw_form, const float *part, int C, int K, int nblk, floa
 /* ---- optimizer: torch.optim.AdamW (train/optimizers.py:110-118) over one flat fp32 bucket ------------------
  * p, g, m, v: n floats each, 16-byte aligned, identically laid out; step = 1, 2, ... (bias correction).
  * grad_scale multiplies g on the way in: 1 / world_size turns the SUM all-reduce of the gradient buckets into the
- * mean without a pass of its own (1.0f: plain AdamW, bit-identical).                                              */
-int sty_adamw_step(size_t n, float *p, const float *g, float *m, float *v, float lr, float beta1, float beta2,
+ * mean without a pass of its own (1.0f: plain AdamW, bit-identical).  The betas are doubles: 1 - beta and the bias
+ * corrections are formed in double, as torch forms them (1.0f - 0.99f is 9.5e-7 off 0.01).                        */
+int sty_adamw_step(size_t n, float *p, const float *g, float *m, float *v, float lr, double beta1, double beta2,
                    float eps, float weight_decay, int step, float grad_scale, void *stream);
 /* The same step at the rate lr * *lr_mult, lr_mult a DEVICE double: the discriminators' learning-rate multiplier
  * (train/optimizers.py:54-65) never leaves the GPU, so a GAN step has no host read-back.  sty_disc_lr_track keeps it:
@@ -474,7 +475,7 @@ int sty_adamw_step(size_t n, float *p, const float *g, float *m, float *v, float
  * running mean, last_loss = 0.95 last_loss + 0.05 loss (losses.py:287) -- the order of train/stage.py, where the optimizer
  * steps with the multiplier of the previous mean.                                                                  */
 int sty_adamw_step_scaled(size_t n, float *p, const float *g, float *m, float *v, double lr, const double *lr_mult,
-                          float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                          double beta1, double beta2, float eps, float weight_decay, int step, float grad_scale,
                           void *stream);
 int sty_disc_lr_track(double *state, const float *loss, double ideal_loss, double f_max, double h_min, double x_max,
                       double x_min, void *stream);

@@ -8,9 +8,19 @@
 
 namespace sty {
 
+// 1 - lr*wd, on the host and on the device: the product rounded to fp32, then the difference.  Device code would
+// contract `1.0f - lr * wd` into one FMA (a single rounding), which differs from the host's value by one ulp at about one
+// (lr, wd) pair in a thousand -- and then in nearly every parameter of the bucket.
+__host__ __device__ __forceinline__ float decay_of(float lr, float wd) {
+#pragma clang fp contract(off)
+  const float prod = lr * wd;
+  return 1.0f - prod;
+}
+
 // lr_mult (optional, DEVICE): the learning rate of this launch is lr * *lr_mult -- the discriminators' rate multiplier
 // (optimizers.py:54-65) computed on the device by disc_lr_track_kernel, so that the host never reads a loss back; the
-// two scalars that depend on the rate are then formed here, in the host path's arithmetic (lr_d, wd, bc1 given).
+// two scalars that depend on the rate are then formed here, in the host path's arithmetic (lr_d, wd, bc1 given): the
+// step is bit for bit that of sty_adamw_step at lr = (float)(lr_d * *lr_mult) (tests/test_optim_edges.py).
 __global__ __launch_bounds__(256) void adamw_kernel(size_t n4, size_t n, float4* __restrict__ p,
                                                     const float4* __restrict__ g, float4* __restrict__ m,
                                                     float4* __restrict__ v, float decay, float w1, float b2, float w2,
@@ -18,7 +28,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(size_t n4, size_t n, float4*
                                                     const double* __restrict__ lr_mult, double lr_d, float wd, double bc1) {
   if (lr_mult) {
     const float lr = (float)(lr_d * lr_mult[0]);
-    decay = 1.0f - lr * wd;
+    decay = decay_of(lr, wd);
     step_size = (float)((double)lr / bc1);
   }
   const size_t stride = (size_t)gridDim.x * 256;
@@ -73,10 +83,13 @@ __global__ void disc_lr_track_kernel(double* state, const float* loss, double id
   if (loss) state[0] = last * 0.95 + (double)loss[0] * 0.05;
 }
 
-int launch_adamw(size_t n, float* p, const float* g, float* m, float* v, double lr_d, float beta1, float beta2, float eps,
+// beta1, beta2 are doubles: 1 - beta and the bias corrections are formed in double and rounded once, as torch forms them from
+// its Python floats.  From fp32 betas, 1.0f - 0.99f is 0.00999999046 (9.5e-7 off 0.01, and so was v) and 1.0f - 0.85f is
+// 1.6e-7 off 0.15.
+int launch_adamw(size_t n, float* p, const float* g, float* m, float* v, double lr_d, double beta1, double beta2, float eps,
                  float weight_decay, int step, float grad_scale, const double* lr_mult, hipStream_t st) {
   const float lr = (float)lr_d;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+  const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
   const float step_size = (float)((double)lr / bc1);
   const float bc2s = (float)sqrt(bc2);
   const size_t n4 = n / 4;
@@ -86,7 +99,8 @@ int launch_adamw(size_t n, float* p, const float* g, float* m, float* v, double 
   ProfScope prof("adamw_kernel", 12.0 * n, 28.0 * n, st);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n4, n, reinterpret_cast<float4*>(p),
                      reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v),
-                     1.0f - lr * weight_decay, 1.0f - beta1, beta2, 1.0f - beta2, step_size, bc2s, eps, grad_scale,
+                     decay_of(lr, weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), step_size, bc2s, eps,
+                     grad_scale,
                      lr_mult, lr_d, weight_decay, bc1);
   STY_LAUNCH_CHECK();
   return STY_OK;
@@ -94,8 +108,8 @@ int launch_adamw(size_t n, float* p, const float* g, float* m, float* v, double 
 
 }  // namespace sty
 
-extern "C" int sty_adamw_step(size_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int step, float grad_scale,
+extern "C" int sty_adamw_step(size_t n, float* p, const float* g, float* m, float* v, float lr, double beta1,
+                              double beta2, float eps, float weight_decay, int step, float grad_scale,
                               void* stream) {
   using namespace sty;
   if (!p || !g || !m || !v || step < 1 || ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) {
@@ -108,8 +122,8 @@ extern "C" int sty_adamw_step(size_t n, float* p, const float* g, float* m, floa
 }
 
 extern "C" int sty_adamw_step_scaled(size_t n, float* p, const float* g, float* m, float* v, double lr,
-                                     const double* lr_mult, float beta1, float beta2, float eps, float weight_decay,
-                                     int step, float grad_scale, void* stream) {
+                                     const double* lr_mult, double beta1, double beta2, float eps,
+                                     float weight_decay, int step, float grad_scale, void* stream) {
   using namespace sty;
   if (!p || !g || !m || !v || !lr_mult || step < 1 ||
       ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) {

@@ -142,9 +142,9 @@ SYMBOLS = {
     "sty_grn_bwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, C.c_size_t, _P]),
     "sty_act_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
     "sty_adain_finalize": (C.c_int, [_I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
-    "sty_adamw_step": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+    "sty_adamw_step": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float,
                                  _I, C.c_float, _P]),
-    "sty_adamw_step_scaled": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_double, _P, C.c_float, C.c_float, C.c_float,
+    "sty_adamw_step_scaled": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_double, _P, C.c_double, C.c_double, C.c_float,
                                         C.c_float, _I, C.c_float, _P]),
     "sty_disc_lr_track": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "sty_model_set_grad_hook": (C.c_int, [_P, _P, _P]),
