@@ -44,7 +44,7 @@ const char *sty_last_error(void);
  *       "text_aligner"       = train/models/text_aligner.py:33-45 (inference only, see sty_aligner_fwd)
  *       "text_aligner_train" = the same module with a training graph (see sty_aligner_fwd_train)
  *       "rmvpe"              = train/dataprep/rmvpe/model.py:49-86 E2E0 (inference only, see sty_rmvpe_fwd)
- *       "wavlm"              = transformers WavLMModel in eval mode (forward only, see sty_wavlm_fwd)
+ *       "wavlm"              = transformers WavLMModel in eval mode (frozen, see sty_wavlm_fwd / sty_wavlm_bwd)
  * Dimensions are taken from the bound tensors' shapes (train/config/model.yml defaults are checked).   */
 int sty_model_create(const char *kind, sty_model **out);
 void sty_model_destroy(sty_model *m);
@@ -528,8 +528,9 @@ int sty_duration_loss_fwd(int B, int L, int NC, const float *pred, const int64_t
  * encoder.layers.0.attention.rel_attn_embed.weight.  Widths, depths, heads, kernels, groups and num_buckets are read from
  * the bound shapes; what no shape shows (the conv strides, max_bucket_distance, layer_norm_eps) comes from
  * sty_wavlm_set_config, called before sty_model_finalize.  Built: feat_extract_norm "group", do_stable_layer_norm false,
- * conv_bias false, exact GELU.  Forward only, fp32 operands on the fp32 matrix cores: compute_bf16,
- * sty_model_enable_training and sty_model_bind_grad return STY_EINVAL for this kind.
+ * conv_bias false, exact GELU.  Frozen, fp32 operands on the fp32 matrix cores: compute_bf16,
+ * sty_model_enable_training and sty_model_bind_grad return STY_EINVAL for this kind (the gradient with respect to the wave is
+ * built, see below; no weight gradient is).
  * Resampler: torchaudio.transforms.Resample(orig, new) with its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff
  * 0.99) restated from the documented closed form -- torchaudio is no dependency: PARITY UNPINNED at this boundary.  The rates are
  * reduced by their gcd (24000 -> 16000 is 3 -> 2: two phases of 23 taps at stride 3); sty_slm_resample_len = ceil(N new /
@@ -551,6 +552,26 @@ int sty_wavlm_fwd(sty_model *m, int B, int N16, const float *audio16, float *hid
 int sty_wavlm_rel_buckets_host(int T, int num_buckets, int max_distance, int32_t *out);
 int sty_slm_loss_workspace_bytes(size_t n, size_t *bytes);
 int sty_slm_loss_fwd(size_t n, const float *a, const float *b, float *loss, void *workspace, size_t ws_bytes, void *stream);
+/* The gradient of the slm term with respect to the predicted wave: the input-gradient chain of the frozen network.  No kernel
+ * of it uses a float atomic: the same inputs give the same bits, in default and deterministic mode alike.
+ * sty_wavlm_fwd_keep: the hidden states of sty_wavlm_fwd, bit for bit, keeping in the workspace what the backward reads (every
+ *   layer's inputs, pre-activations, q / k / v / o and the attention's row log-sum-exp; nothing is recomputed).  The workspace
+ *   is sized by sty_wavlm_grad_workspace_bytes and must stay untouched until sty_wavlm_bwd.
+ * sty_wavlm_bwd: d_hidden [layers + 1, B, T, hidden_size] (the cotangent of the stack) -> d_audio16 [B, N16], written whole
+ *   (samples no frame reads get 0); d_enc_in (optional, [B, hidden_size, T]): the gradient at the feature projection's output, in
+ *   front of the positional conv.  Consumes the workspace of the sty_wavlm_fwd_keep call before it: without one STY_ESTATE,
+ *   another (B, N16) or workspace STY_ESHAPE, a workspace too small STY_ENOMEM -- all refused on the host, nothing launched.
+ * sty_slm_loss_fwd_bwd: loss as sty_slm_loss_fwd (the same bits) and d_b[i] = scale * sign(b[i] - a[i]) / n, 0 at a tie.
+ * sty_slm_resample_bwd: the adjoint of sty_slm_resample_fwd, d_out [B, ceil(N new / orig)] -> d_audio [B, N]; accumulate != 0:
+ *   d_audio[i] = d_audio[i] + g[i] in one fp32 add. */
+int sty_wavlm_grad_workspace_bytes(const sty_model *m, int B, int N16, size_t *bytes);
+int sty_wavlm_fwd_keep(sty_model *m, int B, int N16, const float *audio16, float *hidden, void *workspace, size_t ws_bytes,
+                       void *stream);
+int sty_wavlm_bwd(sty_model *m, int B, int N16, const float *d_hidden, float *d_audio16, float *d_enc_in, void *workspace,
+                  size_t ws_bytes, void *stream);
+int sty_slm_loss_fwd_bwd(size_t n, const float *a, const float *b, float scale, float *loss, float *d_b, void *workspace,
+                         size_t ws_bytes, void *stream);
+int sty_slm_resample_bwd(int B, int N, int orig, int new_rate, const float *d_out, float *d_audio, int accumulate, void *stream);
 
 /* ---- adversarial terms of the acoustic stage: spectrogram discriminators ---------------
  * SpecDiscriminator (train/models/discriminator.py:13-68): five weight-normed Conv2d 3x9 / 3x3 with LeakyReLU(0.1),

@@ -72,7 +72,8 @@ class AcousticTrainer:
 
     def __init__(self, speech_predictor, style_encoder, lr=1e-4, betas=(0.85, 0.99), eps=1e-9, weight_decay=1e-4,
                  w_mel=5.0, w_phase=8.0, mean=-4.0, std=4.0, bucket_bytes=25 << 20, train_mode=True, seed=0,
-                 text_dropout=0.2, compute="fp32", mrd=None, w_gen=1.0, disc=None, shared_seed=1, deterministic=False):
+                 text_dropout=0.2, compute="fp32", mrd=None, w_gen=1.0, disc=None, shared_seed=1, deterministic=False,
+                 slm_train=None, w_slm=0.0):
         import random
         # deterministic=True switches the process-wide deterministic mode on (lib.set_deterministic) before anything is sized;
         # False leaves the switch as it is (STY_DETERMINISTIC=1 or an earlier call may have set it)
@@ -116,6 +117,11 @@ class AcousticTrainer:
                 m.compute_bf16 = self.bf16
                 self.opt[f"mrd{i}"] = FlatAdamW(list(m.named_parameters()), **kw)
             self.disc_helpers = [DiscriminatorLossHelper(m, 5) for m in self.mrd]
+        # slm_train: a slm.WavLMLoss on the trainer's device -- the fourth term of the reference's acoustic step
+        # (stage_type.py:340-363: mel + multi_phase + generator + slm), w_slm = loss_weight.slm.  The network is frozen and its
+        # gradient local: no parameter, no optimizer state, no collective.  It runs fp32 operands also when compute="bf16".
+        self.slm_train, self.w_slm = slm_train, float(w_slm)
+        self.slm_value = None  # the step's unweighted slm value, a device scalar (like self.gan)
         self.disc = disc  # ContextFreeDiscriminator shell (models.py:74), weight 3 in both losses (losses.py:14)
         if disc is not None:
             from .discriminators import DiscriminatorLossHelper
@@ -186,6 +192,15 @@ class AcousticTrainer:
         """One optimizer step; returns the (mel, multi_phase) loss values as a device tensor [2] (with `mrd`: self.gan
         holds the generator loss and the three discriminator losses of the step, a device tensor [7])."""
         from .losses import acoustic_gan_loss, acoustic_loss, acoustic_loss_target
+        if self.slm_train is not None:
+            # the slm path's host-side refusals (no frame left behind the feature encoder, a shape) are raised here, before the
+            # step has touched anything, as every other refusal of a batch is
+            from .slm import wavlm_frames
+            s = self.slm_train
+            n16 = audio_gt.shape[-1] if s.model_sr == s.slm_sr else L.load().sty_slm_resample_len(int(audio_gt.shape[-1]), s.model_sr, s.slm_sr)
+            if audio_gt.dim() != 2 or wavlm_frames(n16, s.wavlm.cfg) < 1:
+                raise L.StyError(f"AcousticTrainer: the slm term refuses a batch of shape {tuple(audio_gt.shape)}: {n16} samples at "
+                                 f"{s.slm_sr} Hz leave no frame behind the feature encoder")
         for o in self.opt.values():
             o.zero_grad()
         if self.train_mode:
@@ -252,6 +267,9 @@ class AcousticTrainer:
                 gen_w, dsc_w = self.disc.losses(audio_gt, audio.squeeze(1), gen_scale=3.0 * self.w_gen, d_pred=d_audio,
                                                 disc_scale=3.0 * float(texts.shape[0]) ** 0.5, bn_momentum=0.19)
                 self.gan_wave = torch.cat([gen_w, dsc_w])  # generator loss, discriminator loss, the same without tprls
+        if self.slm_train is not None:
+            # + loss_weight.slm x WavLMLoss(audio_gt, audio): the value for the log, the gradient added into d_audio
+            self.slm_value, d_audio = self.slm_train.loss_and_grad(audio_gt, audio.squeeze(1), self.w_slm, d_pred=d_audio)
         if self.mrd is not None:
             # the discriminators' weight gradients are final here (the loss calls above produced them from the same forward
             # pass as the generator term): their buckets travel while the whole predictor / style-encoder backward runs

@@ -163,7 +163,7 @@ struct Builder {
     if (!dry)
       m->jobs.push_back(PackJob::conv(glu ? PK_CONV_GLU : (wn ? PK_CONV_WN : PK_CONV), pc, wn ? nullptr : w->p,
                                       g ? g->p : nullptr, wn ? w->p : nullptr, b, wp, bp));
-    if (m->train_enabled) {
+    if (m->train_enabled || m->kind == "wavlm") {  // (wavlm: frozen, but its input-gradient chain is built)
       if (glu) {  // the training graph runs GLU as a separate op: it needs the plain channel order
         PackedConv pl = pc;
         pl.CoutP = (int)align_up(pc.Cout, 32);
@@ -184,16 +184,20 @@ struct Builder {
   }
 
   // input-gradient weights Wd[k'][co][ci] = Wp[K-1-k'][ci][co] of a packed conv (prepared after the pack jobs)
-  void add_dgrad(const PackedConv& pc) {
+  PackedConv dgrad_shape(const PackedConv& pc) {
     PackedConv d;
     d.Cin = pc.Cout;
     d.CinP = pc.CoutP;
     d.Cout = pc.Cin;
     d.CoutP = pc.CinP;
     d.K = pc.K;
-    float* wd = m->ab.take<float>((size_t)pc.K * pc.CinP * pc.CoutP);
-    d.wp = wd;
+    d.wp = m->ab.take<float>((size_t)pc.K * pc.CinP * pc.CoutP);
     d.bias = nullptr;
+    return d;
+  }
+  void add_dgrad(const PackedConv& pc) {
+    const PackedConv d = dgrad_shape(pc);
+    float* wd = const_cast<float*>(d.wp);
     if (!dry) {
       m->jobs.push_back(PackJob::dgrad(pc, wd));
       m->dgrad[pc.wp] = d;
@@ -690,6 +694,8 @@ struct Builder {
     if (!dry) p.packs.clear();
     p.layers.clear();
     p.pos.clear();
+    p.pos_d.clear();
+    m->wav_keep = WavlmKeep();
     if (p.n_conv < 2) {
       if (ok) m->missing = "the conv strides (sty_wavlm_set_config was not called)";
       ok = false;
@@ -718,6 +724,7 @@ struct Builder {
         j.Cout = C, j.Cin = cin, j.K = k, j.s = s, j.CinP = pc.CinP, j.CoutP = pc.CoutP;
         pc.wp = j.wp;
         p.conv[i] = pc;
+        p.conv_d[i] = dgrad_shape(pc);
         if (!dry && ok) p.packs.push_back(j);
       }
       cin = C;
@@ -750,6 +757,7 @@ struct Builder {
         j.Cout = Cg, j.Cin = Cg, j.K = K, j.s = 1, j.CinP = pc.CinP, j.CoutP = pc.CoutP, j.co0 = gi * Cg;
         pc.wp = j.wp, pc.bias = j.bp;
         p.pos.push_back(pc);
+        p.pos_d.push_back(dgrad_shape(pc));
         if (!dry && ok) p.packs.push_back(j);
       }
     }
@@ -1764,10 +1772,35 @@ static int wavlm_frames_at(const WavlmPlan& p, int N16, int layer) {
 }
 // WavLMModel.forward(output_hidden_states=True) in eval mode (modeling_wavlm.py): audio16 [B][N16] -> hidden [layers + 1][B][T][H].
 // Every activation is channel-major [B][C][T]; wavlm.hip says what each of its kernels does.
-static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden) {
+// kp (sty_wavlm_fwd_keep): the same launches on the same operands, so the same bits, except that (a) every tensor the backward
+// reads gets a buffer of its own at the front of the workspace, (b) a conv followed by GELU leaves its pre-activation and the
+// GELU runs behind it (wavlm_stage_kernel / wavlm_gelu_kernel: the conv epilogue's expression on the same fp32 value),
+// (c) the attention keeps its row log-sum-exp.
+static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden, WavlmKeep* kp = nullptr) {
   sty_model* m = r.m;
   const WavlmPlan& p = m->wav;
   const int B = r.B, nc = p.n_conv, H = p.hidden, NH = p.heads, DH = H / NH;
+  if (kp) {
+    *kp = WavlmKeep();
+    const size_t bc0 = (size_t)B * p.dim[0], nn = (size_t)B * H * wavlm_frames_at(p, N16, nc - 1);
+    const size_t nh = nn / H * NH, nf = nn / H * p.layers[0].f1.Cout;
+    kp->out0 = r.ws.take<float>(bc0 * wavlm_frames_at(p, N16, 0));
+    kp->ga = r.ws.take<float>(bc0), kp->gs = r.ws.take<float>(bc0), kp->gmean = r.ws.take<float>(bc0), kp->grstd = r.ws.take<float>(bc0);
+    for (int i = 1; i < nc; ++i) kp->pre[i] = r.ws.take<float>((size_t)B * p.dim[i] * wavlm_frames_at(p, N16, i));
+    kp->feat = r.ws.take<float>(nn / H * p.dim[nc - 1]);
+    kp->pre_pos = r.ws.take<float>(nn), kp->xa_enc = r.ws.take<float>(nn);
+    kp->tab = r.ws.take<float>((size_t)NH * (2 * (nn / H / B) - 1));
+    for (size_t l = 0; l <= p.layers.size(); ++l) kp->x.push_back(r.ws.take<float>(nn));
+    for (size_t l = 0; l < p.layers.size(); ++l) {
+      WavlmKeepLayer y;
+      y.q = r.ws.take<float>(nn), y.k = r.ws.take<float>(nn), y.v = r.ws.take<float>(nn), y.o = r.ws.take<float>(nn);
+      y.a1 = r.ws.take<float>(nn), y.a2 = r.ws.take<float>(nn);
+      y.lse = r.ws.take<float>(nh), y.gate = r.ws.take<float>(nh);
+      y.pre = r.ws.take<float>(nf);
+      kp->layers.push_back(y);
+    }
+    kp->saved_end = r.ws.off;
+  }
   int Tl[WAVLM_MAX_CONV], Tp[WAVLM_MAX_CONV] = {0};
   size_t max_out = 0, max_stage = 0;
   for (int i = 0; i < nc; ++i) {
@@ -1790,20 +1823,25 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden) {
     double* part = r.ws.take<double>((size_t)B * p.dim[0] * nt * 2);
     float* ga = r.ws.take<float>((size_t)B * p.dim[0]);
     float* gs = r.ws.take<float>((size_t)B * p.dim[0]);
+    if (kp) ga = kp->ga, gs = kp->gs;
     if (r.live()) {
-      r.chk(launch_wavlm_conv0(audio, p.conv0_w, B, N16, p.dim[0], p.kern[0], p.stride[0], Tl[0], out, part, r.st));
-      r.chk(launch_wavlm_gn_finalize(part, nt, p.gn_w, p.gn_b, B * p.dim[0], p.dim[0], Tl[0], 1e-5f, ga, gs, r.st));
+      r.chk(launch_wavlm_conv0(audio, p.conv0_w, B, N16, p.dim[0], p.kern[0], p.stride[0], Tl[0], kp ? kp->out0 : out, part, r.st));
+      r.chk(launch_wavlm_gn_finalize(part, nt, p.gn_w, p.gn_b, B * p.dim[0], p.dim[0], Tl[0], 1e-5f, ga, gs, r.st,
+                                     kp ? kp->gmean : nullptr, kp ? kp->grstd : nullptr));
     }
     for (int i = 1; i < nc && r.live(); ++i) {
-      r.chk(launch_wavlm_stage(out, i == 1 ? ga : nullptr, gs, B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], stg, r.st));
-      ConvArgs a = r.base(p.conv[i], stg, Tl[i], out);
+      const float* below = !kp ? out : (i == 1 ? kp->out0 : kp->pre[i - 1]);
+      r.chk(launch_wavlm_stage(below, i == 1 ? ga : nullptr, gs, B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], stg, r.st,
+                               kp && i > 1));
+      ConvArgs a = r.base(p.conv[i], stg, Tl[i], kp ? kp->pre[i] : out);
       a.pad = 0;
       a.Tin = Tp[i] != Tl[i] ? Tp[i] : 0;
-      a.act = ACT_GELU;
+      a.act = kp ? ACT_NONE : ACT_GELU;
       r.conv(a);
     }
     if (r.live()) {
-      r.chk(launch_chan_layernorm(out, stg, B, Cl, T, p.ln_eps, 0, p.fp_ln_w, p.fp_ln_b, nullptr, 0, nullptr, r.st));
+      if (kp) r.chk(launch_wavlm_gelu(kp->pre[nc - 1], nullptr, (size_t)B * Cl * T, kp->feat, r.st));
+      r.chk(launch_chan_layernorm(kp ? kp->feat : out, stg, B, Cl, T, p.ln_eps, 0, p.fp_ln_w, p.fp_ln_b, nullptr, 0, nullptr, r.st));
       r.conv(r.base(p.proj, stg, T, x));
     }
   }
@@ -1818,21 +1856,27 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden) {
   float* big = r.ws.take<float>((size_t)B * FF * T);
   float* gate = r.ws.take<float>((size_t)B * NH * T);
   float* tab = r.ws.take<float>((size_t)NH * (2 * T - 1));
+  if (kp) tab = kp->tab;
   r.note_peak();
   if (!r.live()) return;
   {  // x + GELU(pos_conv(x)) in the group-major layout (q, k as scratch), then the LayerNorm
     r.chk(launch_wavlm_group_perm(x, B, G, Cg, T, 1, q, r.st));
     for (int g = 0; g < G && r.live(); ++g) {
       const size_t off = (size_t)g * B * Cg * T;
-      ConvArgs a = r.base(p.pos[g], q + off, T, k + off);
+      ConvArgs a = r.base(p.pos[g], q + off, T, (kp ? kp->pre_pos : k) + off);
       a.pad = p.pos_k / 2;
-      a.act = ACT_GELU;
-      a.residual = q + off;
+      if (!kp) {
+        a.act = ACT_GELU;
+        a.residual = q + off;
+      }
       r.conv(a);
     }
     if (!r.live()) return;
-    r.chk(launch_wavlm_group_perm(k, B, G, Cg, T, 0, xa, r.st));
-    r.chk(launch_chan_layernorm(xa, x, B, H, T, p.ln_eps, 0, p.enc_ln_w, p.enc_ln_b, nullptr, 0, nullptr, r.st));
+    if (kp) r.chk(launch_wavlm_gelu(kp->pre_pos, q, n, k, r.st));
+    float* ln_in = kp ? kp->xa_enc : xa;
+    if (kp) x = kp->x[0];
+    r.chk(launch_wavlm_group_perm(k, B, G, Cg, T, 0, ln_in, r.st));
+    r.chk(launch_chan_layernorm(ln_in, x, B, H, T, p.ln_eps, 0, p.enc_ln_w, p.enc_ln_b, nullptr, 0, nullptr, r.st));
     r.chk(launch_wavlm_transpose_out(x, B, H, T, hidden, r.st));
   }
   {  // the position bias table of this frame count, shared by every layer.  The bucket table is one per model: sized for the
@@ -1857,6 +1901,13 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden) {
   }
   for (size_t l = 0; l < p.layers.size() && r.live(); ++l) {
     const WavlmLayer& y = p.layers[l];
+    float* a2 = xa;
+    if (kp) {  // this layer's kept tensors in the scratch buffers' places; x = its input, xo its output
+      const WavlmKeepLayer& kl = kp->layers[l];
+      q = kl.q, k = kl.k, v = kl.v, o = kl.o, gate = kl.gate, xa = kl.a1, a2 = kl.a2;
+      x = kp->x[l];
+    }
+    float* xo = kp ? kp->x[l + 1] : x;
     r.chk(launch_wavlm_gate(x, y.gate_w, y.gate_b, y.gate_c, B, NH, DH, T, gate, r.st));
     r.conv(r.base(y.q, x, T, q));
     r.conv(r.base(y.k, x, T, k));
@@ -1869,22 +1920,173 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden) {
     at.scale = 1.0f / sqrtf((float)DH);
     at.lengths = nullptr;
     at.rel_tab = tab, at.rel_gate = gate;
+    if (kp) at.lse = kp->layers[l].lse;
     r.chk(launch_attention(at, B, DH, r.st));
     ConvArgs ao = r.base(y.o, o, T, xa);
     ao.residual = x;
     r.conv(ao);
     if (!r.live()) return;
     r.chk(launch_chan_layernorm(xa, xb, B, H, T, p.ln_eps, 0, y.ln1_w, y.ln1_b, nullptr, 0, nullptr, r.st));
-    ConvArgs f1 = r.base(y.f1, xb, T, big);
-    f1.act = ACT_GELU;
+    ConvArgs f1 = r.base(y.f1, xb, T, kp ? kp->layers[l].pre : big);
+    f1.act = kp ? ACT_NONE : ACT_GELU;
     r.conv(f1);
-    ConvArgs f2 = r.base(y.f2, big, T, xa);
+    if (kp && r.live()) r.chk(launch_wavlm_gelu(kp->layers[l].pre, nullptr, (size_t)B * FF * T, big, r.st));
+    ConvArgs f2 = r.base(y.f2, big, T, a2);
     f2.residual = xb;
     r.conv(f2);
     if (!r.live()) return;
-    r.chk(launch_chan_layernorm(xa, x, B, H, T, p.ln_eps, 0, y.ln2_w, y.ln2_b, nullptr, 0, nullptr, r.st));
-    r.chk(launch_wavlm_transpose_out(x, B, H, T, hidden + (l + 1) * n, r.st));
+    r.chk(launch_chan_layernorm(a2, xo, B, H, T, p.ln_eps, 0, y.ln2_w, y.ln2_b, nullptr, 0, nullptr, r.st));
+    r.chk(launch_wavlm_transpose_out(xo, B, H, T, hidden + (l + 1) * n, r.st));
   }
+}
+
+// The backward of wavlm_forward to the wave: d_hidden [layers + 1][B][T][H] -> d_audio [B][N16] (and the optional tap d_enc_in
+// [B][H][T] in front of the positional conv), on the tensors a keep-mode forward left.  Input gradients only (the network is
+// frozen); the steps cite modeling_wavlm.py as the forward does.  Scratch starts behind the kept tensors.
+static void wavlm_backward(Run& r, int N16, const WavlmKeep& kp, const float* d_hidden, float* d_audio, float* d_enc_in) {
+  sty_model* m = r.m;
+  const WavlmPlan& p = m->wav;
+  const int B = r.B, nc = p.n_conv, H = p.hidden, NH = p.heads, DH = H / NH;
+  int Tl[WAVLM_MAX_CONV], Tp[WAVLM_MAX_CONV] = {0};
+  size_t max_out = 0, max_stage = 0;
+  for (int i = 0; i < nc; ++i) {
+    Tl[i] = wavlm_frames_at(p, N16, i);
+    max_out = std::max(max_out, (size_t)B * p.dim[i] * Tl[i]);
+    if (i) {
+      Tp[i] = Tl[i] + p.conv[i].K - 1;
+      max_stage = std::max(max_stage, (size_t)B * p.conv[i].Cin * Tp[i]);
+    }
+  }
+  const int T = Tl[nc - 1], Cl = p.dim[nc - 1], G = p.pos_groups, Cg = H / G, FF = p.layers[0].f1.Cout;
+  const int L = (int)p.layers.size();
+  const size_t n = (size_t)B * H * T;
+  r.ws.off = kp.saved_end;
+  float* g = r.ws.take<float>(n);   // gradient at the current layer's output
+  float* t1 = r.ws.take<float>(n);
+  float* t2 = r.ws.take<float>(n);
+  float* dq = r.ws.take<float>(n);
+  float* dk = r.ws.take<float>(n);
+  float* dv = r.ws.take<float>(n);
+  float* dbig = r.ws.take<float>((size_t)B * FF * T);
+  float* dpre = r.ws.take<float>((size_t)B * FF * T);
+  float* dgate = r.ws.take<float>((size_t)B * NH * T);
+  float* aws = r.ws.take<float>(attention_bwd_ws_floats(B, NH, T));
+  float* mu = r.ws.take<float>((size_t)B * std::max(T, 64));
+  float* rt = r.ws.take<float>((size_t)B * std::max(T, 64));
+  float* fa = r.ws.take<float>(max_out);
+  float* fb = r.ws.take<float>(max_out);
+  float* dvw = r.ws.take<float>(max_stage);
+  const int gnt = wavlm_gn_bwd_ntiles(Tl[0]);
+  double* gpart = r.ws.take<double>((size_t)B * p.dim[0] * gnt * 2);
+  float* gcoef = r.ws.take<float>((size_t)B * p.dim[0] * 2);
+  r.note_peak();
+  if (!r.live()) return;
+  static const PackedConv none;
+  auto D = [&](const PackedConv& w) -> const PackedConv& {  // the input-gradient weights of a conv of the dgrad table
+    auto it = m->dgrad.find(w.wp);
+    if (it != m->dgrad.end()) return it->second;
+    if (r.rc == STY_OK) {
+      set_error("wavlm_backward: a conv without input-gradient weights (the model was not finalized for the kind)");
+      r.rc = STY_ESTATE;
+    }
+    return none;
+  };
+  auto ln_bwd = [&](const float* x, const float* dy, int C, const float* w, float* dx) {  // input gradient alone
+    r.chk(launch_chan_ln_bwd(x, dy, nullptr, B, C, T, p.ln_eps, 0, w, nullptr, 0, nullptr, dx, 0, mu, rt, nullptr, nullptr, nullptr, r.st));
+  };
+  auto zero = [&](float* x, size_t cnt) {
+    if (r.live() && hipMemsetAsync(x, 0, cnt * sizeof(float), r.st) != hipSuccess) {
+      set_error("wavlm_backward: hipMemsetAsync failed");
+      r.rc = STY_EHIP;
+    }
+  };
+  // (1) cotangent of the last hidden state; every other one is added where its layer's gradient is complete
+  r.chk(launch_wavlm_intake(d_hidden + (size_t)L * n, B, H, T, 0, g, r.st));
+  // (2) encoder layers, post-norm: x_out = LN2(xb + f2(GELU(f1(xb)))), xb = LN1(x + out_proj(attn(x)))
+  for (int l = L - 1; l >= 0 && r.live(); --l) {
+    const WavlmLayer& y = p.layers[l];
+    const WavlmKeepLayer& kl = kp.layers[l];
+    ln_bwd(kl.a2, g, H, y.ln2_w, t1);                      // t1 = d (xb + f2(..))
+    r.conv(r.base(D(y.f2), t1, T, dbig));
+    if (!r.live()) return;
+    r.chk(launch_act_bwd(ACT_GELU, kl.pre, dbig, nullptr, B, FF, T, dpre, 0, nullptr, r.st));
+    ConvArgs f1 = r.base(D(y.f1), dpre, T, t2);
+    f1.residual = t1;
+    r.conv(f1);                                            // t2 = d xb
+    if (!r.live()) return;
+    ln_bwd(kl.a1, t2, H, y.ln1_w, t1);                     // t1 = d (x + out_proj(attn))
+    r.conv(r.base(D(y.o), t1, T, t2));                     // t2 = d attn output
+    zero(dq, n), zero(dk, n), zero(dv, n);                 // (the attention backward accumulates)
+    if (!r.live()) return;
+    // (3) attention with the gated relative position bias: dq, dk, dv and d gate, no [B H][T][T] bias tensor
+    AttnArgs at;
+    at.q = kl.q, at.k = kl.k, at.v = kl.v, at.o = kl.o;
+    at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * T;
+    at.T = T, at.H = NH;
+    at.scale = 1.0f / sqrtf((float)DH);
+    at.lengths = nullptr;
+    at.lse = kl.lse;
+    at.rel_tab = kp.tab, at.rel_gate = kl.gate, at.rel_dgate = dgate;
+    r.chk(launch_attention_bwd(at, t2, dq, dk, dv, at.qbs, at.kbs, at.vbs, at.obs, B, DH, aws, r.st));
+    // dx = residual + q / k / v projections' input gradients (+ the gate path, + this layer input's own cotangent)
+    ConvArgs cq = r.base(D(y.q), dq, T, t2);
+    cq.residual = t1;
+    r.conv(cq);
+    ConvArgs ck = r.base(D(y.k), dk, T, t1);
+    ck.residual = t2;
+    r.conv(ck);
+    ConvArgs cv = r.base(D(y.v), dv, T, g);
+    cv.residual = t1;
+    r.conv(cv);
+    if (!r.live()) return;
+    // (4) gate backward into the head slices
+    r.chk(launch_wavlm_gate_bwd(kp.x[l], y.gate_w, y.gate_b, y.gate_c, dgate, B, NH, DH, T, g, r.st));
+    r.chk(launch_wavlm_intake(d_hidden + (size_t)l * n, B, H, T, 1, g, r.st));
+  }
+  if (!r.live()) return;
+  // (5) encoder LayerNorm, then x + GELU(pos_conv(x)): GELU' in front of the grouped dgrad, the residual around it.  The forward
+  // pads k / 2 and never computes the even kernel's last frame, so the flipped taps are padded k / 2 - 1.
+  ln_bwd(kp.xa_enc, g, H, p.enc_ln_w, t1);
+  r.chk(launch_wavlm_group_perm(t1, B, G, Cg, T, 1, t2, r.st));
+  r.chk(launch_act_bwd(ACT_GELU, kp.pre_pos, t2, nullptr, G * B, Cg, T, dq, 0, nullptr, r.st));
+  for (int gi = 0; gi < G && r.live(); ++gi) {
+    const size_t off = (size_t)gi * B * Cg * T;
+    ConvArgs a = r.base(p.pos_d[gi], dq + off, T, dk + off);
+    a.pad = p.pos_k - 1 - p.pos_k / 2;
+    a.residual = t2 + off;
+    r.conv(a);
+  }
+  if (!r.live()) return;
+  r.chk(launch_wavlm_group_perm(dk, B, G, Cg, T, 0, t1, r.st));  // t1 = gradient at the feature projection's output
+  if (d_enc_in && hipMemcpyAsync(d_enc_in, t1, n * sizeof(float), hipMemcpyDeviceToDevice, r.st) != hipSuccess) {
+    set_error("wavlm_backward: the copy of the tap failed");
+    r.rc = STY_EHIP;
+    return;
+  }
+  // (6) feature projection: 1x1 dgrad, LayerNorm, then the GELU' of the last feature conv
+  r.conv(r.base(D(p.proj), t1, T, fa));
+  if (!r.live()) return;
+  ln_bwd(kp.feat, fa, Cl, p.fp_ln_w, fb);
+  r.chk(launch_act_bwd(ACT_GELU, kp.pre[nc - 1], fb, nullptr, B, Cl, T, fa, 0, nullptr, r.st));
+  // (7) strided feature convs: the stride-1 conv over the s-frames-at-a-time view, transposed (full correlation: pad K - 1), then
+  // the un-staging permutation with the GELU' of the layer below; (8) behind layer 0 the GroupNorm backward takes its place
+  float *cur = fa, *other = fb;
+  for (int i = nc - 1; i >= 1 && r.live(); --i) {
+    ConvArgs a = r.base(p.conv_d[i], cur, Tp[i], dvw);
+    a.pad = p.conv[i].K - 1;
+    a.Tin = Tp[i] != Tl[i] ? Tl[i] : 0;
+    r.conv(a);
+    if (!r.live()) return;
+    if (i > 1)
+      r.chk(launch_wavlm_unstage(dvw, kp.pre[i - 1], B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], other, r.st));
+    else
+      r.chk(launch_wavlm_gn_bwd(kp.out0, dvw, kp.ga, kp.gs, kp.gmean, kp.grstd, B, p.dim[0], Tl[0], p.stride[1], Tp[1], gpart, gcoef, other,
+                                r.st));
+    std::swap(cur, other);
+  }
+  if (!r.live()) return;
+  // (9) layer 0 transposed: the whole d_audio, the tail no frame reads included (zero)
+  r.chk(launch_wavlm_conv0_bwd(cur, p.conv0_w, B, N16, p.dim[0], p.kern[0], p.stride[0], Tl[0], d_audio, r.st));
 }
 
 static int run_style_fc(Run& r, const float* style) {
@@ -2585,15 +2787,17 @@ int sty_slm_resample_kernel_host(int orig, int new_rate, float* out) {
   if (out) build_resample_kernel(o, n, 6.0, out);
   return n * (2 * resample_width(o, n, 6.0) + o);
 }
-int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float* audio, float* out, void* stream) {
-  if (!audio || !out || B <= 0 || N <= 0 || !resample_rates_ok(orig, new_rate)) {
-    set_error("sty_slm_resample_fwd: bad argument");
+// the forward (d_accumulate < 0: x = audio [B][N] -> y = out [B][M]) and its adjoint (y = d_out -> x = d_audio, written or added to)
+static int slm_resample_run(const char* who, int B, int N, int orig, int new_rate, const float* src, float* dst, int d_accumulate,
+                            void* stream) {
+  if (!src || !dst || B <= 0 || N <= 0 || !resample_rates_ok(orig, new_rate)) {
+    set_error("%s: bad argument", who);
     return STY_EINVAL;
   }
   const int g = gcd_(orig, new_rate), o = orig / g, n = new_rate / g, width = resample_width(o, n, 6.0);
   const size_t floats = (size_t)n * (2 * width + o);
   if (floats * sizeof(float) > 48 * 1024) {
-    set_error("sty_slm_resample_fwd: %d -> %d needs a table of %zu taps (more than the kernel keeps)", orig, new_rate, floats);
+    set_error("%s: %d -> %d needs a table of %zu taps (more than the kernel keeps)", who, orig, new_rate, floats);
     return STY_EINVAL;
   }
   // device tables by (device, reduced rate pair), built on first use under a lock; a table is cached only once it is filled
@@ -2619,7 +2823,15 @@ int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float* audi
     }
     dev = slot;
   }
-  return launch_resample_fir(audio, dev, B, N, sty_slm_resample_len(N, orig, new_rate), o, n, width, out, S(stream));
+  const int M = sty_slm_resample_len(N, orig, new_rate);
+  if (d_accumulate >= 0) return launch_resample_fir_bwd(src, dev, B, N, M, o, n, width, d_accumulate, dst, S(stream));
+  return launch_resample_fir(src, dev, B, N, M, o, n, width, dst, S(stream));
+}
+int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float* audio, float* out, void* stream) {
+  return slm_resample_run("sty_slm_resample_fwd", B, N, orig, new_rate, audio, out, -1, stream);
+}
+int sty_slm_resample_bwd(int B, int N, int orig, int new_rate, const float* d_out, float* d_audio, int accumulate, void* stream) {
+  return slm_resample_run("sty_slm_resample_bwd", B, N, orig, new_rate, d_out, d_audio, accumulate ? 1 : 0, stream);
 }
 int sty_wavlm_frames(const sty_model* m, int N16, int* T) {
   int rc = model_ready(m, "wavlm");
@@ -2660,6 +2872,76 @@ int sty_wavlm_fwd(sty_model* m, int B, int N16, const float* audio16, float* hid
   if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
   return wavlm_run(m, B, N16, audio16, hidden, workspace, ws_bytes, stream, nullptr);
 }
+// ---- the backward to the wave: forward that keeps, then sty_wavlm_bwd on the same workspace ----
+static int wavlm_grad_need(sty_model* m, int B, int N16, size_t* need) {
+  Run r(m, B, nullptr, 0, nullptr);
+  WavlmKeep kp;
+  wavlm_forward(r, N16, nullptr, nullptr, &kp);
+  wavlm_backward(r, N16, kp, nullptr, nullptr, nullptr);
+  return r.finish(need, nullptr, 0);
+}
+int sty_wavlm_grad_workspace_bytes(const sty_model* m, int B, int N16, size_t* bytes) {
+  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
+  if (rc) return rc;
+  if (!bytes || B <= 0) {
+    set_error("sty_wavlm_grad_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  return wavlm_grad_need(const_cast<sty_model*>(m), B, N16, bytes);
+}
+int sty_wavlm_fwd_keep(sty_model* m, int B, int N16, const float* audio16, float* hidden, void* workspace, size_t ws_bytes, void* stream) {
+  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
+  if (rc) return rc;
+  if (!audio16 || !hidden || !workspace || B <= 0) {
+    set_error("sty_wavlm_fwd_keep: bad argument");
+    return STY_EINVAL;
+  }
+  m->wav_keep.valid = false;
+  size_t need = 0;
+  if ((rc = wavlm_grad_need(m, B, N16, &need))) return rc;
+  if (ws_bytes < need) {  // refused on the host: nothing is launched into a workspace that cannot hold the kept tensors
+    set_error("sty_wavlm_fwd_keep: workspace too small: need %zu bytes, have %zu", need, ws_bytes);
+    return STY_ENOMEM;
+  }
+  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  Run r(m, B, workspace, ws_bytes, stream);
+  wavlm_forward(r, N16, audio16, hidden, &m->wav_keep);
+  rc = r.finish(nullptr, workspace, ws_bytes);
+  if (rc == STY_OK) {
+    m->wav_keep.valid = true;
+    m->wav_keep.B = B, m->wav_keep.N16 = N16, m->wav_keep.ws = workspace;
+  }
+  return rc;
+}
+int sty_wavlm_bwd(sty_model* m, int B, int N16, const float* d_hidden, float* d_audio16, float* d_enc_in, void* workspace,
+                  size_t ws_bytes, void* stream) {
+  int rc = model_ready(m, "wavlm");
+  if (rc) return rc;
+  if (!d_hidden || !d_audio16 || !workspace || B <= 0 || N16 <= 0) {
+    set_error("sty_wavlm_bwd: bad argument");
+    return STY_EINVAL;
+  }
+  WavlmKeep& kp = m->wav_keep;
+  if (!kp.valid) {
+    set_error("sty_wavlm_bwd: no sty_wavlm_fwd_keep call precedes it (a backward consumes its forward's workspace)");
+    return STY_ESTATE;
+  }
+  if (kp.B != B || kp.N16 != N16 || kp.ws != workspace) {
+    set_error("sty_wavlm_bwd: (B, N16) = (%d, %d) on this workspace, but the forward kept (%d, %d)%s", B, N16, kp.B, kp.N16,
+              kp.ws != workspace ? " in another workspace" : "");
+    return STY_ESHAPE;
+  }
+  size_t need = 0;
+  if ((rc = wavlm_grad_need(m, B, N16, &need))) return rc;
+  if (ws_bytes < need) {
+    set_error("sty_wavlm_bwd: workspace too small: need %zu bytes, have %zu", need, ws_bytes);
+    return STY_ENOMEM;
+  }
+  kp.valid = false;  // consumed: the scratch of this call overwrites nothing kept, but a second backward is not the contract
+  Run r(m, B, workspace, ws_bytes, stream);
+  wavlm_backward(r, N16, kp, d_hidden, d_audio16, d_enc_in);
+  return r.finish(nullptr, workspace, ws_bytes);
+}
 int sty_wavlm_rel_buckets_host(int T, int num_buckets, int max_distance, int32_t* out) {
   if (T < 1 || num_buckets < 4 || max_distance < 2 || !out || max_distance <= num_buckets / 4) {
     set_error("sty_wavlm_rel_buckets_host: bad argument");
@@ -2686,6 +2968,21 @@ int sty_slm_loss_fwd(size_t n, const float* a, const float* b, float* loss, void
     return STY_ENOMEM;
   }
   return launch_slm_loss(n, a, b, loss, (double*)workspace, S(stream));
+}
+int sty_slm_loss_fwd_bwd(size_t n, const float* a, const float* b, float scale, float* loss, float* d_b, void* workspace, size_t ws_bytes,
+                         void* stream) {
+  if (!a || !b || !loss || !d_b || !workspace || n == 0 || ((uintptr_t)workspace & 7)) {
+    set_error("sty_slm_loss_fwd_bwd: bad argument");
+    return STY_EINVAL;
+  }
+  if (ws_bytes < (size_t)slm_loss_groups(n) * sizeof(double)) {
+    set_error("sty_slm_loss_fwd_bwd: workspace too small");
+    return STY_ENOMEM;
+  }
+  // d mean|a - b| / d b = sign(b - a) / n, times scale: one magnitude, formed as torch's division by a host scalar is
+  // (a multiplication by the fp32 reciprocal)
+  const float mag = scale * (1.0f / (float)n);
+  return launch_slm_loss(n, a, b, loss, (double*)workspace, S(stream), mag, d_b);
 }
 // ---- text aligner in the training graph (train_alignment, stage_type.py:268-341): forward, then sty_aligner_bwd ----
 int sty_aligner_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {

@@ -12,7 +12,10 @@
 
 namespace sty {
 
-template <int DH>
+// REL (kernels A, B, C and the matrix-core pair): the gated relative position bias of WavLM, s_ij += rel_gate[b][h][i] *
+// rel_tab[h][j - i + T - 1].  The table is frozen; the one new quantity is d gate[b][h][i] = sum_j ds_ij tab[h][j - i], summed by
+// the kernel that owns query row i (C, the q kernel) in a fixed order and WRITTEN to a.rel_dgate: no atomic.
+template <int DH, bool REL = false>
 __global__ __launch_bounds__(64) void attn_bwd_a_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                         float* __restrict__ lse, float* __restrict__ delta) {
   const int T = a.T, b = blockIdx.z, h = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
@@ -31,10 +34,13 @@ __global__ __launch_bounds__(64) void attn_bwd_a_kernel(AttnArgs a, const float*
   }
   float m = -3.0e38f, l = 0.f;
   const bool qpad = a.lengths && i >= len;
+  const float rg = REL ? a.rel_gate[((size_t)b * a.H + h) * T + i] : 0.f;
+  const float* rrow = REL ? a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 - i) : nullptr;
   for (int j = 0; j < T; ++j) {
     float s = 0.f;
 #pragma unroll
     for (int d = 0; d < DH; ++d) s = fmaf(q[d], kb[(size_t)d * T + j], s);
+    if constexpr (REL) s = fmaf(rg, rrow[j], s);
     if (a.lengths && (qpad || j >= len)) s += -1e4f;
     const float mn = fmaxf(m, s);
     l = l * expf(m - mn) + expf(s - mn);
@@ -45,7 +51,7 @@ __global__ __launch_bounds__(64) void attn_bwd_a_kernel(AttnArgs a, const float*
   delta[o] = dl;
 }
 
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool REL = false>
 __global__ __launch_bounds__(64) void attn_bwd_c_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                         const float* __restrict__ lse, const float* __restrict__ delta,
                                                         float* __restrict__ dQ, size_t dqbs) {
@@ -66,6 +72,9 @@ __global__ __launch_bounds__(64) void attn_bwd_c_kernel(AttnArgs a, const float*
     acc[d] = 0.f;
   }
   const bool qpad = a.lengths && i >= len;
+  const float rg = REL ? a.rel_gate[oi] : 0.f;
+  const float* rrow = REL ? a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 - i) : nullptr;
+  float dgate = 0.f;
   for (int j = 0; j < T; ++j) {
     float s = 0.f, dp = 0.f;
 #pragma unroll
@@ -73,15 +82,18 @@ __global__ __launch_bounds__(64) void attn_bwd_c_kernel(AttnArgs a, const float*
       s = fmaf(q[d], kb[(size_t)d * T + j], s);
       dp = fmaf(g[d], vb[(size_t)d * T + j], dp);
     }
+    if constexpr (REL) s = fmaf(rg, rrow[j], s);
     if (a.lengths && (qpad || j >= len)) s += -1e4f;
     if constexpr (DROP) {
       const unsigned idx = ((unsigned)(b * a.H + h) * (unsigned)T + (unsigned)i) * (unsigned)T + (unsigned)j;
       dp = sty_hash_u(a.drop_seed, a.drop_site, idx) >= a.drop_p ? dp / (1.0f - a.drop_p) : 0.f;
     }
     const float ds = expf(s - L) * (dp - dl);
+    if constexpr (REL) dgate = fmaf(ds, rrow[j], dgate);
 #pragma unroll
     for (int d = 0; d < DH; ++d) acc[d] = fmaf(ds, kb[(size_t)d * T + j], acc[d]);
   }
+  if constexpr (REL) a.rel_dgate[oi] = dgate;
   float* dq = dQ + (size_t)b * dqbs + (size_t)h * DH * T;
 #pragma unroll
   for (int d = 0; d < DH; ++d) dq[(size_t)d * T + i] += acc[d] * a.scale;
@@ -90,7 +102,7 @@ __global__ __launch_bounds__(64) void attn_bwd_c_kernel(AttnArgs a, const float*
 // 4 waves per workgroup share one 64-key tile and split the query range; their partial dK / dV are summed through
 // LDS in a fixed order (wave 0 + 1 + 2 + 3).  (One wave per tile took 2.6 ms for the conformer's 8 x 64 heads at
 // T = 160: 384 waves on 1024 SIMDs.)
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool REL = false>
 __global__ __launch_bounds__(256) void attn_bwd_b_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                          const float* __restrict__ lse, const float* __restrict__ delta,
                                                          float* __restrict__ dK, size_t dkbs, float* __restrict__ dV,
@@ -126,6 +138,8 @@ __global__ __launch_bounds__(256) void attn_bwd_b_kernel(AttnArgs a, const float
       dp = fmaf(gb[(size_t)d * T + i], vs[d * 65 + lane], dp);
     }
     s *= a.scale;
+    if constexpr (REL)
+      if (j < T) s = fmaf(a.rel_gate[((size_t)b * a.H + h) * T + i], a.rel_tab[(size_t)h * (2 * T - 1) + (j - i + T - 1)], s);
     if (a.lengths && (i >= len || j >= len)) s += -1e4f;
     const float p = j < T ? expf(s - Lb[i]) : 0.f;
     float pm = p;  // dropped / rescaled probability that multiplied V in the forward
@@ -200,17 +214,18 @@ __global__ void attn_delta_kernel(const float* __restrict__ o, size_t obs, const
 
 __device__ __forceinline__ int frag_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool REL = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_mfma_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                                const float* __restrict__ lse,
                                                                const float* __restrict__ delta,
                                                                float* __restrict__ dK, size_t dkbs,
                                                                float* __restrict__ dV, size_t dvbs) {
   constexpr int LS = 33, NB = DH / 32;
-  __shared__ float qs[DH * LS], gs[DH * LS], lse_s[32], del_s[32];
+  __shared__ float qs[DH * LS], gs[DH * LS], lse_s[32], del_s[32], gate_s[32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y, T = a.T;
   const int j = blockIdx.x * 128 + wave * 32 + l31;
+  const float* rtab = REL ? a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1) : nullptr;  // entry of distance 0
   const float* qb = a.q + (size_t)b * a.qbs + (size_t)h * DH * T;
   const float* kb = a.k + (size_t)b * a.kbs + (size_t)h * DH * T;
   const float* vb = a.v + (size_t)b * a.vbs + (size_t)h * DH * T;
@@ -245,6 +260,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_mfma_kernel(AttnArgs a, const
     if (tid < 32) {
       lse_s[tid] = i0 + tid < T ? Lb[i0 + tid] : 0.f;
       del_s[tid] = i0 + tid < T ? Db[i0 + tid] : 0.f;
+      if constexpr (REL) gate_s[tid] = i0 + tid < T ? a.rel_gate[((size_t)b * a.H + h) * T + i0 + tid] : 0.f;
     }
     __syncthreads();
     f32x16 s, dp;
@@ -260,6 +276,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_mfma_kernel(AttnArgs a, const
       const int ii = frag_row(r, hi);
       const bool ok = i0 + ii < T && j < T;
       float sv = s[r] * a.scale;
+      if constexpr (REL)
+        if (ok) sv = fmaf(gate_s[ii], rtab[j - (i0 + ii)], sv);
       if (a.lengths && (kpad || i0 + ii >= len)) sv += -1e4f;
       const float p = ok ? expf(sv - lse_s[ii]) : 0.f;
       float mf = 1.f;
@@ -291,7 +309,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_mfma_kernel(AttnArgs a, const
   }
 }
 
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool REL = false>
 __global__ __launch_bounds__(256) void attn_bwd_q_mfma_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                               const float* __restrict__ lse,
                                                               const float* __restrict__ delta,
@@ -311,6 +329,9 @@ __global__ __launch_bounds__(256) void attn_bwd_q_mfma_kernel(AttnArgs a, const 
   const bool qpad = a.lengths && i >= len;
   const float inv_keep = DROP ? 1.0f / (1.0f - a.drop_p) : 1.f;
   const unsigned rowi = ((unsigned)(b * a.H + h) * (unsigned)T + (unsigned)i) * (unsigned)T;
+  const float rg = (REL && i < T) ? a.rel_gate[((size_t)b * a.H + h) * T + i] : 0.f;
+  const float* rrow = REL ? a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 - (i < T ? i : T - 1)) : nullptr;  // rrow[j]: distance j - i
+  float dgate = 0.f;
   float qreg[DH / 2], greg[DH / 2];
 #pragma unroll
   for (int c2 = 0; c2 < DH / 2; ++c2) {
@@ -343,17 +364,27 @@ __global__ __launch_bounds__(256) void attn_bwd_q_mfma_kernel(AttnArgs a, const 
       const int jx = j0 + frag_row(r, hi);
       const bool ok = jx < T && i < T;
       float sv = s[r] * a.scale;
+      float tv = 0.f;
+      if constexpr (REL) {
+        tv = ok ? rrow[jx] : 0.f;
+        sv = fmaf(rg, tv, sv);
+      }
       if (a.lengths && (qpad || jx >= len)) sv += -1e4f;
       const float p = ok ? expf(sv - L) : 0.f;
       float mf = 1.f;
       if constexpr (DROP) mf = sty_hash_u(a.drop_seed, a.drop_site, rowi + (unsigned)jx) >= a.drop_p ? inv_keep : 0.f;
       dp[r] = p * (dp[r] * mf - dl);
+      if constexpr (REL) dgate = fmaf(dp[r], tv, dgate);
     }
 #pragma unroll
     for (int n = 0; n < NB; ++n)
 #pragma unroll
       for (int q = 0; q < 16; ++q)
         dq[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(ks[(n * 32 + l31) * LS + frag_row(q, hi)], dp[q], dq[n], 0, 0, 0);
+  }
+  if constexpr (REL) {  // the two lane halves hold the two halves of every key tile's rows: lower half + upper half, one writer
+    dgate += __shfl_xor(dgate, 32);
+    if (i < T && hi == 0) a.rel_dgate[((size_t)b * a.H + h) * T + i] = dgate;
   }
   if (i < T) {
     float* dqb = dQ + (size_t)b * dqbs + (size_t)h * DH * T;
@@ -536,6 +567,7 @@ bool attention_bwd_mfma_dh(int DH) { return DH == 64 || DH == 96 || DH == 160; }
 static bool attn_bwd_mfma_path(const AttnArgs& a, int DH) { return a.lse && attention_bwd_mfma_dh(DH); }
 static bool attn_bwd_small_path(const AttnArgs& a, int DH) {
   if (attention16_eligible(a, DH) && a.lse) return false;
+  if (a.rel_tab) return false;  // the gated bias is built on the tiled kernels alone
   if (attn_bwd_mfma_path(a, DH)) return false;
   return DH == 16 && a.T <= 128;
 }
@@ -550,6 +582,31 @@ int launch_attention_bwd(const AttnArgs& a, const float* dO, float* dQ, float* d
   if (overwrite && !attn_bwd_small_path(a, DH)) {
     set_error("attention_bwd: overwrite requested on a path that accumulates");
     return STY_EINVAL;
+  }
+  if (a.rel_tab || a.rel_gate || a.rel_dgate) {  // the gated relative position bias (WavLM), refused by name as the forward does
+    if (!a.rel_tab || !a.rel_gate || !a.rel_dgate || a.drop_p > 0.f || a.lengths || a.bf16 || (DH != 64 && DH != 16) ||
+        (DH == 64 && !a.lse)) {
+      set_error("attention_bwd: the gated relative position bias is built for head dims 64 (with the forward's log-sum-exp) and 16, "
+                "fp32, without dropout or a length mask, with rel_tab, rel_gate and rel_dgate all set (got head dim %d)", DH);
+      return STY_EINVAL;
+    }
+    float* delta = ws + (size_t)B * a.H * a.T;
+    ProfScope prof(DH == 64 ? "attn_bwd_rel_mfma_kernels" : "attn_bwd_rel_valu_kernels", 5 * 2.0 * B * a.H * (double)a.T * a.T * DH,
+                   4.0 * 8 * B * a.H * (double)DH * a.T, st);
+    if (DH == 64) {
+      hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv(a.T, 256), a.H, B), dim3(256), 0, st, a.o, a.obs, dO, dobs, a.H, DH, a.T, delta);
+      const dim3 g2(cdiv(a.T, 128), a.H, B);
+      hipLaunchKernelGGL((attn_bwd_kv_mfma_kernel<64, false, true>), g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dK, dkbs, dV, dvbs);
+      hipLaunchKernelGGL((attn_bwd_q_mfma_kernel<64, false, true>), g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dQ, dqbs);
+    } else {  // VALU kernels at every T (kernel A rebuilds the row log-sum-exp with the bias in)
+      const dim3 grid(cdiv(a.T, 64), a.H, B);
+      hipLaunchKernelGGL((attn_bwd_a_kernel<16, true>), grid, dim3(64), 0, st, a, dO, dobs, ws, delta);
+      hipLaunchKernelGGL((attn_bwd_b_kernel<16, false, true>), grid, dim3(256), 2 * 16 * 65 * sizeof(float), st, a, dO, dobs, ws, delta,
+                         dK, dkbs, dV, dvbs);
+      hipLaunchKernelGGL((attn_bwd_c_kernel<16, false, true>), grid, dim3(64), 0, st, a, dO, dobs, ws, delta, dQ, dqbs);
+    }
+    STY_LAUNCH_CHECK();
+    return STY_OK;
   }
   if (attention16_eligible(a, DH) && a.lse)
     return launch_attention16_bwd(a, dO, dQ, dK, dV, dqbs, dkbs, dvbs, dobs, B, ws, st);

@@ -732,7 +732,8 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
     else
       hipLaunchKernelGGL(chan_ln32_bwd_kernel<false>, dim3(nblk, B), dim3(256), 0, st, x, dy, T, eps, ada, w, gb, out_mask, dx,
                          accumulate, mu_tmp, h16);
-    hipLaunchKernelGGL(chan_ln32_param_sum_kernel, dim3(ada ? B * 64 : 64), dim3(64), 0, st, mu_tmp, B, nblk, ada, dgb, dw, db);
+    if (dgb || dw || db)  // (a frozen network asks for the input gradient alone)
+      hipLaunchKernelGGL(chan_ln32_param_sum_kernel, dim3(ada ? B * 64 : 64), dim3(64), 0, st, mu_tmp, B, nblk, ada, dgb, dw, db);
     STY_LAUNCH_CHECK();
     return STY_OK;
   }
@@ -749,7 +750,8 @@ int launch_chan_ln_bwd(const float* x, const float* dy, const float* y, int B, i
   else
     hipLaunchKernelGGL(chan_ln_bwd_dx_kernel<16>, dim3(cdiv(T, 16), B), dim3(256), 0, st, x, dy, y, C, T, eps, ada, w, gb,
                        relu, out_mask, dx, accumulate, mu_tmp, r_tmp);
-  if (det)
+  if (!dgb && !dw && !db) {  // input gradient alone (a frozen network: WavLM)
+  } else if (det)
     hipLaunchKernelGGL(chan_ln_bwd_param_kernel<true>, dim3(C, B), dim3(256), 0, st, x, dy, y, mu_tmp, r_tmp, C, T, ada, relu,
                        out_mask, dgb, dw, db);
   else

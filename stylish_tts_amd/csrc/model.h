@@ -290,14 +290,37 @@ struct WavlmPlan {
   std::vector<PackedConv> pos;     // one per group
   std::vector<WavlmLayer> layers;
   std::vector<WavlmPackJob> packs;
+  // input-gradient weights of the convs packed by `packs` (made from their packed form behind them; the 1x1 convs go through
+  // the model's dgrad table as every other kind's do)
+  PackedConv conv_d[WAVLM_MAX_CONV];
+  std::vector<PackedConv> pos_d;
+};
+// what sty_wavlm_fwd_keep leaves in the caller's workspace for sty_wavlm_bwd (all pointers into it)
+struct WavlmKeepLayer {
+  float *q = nullptr, *k = nullptr, *v = nullptr, *o = nullptr, *lse = nullptr, *gate = nullptr, *a1 = nullptr, *a2 = nullptr,
+        *pre = nullptr;
+};
+struct WavlmKeep {
+  bool valid = false;
+  int B = 0, N16 = 0;
+  const void* ws = nullptr;
+  size_t saved_end = 0;  // workspace offset behind the kept tensors: the backward's scratch starts here
+  float *out0 = nullptr, *ga = nullptr, *gs = nullptr, *gmean = nullptr, *grstd = nullptr;
+  float* pre[WAVLM_MAX_CONV] = {nullptr};  // pre-activation of feature conv i >= 1
+  float *feat = nullptr, *pre_pos = nullptr, *xa_enc = nullptr, *tab = nullptr;
+  std::vector<float*> x;  // layer inputs: x[l] enters layer l, x[layers] is the last output
+  std::vector<WavlmKeepLayer> layers;
 };
 int wavlm_prepare(const WavlmPlan& p, hipStream_t st);  // weights.hip
 int launch_wavlm_conv0(const float* x, const float* w, int B, int N, int C, int K, int S, int T, float* y, double* part, hipStream_t st);
 int wavlm_conv0_ntiles(int T);
+// mean_out / rstd_out (optional, [BC]): the row statistics themselves, kept for the backward
 int launch_wavlm_gn_finalize(const double* part, int ntiles, const float* w, const float* b, int BC, int C, int T, float eps, float* a,
-                             float* s, hipStream_t st);
+                             float* s, hipStream_t st, float* mean_out = nullptr, float* rstd_out = nullptr);
 // x [B][C][Tin] -> y [B][S C][Tp], y[b][p C + c][t] = f(x[b][c][S t + p]) (0 past Tin); f = GELU(a[b][c] x + s[b][c]) with a set, else x
-int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st);
+// gelu_in (without a): f = GELU(x), the input being a pre-activation (forward_keep)
+int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st,
+                       int gelu_in = 0);
 // [B][G Cg][T] <-> [G][B][Cg][T]
 int launch_wavlm_group_perm(const float* x, int B, int G, int Cg, int T, int to_groups, float* y, hipStream_t st);
 // bucket: the entry of distance -(T - 1) (the caller offsets a larger table)
@@ -307,7 +330,24 @@ int launch_wavlm_gate(const float* x, const float* w, const float* b, const floa
 int launch_wavlm_transpose_out(const float* x, int B, int C, int T, float* y, hipStream_t st);  // [B][C][T] -> [B][T][C]
 void wavlm_rel_buckets(int T, int num_buckets, int max_distance, int32_t* out);
 int slm_loss_groups(size_t n);
-int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st);
+// d_b (optional): also d_b[i] = mag sign(b[i] - a[i]), 0 at a tie
+int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st, float mag = 0.f,
+                    float* d_b = nullptr);
+// ---- WavLM backward to the wave (wavlm.hip; api.hip: wavlm_backward) ----
+int launch_wavlm_gelu(const float* pre, const float* res, size_t n, float* y, hipStream_t st);  // y = res + GELU(pre), res optional
+int launch_wavlm_intake(const float* dh, int B, int C, int T, int accumulate, float* dx, hipStream_t st);  // dx[b][c][t] (+)= dh[b][t][c]
+int launch_wavlm_gate_bwd(const float* x, const float* w, const float* b, const float* c, const float* dgate, int B, int H, int DH,
+                          int T, float* dx, hipStream_t st);  // dx += (accumulated into the head slices)
+// dx [B][C][Tin] = (dview [B][S C][Tp] un-staged, zero past the view) * GELU'(pre [B][C][Tin])
+int launch_wavlm_unstage(const float* dview, const float* pre, int B, int C, int Tin, int S, int Tp, float* dx, hipStream_t st);
+int wavlm_gn_bwd_ntiles(int T);
+// GroupNorm(C, C) backward with layer 1's un-staging and GELU' fused; part: B C ntiles 2 doubles, coef: B C 2 floats
+int launch_wavlm_gn_bwd(const float* x, const float* dview, const float* ga, const float* gs, const float* mean, const float* rstd, int B,
+                        int C, int T, int S, int Tp, double* part, float* coef, float* dx, hipStream_t st);
+int launch_wavlm_conv0_bwd(const float* dy, const float* w, int B, int N, int C, int K, int S, int T, float* dx, hipStream_t st);
+// the adjoint of launch_resample_fir in gather form: dx[b][i] (+)= sum over the outputs that read sample i (rmvpe.hip)
+int launch_resample_fir_bwd(const float* dy, const float* taps, int B, int N, int M, int orig, int nw, int width, int accumulate,
+                            float* dx, hipStream_t st);
 
 struct Trainer;
 struct StyleResBlk {  // mel_style_encoder.py:69-118
@@ -353,6 +393,7 @@ struct sty_model {
   sty::AlignerPlan ali;
   sty::RmvpePlan rmv;
   sty::WavlmPlan wav;
+  sty::WavlmKeep wav_keep;
   // device bucket table of the distances -(wav_bucket_T - 1) .. wav_bucket_T - 1: a bucket depends on the distance alone, so one
   // table sized for the largest frame count seen serves every smaller one at an offset
   int32_t* wav_bucket_dev = nullptr;

@@ -101,6 +101,42 @@ int launch_resample_fir(const float* x, const float* taps, int B, int N, int M, 
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
+// The adjoint in gather form: sample i of row b is read by output m = nw q + p at tap j = i + width - orig q, so
+// dx[b][i] (+)= sum_q sum_p k[p][i + width - orig q] dy[b][nw q + p], q ascending and p inside it: a fixed order, no atomic.
+__global__ __launch_bounds__(256) void resample_fir_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ taps, int N,
+                                                               int M, int orig, int nw, int width, int accumulate,
+                                                               float* __restrict__ dx) {
+  extern __shared__ float k[];
+  const int nt = 2 * width + orig;
+  for (int i = threadIdx.x; i < nw * nt; i += 256) k[i] = taps[i];
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (i >= N) return;
+  const float* gb = dy + (size_t)b * M;
+  const int top = i + width;             // j = top - orig q in [0, nt)
+  int q0 = (top - nt + orig) / orig;     // ceil((top - nt + 1) / orig) for a non-negative numerator
+  if (top - nt + 1 <= 0) q0 = 0;
+  const int q1 = top / orig;
+  float acc = 0.f;
+  for (int q = q0; q <= q1; ++q) {
+    const int j = top - orig * q;
+    for (int p = 0; p < nw; ++p) {
+      const int m = nw * q + p;
+      if (m < M) acc = fmaf(k[p * nt + j], gb[m], acc);
+    }
+  }
+  const size_t o = (size_t)b * N + i;
+  dx[o] = accumulate ? dx[o] + acc : acc;
+}
+int launch_resample_fir_bwd(const float* dy, const float* taps, int B, int N, int M, int orig, int nw, int width, int accumulate,
+                            float* dx, hipStream_t st) {
+  const int nt = 2 * width + orig;
+  ProfScope prof("resample_fir_bwd_kernel", 2.0 * nt * B * M, 4.0 * B * ((double)N + M), st);
+  hipLaunchKernelGGL(resample_fir_bwd_kernel, dim3(cdiv(N, 256), B), dim3(256), (size_t)nw * nt * sizeof(float), st, dy, taps, N, M, orig,
+                     nw, width, accumulate, dx);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
 // in place: log(clamp(x, 1e-5)); the clamped value is the constant, so that silence is one bit pattern
 __global__ __launch_bounds__(256) void rmvpe_logmel_kernel(float* __restrict__ x, size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

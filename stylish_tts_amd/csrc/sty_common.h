@@ -490,6 +490,7 @@ struct AttnArgs {
   // rel_gate [B][H][T]; both or neither (head dims 64 and 16, no dropout)
   const float* rel_tab = nullptr;
   const float* rel_gate = nullptr;
+  float* rel_dgate = nullptr;  // backward only: d loss / d rel_gate [B][H][T], written (one writer per row, no atomic)
 };
 // attn16.hip: the conformer's attention in the bf16 compute mode
 bool attention16_eligible(const AttnArgs& a, int DH);

@@ -17,7 +17,12 @@
 // (4) Attention glue: wavlm_rel_table_kernel (rel_attn_embed through the host bucket table -> [H][2T - 1], once per call),
 //     wavlm_gate_kernel (gru_rel_pos_linear on the layer INPUT's head slice -> [B][H][T]).
 // (5) wavlm_transpose_out_kernel: [B][C][T] -> the [B][T][C] hidden state the loss reads.
-// (6) slm_loss kernels: mean |a - b| with float64 partials at fixed indices, added in index order (val_loss.hip's discipline).
+// (6) slm_loss kernels: mean |a - b| with float64 partials at fixed indices, added in index order (val_loss.hip's discipline);
+//     with d_b set also scale * sign(b - a) / n, the term's cotangent.
+// (7) The backward to the wave (the network is frozen: input gradients only; api.hip has the plan, wavlm_backward): the
+//     cotangent intake, the gate backward, the un-staging of a strided conv's view with the GELU' of the layer below, the
+//     GroupNorm(C, C) backward with float64 tile partials, layer 0 transposed.  The dense steps are launch_conv1d on
+//     input-gradient packs, the attention backward with the gated bias is attn_bwd.hip's, the resampler adjoint rmvpe.hip's.
 #include <math.h>
 
 #include "model.h"
@@ -88,7 +93,8 @@ int launch_wavlm_conv0(const float* x, const float* w, int B, int N, int C, int 
 // a = w[c] rstd, s = b[c] - a mean
 __global__ __launch_bounds__(256) void wavlm_gn_finalize_kernel(const double* __restrict__ part, int ntiles, const float* __restrict__ w,
                                                                 const float* __restrict__ bv, int BC, int C, int T, float eps,
-                                                                float* __restrict__ a, float* __restrict__ s) {
+                                                                float* __restrict__ a, float* __restrict__ s,
+                                                                float* __restrict__ mean_out, float* __restrict__ rstd_out) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= BC) return;
   const double* p = part + (size_t)row * ntiles * 2;
@@ -104,10 +110,15 @@ __global__ __launch_bounds__(256) void wavlm_gn_finalize_kernel(const double* __
   const double av = (double)w[c] / sqrt(var + (double)eps);
   a[row] = (float)av;
   s[row] = (float)((double)bv[c] - av * mean);
+  if (mean_out) {  // kept for the backward (forward_keep)
+    mean_out[row] = (float)mean;
+    rstd_out[row] = (float)(1.0 / sqrt(var + (double)eps));
+  }
 }
 int launch_wavlm_gn_finalize(const double* part, int ntiles, const float* w, const float* b, int BC, int C, int T, float eps, float* a,
-                             float* s, hipStream_t st) {
-  hipLaunchKernelGGL(wavlm_gn_finalize_kernel, dim3(cdiv(BC, 256)), dim3(256), 0, st, part, ntiles, w, b, BC, C, T, eps, a, s);
+                             float* s, hipStream_t st, float* mean_out, float* rstd_out) {
+  hipLaunchKernelGGL(wavlm_gn_finalize_kernel, dim3(cdiv(BC, 256)), dim3(256), 0, st, part, ntiles, w, b, BC, C, T, eps, a, s, mean_out,
+                     rstd_out);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -115,7 +126,8 @@ int launch_wavlm_gn_finalize(const double* part, int ntiles, const float* w, con
 // ---------------------------------------------------------------------------------------------------------------------
 // the s-frames-at-a-time view of a strided conv's input
 // ---------------------------------------------------------------------------------------------------------------------
-template <bool NORM>
+// MODE 0: the view alone; 1: layer 0's norm and GELU on the way; 2: GELU alone (forward_keep: the convs leave pre-activations)
+template <int MODE>
 __global__ __launch_bounds__(256) void wavlm_stage_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                           const float* __restrict__ s, int C, int Tin, int S, int Tp,
                                                           float* __restrict__ y) {
@@ -126,17 +138,21 @@ __global__ __launch_bounds__(256) void wavlm_stage_kernel(const float* __restric
   float v = 0.f;
   if (ts < Tin) {
     v = x[((size_t)b * C + c) * Tin + ts];
-    if constexpr (NORM) v = gelu_erf(fmaf(v, a[(size_t)b * C + c], s[(size_t)b * C + c]));
+    if constexpr (MODE == 1) v = gelu_erf(fmaf(v, a[(size_t)b * C + c], s[(size_t)b * C + c]));
+    if constexpr (MODE == 2) v = gelu_erf(v);
   }
   y[((size_t)b * S * C + pc) * Tp + t] = v;
 }
-int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st) {
+int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st,
+                       int gelu_in) {
   const dim3 grid(cdiv(Tp, 256), S * C, B);
   ProfScope prof("wavlm_stage_kernel", 0.0, 8.0 * B * S * (double)C * Tp, st);
   if (a)
-    hipLaunchKernelGGL(wavlm_stage_kernel<true>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
+    hipLaunchKernelGGL(wavlm_stage_kernel<1>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
+  else if (gelu_in)
+    hipLaunchKernelGGL(wavlm_stage_kernel<2>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
   else
-    hipLaunchKernelGGL(wavlm_stage_kernel<false>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
+    hipLaunchKernelGGL(wavlm_stage_kernel<0>, grid, dim3(256), 0, st, x, a, s, C, Tin, S, Tp, y);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -256,11 +272,19 @@ int slm_loss_groups(size_t n) {
   const size_t g = (n + SLM_PER_WG - 1) / SLM_PER_WG;
   return g < 1 ? 1 : (g < (size_t)SLM_G_MAX ? (int)g : SLM_G_MAX);
 }
+// GRAD: also d_b[i] = mag sign(b[i] - a[i]) (0 at a tie), mag = scale / n formed on the host
+template <bool GRAD>
 __global__ __launch_bounds__(256) void slm_loss_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, size_t n,
-                                                               double* __restrict__ part) {
+                                                               double* __restrict__ part, float mag, float* __restrict__ d_b) {
   __shared__ double red[4];
   double acc = 0.0;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc += (double)fabsf(a[i] - b[i]);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    acc += (double)fabsf(a[i] - b[i]);
+    if constexpr (GRAD) {
+      const float d = b[i] - a[i];
+      d_b[i] = d > 0.f ? mag : (d < 0.f ? -mag : 0.f);
+    }
+  }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
@@ -271,11 +295,225 @@ __global__ void slm_loss_finalize_kernel(const double* __restrict__ part, int G,
   for (int g = 0; g < G; ++g) s += part[g];
   loss[0] = (float)(s / (double)n);
 }
-int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st) {
+int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st, float mag, float* d_b) {
   const int G = slm_loss_groups(n);
-  ProfScope prof("slm_loss_partial_kernel", 2.0 * n, 8.0 * n, st);
-  hipLaunchKernelGGL(slm_loss_partial_kernel, dim3(G), dim3(256), 0, st, a, b, n, part);
+  ProfScope prof("slm_loss_partial_kernel", 2.0 * n, (d_b ? 12.0 : 8.0) * n, st);
+  if (d_b)
+    hipLaunchKernelGGL(slm_loss_partial_kernel<true>, dim3(G), dim3(256), 0, st, a, b, n, part, mag, d_b);
+  else
+    hipLaunchKernelGGL(slm_loss_partial_kernel<false>, dim3(G), dim3(256), 0, st, a, b, n, part, mag, d_b);
   hipLaunchKernelGGL(slm_loss_finalize_kernel, dim3(1), dim3(1), 0, st, part, G, n, loss);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// backward to the wave (api.hip: wavlm_backward).  The network is frozen: input gradients only, no float atomic anywhere --
+// every output element has one writer and every sum a fixed order, so the gradient repeats to the bit.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+__device__ __forceinline__ float gelu_erf_grad(float v) {
+  return 0.5f * (1.0f + erff(v * 0.70710678118654752f)) + v * 0.3989422804014327f * expf(-0.5f * v * v);
+}
+}  // namespace
+
+// forward_keep: y = res + GELU(pre) (res optional), the epilogue the convs apply themselves in the plain forward
+__global__ __launch_bounds__(256) void wavlm_gelu_kernel(const float* __restrict__ pre, const float* __restrict__ res, size_t n,
+                                                         float* __restrict__ y) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float g = gelu_erf(pre[i]);
+  y[i] = res ? fmaf(1.f, g, res[i]) : g;
+}
+int launch_wavlm_gelu(const float* pre, const float* res, size_t n, float* y, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_gelu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pre, res, n, y);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// cotangent intake, the inverse of wavlm_transpose_out_kernel with an add: dx[b][c][t] (+)= dh[b][t][c]
+__global__ __launch_bounds__(256) void wavlm_intake_kernel(const float* __restrict__ dh, int C, int T, int accumulate,
+                                                           float* __restrict__ dx) {
+  __shared__ float tile[32][33];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32, b = blockIdx.z;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int t = t0 + r, c = c0 + tx;
+    tile[r][tx] = (t < T && c < C) ? dh[((size_t)b * T + t) * C + c] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int c = c0 + r, t = t0 + tx;
+    if (c < C && t < T) {
+      const size_t o = ((size_t)b * C + c) * T + t;
+      dx[o] = accumulate ? dx[o] + tile[tx][r] : tile[tx][r];
+    }
+  }
+}
+int launch_wavlm_intake(const float* dh, int B, int C, int T, int accumulate, float* dx, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_intake_kernel, dim3(cdiv(T, 32), cdiv(C, 32), B), dim3(256), 0, st, dh, C, T, accumulate, dx);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// gate = ga (gb const_h - 1) + 2 backward: dgate [B][H][T] through the two sigmoids and Linear(DH, 8) into the head slice of the
+// layer input's gradient, dx[b][h DH + d][t] += ...; one thread owns (b, h, t) and with it the DH elements it adds to
+__global__ __launch_bounds__(256) void wavlm_gate_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bv, const float* __restrict__ cst,
+                                                             const float* __restrict__ dgate, int H, int DH, int T,
+                                                             float* __restrict__ dx) {
+  const int t = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  const size_t off = ((size_t)b * H + h) * DH * T + t;
+  const float* xp = x + off;
+  float r[8];
+#pragma unroll
+  for (int o = 0; o < 8; ++o) r[o] = 0.f;
+  for (int d = 0; d < DH; ++d) {
+    const float v = xp[(size_t)d * T];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) r[o] = fmaf(w[o * DH + d], v, r[o]);
+  }
+#pragma unroll
+  for (int o = 0; o < 8; ++o) r[o] += bv[o];
+  const float sa = ((r[0] + r[1]) + r[2]) + r[3], sb = ((r[4] + r[5]) + r[6]) + r[7];
+  const float ga = 1.0f / (1.0f + expf(-sa)), gb = 1.0f / (1.0f + expf(-sb));
+  const float dg = dgate[((size_t)b * H + h) * T + t], c = cst[h];
+  const float dsa = dg * fmaf(gb, c, -1.0f) * ga * (1.0f - ga), dsb = dg * ga * c * gb * (1.0f - gb);
+  float* dp = dx + off;
+  for (int d = 0; d < DH; ++d) {
+    const float wa = ((w[d] + w[DH + d]) + w[2 * DH + d]) + w[3 * DH + d];
+    const float wb = ((w[4 * DH + d] + w[5 * DH + d]) + w[6 * DH + d]) + w[7 * DH + d];
+    dp[(size_t)d * T] += fmaf(wa, dsa, wb * dsb);
+  }
+}
+int launch_wavlm_gate_bwd(const float* x, const float* w, const float* b, const float* c, const float* dgate, int B, int H, int DH,
+                          int T, float* dx, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_gate_bwd_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, st, x, w, b, c, dgate, H, DH, T, dx);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// un-staging, the adjoint of wavlm_stage_kernel: dx[b][c][S t + p] = dview[b][p C + c][t], zero for frames past the view
+// (t >= Tp), times GELU'(pre) of the layer below (pre [B][C][Tin], its conv's pre-activation)
+__global__ __launch_bounds__(256) void wavlm_unstage_kernel(const float* __restrict__ dview, const float* __restrict__ pre, int C,
+                                                            int Tin, int S, int Tp, float* __restrict__ dx) {
+  const int ts = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (ts >= Tin) return;
+  const int t = ts / S, p = ts - t * S;
+  const size_t o = ((size_t)b * C + c) * Tin + ts;
+  const float g = t < Tp ? dview[((size_t)b * S * C + (size_t)p * C + c) * Tp + t] : 0.f;
+  dx[o] = g * gelu_erf_grad(pre[o]);
+}
+int launch_wavlm_unstage(const float* dview, const float* pre, int B, int C, int Tin, int S, int Tp, float* dx, hipStream_t st) {
+  ProfScope prof("wavlm_unstage_kernel", 0.0, 12.0 * B * (double)C * Tin, st);
+  hipLaunchKernelGGL(wavlm_unstage_kernel, dim3(cdiv(Tin, 256), C, B), dim3(256), 0, st, dview, pre, C, Tin, S, Tp, dx);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// GroupNorm(C, C) backward behind layer 0, with layer 1's un-staging and the GELU' between them fused in: per row (b, c) over the T
+// frames, z = a x + s, dz = dview[p C + c][t / S] GELU'(z), xhat = (x - mean) rstd;
+//   dx = w rstd (dz - mean_t dz - xhat mean_t (dz xhat)).
+// Pass 1 leaves the float64 (sum dz, sum dz xhat) of every 1024-frame tile, the finalize adds the tiles in index order (the
+// forward's discipline), pass 2 is elementwise.
+constexpr int GNB_TILE = 1024;
+int wavlm_gn_bwd_ntiles(int T) { return cdiv(T, GNB_TILE); }
+namespace {
+__device__ __forceinline__ float gn_dz(const float* __restrict__ x, const float* __restrict__ dview, size_t row, int c, int b, int C,
+                                       int T, int S, int Tp, int t, float a, float s, float* xv) {
+  const float v = x[row * T + t];
+  *xv = v;
+  const int tv = t / S, p = t - tv * S;
+  const float g = tv < Tp ? dview[((size_t)b * S * C + (size_t)p * C + c) * Tp + tv] : 0.f;
+  return g * gelu_erf_grad(fmaf(v, a, s));
+}
+}  // namespace
+__global__ __launch_bounds__(256) void wavlm_gn_bwd_part_kernel(const float* __restrict__ x, const float* __restrict__ dview,
+                                                                const float* __restrict__ ga, const float* __restrict__ gs,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd, int C,
+                                                                int T, int S, int Tp, double* __restrict__ part) {
+  __shared__ double red[2][4];
+  const int c = blockIdx.y, b = blockIdx.z;
+  const size_t row = (size_t)b * C + c;
+  const float a = ga[row], s = gs[row], mu = mean[row], rs = rstd[row];
+  double s1 = 0.0, s2 = 0.0;
+  for (int k = 0; k < GNB_TILE / 256; ++k) {
+    const int t = blockIdx.x * GNB_TILE + k * 256 + threadIdx.x;
+    if (t < T) {
+      float xv;
+      const float dz = gn_dz(x, dview, row, c, b, C, T, S, Tp, t, a, s, &xv);
+      s1 += (double)dz;
+      s2 += (double)dz * (double)((xv - mu) * rs);
+    }
+  }
+  s1 = wave_sum(s1), s2 = wave_sum(s2);
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s1, red[1][threadIdx.x >> 6] = s2;
+  __syncthreads();
+  if (threadIdx.x < 2)
+    part[(row * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
+        ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+}
+__global__ __launch_bounds__(256) void wavlm_gn_bwd_finalize_kernel(const double* __restrict__ part, int ntiles, int BC, int T,
+                                                                    float* __restrict__ coef) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= BC) return;
+  const double* p = part + (size_t)row * ntiles * 2;
+  double s1 = 0.0, s2 = 0.0;
+  for (int i = 0; i < ntiles; ++i) {
+    s1 += p[2 * i];
+    s2 += p[2 * i + 1];
+  }
+  coef[2 * (size_t)row] = (float)(s1 / T);
+  coef[2 * (size_t)row + 1] = (float)(s2 / T);
+}
+__global__ __launch_bounds__(256) void wavlm_gn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dview,
+                                                                 const float* __restrict__ ga, const float* __restrict__ gs,
+                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                 const float* __restrict__ coef, int C, int T, int S, int Tp,
+                                                                 float* __restrict__ dx) {
+  const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  const size_t row = (size_t)b * C + c;
+  float xv;
+  const float a = ga[row];
+  const float dz = gn_dz(x, dview, row, c, b, C, T, S, Tp, t, a, gs[row], &xv);
+  const float xh = (xv - mean[row]) * rstd[row];
+  dx[row * T + t] = a * ((dz - coef[2 * row]) - xh * coef[2 * row + 1]);  // a = w rstd
+}
+int launch_wavlm_gn_bwd(const float* x, const float* dview, const float* ga, const float* gs, const float* mean, const float* rstd, int B,
+                        int C, int T, int S, int Tp, double* part, float* coef, float* dx, hipStream_t st) {
+  const int nt = wavlm_gn_bwd_ntiles(T);
+  ProfScope prof("wavlm_gn_bwd_kernels", 0.0, 20.0 * B * (double)C * T, st);
+  hipLaunchKernelGGL(wavlm_gn_bwd_part_kernel, dim3(nt, C, B), dim3(256), 0, st, x, dview, ga, gs, mean, rstd, C, T, S, Tp, part);
+  hipLaunchKernelGGL(wavlm_gn_bwd_finalize_kernel, dim3(cdiv(B * C, 256)), dim3(256), 0, st, part, nt, B * C, T, coef);
+  hipLaunchKernelGGL(wavlm_gn_bwd_apply_kernel, dim3(cdiv(T, 256), C, B), dim3(256), 0, st, x, dview, ga, gs, mean, rstd, coef, C, T, S,
+                     Tp, dx);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// layer 0 transposed: d audio[b][n] = sum_c sum_{k = n mod S, + S, ... < K} w[c][k] dy[b][c][(n - k) / S]; one thread per sample,
+// the channels in index order; samples no frame reads (the tail) come out zero
+__global__ __launch_bounds__(256) void wavlm_conv0_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ w, int N, int C,
+                                                              int K, int S, int T, float* __restrict__ dx) {
+  const int n = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (n >= N) return;
+  const int k0 = n % S;
+  float acc = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float* dyc = dy + ((size_t)b * C + c) * T;
+    const float* wc = w + (size_t)c * K;
+    for (int k = k0; k < K && k <= n; k += S) {
+      const int t = (n - k) / S;
+      if (t < T) acc = fmaf(wc[k], dyc[t], acc);
+    }
+  }
+  dx[(size_t)b * N + n] = acc;
+}
+int launch_wavlm_conv0_bwd(const float* dy, const float* w, int B, int N, int C, int K, int S, int T, float* dx, hipStream_t st) {
+  ProfScope prof("wavlm_conv0_bwd_kernel", 2.0 * K * B * C * T, 4.0 * B * ((double)N + (double)C * T), st);
+  hipLaunchKernelGGL(wavlm_conv0_bwd_kernel, dim3(cdiv(N, 256), B), dim3(256), 0, st, dy, w, N, C, K, S, T, dx);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

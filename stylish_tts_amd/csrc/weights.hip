@@ -396,7 +396,7 @@ int weights_sn_power_iter(sty_model* m, hipStream_t st) {
   return launch_sn_prep_table(m->wt.sn_prep, m->wt.sn_wtu, true, false, st);  // every layer in four launches
 }
 
-// ---- WavLM (kind "wavlm", forward only: nothing to un-pack) ----
+// ---- WavLM (kind "wavlm", frozen: nothing to un-pack) ----
 // nrm[k] = || v[:, :, k] || over the n = Cout Cin rows of v [n][K] (weight-norm dim = 2 of the positional conv): one workgroup
 // per tap, float64 partials added in a fixed order
 __global__ __launch_bounds__(256) void wavlm_tap_norm_kernel(const float* __restrict__ v, int n, int K, float* __restrict__ nrm) {
@@ -433,6 +433,15 @@ int wavlm_prepare(const WavlmPlan& p, hipStream_t st) {
                        p.pos_nrm);
   for (const WavlmPackJob& j : p.packs) hipLaunchKernelGGL(wavlm_pack_kernel, dim3(j.Cout), dim3(256), 0, st, j);
   STY_LAUNCH_CHECK();
+  // the input-gradient weights of these packs (taps flipped, channels transposed), once per model: the backward to the wave
+  int r;
+  for (int i = 1; i < p.n_conv; ++i)
+    if (p.conv_d[i].wp &&
+        (r = launch_pack_dgrad(p.conv[i].wp, p.conv[i].K, p.conv[i].CinP, p.conv[i].CoutP, const_cast<float*>(p.conv_d[i].wp), st)) != STY_OK)
+      return r;
+  for (size_t g = 0; g < p.pos_d.size(); ++g)
+    if ((r = launch_pack_dgrad(p.pos[g].wp, p.pos[g].K, p.pos[g].CinP, p.pos[g].CoutP, const_cast<float*>(p.pos_d[g].wp), st)) != STY_OK)
+      return r;
   return STY_OK;
 }
 

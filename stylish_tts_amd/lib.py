@@ -213,6 +213,11 @@ SYMBOLS = {
     "sty_wavlm_rel_buckets_host": (C.c_int, [_I, _I, _I, _P]),
     "sty_slm_loss_workspace_bytes": (C.c_int, [C.c_size_t, _SZP]),
     "sty_slm_loss_fwd": (C.c_int, [C.c_size_t, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_wavlm_grad_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
+    "sty_wavlm_fwd_keep": (C.c_int, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "sty_wavlm_bwd": (C.c_int, [_P, _I, _I, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_slm_loss_fwd_bwd": (C.c_int, [C.c_size_t, _P, _P, C.c_float, _P, _P, _P, C.c_size_t, _P]),
+    "sty_slm_resample_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _I, _P]),
     "sty_aligner_train_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
     "sty_aligner_fwd_train": (C.c_int, [_P, _I, _I, _P, _P, C.c_float, C.c_uint, _P, _P, C.c_size_t, _P]),
     "sty_aligner_bwd": (C.c_int, [_P, _P, _P]),

@@ -3,9 +3,12 @@
 WavLM (`microsoft/wavlm-base-plus` in the reference's model.yml), and the loss is the L1 distance between the stacks of all
 hidden states (13 at full depth); the trainer weights it with `loss_weight.slm`.
 
-What is built is the VALUE: the network's forward in HIP (csrc/wavlm.hip) and its first user, the validation pass
-(`train --slm DIR`).  The gradient with respect to the predicted wave, the term inside `AcousticTrainer.train_batch` and a bf16
-operand mode are not built: `WavLMLoss.forward` raises in grad mode when the prediction requires a gradient.
+What is built: the value -- the network's forward in HIP (csrc/wavlm.hip), logged by the validation pass (`train --slm DIR`) --
+and the gradient with respect to the predicted wave: `WavLMLoss.loss_and_grad`, the term inside `AcousticTrainer.train_batch`
+(`train --slm DIR --slm-train`).  The network is frozen, so the backward is the input-gradient chain alone: resampler adjoint,
+feature-encoder and transformer input gradients, the L1 sign.  It is an explicit call, this package's idiom; there is no
+autograd node: `WavLMLoss.forward` still raises in grad mode when the prediction requires a gradient.  The kind runs fp32
+operands whatever the trainer's compute mode is; a bf16 operand mode is not built.
 
 Nothing is downloaded.  `model` is a local directory in the hub snapshot layout: `config.json` plus `model.safetensors`, or
 `pytorch_model.bin` read with `torch.load(weights_only=True)`.  The `transformers` package is not imported: `config.json` is read
@@ -109,7 +112,8 @@ class WavLM(_HipModule):
         self._build(wavlm_manifest(**{k: v for k, v in self.cfg.items() if k != "layer_norm_eps"}))
 
     def enable_training(self):
-        raise L.StyError("WavLM: forward only (the network is frozen; its backward is not built)")
+        raise L.StyError("WavLM: the network is frozen (no weight gradient is built; forward_keep / backward give the gradient "
+                         "with respect to the wave)")
 
     def set_train_opts(self, **kw):
         if kw.get("compute_bf16"):
@@ -147,6 +151,61 @@ class WavLM(_HipModule):
         L.check(lib.sty_wavlm_fwd(self._handle, B, n16, L.ptr(x), L.ptr(out), L.ptr(ws), ws.numel(), _stream(dev)))
         return out
 
+    def _check_audio(self, audio16):
+        if audio16.dim() != 2 or not audio16.is_cuda:
+            raise L.StyError(f"WavLM: audio must be [B, N] on a HIP device (got {tuple(audio16.shape)} on {audio16.device}); "
+                             "there is no CPU path")
+        B, n16 = audio16.shape
+        T = wavlm_frames(n16, self.cfg)
+        if T < 1:
+            raise L.StyError(f"WavLM: {n16} samples leave no frame behind the feature encoder")
+        return B, n16, T
+
+    def grad_workspace_bytes(self, B, n16, device):
+        lib = self._ensure(device)
+        need = C.c_size_t()
+        L.check(lib.sty_wavlm_grad_workspace_bytes(self._handle, B, n16, C.byref(need)))
+        return need.value
+
+    def forward_keep(self, audio16):
+        """forward() -- the same bits -- that keeps in a workspace of its own what backward() reads.  Under no_grad semantics:
+        nothing is recorded for autograd."""
+        B, n16, T = self._check_audio(audio16)
+        dev = audio16.device
+        lib = self._ensure(dev)
+        x = _f32(audio16.detach(), dev)
+        out = torch.empty(self.cfg["num_hidden_layers"] + 1, B, T, self.cfg["hidden_size"], dtype=torch.float32, device=dev)
+        need = self.grad_workspace_bytes(B, n16, dev)
+        ws = self.__dict__.get("_grad_ws")
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self.__dict__["_grad_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        self.__dict__["_kept"] = None
+        L.check(lib.sty_wavlm_fwd_keep(self._handle, B, n16, L.ptr(x), L.ptr(out), L.ptr(ws), ws.numel(), _stream(dev)))
+        self.__dict__["_kept"] = (B, n16, T)
+        return out
+
+    def backward(self, d_hidden, tap=False):
+        """d_hidden [layers + 1, B, T, H], the cotangent of forward_keep's stack -> d_audio16 [B, N16] (whole: the tail no frame
+        reads is zero); tap=True: (d_audio16, d_enc_in [B, H, T]), the gradient at the feature projection's output.  Consumes the
+        forward_keep call before it."""
+        kept = self.__dict__.get("_kept")
+        if kept is None:
+            raise L.StyError("WavLM.backward: no forward_keep call precedes it (a backward consumes its forward's workspace)")
+        B, n16, T = kept
+        want = (self.cfg["num_hidden_layers"] + 1, B, T, self.cfg["hidden_size"])
+        if tuple(d_hidden.shape) != want or not d_hidden.is_cuda:
+            raise L.StyError(f"WavLM.backward: d_hidden must be {want} on the device of the forward_keep call (got "
+                             f"{tuple(d_hidden.shape)} on {d_hidden.device}); the shape belongs to another forward_keep")
+        dev = d_hidden.device
+        lib = self._ensure(dev)
+        g = _f32(d_hidden.detach(), dev)
+        ws = self.__dict__["_grad_ws"]
+        d_audio = torch.empty(B, n16, dtype=torch.float32, device=dev)
+        d_enc = torch.empty(B, self.cfg["hidden_size"], T, dtype=torch.float32, device=dev) if tap else None
+        self.__dict__["_kept"] = None
+        L.check(lib.sty_wavlm_bwd(self._handle, B, n16, L.ptr(g), L.ptr(d_audio), L.ptr(d_enc), L.ptr(ws), ws.numel(), _stream(dev)))
+        return (d_audio, d_enc) if tap else d_audio
+
 
 def resample(audio, orig, new):
     """torchaudio.transforms.Resample(orig, new) with its defaults, restated (PARITY UNPINNED): [B, N] -> [B, ceil(N new / orig)]"""
@@ -161,6 +220,42 @@ def resample(audio, orig, new):
     out = torch.empty(B, M, dtype=torch.float32, device=audio.device)
     L.check(lib.sty_slm_resample_fwd(B, N, int(orig), int(new), L.ptr(x), L.ptr(out), _stream(audio.device)))
     return out
+
+
+def resample_backward(d_out, n, orig, new, out=None):
+    """the adjoint of resample(): d_out [B, ceil(n new / orig)] -> d_audio [B, n]; with `out` given the result is added into it
+    (one fp32 add per sample) and `out` is returned"""
+    if d_out.dim() != 2 or not d_out.is_cuda:
+        raise L.StyError(f"slm.resample_backward: d_out must be [B, M] on a HIP device (got {tuple(d_out.shape)} on {d_out.device})")
+    lib = L.load()
+    B, M = d_out.shape
+    if lib.sty_slm_resample_len(int(n), int(orig), int(new)) != M:
+        raise L.StyError(f"slm.resample_backward: {orig} -> {new} on {n} samples gives "
+                         f"{lib.sty_slm_resample_len(int(n), int(orig), int(new))} outputs, d_out has {M}")
+    if out is not None and (tuple(out.shape) != (B, int(n)) or out.dtype != torch.float32 or not out.is_contiguous()
+                            or out.device != d_out.device):
+        raise L.StyError(f"slm.resample_backward: out must be a contiguous fp32 [{B}, {n}] on {d_out.device}")
+    g = _f32(d_out.detach(), d_out.device)
+    res = out if out is not None else torch.empty(B, int(n), dtype=torch.float32, device=d_out.device)
+    L.check(lib.sty_slm_resample_bwd(B, int(n), int(orig), int(new), L.ptr(g), L.ptr(res), 1 if out is not None else 0,
+                                     _stream(d_out.device)))
+    return res
+
+
+def l1_mean_and_grad(a, b, scale=1.0):
+    """(mean |a - b| with the bits of l1_mean, scale * sign(b - a) / n: its gradient with respect to b times `scale`, 0 at a tie)"""
+    if a.shape != b.shape or not a.is_cuda:
+        raise L.StyError(f"slm.l1_mean_and_grad: shapes {tuple(a.shape)} and {tuple(b.shape)} on {a.device}")
+    lib = L.load()
+    a, b = _f32(a, a.device), _f32(b, a.device)
+    need = C.c_size_t()
+    L.check(lib.sty_slm_loss_workspace_bytes(a.numel(), C.byref(need)))
+    ws = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=a.device)
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    d_b = torch.empty_like(b)
+    L.check(lib.sty_slm_loss_fwd_bwd(a.numel(), L.ptr(a), L.ptr(b), float(scale), L.ptr(loss), L.ptr(d_b), L.ptr(ws), ws.numel() * 8,
+                                     _stream(a.device)))
+    return loss[0], d_b
 
 
 def l1_mean(a, b):
@@ -200,7 +295,8 @@ def load_snapshot(model):
 
 class WavLMLoss(torch.nn.Module):
     """WavLMLoss(model, model_sr, slm_sr=16000) (train/losses.py:376-394): the reference's constructor; `model` is a local
-    snapshot directory.  forward(wav [B, N], y_rec [B, 1, N] or [B, N]) -> scalar, under torch.no_grad()."""
+    snapshot directory.  forward(wav [B, N], y_rec [B, 1, N] or [B, N]) -> scalar, under torch.no_grad().
+    loss_and_grad(wav, y_rec, weight, d_pred) -> (the same scalar, weight * d value / d y_rec [B, N])."""
 
     def __init__(self, model, model_sr, slm_sr=16000):
         super().__init__()
@@ -214,7 +310,11 @@ class WavLMLoss(torch.nn.Module):
 
     def hidden_states(self, wav):
         """[B, N] at model_sr -> [layers + 1, B, T, H]"""
-        return self.wavlm(resample(wav, self.model_sr, self.slm_sr))
+        return self.wavlm(self._to_slm_rate(wav))
+
+    def _to_slm_rate(self, wav):
+        # (equal rates: torchaudio's Resample.forward hands the wave back unchanged; the 15-tap table of 1 -> 1 is no identity)
+        return wav if self.model_sr == self.slm_sr else resample(wav, self.model_sr, self.slm_sr)
 
     def forward(self, wav, y_rec):
         if torch.is_grad_enabled() and y_rec.requires_grad:
@@ -230,3 +330,32 @@ class WavLMLoss(torch.nn.Module):
             # (the ground-truth stack is kept; the second forward reuses the network's workspace)
             ref = self.hidden_states(wav)
             return l1_mean(ref, self.hidden_states(y_rec))
+
+    def _pair(self, wav, y_rec):
+        if y_rec.dim() == 3 and y_rec.shape[1] == 1:
+            y_rec = y_rec[:, 0]
+        if wav.dim() != 2 or y_rec.dim() != 2:
+            raise L.StyError(f"WavLMLoss: wav must be [B, N] and y_rec [B, 1, N] or [B, N] (got {tuple(wav.shape)}, "
+                             f"{tuple(y_rec.shape)})")
+        if wav.shape != y_rec.shape:
+            raise L.StyError(f"WavLMLoss: unequal lengths {tuple(wav.shape)} and {tuple(y_rec.shape)}")
+        return y_rec
+
+    @torch.no_grad()
+    def loss_and_grad(self, wav, y_rec, weight=1.0, d_pred=None):
+        """(value, d_audio [B, N]): the unweighted value with the bits forward() gives, and weight * d value / d y_rec -- the weight
+        folded into the L1 cotangent.  With `d_pred` (a contiguous fp32 [B, N]) the gradient is accumulated into that tensor, which
+        is returned.  Every host-side refusal (shapes, no frame left) is raised before anything is launched."""
+        y_rec = self._pair(wav, y_rec)
+        B, N = y_rec.shape
+        if d_pred is not None and (tuple(d_pred.shape) != (B, N) or d_pred.dtype != torch.float32 or not d_pred.is_contiguous()):
+            raise L.StyError(f"WavLMLoss.loss_and_grad: d_pred must be a contiguous fp32 [{B}, {N}] (got {tuple(d_pred.shape)})")
+        ref = self.hidden_states(wav)
+        value, d_h = l1_mean_and_grad(ref, self.wavlm.forward_keep(self._to_slm_rate(y_rec)), weight)
+        d16 = self.wavlm.backward(d_h)
+        if self.model_sr == self.slm_sr:
+            if d_pred is None:
+                return value, d16
+            d_pred.add_(d16)
+            return value, d_pred
+        return value, resample_backward(d16, N, self.model_sr, self.slm_sr, out=d_pred)

@@ -4,6 +4,7 @@ the HIP path -> accelerate-layout checkpoints, stage after stage (acoustic -> te
 
     python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic [--checkpoint DIR] [--reset-stage]
     python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage S --checkpoint DIR --validate-only [--slm DIR]
+    python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic --slm DIR --slm-train
 
 or `stylish_tts_amd.train.train(config_path, model_config_path, out, stage, checkpoint, reset_stage)` -- the reference
 command's arguments in the reference command's order.  What is joined here exists piece by piece elsewhere in this package
@@ -16,11 +17,15 @@ The reference's other two commands on the same files: `convert` is below (--conv
 stylish_tts_amd/voicepack.py (its consumer, `speak`, is stylish_tts_amd/speak.py); both take the last stage's checkpoint.
 
 What the reference's loop does and this one does NOT (out of scope): the alignment stage (its own command, as in
-the reference: train_align.py), validation figures / tensorboard, the WavLM loss term INSIDE the training step (slm.py has its value: `--slm DIR` logs it in the
-validation pass; its backward is not built), the batch-size PROBE
+the reference: train_align.py), validation figures / tensorboard, the batch-size PROBE
 (train/batch_manager.py probe_loop: an out-of-memory search for 24-80 GB cards) -- with 288 GB of HBM every length bin runs at
 `training_plan.<stage>.probe_batch_max` and that table is written to `<stage>_batch_sizes.json` exactly where the probe
 would have left it, so a table the reference probed is used as it is when the file is already there.
+
+The WavLM term of the acoustic step (stage_type.py:340-363, `loss_weight.slm`): `--slm DIR` alone logs its value in the validation
+pass; with `--slm-train` the acoustic stage also trains with it (slm.WavLMLoss.loss_and_grad inside AcousticTrainer.train_batch,
+every rank with its own copy of the frozen network, fp32 operands whatever `mixed_precision` says) and the step log line gains
+`, slm V`.  The reference has the term in no other stage, and neither has this loop.
 """
 import json
 import os
@@ -123,6 +128,7 @@ class TrainContext:
         self.adversarial = adversarial
         self.deterministic = bool(deterministic)  # handed to every stage's trainer
         self.slm = None  # slm.WavLMLoss on the device (train_model(slm_path=...), rank 0): the validation pass hands it to the trainer
+        self.slm_train = False  # train_model(slm_train=True): every rank holds self.slm and the acoustic trainer trains with it
         self.rank, self.world = dist.init() if "WORLD_SIZE" in os.environ else (0, 1)
         mp = config.training.mixed_precision
         if mp not in ("no", "bf16"):
@@ -180,6 +186,8 @@ class TrainContext:
             from .acoustic import AcousticTrainer
             adv = dict(mrd=[self.model(f"mrd{i}") for i in range(3)], disc=self.model("disc"),
                        w_gen=float(w.generator)) if self.adversarial else {}
+            if getattr(self, "slm_train", False):  # --slm-train: the fourth term, weighted by loss_weight.slm
+                adv = dict(adv, slm_train=self.slm, w_slm=float(w.slm))
             return AcousticTrainer(self.model("speech_predictor"), self.model("speech_style_encoder"), w_mel=float(w.mel),
                                    w_phase=float(w.multi_phase), text_dropout=float(self.model_config.text_encoder.dropout),
                                    **adv, **common)
@@ -202,7 +210,8 @@ class TrainContext:
 
 
 def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage=False, config_path="", model_config_path="",
-                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False, deterministic=False, slm_path=None):
+                max_steps=None, adversarial=True, device=None, log=_log, validate_only=False, deterministic=False, slm_path=None,
+                slm_train=False):
     """train/train.py:76-338.  `deterministic`: the library's deterministic mode for the run (fixed-order sums: two runs from one
     seed give the same bits on one rank; the order of the gradient exchange between ranks is the backend's).  `max_steps`: stop after that many optimizer steps IN TOTAL (tests; None = the plan's epochs).
     `validate_only`: load `checkpoint`, run ONE validation pass of `stage` (log line, samples, eval/validation.jsonl; the record
@@ -211,12 +220,16 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
     never picked up by itself): the validation passes of the acoustic and the textual stage then also log the slm value
     (WavLMLoss of `model_config.sample_rate` -> `model_config.slm.sr`) and write it as the record's "slm"; metrics, total and
     best_loss do not see it.
+    `slm_train` (needs `slm_path`): the acoustic stage trains with the term, weighted by `loss_weight.slm`; every rank loads the
+    network, the gradient is local (no new collective), and the step log line gains `, slm V`.  The other stages do not change.
     Returns the context (models, manifest, the last stage's trainer under `.stage`)."""
     from . import data as D
     from . import stage_io as IO
     if slm_path is not None and not osp.isdir(slm_path):  # (before anything is loaded; slm.load_snapshot says the same)
         raise L.StyError(f"--slm {slm_path!r} is not an existing directory.  Nothing is downloaded: pass the local snapshot "
                          "directory of the WavLM model (config.json + model.safetensors or pytorch_model.bin)")
+    if slm_train and slm_path is None:
+        raise L.StyError("--slm-train needs --slm DIR (the local snapshot directory of the WavLM model; nothing is downloaded)")
     if deterministic:  # first of all: nothing is sized, loaded or normalised in the other mode
         L.set_deterministic(True)
     random.seed(1)  # train/train.py:87-88
@@ -232,11 +245,17 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
     ctx = TrainContext(config, model_config, out_dir, device, adversarial=adversarial, log=log, deterministic=deterministic)
     if slm_path is not None and stage == "duration":  # (the last stage: no later stage would use the network either)
         log("--slm has no effect on the duration stage (its validation synthesises row by row): the WavLM model is not loaded")
-    elif slm_path is not None and ctx.rank == 0:  # (validation runs on rank 0 alone, and so does this)
+    elif slm_path is not None and (ctx.rank == 0 or slm_train):  # (validation runs on rank 0 alone; the training term on every rank)
         from .slm import WavLMLoss
         slm_cfg = model_config.get("slm") or {}
-        ctx.slm = WavLMLoss(slm_path, int(model_config.sample_rate), int(slm_cfg.get("sr", 16000))).to(device)
+        with torch.random.fork_rng(devices=[]):
+            # (the module draws an initialisation before the snapshot overwrites it: the run's own random stream -- what the
+            # trained models are initialised from -- must not see that, or `--slm DIR` alone would change the training)
+            ctx.slm = WavLMLoss(slm_path, int(model_config.sample_rate), int(slm_cfg.get("sr", 16000))).to(device)
         log(f"slm: WavLM from {slm_path} ({ctx.slm.model_sr} -> {ctx.slm.slm_sr} Hz): validation also logs the slm value")
+        if slm_train:
+            ctx.slm_train = True
+            log(f"slm: the acoustic stage trains with the term, loss_weight.slm = {float(config.loss_weight.slm):g}")
 
     def enter(name):
         st = _Stage(name, ctx)
@@ -351,7 +370,9 @@ def _train_loop(ctx, st, fast_forward, max_steps, total, D, IO, log):
                 vals = out if torch.is_tensor(out) else torch.stack([v.reshape(()) for v in out.values()])
                 first = float(vals.reshape(-1)[0])
                 running = first if running is None else 0.9 * running + 0.1 * first
-                log(f"{st.name} epoch {m.current_epoch} step {m.current_step}/{m.steps_per_epoch}: first logged loss {first:.4f}")
+                slm_v = getattr(st.trainer, "slm_value", None) if getattr(st.trainer, "slm_train", None) is not None else None
+                log(f"{st.name} epoch {m.current_epoch} step {m.current_step}/{m.steps_per_epoch}: first logged loss {first:.4f}"
+                    + (f", slm {float(slm_v):.4f}" if slm_v is not None else ""))
             if should_validate(num, cfg.val_interval, cfg.save_interval):
                 validate()
             if num % int(cfg.save_interval) == 0:
@@ -416,12 +437,14 @@ def main(argv=None):
     ap.add_argument("--slm", dest="slm_path", default=None, metavar="DIR",
                     help="local snapshot directory of the WavLM model (config.json + model.safetensors / pytorch_model.bin): the "
                          "validation passes of the acoustic and textual stage also log the slm value; nothing is downloaded")
+    ap.add_argument("--slm-train", dest="slm_train", action="store_true",
+                    help="with --slm DIR: the acoustic stage trains with the WavLM term, weighted by loss_weight.slm")
     a = ap.parse_args(argv)
     if a.convert:
         convert(a.config_path, a.model_config_path, a.out, a.checkpoint)
         return
     train(a.config_path, a.model_config_path, a.out, a.stage, a.checkpoint, a.reset_stage, max_steps=a.max_steps,
-          validate_only=a.validate_only, deterministic=a.deterministic, slm_path=a.slm_path)
+          validate_only=a.validate_only, deterministic=a.deterministic, slm_path=a.slm_path, slm_train=a.slm_train)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,11 @@
 B = 32 x 156 000 samples at 24 kHz, full width (the class defaults, 12 layers), key-filled weights, fp32 operands.  ms per call from
 device events around blocks of calls after a warm-up; then one profiled call for the per-family split (sty_prof_report).
 Dense work by the issue's count: 87 GFLOP per utterance and forward, 5.6 TFLOP per call; the fp32 matrix-core figure it is set
-against is 157.3 TFLOP/s (v_mfma_f32_32x32x2_f32).  python tools/slm_bench.py [B]"""
+against is 157.3 TFLOP/s (v_mfma_f32_32x32x2_f32).  python tools/slm_bench.py [B]
+
+--grad: the gradient path at the same size instead -- WavLM.forward_keep and WavLM.backward timed apart, the whole
+WavLMLoss.loss_and_grad, the gradient workspace in bytes and the per-family split of one loss_and_grad call.
+python tools/slm_bench.py --grad [B]"""
 import json
 import os
 import statistics
@@ -37,9 +41,73 @@ def dense_flops(n16, cfg=WAVLM_DEFAULT_CFG):
     return fl, T
 
 
+def timed(fn, rounds=ROUNDS, block=BLOCK):
+    ms = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(block):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1) / block)
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def grad_main(B):
+    """forward-keep, backward, the whole loss_and_grad and its per-family split at the c3 wave size"""
+    with tempfile.TemporaryDirectory() as d:
+        from safetensors.torch import save_file
+        json.dump({}, open(os.path.join(d, "config.json"), "w"))
+        save_file(fill_state_dict(wavlm_manifest(), 23), os.path.join(d, "model.safetensors"))
+        loss = slm.WavLMLoss(d, 24000, 16000).to(DEV)
+    g = torch.Generator().manual_seed(3)
+    gt = (0.3 * torch.randn(B, N, generator=g)).to(DEV)
+    pr = gt + (0.03 * torch.randn(B, N, generator=g)).to(DEV)
+    net = loss.wavlm
+    with torch.no_grad():
+        x16 = slm.resample(pr, 24000, 16000)
+        n16 = x16.shape[1]
+        ws = net.grad_workspace_bytes(B, n16, torch.device(DEV))
+        h = net.forward_keep(x16)
+        cot = torch.randn_like(h) / h.numel()
+        net.backward(cot)
+        v, _ = loss.loss_and_grad(gt, pr, 0.2)
+        torch.cuda.synchronize()
+        fwd = timed(lambda: net.forward_keep(x16))
+        plain = timed(lambda: net(x16))
+
+        def both():
+            net.forward_keep(x16)
+            net.backward(cot)
+
+        fb = timed(both)
+        whole = timed(lambda: loss.loss_and_grad(gt, pr, 0.2))
+        fl, T = dense_flops(n16)
+        print(f"slm gradient B={B} N={N} (N16={n16}, T={T}): value {v.item():.6f}; gradient workspace {ws} bytes ({ws / 2**30:.2f} GiB)")
+        print(f"  WavLM.forward {plain[0]:.2f} ms; WavLM.forward_keep {fwd[0]:.2f} ms (min {fwd[1]:.2f}, max {fwd[2]:.2f}); "
+              f"forward_keep + backward {fb[0]:.2f} ms -> backward {fb[0] - fwd[0]:.2f} ms (by difference); {ROUNDS} blocks of {BLOCK}")
+        print(f"  WavLMLoss.loss_and_grad (two resamplings, forward, forward_keep, L1 + sign, backward, resampler adjoint) {whole[0]:.2f} ms "
+              f"(min {whole[1]:.2f}, max {whole[2]:.2f}); backward dense work 2 x {B * fl / 1e12:.2f} TFLOP")
+        lib = L.load()
+        L.check(lib.sty_prof_enable(1))
+        loss.loss_and_grad(gt, pr, 0.2)
+        torch.cuda.synchronize()
+        rows = sorted(L.prof_report(cap=256), key=lambda r: -r["ms"])
+        L.check(lib.sty_prof_enable(0))
+        tot = sum(r["ms"] for r in rows)
+        print(f"per-family split of one loss_and_grad call under the in-situ timers ({tot:.2f} ms in timed launches; untimed glue kernels are not in it):")
+        for r in rows:
+            tf = r["flops"] / (r["ms"] * 1e-3) / 1e12 if r["ms"] > 0 else 0.0
+            print(f"  {r['name']:44s} {r['launches']:5d} launches {r['ms']:9.3f} ms {100 * r['ms'] / tot:5.1f} %  {tf:6.1f} TFLOP/s")
+
+
 def main():
     assert torch.cuda.is_available(), "needs a HIP device"
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+    args = [a for a in sys.argv[1:] if a != "--grad"]
+    B = int(args[0]) if args else 32
+    if "--grad" in sys.argv[1:]:
+        return grad_main(B)
     with tempfile.TemporaryDirectory() as d:
         from safetensors.torch import save_file
         json.dump({}, open(os.path.join(d, "config.json"), "w"))  # the class defaults
