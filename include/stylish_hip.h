@@ -262,6 +262,13 @@ int sty_attention_workspace_bytes(int B, int H, int T, size_t *bytes);
 int sty_attention_fwd_bwd(int B, int H, int DH, int T, const float *q, const float *k, const float *v,
                           const int64_t *lengths, const float *d_o, float *o, float *dq, float *dk, float *dv,
                           void *workspace, size_t ws_bytes, void *stream);
+/* The same with WavLM's gated relative position bias (modeling_wavlm.py, WavLMAttention): logit (i, j) = q_i . k_j / sqrt(DH) +
+ * gate[b, h, i] * tab[h, j - i + T - 1]; gate [B, H, T], tab [H, 2T - 1] (fp32, never rounded), d_o -> dq, dk, dv and d_gate
+ * [B, H, T] (written, no atomic).  compute_bf16 = 1 (DH 64 only): the five products on v_mfma_f32_32x32x16_bf16 with both operands
+ * rounded to bf16, the bias added to the logit in fp32; 0: the fp32 kernels (DH 64 or 16).  Workspace as above.               */
+int sty_attention_rel_fwd_bwd(int B, int H, int DH, int T, const float *q, const float *k, const float *v, const float *gate,
+                              const float *tab, const float *d_o, float *o, float *dq, float *dk, float *dv, float *d_gate,
+                              int compute_bf16, void *workspace, size_t ws_bytes, void *stream);
 /* STFT(64, hop 4).transform -> (mag, atan2(y,x)) bins 0..31, last frame dropped (generator.py:724-729);
  * wave [B,N] -> spec, phase [B,32,N/4].                                                               */
 int sty_stft64_fwd(int B, int N, const float *wave, float *spec, float *phase, void *stream);
@@ -528,9 +535,9 @@ int sty_duration_loss_fwd(int B, int L, int NC, const float *pred, const int64_t
  * encoder.layers.0.attention.rel_attn_embed.weight.  Widths, depths, heads, kernels, groups and num_buckets are read from
  * the bound shapes; what no shape shows (the conv strides, max_bucket_distance, layer_norm_eps) comes from
  * sty_wavlm_set_config, called before sty_model_finalize.  Built: feat_extract_norm "group", do_stable_layer_norm false,
- * conv_bias false, exact GELU.  Frozen, fp32 operands on the fp32 matrix cores: compute_bf16,
- * sty_model_enable_training and sty_model_bind_grad return STY_EINVAL for this kind (the gradient with respect to the wave is
- * built, see below; no weight gradient is).
+ * conv_bias false, exact GELU.  Frozen; fp32 operands on the fp32 matrix cores unless sty_wavlm_set_compute says bf16: the
+ * compute_bf16 of sty_model_set_train_opts, sty_model_enable_training and sty_model_bind_grad return STY_EINVAL for this kind (the
+ * gradient with respect to the wave is built, see below; no weight gradient is).
  * Resampler: torchaudio.transforms.Resample(orig, new) with its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff
  * 0.99) restated from the documented closed form -- torchaudio is no dependency: PARITY UNPINNED at this boundary.  The rates are
  * reduced by their gcd (24000 -> 16000 is 3 -> 2: two phases of 23 taps at stride 3); sty_slm_resample_len = ceil(N new /
@@ -542,6 +549,12 @@ int sty_duration_loss_fwd(int B, int L, int NC, const float *pred, const int64_t
  * sty_wavlm_rel_buckets_host: _relative_positions_bucket of the distances -(T - 1) .. T - 1 (HOST memory).
  * sty_slm_loss_fwd: loss[0] = mean |a - b| over n floats, float64 partials added in index order (two calls, equal bits). */
 int sty_wavlm_set_config(sty_model *m, int n_conv, const int *conv_stride, int max_bucket_distance, float layer_norm_eps);
+/* sty_wavlm_set_compute: the kind's operand mode, 0 = fp32 (the default), 1 = bf16: the dense contractions and, at head dim 64, the
+ *   attention's products round both operands to bf16 (RNE) and run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; everything
+ *   returned or kept stays fp32 (DESIGN.md section 4.24 lists the rounding points).  Kind "wavlm" and values 0 / 1 only (STY_EINVAL
+ *   otherwise); callable before or after finalize and between calls, nothing is re-packed.  The workspace queries answer for the
+ *   current mode; a sty_wavlm_bwd in another mode than its sty_wavlm_fwd_keep returns STY_ESTATE. */
+int sty_wavlm_set_compute(sty_model *m, int bf16);
 int sty_slm_resample_len(int N, int orig, int new_rate);
 int sty_slm_resample_kernel_host(int orig, int new_rate, float *out);
 int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float *audio, float *out, void *stream);
@@ -569,6 +582,17 @@ int sty_wavlm_fwd_keep(sty_model *m, int B, int N16, const float *audio16, float
                        void *stream);
 int sty_wavlm_bwd(sty_model *m, int B, int N16, const float *d_hidden, float *d_audio16, float *d_enc_in, void *workspace,
                   size_t ws_bytes, void *stream);
+/* One strided feature conv alone (Conv1d(Cin, Cout, k, stride s), bias-free), forward and input gradient, through the stage +
+ * conv and dgrad + un-stage launches the plan makes for it in the mode asked for: x [B, Cin, Nin] a pre-activation, w [Cout, Cin, k]
+ * -> y = conv(GELU(x)) [B, Cout, T], T = (Nin - k) / s + 1; gy [B, Cout, T] -> dx [B, Cin, Nin] = GELU'(x) * conv^T(gy), zero where no
+ * frame reads.  view (optional, fp32 [B, s Cin, T + ceil(k / s) - 1]): the phase-major view the fp32 mode stages; view16 (optional,
+ * bf16, the same shape; compute_bf16 = 1 on a twin family only): the operand twin the bf16 mode stages in its place.  routes
+ * (optional, int[4], HOST): kernel family of the conv and of the transposed conv (sty_conv1d_route's numbers), and whether each read
+ * a bf16 twin. */
+int sty_wavlm_strided_conv_workspace_bytes(int B, int Cin, int Cout, int k, int s, int Nin, size_t *bytes);
+int sty_wavlm_strided_conv_fwd_bwd(int B, int Cin, int Cout, int k, int s, int Nin, const float *x, const float *w, int compute_bf16,
+                                   float *y, const float *gy, float *dx, float *view, void *view16, int *routes, void *workspace,
+                                   size_t ws_bytes, void *stream);
 int sty_slm_loss_fwd_bwd(size_t n, const float *a, const float *b, float scale, float *loss, float *d_b, void *workspace,
                          size_t ws_bytes, void *stream);
 int sty_slm_resample_bwd(int B, int N, int orig, int new_rate, const float *d_out, float *d_audio, int accumulate, void *stream);

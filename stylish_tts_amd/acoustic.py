@@ -73,7 +73,7 @@ class AcousticTrainer:
     def __init__(self, speech_predictor, style_encoder, lr=1e-4, betas=(0.85, 0.99), eps=1e-9, weight_decay=1e-4,
                  w_mel=5.0, w_phase=8.0, mean=-4.0, std=4.0, bucket_bytes=25 << 20, train_mode=True, seed=0,
                  text_dropout=0.2, compute="fp32", mrd=None, w_gen=1.0, disc=None, shared_seed=1, deterministic=False,
-                 slm_train=None, w_slm=0.0):
+                 slm_train=None, w_slm=0.0, slm_compute="fp32"):
         import random
         # deterministic=True switches the process-wide deterministic mode on (lib.set_deterministic) before anything is sized;
         # False leaves the switch as it is (STY_DETERMINISTIC=1 or an earlier call may have set it)
@@ -119,8 +119,11 @@ class AcousticTrainer:
             self.disc_helpers = [DiscriminatorLossHelper(m, 5) for m in self.mrd]
         # slm_train: a slm.WavLMLoss on the trainer's device -- the fourth term of the reference's acoustic step
         # (stage_type.py:340-363: mel + multi_phase + generator + slm), w_slm = loss_weight.slm.  The network is frozen and its
-        # gradient local: no parameter, no optimizer state, no collective.  It runs fp32 operands also when compute="bf16".
-        self.slm_train, self.w_slm = slm_train, float(w_slm)
+        # gradient local: no parameter, no optimizer state, no collective.  It runs fp32 operands also when compute="bf16",
+        # unless slm_compute="bf16" (handed to loss_and_grad alone: the validation value of the same object stays fp32).
+        if slm_compute not in ("fp32", "bf16"):
+            raise ValueError(f"slm_compute must be 'fp32' or 'bf16', not {slm_compute!r}")
+        self.slm_train, self.w_slm, self.slm_compute = slm_train, float(w_slm), slm_compute
         self.slm_value = None  # the step's unweighted slm value, a device scalar (like self.gan)
         self.disc = disc  # ContextFreeDiscriminator shell (models.py:74), weight 3 in both losses (losses.py:14)
         if disc is not None:
@@ -269,7 +272,8 @@ class AcousticTrainer:
                 self.gan_wave = torch.cat([gen_w, dsc_w])  # generator loss, discriminator loss, the same without tprls
         if self.slm_train is not None:
             # + loss_weight.slm x WavLMLoss(audio_gt, audio): the value for the log, the gradient added into d_audio
-            self.slm_value, d_audio = self.slm_train.loss_and_grad(audio_gt, audio.squeeze(1), self.w_slm, d_pred=d_audio)
+            self.slm_value, d_audio = self.slm_train.loss_and_grad(audio_gt, audio.squeeze(1), self.w_slm, d_pred=d_audio,
+                                                                        **({"compute": "bf16"} if self.slm_compute == "bf16" else {}))
         if self.mrd is not None:
             # the discriminators' weight gradients are final here (the loss calls above produced them from the same forward
             # pass as the generator term): their buckets travel while the whole predictor / style-encoder backward runs
@@ -352,7 +356,7 @@ class AcousticTrainer:
             # `train --slm`: the batch's slm value beside the log, never in it (validation.py).  A host-side refusal of the slm
             # path (no frame left, a shape) comes back as a value: it must not cost the batch its numbers
             from .validation import or_refusal
-            extra["slm"] = or_refusal(lambda: self.slm(audio_gt, audio))
+            extra["slm"] = or_refusal(lambda: self.slm(audio_gt, audio, compute="fp32"))  # (fp32 whatever the term trains on)
         return {"mel": loss[0]}, extra
 
     @staticmethod

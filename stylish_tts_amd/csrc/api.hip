@@ -864,7 +864,7 @@ struct Run {
 
   void conv(const ConvArgs& a0) {
     ConvArgs a = a0;
-    a.bf16 = m->topts.compute_bf16;  // the compute mode also applies to the inference plans
+    a.bf16 = m->topts.compute_bf16 | m->wav_bf16;  // the compute mode also applies to the inference plans (wavlm: its own door)
     if (live()) chk(launch_conv1d(a, st));
   }
   ConvArgs base(const PackedConv& w, const float* x, int T, float* y) {
@@ -1770,6 +1770,78 @@ static int wavlm_frames_at(const WavlmPlan& p, int N16, int layer) {
   }
   return (int)n;
 }
+// ---- one strided feature conv of the plan, both directions (wavlm_forward / wavlm_backward and the unit entry
+//      sty_wavlm_strided_conv_fwd_bwd run these) ----
+// bf16 mode: does this conv over T columns run on a family that reads source 0 as its bf16 twin alone (convp16 / convq)?  Asked
+// with a placeholder twin, so that sizing calls and launches decide alike.
+static bool wavlm_twin_route(const Run& r, ConvArgs a, ConvKernel* kernel = nullptr, bool offer_twin = true) {
+  a.bf16 = r.m->wav_bf16;
+  if (a.bf16 && offer_twin) a.x16 = reinterpret_cast<const __bf16*>(sizeof(__bf16));
+  const ConvRoute rt = conv1d_route(a);
+  if (kernel) *kernel = rt.kernel;
+  return a.bf16 && rt.x16_only;
+}
+// Forward: `below` [B][C] rows of xrs floats with Tin frames (layer 0's output with (ga, gs) set: its norm and GELU on the way;
+// gelu_in: a pre-activation) -> y.  fp32 mode, and bf16 mode where no twin family takes the conv: the fp32 view in `stg` and the
+// valid conv over its Tp = Tl + K - 1 columns (rows of Tl frames; keep_pre: the pre-activation, else GELU in the epilogue).  bf16
+// mode otherwise: the view is written once, as the bf16 operand twin, and the conv runs as a SAME-LENGTH conv over the Tp columns
+// (pad 0: the reads past the row's end are the zero padding) -- the twin families take no separate input length -- leaving the
+// pre-activation on rows of Tp floats whose last K - 1 columns are partial sums nobody reads (may_pad says the caller's buffers
+// and readers allow such rows).  Returns y's row stride; *left_pre: y holds pre-activations.
+static int wavlm_strided_fwd(Run& r, const PackedConv& w, const float* below, int xrs, int C, int Tin, int S, int Tl, const float* ga,
+                             const float* gs, int gelu_in, bool keep_pre, bool may_pad, float* stg, float* y, bool* left_pre,
+                             ConvKernel* kernel = nullptr, bool* twin = nullptr) {
+  const int Tp = Tl + w.K - 1;
+  ConvArgs a = r.base(w, stg, Tl, y);
+  a.pad = 0;
+  ConvArgs c = a;
+  c.T = Tp;
+  if ((Tp == Tl || may_pad) && wavlm_twin_route(r, c, kernel)) {
+    r.chk(launch_wavlm_stage_rs(below, ga, gs, r.B, C, Tin, xrs, S, Tp, stg, 1, r.st, gelu_in));
+    c.x16 = reinterpret_cast<const __bf16*>(stg);
+    r.conv(c);
+    *left_pre = true;
+    if (twin) *twin = true;
+    return Tp;
+  }
+  if (twin) *twin = false;
+  if (xrs != Tin)
+    r.chk(launch_wavlm_stage_rs(below, ga, gs, r.B, C, Tin, xrs, S, Tp, stg, 0, r.st, gelu_in));
+  else
+    r.chk(launch_wavlm_stage(below, ga, gs, r.B, C, Tin, S, Tp, stg, r.st, gelu_in));
+  a.Tin = Tp != Tl ? Tp : 0;
+  a.act = keep_pre ? ACT_NONE : ACT_GELU;
+  if (kernel) wavlm_twin_route(r, a, kernel, false);
+  r.conv(a);
+  *left_pre = keep_pre;
+  return Tl;
+}
+// Backward: the transposed conv (full correlation: pad K - 1) from the gradient at the conv's pre-activation to the gradient
+// of its view, dvw [B][S C][Tp].  cur16 set: that gradient comes as its bf16 twin on rows of Tp columns, zero from Tl on, and the
+// conv is a same-length conv over them; else cur is the fp32 tensor on rows of Tl floats.
+static void wavlm_strided_dgrad(Run& r, const PackedConv& wd, int K, const float* cur, const __bf16* cur16, int Tl, float* dvw) {
+  const int Tp = Tl + K - 1;
+  ConvArgs a = r.base(wd, cur, Tp, dvw);
+  a.pad = K - 1;
+  if (cur16)
+    a.x16 = cur16;
+  else
+    a.Tin = Tp != Tl ? Tl : 0;
+  r.conv(a);
+}
+// ... and whether it takes the twin (asked by whoever produces the gradient, ahead of producing it)
+static bool wavlm_dgrad_twin(const Run& r, const PackedConv& wd, int K, int Tl, ConvKernel* kernel = nullptr) {
+  Run& rr = const_cast<Run&>(r);
+  ConvArgs a = rr.base(wd, nullptr, Tl + K - 1, nullptr);
+  a.pad = K - 1;
+  if (wavlm_twin_route(r, a, kernel)) return true;
+  if (kernel) {  // (the route the fp32 tensor takes)
+    a.Tin = K > 1 ? Tl : 0;
+    wavlm_twin_route(r, a, kernel, false);
+  }
+  return false;
+}
+
 // WavLMModel.forward(output_hidden_states=True) in eval mode (modeling_wavlm.py): audio16 [B][N16] -> hidden [layers + 1][B][T][H].
 // Every activation is channel-major [B][C][T]; wavlm.hip says what each of its kernels does.
 // kp (sty_wavlm_fwd_keep): the same launches on the same operands, so the same bits, except that (a) every tensor the backward
@@ -1786,7 +1858,9 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden, Wa
     const size_t nh = nn / H * NH, nf = nn / H * p.layers[0].f1.Cout;
     kp->out0 = r.ws.take<float>(bc0 * wavlm_frames_at(p, N16, 0));
     kp->ga = r.ws.take<float>(bc0), kp->gs = r.ws.take<float>(bc0), kp->gmean = r.ws.take<float>(bc0), kp->grstd = r.ws.take<float>(bc0);
-    for (int i = 1; i < nc; ++i) kp->pre[i] = r.ws.take<float>((size_t)B * p.dim[i] * wavlm_frames_at(p, N16, i));
+    // (bf16 mode: rows of Tp = T + K - 1 columns where the conv ran over its padded view)
+    for (int i = 1; i < nc; ++i)
+      kp->pre[i] = r.ws.take<float>((size_t)B * p.dim[i] * (wavlm_frames_at(p, N16, i) + (m->wav_bf16 ? p.conv[i].K - 1 : 0)));
     kp->feat = r.ws.take<float>(nn / H * p.dim[nc - 1]);
     kp->pre_pos = r.ws.take<float>(nn), kp->xa_enc = r.ws.take<float>(nn);
     kp->tab = r.ws.take<float>((size_t)NH * (2 * (nn / H / B) - 1));
@@ -1809,6 +1883,7 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden, Wa
     if (i) {
       Tp[i] = Tl[i] + p.conv[i].K - 1;  // columns of the staged view the conv reads
       max_stage = std::max(max_stage, (size_t)B * p.conv[i].Cin * Tp[i]);
+      if (m->wav_bf16) max_out = std::max(max_out, (size_t)B * p.dim[i] * Tp[i]);
     }
   }
   const int T = Tl[nc - 1], Cl = p.dim[nc - 1];
@@ -1829,20 +1904,25 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden, Wa
       r.chk(launch_wavlm_gn_finalize(part, nt, p.gn_w, p.gn_b, B * p.dim[0], p.dim[0], Tl[0], 1e-5f, ga, gs, r.st,
                                      kp ? kp->gmean : nullptr, kp ? kp->grstd : nullptr));
     }
+    int xrs = Tl[0];        // row stride of the layer below's output
+    bool pre_below = false;  // ... which holds pre-activations: the GELU runs in the staging pass
     for (int i = 1; i < nc && r.live(); ++i) {
       const float* below = !kp ? out : (i == 1 ? kp->out0 : kp->pre[i - 1]);
-      r.chk(launch_wavlm_stage(below, i == 1 ? ga : nullptr, gs, B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], stg, r.st,
-                               kp && i > 1));
-      ConvArgs a = r.base(p.conv[i], stg, Tl[i], kp ? kp->pre[i] : out);
-      a.pad = 0;
-      a.Tin = Tp[i] != Tl[i] ? Tp[i] : 0;
-      a.act = kp ? ACT_NONE : ACT_GELU;
-      r.conv(a);
+      // (the last conv's output goes to an element-wise pass and a LayerNorm over dense rows: no padded rows there)
+      xrs = wavlm_strided_fwd(r, p.conv[i], below, xrs, p.dim[i - 1], Tl[i - 1], p.stride[i], Tl[i], i == 1 ? ga : nullptr, gs,
+                              i > 1 && pre_below, kp != nullptr, i < nc - 1, stg, kp ? kp->pre[i] : out, &pre_below);
+      if (kp) kp->prs[i] = xrs;
     }
     if (r.live()) {
-      if (kp) r.chk(launch_wavlm_gelu(kp->pre[nc - 1], nullptr, (size_t)B * Cl * T, kp->feat, r.st));
-      r.chk(launch_chan_layernorm(kp ? kp->feat : out, stg, B, Cl, T, p.ln_eps, 0, p.fp_ln_w, p.fp_ln_b, nullptr, 0, nullptr, r.st));
-      r.conv(r.base(p.proj, stg, T, x));
+      if (kp)
+        r.chk(launch_wavlm_gelu(kp->pre[nc - 1], nullptr, (size_t)B * Cl * T, kp->feat, r.st));
+      float *ln_in = kp ? kp->feat : out, *ln_out = stg;
+      if (!kp && pre_below) {  // (bf16 mode: the twin families leave the pre-activation; the view in stg has been consumed)
+        r.chk(launch_wavlm_gelu(out, nullptr, (size_t)B * Cl * T, stg, r.st));
+        ln_in = stg, ln_out = out;
+      }
+      r.chk(launch_chan_layernorm(ln_in, ln_out, B, Cl, T, p.ln_eps, 0, p.fp_ln_w, p.fp_ln_b, nullptr, 0, nullptr, r.st));
+      r.conv(r.base(p.proj, ln_out, T, x));
     }
   }
   // ---- encoder ----
@@ -1920,6 +2000,7 @@ static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden, Wa
     at.scale = 1.0f / sqrtf((float)DH);
     at.lengths = nullptr;
     at.rel_tab = tab, at.rel_gate = gate;
+    at.bf16 = m->wav_bf16 && DH == 64;  // (head dim 16, the small test config: the fp32 kernels in both modes)
     if (kp) at.lse = kp->layers[l].lse;
     r.chk(launch_attention(at, B, DH, r.st));
     ConvArgs ao = r.base(y.o, o, T, xa);
@@ -1955,6 +2036,7 @@ static void wavlm_backward(Run& r, int N16, const WavlmKeep& kp, const float* d_
     if (i) {
       Tp[i] = Tl[i] + p.conv[i].K - 1;
       max_stage = std::max(max_stage, (size_t)B * p.conv[i].Cin * Tp[i]);
+      if (m->wav_bf16) max_out = std::max(max_out, (size_t)B * p.dim[i] * Tp[i]);  // (padded rows of a gradient twin fit as well)
     }
   }
   const int T = Tl[nc - 1], Cl = p.dim[nc - 1], G = p.pos_groups, Cg = H / G, FF = p.layers[0].f1.Cout;
@@ -2027,6 +2109,7 @@ static void wavlm_backward(Run& r, int N16, const WavlmKeep& kp, const float* d_
     at.lengths = nullptr;
     at.lse = kl.lse;
     at.rel_tab = kp.tab, at.rel_gate = kl.gate, at.rel_dgate = dgate;
+    at.bf16 = m->wav_bf16 && DH == 64;
     r.chk(launch_attention_bwd(at, t2, dq, dk, dv, at.qbs, at.kbs, at.vbs, at.obs, B, DH, aws, r.st));
     // dx = residual + q / k / v projections' input gradients (+ the gate path, + this layer input's own cotangent)
     ConvArgs cq = r.base(D(y.q), dq, T, t2);
@@ -2071,13 +2154,17 @@ static void wavlm_backward(Run& r, int N16, const WavlmKeep& kp, const float* d_
   // (7) strided feature convs: the stride-1 conv over the s-frames-at-a-time view, transposed (full correlation: pad K - 1), then
   // the un-staging permutation with the GELU' of the layer below; (8) behind layer 0 the GroupNorm backward takes its place
   float *cur = fa, *other = fb;
+  // bf16 mode: a layer whose transposed conv runs on a twin family gets its gradient from the un-staging above it as the bf16
+  // twin on zero-padded rows (the top layer's comes from the GELU' pass in fp32)
+  bool cur_twin = false;
   for (int i = nc - 1; i >= 1 && r.live(); --i) {
-    ConvArgs a = r.base(p.conv_d[i], cur, Tp[i], dvw);
-    a.pad = p.conv[i].K - 1;
-    a.Tin = Tp[i] != Tl[i] ? Tl[i] : 0;
-    r.conv(a);
+    wavlm_strided_dgrad(r, p.conv_d[i], p.conv[i].K, cur, cur_twin ? reinterpret_cast<const __bf16*>(cur) : nullptr, Tl[i], dvw);
     if (!r.live()) return;
-    if (i > 1)
+    if (i > 1 && m->wav_bf16) {
+      cur_twin = wavlm_dgrad_twin(r, p.conv_d[i - 1], p.conv[i - 1].K, Tl[i - 1]);
+      r.chk(launch_wavlm_unstage_rs(dvw, kp.pre[i - 1], B, p.dim[i - 1], Tl[i - 1], kp.prs[i - 1], p.stride[i], Tp[i],
+                                    cur_twin ? Tp[i - 1] : Tl[i - 1], other, cur_twin, r.st));
+    } else if (i > 1)
       r.chk(launch_wavlm_unstage(dvw, kp.pre[i - 1], B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], other, r.st));
     else
       r.chk(launch_wavlm_gn_bwd(kp.out0, dvw, kp.ga, kp.gs, kp.gmean, kp.grstd, B, p.dim[0], Tl[0], p.stride[1], Tp[1], gpart, gcoef, other,
@@ -2279,7 +2366,8 @@ int sty_model_finalize(sty_model* m) {
 static int refuse_aligner(const sty_model* m, const char* what) {
   // (rmvpe: pitch values hang on an arg-max too; wavlm: a frozen network whose forward alone is built)
   if (m->kind != "text_aligner" && m->kind != "rmvpe" && m->kind != "wavlm") return STY_OK;
-  set_error("%s: model kind '%s' is inference-only and runs fp32 operands", what, m->kind.c_str());
+  set_error("%s: model kind '%s' is inference-only and runs fp32 operands%s", what, m->kind.c_str(),
+            m->kind == "wavlm" ? " (its bf16 operand mode has a door of its own: sty_wavlm_set_compute)" : "");
   return STY_EINVAL;
 }
 
@@ -2776,6 +2864,25 @@ int sty_wavlm_set_config(sty_model* m, int n_conv, const int* conv_stride, int m
   m->finalized = false;
   return STY_OK;
 }
+// The kind's own operand mode (sty_model_set_train_opts(compute_bf16) keeps refusing it, as every inference-only kind's does).
+// Nothing is re-packed here: the bf16 fragments of a packed weight are made at its first bf16 launch and live beside the fp32
+// pack for the life of the arena (convp16.hip), so switching back and forth costs nothing after the first call of each mode.
+int sty_wavlm_set_compute(sty_model* m, int bf16) {
+  if (!m) {
+    set_error("sty_wavlm_set_compute: null model");
+    return STY_EINVAL;
+  }
+  if (m->kind != "wavlm") {
+    set_error("sty_wavlm_set_compute: model kind '%s' (the operand mode of kind 'wavlm' alone is set here)", m->kind.c_str());
+    return STY_EINVAL;
+  }
+  if (bf16 != 0 && bf16 != 1) {
+    set_error("sty_wavlm_set_compute: mode %d (0 = fp32 operands, 1 = bf16 operands)", bf16);
+    return STY_EINVAL;
+  }
+  m->wav_bf16 = bf16;
+  return STY_OK;
+}
 int sty_slm_resample_len(int N, int orig, int new_rate) {
   if (N <= 0 || !resample_rates_ok(orig, new_rate)) return -1;
   const int g = gcd_(orig, new_rate);
@@ -2910,6 +3017,7 @@ int sty_wavlm_fwd_keep(sty_model* m, int B, int N16, const float* audio16, float
   if (rc == STY_OK) {
     m->wav_keep.valid = true;
     m->wav_keep.B = B, m->wav_keep.N16 = N16, m->wav_keep.ws = workspace;
+    m->wav_keep.bf16 = m->wav_bf16;
   }
   return rc;
 }
@@ -2931,6 +3039,11 @@ int sty_wavlm_bwd(sty_model* m, int B, int N16, const float* d_hidden, float* d_
               kp.ws != workspace ? " in another workspace" : "");
     return STY_ESHAPE;
   }
+  if (kp.bf16 != m->wav_bf16) {
+    set_error("sty_wavlm_bwd: the model runs %s operands now, but the forward kept in %s mode (sty_wavlm_set_compute between the two)",
+              m->wav_bf16 ? "bf16" : "fp32", kp.bf16 ? "bf16" : "fp32");
+    return STY_ESTATE;
+  }
   size_t need = 0;
   if ((rc = wavlm_grad_need(m, B, N16, &need))) return rc;
   if (ws_bytes < need) {
@@ -2941,6 +3054,101 @@ int sty_wavlm_bwd(sty_model* m, int B, int N16, const float* d_hidden, float* d_
   Run r(m, B, workspace, ws_bytes, stream);
   wavlm_backward(r, N16, kp, d_hidden, d_audio16, d_enc_in);
   return r.finish(nullptr, workspace, ws_bytes);
+}
+// ---- one strided feature conv alone, forward and input gradient: the stage + conv / dgrad + un-stage pair of the plan ----
+// x [B][Cin][Nin] is a pre-activation (what the layer below leaves in keep mode): y = conv1d(GELU(x), w, stride s) [B][Cout][T],
+// T = (Nin - k) / s + 1, no activation; dx = GELU'(x) * (the transposed conv of gy) [B][Cin][Nin], zero where no frame reads.
+static int wavlm_strided_unit(int B, int Cin, int Cout, int k, int s, int Nin, const float* x, const float* w, int compute_bf16,
+                              float* y, const float* gy, float* dx, float* view, void* view16, int* routes, void* ws, size_t ws_bytes,
+                              void* stream, size_t* need) {
+  if (B <= 0 || Cin <= 0 || Cout <= 0 || k < 1 || s < 1 || s > 16 || Nin < k || (compute_bf16 != 0 && compute_bf16 != 1)) {
+    set_error("sty_wavlm_strided_conv: bad argument (k >= 1, stride 1 to 16, Nin >= k, compute_bf16 0 or 1)");
+    return STY_EINVAL;
+  }
+  sty_model tmp;
+  tmp.kind = "wavlm";
+  tmp.wav_bf16 = compute_bf16;
+  Run r(&tmp, B, ws, ws_bytes, stream);
+  const int Tl = (Nin - k) / s + 1;
+  PackedConv pc;
+  pc.Cin = s * Cin, pc.Cout = Cout, pc.K = cdiv(k, s);
+  pc.CinP = (int)align_up(pc.Cin, CI_CHUNK), pc.CoutP = (int)align_up(Cout, 32);
+  const int Tp = Tl + pc.K - 1;
+  const size_t wn = (size_t)pc.K * pc.CinP * pc.CoutP, nv = (size_t)B * pc.Cin * Tp, ny = (size_t)B * Cout * Tp;
+  float* wp = r.ws.take<float>(wn);
+  float* wd = r.ws.take<float>(wn);
+  float* stg = r.ws.take<float>(nv);
+  float* ybuf = r.ws.take<float>(ny);
+  float* gpad = r.ws.take<float>(ny);
+  __bf16* g16 = r.ws.take<__bf16>(ny);
+  float* dvw = r.ws.take<float>(nv);
+  r.note_peak();
+  if (!r.live()) return r.finish(need, ws, ws_bytes);
+  pc.wp = wp;
+  PackedConv pd;
+  pd.Cin = pc.Cout, pd.CinP = pc.CoutP, pd.Cout = pc.Cin, pd.CoutP = pc.CinP, pd.K = pc.K, pd.wp = wd;
+  STY_HIP(hipMemsetAsync(wp, 0, wn * sizeof(float), r.st));
+  WavlmPackJob j;
+  j.w = w, j.wp = wp;
+  j.Cout = Cout, j.Cin = Cin, j.K = k, j.s = s, j.CinP = pc.CinP, j.CoutP = pc.CoutP;
+  r.chk(launch_wavlm_pack(j, r.st));
+  r.chk(launch_pack_dgrad(wp, pc.K, pc.CinP, pc.CoutP, wd, r.st));
+  if (!r.live()) return r.rc;
+  ConvKernel kf = CONV_TILED, kd = CONV_TILED;
+  bool left_pre = false, ftwin = false;
+  const int yrs = wavlm_strided_fwd(r, pc, x, Nin, Cin, Nin, s, Tl, nullptr, nullptr, 1, true, true, stg, ybuf, &left_pre, &kf, &ftwin);
+  if (!r.live()) return r.rc;
+  STY_HIP(hipMemcpy2DAsync(y, (size_t)Tl * sizeof(float), ybuf, (size_t)yrs * sizeof(float), (size_t)Tl * sizeof(float), (size_t)B * Cout,
+                           hipMemcpyDeviceToDevice, r.st));
+  if (view16) {
+    if (!ftwin) {
+      set_error("sty_wavlm_strided_conv: the bf16 twin of the view was asked for, but this conv does not run on a twin family");
+      return STY_EINVAL;
+    }
+    STY_HIP(hipMemcpyAsync(view16, stg, nv * sizeof(__bf16), hipMemcpyDeviceToDevice, r.st));
+  }
+  // the gradient as the plan's producers leave it: the twin on zero-padded rows where the transposed conv takes it
+  const bool dtwin = wavlm_dgrad_twin(r, pd, pc.K, Tl, &kd);
+  if (dtwin) {
+    STY_HIP(hipMemsetAsync(gpad, 0, ny * sizeof(float), r.st));
+    STY_HIP(hipMemcpy2DAsync(gpad, (size_t)Tp * sizeof(float), gy, (size_t)Tl * sizeof(float), (size_t)Tl * sizeof(float), (size_t)B * Cout,
+                             hipMemcpyDeviceToDevice, r.st));
+    r.chk(launch_twin_cast(gpad, nullptr, PRO_NONE, B, Cout, Tp, g16, r.st));
+  }
+  wavlm_strided_dgrad(r, pd, pc.K, gy, dtwin ? g16 : nullptr, Tl, dvw);
+  if (!r.live()) return r.rc;
+  if (compute_bf16)
+    r.chk(launch_wavlm_unstage_rs(dvw, x, B, Cin, Nin, Nin, s, Tp, Nin, dx, 0, r.st));
+  else
+    r.chk(launch_wavlm_unstage(dvw, x, B, Cin, Nin, s, Tp, dx, r.st));
+  if (view && r.live()) r.chk(launch_wavlm_stage(x, nullptr, nullptr, B, Cin, Nin, s, Tp, view, r.st, 1));  // (the fp32 mode's view)
+  if (routes) routes[0] = (int)kf, routes[1] = (int)kd, routes[2] = ftwin, routes[3] = dtwin;
+  return r.rc;
+}
+int sty_wavlm_strided_conv_workspace_bytes(int B, int Cin, int Cout, int k, int s, int Nin, size_t* bytes) {
+  if (!bytes) {
+    set_error("sty_wavlm_strided_conv_workspace_bytes: bad argument");
+    return STY_EINVAL;
+  }
+  return wavlm_strided_unit(B, Cin, Cout, k, s, Nin, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                            nullptr, bytes);
+}
+int sty_wavlm_strided_conv_fwd_bwd(int B, int Cin, int Cout, int k, int s, int Nin, const float* x, const float* w, int compute_bf16,
+                                   float* y, const float* gy, float* dx, float* view, void* view16, int* routes, void* workspace,
+                                   size_t ws_bytes, void* stream) {
+  if (!x || !w || !y || !gy || !dx || !workspace) {
+    set_error("sty_wavlm_strided_conv_fwd_bwd: bad argument");
+    return STY_EINVAL;
+  }
+  size_t need = 0;
+  int rc = sty_wavlm_strided_conv_workspace_bytes(B, Cin, Cout, k, s, Nin, &need);
+  if (rc) return rc;
+  if (ws_bytes < need) {
+    set_error("sty_wavlm_strided_conv_fwd_bwd: workspace too small: need %zu bytes, have %zu", need, ws_bytes);
+    return STY_ENOMEM;
+  }
+  return wavlm_strided_unit(B, Cin, Cout, k, s, Nin, x, w, compute_bf16, y, gy, dx, view, view16, routes, workspace, ws_bytes, stream,
+                            nullptr);
 }
 int sty_wavlm_rel_buckets_host(int T, int num_buckets, int max_distance, int32_t* out) {
   if (T < 1 || num_buckets < 4 || max_distance < 2 || !out || max_distance <= num_buckets / 4) {
@@ -3305,6 +3513,43 @@ int sty_attention_fwd_bwd(int B, int H, int DH, int T, const float* q, const flo
   at.bf16 = getenv("STY_ATTN_UNIT_BF16") != nullptr;  // (read per call: the unit test of attn16.hip sets it)
   float* ws = static_cast<float*>(workspace);
   at.lse = ws;  // row log-sum-exp, kept for the MFMA backward
+  float* w2 = ws + (size_t)B * H * T;
+  STY_HIP(hipMemsetAsync(dq, 0, n * sizeof(float), st));
+  STY_HIP(hipMemsetAsync(dk, 0, n * sizeof(float), st));
+  STY_HIP(hipMemsetAsync(dv, 0, n * sizeof(float), st));
+  int rc = launch_attention(at, B, DH, st);
+  if (rc) return rc;
+  return launch_attention_bwd(at, d_o, dq, dk, dv, at.qbs, at.kbs, at.vbs, at.obs, B, DH, w2, st);
+}
+
+// ... with WavLM's gated relative position bias: logit (i, j) = scale q_i . k_j + gate[b][h][i] * tab[h][j - i + T - 1]; the
+// launches wavlm_forward (keep mode) and wavlm_backward make for one layer, in the mode asked for.  workspace: sty_attention_workspace_bytes
+int sty_attention_rel_fwd_bwd(int B, int H, int DH, int T, const float* q, const float* k, const float* v, const float* gate,
+                              const float* tab, const float* d_o, float* o, float* dq, float* dk, float* dv, float* d_gate,
+                              int compute_bf16, void* workspace, size_t ws_bytes, void* stream) {
+  size_t need = 0;
+  if (sty_attention_workspace_bytes(B, H, T, &need)) return STY_EINVAL;
+  if (!q || !k || !v || !gate || !tab || !d_o || !o || !dq || !dk || !dv || !d_gate || !workspace || ws_bytes < need ||
+      (DH != 16 && DH != 64) || (compute_bf16 != 0 && compute_bf16 != 1)) {
+    set_error("sty_attention_rel_fwd_bwd: bad argument (DH = 16 or 64, compute_bf16 0 or 1, workspace >= %zu bytes)", need);
+    return STY_EINVAL;
+  }
+  if (compute_bf16 && DH != 64) {
+    set_error("sty_attention_rel_fwd_bwd: head dim %d runs the fp32 kernels in both modes (the bf16 matrix-core variant is head dim 64)", DH);
+    return STY_EINVAL;
+  }
+  hipStream_t st = S(stream);
+  const size_t n = (size_t)B * H * DH * T;
+  AttnArgs at;
+  at.q = q, at.k = k, at.v = v, at.o = o;
+  at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * DH * T;
+  at.T = T, at.H = H;
+  at.scale = 1.0f / sqrtf((float)DH);
+  at.lengths = nullptr;
+  at.bf16 = compute_bf16;
+  at.rel_tab = tab, at.rel_gate = gate, at.rel_dgate = d_gate;
+  float* ws = static_cast<float*>(workspace);
+  at.lse = ws;
   float* w2 = ws + (size_t)B * H * T;
   STY_HIP(hipMemsetAsync(dq, 0, n * sizeof(float), st));
   STY_HIP(hipMemsetAsync(dk, 0, n * sizeof(float), st));

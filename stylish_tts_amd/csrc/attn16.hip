@@ -65,6 +65,9 @@ __device__ __forceinline__ void a16_commit(const float (&v)[8], __bf16* row, __b
 }
 
 // ---- forward: O^T[d][i] = sum_j V[d][j] P^T[j][i], P^T = softmax over j of S^T[j][i] = scale sum_d K[d][j] Q[d][i] ----
+// REL (WavLM): S^T[j][i] += rel_gate[b][h][i] * rel_tab[h][j - i + T - 1], added in fp32 to the scaled product; the table is
+// indexed here (a lane owns query i, so its rows j walk one table row) and the kept log-sum-exp has the bias in.
+template <bool REL>
 __global__ __launch_bounds__(256) void attn16_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 krow[32 * A16_PK];
   __shared__ __attribute__((aligned(16))) __bf16 vcol[64 * A16_PV];
@@ -77,6 +80,12 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(AttnArgs a) {
   bf16x8 qf[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) qf[c] = a16_load_d8(qb, T, 16 * c + 8 * hi, qi, qi < T);
+  float rg = 0.f;
+  const float* rrow = nullptr;  // rrow[j]: the table entry of distance j - i (tail lanes stay inside the table and read nothing)
+  if constexpr (REL) {
+    rg = qi < T ? a.rel_gate[((size_t)b * a.H + h) * T + qi] : 0.f;
+    rrow = a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 - (qi < T ? qi : T - 1));
+  }
   f32x16 oacc[2];
 #pragma unroll
   for (int n = 0; n < 2; ++n)
@@ -106,7 +115,10 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int j = j0 + a16_frag_row(r, hi);
-      const float x = j < T ? s[r] * a.scale : -INFINITY;
+      float x = j < T ? s[r] * a.scale : -INFINITY;
+      if constexpr (REL) {
+        if (j < T) x = fmaf(rg, rrow[j], x);
+      }
       s[r] = x;
       mx = fmaxf(mx, x);
     }
@@ -146,16 +158,20 @@ __global__ __launch_bounds__(256) void attn16_fwd_kernel(AttnArgs a) {
 // ---- backward, key side: a wave owns 32 keys j; loop over 32-query tiles ----
 //   S[i][j], dP[i][j] (rows i in registers, columns j across lanes), P = exp(S - lse_i), dS = P (dP - delta_i)
 //   dV[d][j] += sum_i dO[d][i] P[i][j],  dK[d][j] += scale sum_i Q[d][i] dS[i][j]
+// REL: S[i][j] += rel_gate[i] * rel_tab[h][j - i + T - 1] (the gates of the tile's 32 queries beside their lse in LDS)
+template <bool REL>
 __global__ __launch_bounds__(256, 2) void attn16_bwd_kv_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                             const float* __restrict__ lse, const float* __restrict__ delta,
                                                             float* __restrict__ dK, size_t dkbs, float* __restrict__ dV,
                                                             size_t dvbs) {
   __shared__ __attribute__((aligned(16))) __bf16 qrow[32 * A16_PK], grow[32 * A16_PK];
   __shared__ __attribute__((aligned(16))) __bf16 qcol[64 * A16_PV], gcol[64 * A16_PV];
-  __shared__ float lse_s[32], del_s[32];
+  __shared__ float lse_s[32], del_s[32], gate_s[32];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y, T = a.T;
   const int j = blockIdx.x * 128 + wave * 32 + l31;
+  // rcol[-i]: the table entry of distance j - i (tail lanes stay inside the table and read nothing)
+  const float* rcol = REL ? a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 + (j < T ? j : 0)) : nullptr;
   const float* qb = a.q + (size_t)b * a.qbs + (size_t)h * 64 * T;
   const float* kb = a.k + (size_t)b * a.kbs + (size_t)h * 64 * T;
   const float* vb = a.v + (size_t)b * a.vbs + (size_t)h * 64 * T;
@@ -183,6 +199,7 @@ __global__ __launch_bounds__(256, 2) void attn16_bwd_kv_kernel(AttnArgs a, const
     if (tid < 32) {
       lse_s[tid] = i0 + tid < T ? Lb[i0 + tid] : 0.f;
       del_s[tid] = i0 + tid < T ? Db[i0 + tid] : 0.f;
+      if constexpr (REL) gate_s[tid] = i0 + tid < T ? a.rel_gate[((size_t)b * a.H + h) * T + i0 + tid] : 0.f;
     }
     __syncthreads();
     if (i0 + 32 < T) {
@@ -203,7 +220,11 @@ __global__ __launch_bounds__(256, 2) void attn16_bwd_kv_kernel(AttnArgs a, const
     for (int r = 0; r < 16; ++r) {
       const int ii = a16_frag_row(r, hi);
       const bool ok = i0 + ii < T && j < T;
-      const float p = ok ? expf(s[r] * a.scale - lse_s[ii]) : 0.f;
+      float x = s[r] * a.scale;
+      if constexpr (REL) {
+        if (ok) x = fmaf(gate_s[ii], rcol[-(i0 + ii)], x);
+      }
+      const float p = ok ? expf(x - lse_s[ii]) : 0.f;
       s[r] = p;
       dp[r] = p * (dp[r] - del_s[ii]);
     }
@@ -233,6 +254,10 @@ __global__ __launch_bounds__(256, 2) void attn16_bwd_kv_kernel(AttnArgs a, const
 // ---- backward, query side: a wave owns 32 queries i; loop over 32-key tiles ----
 //   S^T[j][i], dP^T[j][i] (rows j in registers, columns i across lanes), dS^T = P^T (dP^T - delta_i)
 //   dQ[d][i] += scale sum_j K[d][j] dS^T[j][i]
+// REL: the bias in S^T as in the forward, and d gate[b][h][i] = sum_j dS^T[j][i] tab[h][j - i + T - 1] in fp32 from the un-rounded
+// dS: a lane sums its rows j in tile order, the two half-waves of a query are added once at the end, the hi = 0 lane WRITES
+// a.rel_dgate (one writer per query row, no atomic).
+template <bool REL>
 __global__ __launch_bounds__(256) void attn16_bwd_q_kernel(AttnArgs a, const float* __restrict__ dO, size_t dobs,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            float* __restrict__ dQ, size_t dqbs) {
@@ -247,6 +272,9 @@ __global__ __launch_bounds__(256) void attn16_bwd_q_kernel(AttnArgs a, const flo
   const float* gb = dO + (size_t)b * dobs + (size_t)h * 64 * T;
   const float L = i < T ? lse[((size_t)b * a.H + h) * T + i] : 0.f;
   const float dl = i < T ? delta[((size_t)b * a.H + h) * T + i] : 0.f;
+  const float rg = (REL && i < T) ? a.rel_gate[((size_t)b * a.H + h) * T + i] : 0.f;
+  const float* rrow = REL ? a.rel_tab + (size_t)h * (2 * T - 1) + (T - 1 - (i < T ? i : T - 1)) : nullptr;  // rrow[j]: distance j - i
+  float dgate = 0.f;
   bf16x8 qf[4], gf[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -282,9 +310,18 @@ __global__ __launch_bounds__(256) void attn16_bwd_q_kernel(AttnArgs a, const flo
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const bool ok = j0 + a16_frag_row(r, hi) < T && i < T;
-      const float p = ok ? expf(s[r] * a.scale - L) : 0.f;
+      const int j = j0 + a16_frag_row(r, hi);
+      const bool ok = j < T && i < T;
+      float x = s[r] * a.scale, tb = 0.f;
+      if constexpr (REL) {
+        if (ok) {
+          tb = rrow[j];
+          x = fmaf(rg, tb, x);
+        }
+      }
+      const float p = ok ? expf(x - L) : 0.f;
       dp[r] = p * (dp[r] - dl);
+      if constexpr (REL) dgate = fmaf(dp[r], tb, dgate);
     }
     const bf16x8 d0 = a16_pack(dp, 0), d1 = a16_pack(dp, 1);
 #pragma unroll
@@ -299,6 +336,10 @@ __global__ __launch_bounds__(256) void attn16_bwd_q_kernel(AttnArgs a, const flo
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int r = 0; r < 16; ++r) dqb[(size_t)(32 * n + a16_frag_row(r, hi)) * T + i] += dq[n][r] * a.scale;
+  }
+  if constexpr (REL) {
+    dgate += __shfl_xor(dgate, 32);
+    if (i < T && hi == 0) a.rel_dgate[((size_t)b * a.H + h) * T + i] = dgate;
   }
 }
 
@@ -316,12 +357,20 @@ __global__ void attn16_delta_kernel(const float* __restrict__ o, size_t obs, con
 
 }  // namespace
 
+// (the gated relative position bias of WavLM goes through: both of rel_tab / rel_gate or neither; head dim 16 stays on the fp32
+// kernels of attn.hip / attn_bwd.hip in both modes)
 bool attention16_eligible(const AttnArgs& a, int DH) {
-  return a.bf16 && DH == 64 && !a.lengths && a.drop_p <= 0.f;
+  return a.bf16 && DH == 64 && !a.lengths && a.drop_p <= 0.f && !a.rel_tab == !a.rel_gate;
 }
 
 int launch_attention16(const AttnArgs& a, int B, hipStream_t st) {
-  hipLaunchKernelGGL(attn16_fwd_kernel, dim3(cdiv(a.T, 128), a.H, B), dim3(256), 0, st, a);
+  const dim3 grid(cdiv(a.T, 128), a.H, B);
+  if (a.rel_tab) {
+    ProfScope prof("attn16_fwd_kernel<true>", 2 * 2.0 * B * a.H * (double)a.T * a.T * 64, 4.0 * 4 * B * a.H * 64.0 * a.T, st);
+    hipLaunchKernelGGL(attn16_fwd_kernel<true>, grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(attn16_fwd_kernel<false>, grid, dim3(256), 0, st, a);
+  }
   STY_LAUNCH_CHECK();
   return STY_OK;
 }
@@ -336,8 +385,18 @@ int launch_attention16_bwd(const AttnArgs& a, const float* dO, float* dQ, float*
   float* delta = ws;
   hipLaunchKernelGGL(attn16_delta_kernel, dim3(cdiv(a.T, 256), a.H, B), dim3(256), 0, st, a.o, a.obs, dO, dobs, a.H, a.T, delta);
   const dim3 g2(cdiv(a.T, 128), a.H, B);
-  hipLaunchKernelGGL(attn16_bwd_kv_kernel, g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dK, dkbs, dV, dvbs);
-  hipLaunchKernelGGL(attn16_bwd_q_kernel, g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dQ, dqbs);
+  if (a.rel_tab) {
+    if (!a.rel_gate || !a.rel_dgate) {
+      set_error("attention16_bwd: the gated relative position bias needs rel_tab, rel_gate and rel_dgate all set");
+      return STY_EINVAL;
+    }
+    ProfScope prof("attn16_bwd_rel_kernels", 5 * 2.0 * B * a.H * (double)a.T * a.T * 64, 4.0 * 8 * B * a.H * 64.0 * a.T, st);
+    hipLaunchKernelGGL(attn16_bwd_kv_kernel<true>, g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dK, dkbs, dV, dvbs);
+    hipLaunchKernelGGL(attn16_bwd_q_kernel<true>, g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dQ, dqbs);
+  } else {
+    hipLaunchKernelGGL(attn16_bwd_kv_kernel<false>, g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dK, dkbs, dV, dvbs);
+    hipLaunchKernelGGL(attn16_bwd_q_kernel<false>, g2, dim3(256), 0, st, a, dO, dobs, a.lse, delta, dQ, dqbs);
+  }
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

@@ -583,6 +583,9 @@ int launch_attention_bwd(const AttnArgs& a, const float* dO, float* dQ, float* d
     set_error("attention_bwd: overwrite requested on a path that accumulates");
     return STY_EINVAL;
   }
+  // (the bias on the bf16 matrix cores, head dim 64: attn16.hip's REL kernels, which need all three operands as well)
+  if (a.rel_tab && a.rel_gate && a.rel_dgate && attention16_eligible(a, DH) && a.lse)
+    return launch_attention16_bwd(a, dO, dQ, dK, dV, dqbs, dkbs, dvbs, dobs, B, ws, st);
   if (a.rel_tab || a.rel_gate || a.rel_dgate) {  // the gated relative position bias (WavLM), refused by name as the forward does
     if (!a.rel_tab || !a.rel_gate || !a.rel_dgate || a.drop_p > 0.f || a.lengths || a.bf16 || (DH != 64 && DH != 16) ||
         (DH == 64 && !a.lse)) {

@@ -303,10 +303,12 @@ struct WavlmKeepLayer {
 struct WavlmKeep {
   bool valid = false;
   int B = 0, N16 = 0;
+  int bf16 = 0;  // the operand mode of the forward that kept (sty_wavlm_set_compute); its backward must run in the same one
   const void* ws = nullptr;
   size_t saved_end = 0;  // workspace offset behind the kept tensors: the backward's scratch starts here
   float *out0 = nullptr, *ga = nullptr, *gs = nullptr, *gmean = nullptr, *grstd = nullptr;
   float* pre[WAVLM_MAX_CONV] = {nullptr};  // pre-activation of feature conv i >= 1
+  int prs[WAVLM_MAX_CONV] = {0};           // ... and its row stride in floats (bf16 mode: a conv over the padded view leaves Tp columns)
   float *feat = nullptr, *pre_pos = nullptr, *xa_enc = nullptr, *tab = nullptr;
   std::vector<float*> x;  // layer inputs: x[l] enters layer l, x[layers] is the last output
   std::vector<WavlmKeepLayer> layers;
@@ -321,6 +323,9 @@ int launch_wavlm_gn_finalize(const double* part, int ntiles, const float* w, con
 // gelu_in (without a): f = GELU(x), the input being a pre-activation (forward_keep)
 int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, int C, int Tin, int S, int Tp, float* y, hipStream_t st,
                        int gelu_in = 0);
+// bf16 operand mode: x on rows of xrs >= Tin floats; y fp32 (y16 = 0) or the bf16 operand twin of the view (y16 = 1)
+int launch_wavlm_stage_rs(const float* x, const float* a, const float* s, int B, int C, int Tin, int xrs, int S, int Tp, void* y,
+                          int y16, hipStream_t st, int gelu_in = 0);
 // [B][G Cg][T] <-> [G][B][Cg][T]
 int launch_wavlm_group_perm(const float* x, int B, int G, int Cg, int T, int to_groups, float* y, hipStream_t st);
 // bucket: the entry of distance -(T - 1) (the caller offsets a larger table)
@@ -340,6 +345,10 @@ int launch_wavlm_gate_bwd(const float* x, const float* w, const float* b, const 
                           int T, float* dx, hipStream_t st);  // dx += (accumulated into the head slices)
 // dx [B][C][Tin] = (dview [B][S C][Tp] un-staged, zero past the view) * GELU'(pre [B][C][Tin])
 int launch_wavlm_unstage(const float* dview, const float* pre, int B, int C, int Tin, int S, int Tp, float* dx, hipStream_t st);
+// bf16 operand mode: pre on rows of prs floats; dx on rows of ors >= Tin elements (zero from Tin on), fp32 or bf16 (dx16 = 1)
+int launch_wavlm_unstage_rs(const float* dview, const float* pre, int B, int C, int Tin, int prs, int S, int Tp, int ors, void* dx,
+                            int dx16, hipStream_t st);
+int launch_wavlm_pack(const WavlmPackJob& j, hipStream_t st);  // weights.hip: one job of wavlm_prepare (the unit entry's pack)
 int wavlm_gn_bwd_ntiles(int T);
 // GroupNorm(C, C) backward with layer 1's un-staging and GELU' fused; part: B C ntiles 2 doubles, coef: B C 2 floats
 int launch_wavlm_gn_bwd(const float* x, const float* dview, const float* ga, const float* gs, const float* mean, const float* rstd, int B,
@@ -394,6 +403,7 @@ struct sty_model {
   sty::RmvpePlan rmv;
   sty::WavlmPlan wav;
   sty::WavlmKeep wav_keep;
+  int wav_bf16 = 0;  // sty_wavlm_set_compute: the dense contractions of the kind on the bf16 matrix cores (0 for every other kind)
   // device bucket table of the distances -(wav_bucket_T - 1) .. wav_bucket_T - 1: a bucket depends on the distance alone, so one
   // table sized for the largest frame count seen serves every smaller one at an offset
   int32_t* wav_bucket_dev = nullptr;

@@ -157,6 +157,57 @@ int launch_wavlm_stage(const float* x, const float* a, const float* s, int B, in
   return STY_OK;
 }
 
+// bf16 operand mode (sty_wavlm_set_compute): the same view with the input's rows `xrs` floats apart (a conv that ran as a
+// same-length conv over its padded view leaves rows of Tp, not T, columns) and, H, written once as the bf16 operand twin the conv
+// multiplies (ConvArgs::x16): the affine, the GELU and the rounding (RNE) happen here, the conv converts nothing.  A thread owns
+// frame t of channel c and walks its S phases: the S consecutive input floats of a frame are read by one thread, the stores of a
+// wave are 128 (H) or 256 consecutive bytes per phase.
+template <int MODE, bool H>
+__global__ __launch_bounds__(256) void wavlm_stage_rs_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                             const float* __restrict__ s, int C, int Tin, int xrs, int S, int Tp,
+                                                             void* __restrict__ y) {
+  const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (t >= Tp) return;
+  const float* xr = x + ((size_t)b * C + c) * xrs;
+  float av = 0.f, sv = 0.f;
+  if constexpr (MODE == 1) av = a[(size_t)b * C + c], sv = s[(size_t)b * C + c];
+  for (int p = 0; p < S; ++p) {
+    const long long ts = (long long)S * t + p;
+    float v = 0.f;
+    if (ts < Tin) {
+      v = xr[ts];
+      if constexpr (MODE == 1) v = gelu_erf(fmaf(v, av, sv));
+      if constexpr (MODE == 2) v = gelu_erf(v);
+    }
+    sty_st_any(y, ((size_t)b * S * C + (size_t)p * C + c) * Tp + t, v, H);
+  }
+}
+int launch_wavlm_stage_rs(const float* x, const float* a, const float* s, int B, int C, int Tin, int xrs, int S, int Tp, void* y,
+                          int y16, hipStream_t st, int gelu_in) {
+  if (xrs < Tin) {
+    set_error("wavlm: staged rows of %d frames on a row stride of %d", Tin, xrs);
+    return STY_EINVAL;
+  }
+  const dim3 grid(cdiv(Tp, 256), C, B);
+  ProfScope prof(y16 ? "wavlm_stage_rs_kernel<16>" : "wavlm_stage_rs_kernel<32>", 0.0, (y16 ? 6.0 : 8.0) * B * S * (double)C * Tp, st);
+#define STY_STAGE_RS(MODE)                                                                                                  \
+  do {                                                                                                                      \
+    if (y16)                                                                                                                \
+      hipLaunchKernelGGL((wavlm_stage_rs_kernel<MODE, true>), grid, dim3(256), 0, st, x, a, s, C, Tin, xrs, S, Tp, y);      \
+    else                                                                                                                    \
+      hipLaunchKernelGGL((wavlm_stage_rs_kernel<MODE, false>), grid, dim3(256), 0, st, x, a, s, C, Tin, xrs, S, Tp, y);     \
+  } while (0)
+  if (a)
+    STY_STAGE_RS(1);
+  else if (gelu_in)
+    STY_STAGE_RS(2);
+  else
+    STY_STAGE_RS(0);
+#undef STY_STAGE_RS
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // positional conv: group-major layout
 // ---------------------------------------------------------------------------------------------------------------------
@@ -408,6 +459,37 @@ __global__ __launch_bounds__(256) void wavlm_unstage_kernel(const float* __restr
 int launch_wavlm_unstage(const float* dview, const float* pre, int B, int C, int Tin, int S, int Tp, float* dx, hipStream_t st) {
   ProfScope prof("wavlm_unstage_kernel", 0.0, 12.0 * B * (double)C * Tin, st);
   hipLaunchKernelGGL(wavlm_unstage_kernel, dim3(cdiv(Tin, 256), C, B), dim3(256), 0, st, dview, pre, C, Tin, S, Tp, dx);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// bf16 operand mode: the same with `pre` on rows of prs floats and the result on rows of ors >= Tin elements, fp32 or (H) the
+// bf16 operand twin of the next input-gradient conv; the columns Tin .. ors - 1 are written zero -- that conv runs as a
+// same-length conv over the padded rows and reads them as the zeros past the gradient's end
+template <bool H>
+__global__ __launch_bounds__(256) void wavlm_unstage_rs_kernel(const float* __restrict__ dview, const float* __restrict__ pre, int C,
+                                                               int Tin, int prs, int S, int Tp, int ors, void* __restrict__ dx) {
+  const int ts = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (ts >= ors) return;
+  float v = 0.f;
+  if (ts < Tin) {
+    const int t = ts / S, p = ts - t * S;
+    const float g = t < Tp ? dview[((size_t)b * S * C + (size_t)p * C + c) * Tp + t] : 0.f;
+    v = g * gelu_erf_grad(pre[((size_t)b * C + c) * prs + ts]);
+  }
+  sty_st_any(dx, ((size_t)b * C + c) * ors + ts, v, H);
+}
+int launch_wavlm_unstage_rs(const float* dview, const float* pre, int B, int C, int Tin, int prs, int S, int Tp, int ors, void* dx,
+                            int dx16, hipStream_t st) {
+  if (prs < Tin || ors < Tin) {
+    set_error("wavlm: un-staged rows of %d frames on row strides of %d and %d", Tin, prs, ors);
+    return STY_EINVAL;
+  }
+  ProfScope prof(dx16 ? "wavlm_unstage_rs_kernel<16>" : "wavlm_unstage_rs_kernel<32>", 0.0, (dx16 ? 10.0 : 12.0) * B * (double)C * Tin, st);
+  if (dx16)
+    hipLaunchKernelGGL(wavlm_unstage_rs_kernel<true>, dim3(cdiv(ors, 256), C, B), dim3(256), 0, st, dview, pre, C, Tin, prs, S, Tp, ors, dx);
+  else
+    hipLaunchKernelGGL(wavlm_unstage_rs_kernel<false>, dim3(cdiv(ors, 256), C, B), dim3(256), 0, st, dview, pre, C, Tin, prs, S, Tp, ors, dx);
   STY_LAUNCH_CHECK();
   return STY_OK;
 }

@@ -427,6 +427,11 @@ __global__ __launch_bounds__(256) void wavlm_pack_kernel(WavlmPackJob j) {
   }
   if (threadIdx.x == 0 && j.bp) j.bp[co] = j.bias ? j.bias[j.co0 + co] : 0.f;
 }
+int launch_wavlm_pack(const WavlmPackJob& j, hipStream_t st) {
+  hipLaunchKernelGGL(wavlm_pack_kernel, dim3(j.Cout), dim3(256), 0, st, j);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
 int wavlm_prepare(const WavlmPlan& p, hipStream_t st) {
   if (p.pos_nrm)
     hipLaunchKernelGGL(wavlm_tap_norm_kernel, dim3(p.pos_k), dim3(256), 0, st, p.pos_v, p.hidden * (p.hidden / p.pos_groups), p.pos_k,

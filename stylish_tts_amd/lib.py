@@ -103,6 +103,7 @@ SYMBOLS = {
     "sty_block_fwd_bwd": (C.c_int, [_P, C.c_char_p, C.c_char_p, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_attention_workspace_bytes": (C.c_int, [_I, _I, _I, _SZP]),
     "sty_attention_fwd_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sty_attention_rel_fwd_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, C.c_size_t, _P]),
     "sty_stft64_fwd": (C.c_int, [_I, _I, _P, _P, _P, _P]),
     "sty_istft64_fwd": (C.c_int, [_I, _I, _P, _P, _P, _P, _P]),
     "sty_source_fwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_uint64, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -204,6 +205,9 @@ SYMBOLS = {
     "sty_rmvpe_fwd": (C.c_int, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
     "sty_rmvpe_decode": (C.c_int, [_I, _I, _P, C.c_float, _P, _P]),
     "sty_wavlm_set_config": (C.c_int, [_P, _I, _P, _I, C.c_float]),
+    "sty_wavlm_set_compute": (C.c_int, [_P, _I]),
+    "sty_wavlm_strided_conv_workspace_bytes": (C.c_int, [_I, _I, _I, _I, _I, _I, _SZP]),
+    "sty_wavlm_strided_conv_fwd_bwd": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "sty_slm_resample_len": (C.c_int, [_I, _I, _I]),
     "sty_slm_resample_kernel_host": (C.c_int, [_I, _I, _P]),
     "sty_slm_resample_fwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P]),

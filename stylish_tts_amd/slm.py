@@ -7,8 +7,17 @@ What is built: the value -- the network's forward in HIP (csrc/wavlm.hip), logge
 and the gradient with respect to the predicted wave: `WavLMLoss.loss_and_grad`, the term inside `AcousticTrainer.train_batch`
 (`train --slm DIR --slm-train`).  The network is frozen, so the backward is the input-gradient chain alone: resampler adjoint,
 feature-encoder and transformer input gradients, the L1 sign.  It is an explicit call, this package's idiom; there is no
-autograd node: `WavLMLoss.forward` still raises in grad mode when the prediction requires a gradient.  The kind runs fp32
-operands whatever the trainer's compute mode is; a bf16 operand mode is not built.
+autograd node: `WavLMLoss.forward` still raises in grad mode when the prediction requires a gradient.
+
+Operand mode.  The kind runs fp32 operands by default, whatever the trainer's compute mode is.  `WavLM.set_compute("bf16")`,
+`WavLMLoss(..., compute="bf16")` or a per-call `compute="bf16"` of `forward` / `loss_and_grad` (`train --slm DIR --slm-train
+--slm-bf16`) put the network's dense contractions -- feature convs 1 .. n - 1, the feature projection, the positional conv,
+q / k / v / o, both FFN convs and, at head dim 64, the attention's products -- on the bf16 matrix cores: both operands rounded to
+bf16 (RNE), fp32 accumulation, fp32 storage of everything returned or kept.  Layer 0's conv, the norms, GELU, the gate, the
+relative bias (added to the logits in fp32), softmax statistics, residual adds, the L1 and the resampler stay fp32 (DESIGN.md
+section 4.24 has the list).  The reference runs WavLM under autocast when `mixed_precision` is bf16; the mode is this path's
+counterpart and is held to be no further from float64 than autocast is (tests/test_slm_bf16_gpu.py).  The validation value is
+always computed on fp32 operands.  `set_train_opts(compute_bf16=True)` keeps refusing the kind: the mode has this door alone.
 
 Nothing is downloaded.  `model` is a local directory in the hub snapshot layout: `config.json` plus `model.safetensors`, or
 `pytorch_model.bin` read with `torch.load(weights_only=True)`.  The `transformers` package is not imported: `config.json` is read
@@ -44,6 +53,12 @@ _WN_OLD = {"weight_g": "parametrizations.weight.original0", "weight_v": "paramet
 
 def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check_compute(compute):
+    if compute not in ("fp32", "bf16"):
+        raise L.StyError(f"WavLM: compute must be 'fp32' or 'bf16', not {compute!r}")
+    return compute
 
 
 def check_wavlm_config(cfg):
@@ -117,8 +132,21 @@ class WavLM(_HipModule):
 
     def set_train_opts(self, **kw):
         if kw.get("compute_bf16"):
-            raise L.StyError("WavLM: compute_bf16 is refused: the kind runs fp32 operands (the bf16 mode is not built)")
+            raise L.StyError("WavLM: compute_bf16 is refused: the train options of the kind stay fp32; its bf16 operand mode is "
+                             "set with WavLM.set_compute('bf16')")
         return super().set_train_opts(**kw)
+
+    def set_compute(self, compute):
+        """the network's operand mode, "fp32" (the default) or "bf16" (see the module docstring); holds until the next call.
+        Nothing is re-packed: both weight forms live side by side once each mode has run."""
+        self.__dict__["_compute"] = _check_compute(compute)
+        if self._handle is not None:
+            L.check(L.load().sty_wavlm_set_compute(self._handle, int(compute == "bf16")))
+        return self
+
+    @property
+    def compute(self):
+        return self.__dict__.get("_compute", "fp32")
 
     def _ensure(self, device):
         if self._handle is None and torch.device(device).type == "cuda":
@@ -128,6 +156,7 @@ class WavLM(_HipModule):
             stride = (C.c_int * len(self.cfg["conv_stride"]))(*self.cfg["conv_stride"])
             L.check(lib.sty_wavlm_set_config(h, len(self.cfg["conv_stride"]), stride, int(self.cfg["max_bucket_distance"]),
                                              float(self.cfg["layer_norm_eps"])))
+            L.check(lib.sty_wavlm_set_compute(h, int(self.compute == "bf16")))
             self._handle = h
         return super()._ensure(device)
 
@@ -294,12 +323,15 @@ def load_snapshot(model):
 
 
 class WavLMLoss(torch.nn.Module):
-    """WavLMLoss(model, model_sr, slm_sr=16000) (train/losses.py:376-394): the reference's constructor; `model` is a local
-    snapshot directory.  forward(wav [B, N], y_rec [B, 1, N] or [B, N]) -> scalar, under torch.no_grad().
-    loss_and_grad(wav, y_rec, weight, d_pred) -> (the same scalar, weight * d value / d y_rec [B, N])."""
+    """WavLMLoss(model, model_sr, slm_sr=16000, compute="fp32") (train/losses.py:376-394): the reference's constructor plus the
+    operand mode; `model` is a local snapshot directory.  forward(wav [B, N], y_rec [B, 1, N] or [B, N]) -> scalar, under
+    torch.no_grad().  loss_and_grad(wav, y_rec, weight, d_pred) -> (the same scalar, weight * d value / d y_rec [B, N]).  Both take
+    `compute=None` ("fp32" / "bf16"): the operand mode of that call alone, so that one object serves the fp32 validation value and
+    the bf16 training term; None = the object's own."""
 
-    def __init__(self, model, model_sr, slm_sr=16000):
+    def __init__(self, model, model_sr, slm_sr=16000, compute="fp32"):
         super().__init__()
+        self.compute = _check_compute(compute)
         cfg, state = load_snapshot(model)
         self.wavlm = WavLM(**{k: v for k, v in cfg.items() if k in SUPPORTED or k in _SHAPE_FIELDS})
         self.wavlm.load_state_dict(state, strict=True)
@@ -308,15 +340,16 @@ class WavLMLoss(torch.nn.Module):
             p.requires_grad_(False)
         self.model_sr, self.slm_sr = int(model_sr), int(slm_sr)
 
-    def hidden_states(self, wav):
+    def hidden_states(self, wav, compute=None):
         """[B, N] at model_sr -> [layers + 1, B, T, H]"""
+        self.wavlm.set_compute(_check_compute(compute or self.compute))
         return self.wavlm(self._to_slm_rate(wav))
 
     def _to_slm_rate(self, wav):
         # (equal rates: torchaudio's Resample.forward hands the wave back unchanged; the 15-tap table of 1 -> 1 is no identity)
         return wav if self.model_sr == self.slm_sr else resample(wav, self.model_sr, self.slm_sr)
 
-    def forward(self, wav, y_rec):
+    def forward(self, wav, y_rec, compute=None):
         if torch.is_grad_enabled() and y_rec.requires_grad:
             raise L.StyError("WavLMLoss: backward is not built")
         if y_rec.dim() == 3 and y_rec.shape[1] == 1:
@@ -328,8 +361,8 @@ class WavLMLoss(torch.nn.Module):
             raise L.StyError(f"WavLMLoss: unequal lengths {tuple(wav.shape)} and {tuple(y_rec.shape)}")
         with torch.no_grad():
             # (the ground-truth stack is kept; the second forward reuses the network's workspace)
-            ref = self.hidden_states(wav)
-            return l1_mean(ref, self.hidden_states(y_rec))
+            ref = self.hidden_states(wav, compute)
+            return l1_mean(ref, self.hidden_states(y_rec, compute))
 
     def _pair(self, wav, y_rec):
         if y_rec.dim() == 3 and y_rec.shape[1] == 1:
@@ -342,7 +375,7 @@ class WavLMLoss(torch.nn.Module):
         return y_rec
 
     @torch.no_grad()
-    def loss_and_grad(self, wav, y_rec, weight=1.0, d_pred=None):
+    def loss_and_grad(self, wav, y_rec, weight=1.0, d_pred=None, compute=None):
         """(value, d_audio [B, N]): the unweighted value with the bits forward() gives, and weight * d value / d y_rec -- the weight
         folded into the L1 cotangent.  With `d_pred` (a contiguous fp32 [B, N]) the gradient is accumulated into that tensor, which
         is returned.  Every host-side refusal (shapes, no frame left) is raised before anything is launched."""
@@ -350,7 +383,7 @@ class WavLMLoss(torch.nn.Module):
         B, N = y_rec.shape
         if d_pred is not None and (tuple(d_pred.shape) != (B, N) or d_pred.dtype != torch.float32 or not d_pred.is_contiguous()):
             raise L.StyError(f"WavLMLoss.loss_and_grad: d_pred must be a contiguous fp32 [{B}, {N}] (got {tuple(d_pred.shape)})")
-        ref = self.hidden_states(wav)
+        ref = self.hidden_states(wav, compute)  # (sets the network's mode for the three calls of this step)
         value, d_h = l1_mean_and_grad(ref, self.wavlm.forward_keep(self._to_slm_rate(y_rec)), weight)
         d16 = self.wavlm.backward(d_h)
         if self.model_sr == self.slm_sr:

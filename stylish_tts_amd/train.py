@@ -4,7 +4,7 @@ the HIP path -> accelerate-layout checkpoints, stage after stage (acoustic -> te
 
     python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic [--checkpoint DIR] [--reset-stage]
     python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage S --checkpoint DIR --validate-only [--slm DIR]
-    python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic --slm DIR --slm-train
+    python -m stylish_tts_amd.train CONFIG.yml --model-config MODEL.yml --out OUT --stage acoustic --slm DIR --slm-train [--slm-bf16]
 
 or `stylish_tts_amd.train.train(config_path, model_config_path, out, stage, checkpoint, reset_stage)` -- the reference
 command's arguments in the reference command's order.  What is joined here exists piece by piece elsewhere in this package
@@ -25,7 +25,9 @@ would have left it, so a table the reference probed is used as it is when the fi
 The WavLM term of the acoustic step (stage_type.py:340-363, `loss_weight.slm`): `--slm DIR` alone logs its value in the validation
 pass; with `--slm-train` the acoustic stage also trains with it (slm.WavLMLoss.loss_and_grad inside AcousticTrainer.train_batch,
 every rank with its own copy of the frozen network, fp32 operands whatever `mixed_precision` says) and the step log line gains
-`, slm V`.  The reference has the term in no other stage, and neither has this loop.
+`, slm V`.  `--slm-bf16` (with `--slm-train`) runs the training term on bf16 operands (slm.py, "Operand mode": the counterpart of
+the reference's autocast around WavLM); the validation value stays on fp32 operands, so validation.jsonl does not change with it.
+The reference has the term in no other stage, and neither has this loop.
 """
 import json
 import os
@@ -129,6 +131,7 @@ class TrainContext:
         self.deterministic = bool(deterministic)  # handed to every stage's trainer
         self.slm = None  # slm.WavLMLoss on the device (train_model(slm_path=...), rank 0): the validation pass hands it to the trainer
         self.slm_train = False  # train_model(slm_train=True): every rank holds self.slm and the acoustic trainer trains with it
+        self.slm_bf16 = False  # train_model(slm_bf16=True): the training term on bf16 operands (the validation value stays fp32)
         self.rank, self.world = dist.init() if "WORLD_SIZE" in os.environ else (0, 1)
         mp = config.training.mixed_precision
         if mp not in ("no", "bf16"):
@@ -187,7 +190,8 @@ class TrainContext:
             adv = dict(mrd=[self.model(f"mrd{i}") for i in range(3)], disc=self.model("disc"),
                        w_gen=float(w.generator)) if self.adversarial else {}
             if getattr(self, "slm_train", False):  # --slm-train: the fourth term, weighted by loss_weight.slm
-                adv = dict(adv, slm_train=self.slm, w_slm=float(w.slm))
+                adv = dict(adv, slm_train=self.slm, w_slm=float(w.slm),
+                           slm_compute="bf16" if getattr(self, "slm_bf16", False) else "fp32")
             return AcousticTrainer(self.model("speech_predictor"), self.model("speech_style_encoder"), w_mel=float(w.mel),
                                    w_phase=float(w.multi_phase), text_dropout=float(self.model_config.text_encoder.dropout),
                                    **adv, **common)
@@ -211,7 +215,7 @@ class TrainContext:
 
 def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage=False, config_path="", model_config_path="",
                 max_steps=None, adversarial=True, device=None, log=_log, validate_only=False, deterministic=False, slm_path=None,
-                slm_train=False):
+                slm_train=False, slm_bf16=False):
     """train/train.py:76-338.  `deterministic`: the library's deterministic mode for the run (fixed-order sums: two runs from one
     seed give the same bits on one rank; the order of the gradient exchange between ranks is the backend's).  `max_steps`: stop after that many optimizer steps IN TOTAL (tests; None = the plan's epochs).
     `validate_only`: load `checkpoint`, run ONE validation pass of `stage` (log line, samples, eval/validation.jsonl; the record
@@ -222,6 +226,7 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
     best_loss do not see it.
     `slm_train` (needs `slm_path`): the acoustic stage trains with the term, weighted by `loss_weight.slm`; every rank loads the
     network, the gradient is local (no new collective), and the step log line gains `, slm V`.  The other stages do not change.
+    `slm_bf16` (needs `slm_train`): the training term runs on bf16 operands (slm.py); the validation value stays on fp32 operands.
     Returns the context (models, manifest, the last stage's trainer under `.stage`)."""
     from . import data as D
     from . import stage_io as IO
@@ -230,6 +235,9 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
                          "directory of the WavLM model (config.json + model.safetensors or pytorch_model.bin)")
     if slm_train and slm_path is None:
         raise L.StyError("--slm-train needs --slm DIR (the local snapshot directory of the WavLM model; nothing is downloaded)")
+    if slm_bf16 and not slm_train:
+        raise L.StyError("--slm-bf16 needs --slm-train (it sets the operands of the training term; the validation value always "
+                         "runs fp32 operands)")
     if deterministic:  # first of all: nothing is sized, loaded or normalised in the other mode
         L.set_deterministic(True)
     random.seed(1)  # train/train.py:87-88
@@ -255,7 +263,9 @@ def train_model(config, model_config, out_dir, stage, checkpoint="", reset_stage
         log(f"slm: WavLM from {slm_path} ({ctx.slm.model_sr} -> {ctx.slm.slm_sr} Hz): validation also logs the slm value")
         if slm_train:
             ctx.slm_train = True
-            log(f"slm: the acoustic stage trains with the term, loss_weight.slm = {float(config.loss_weight.slm):g}")
+            ctx.slm_bf16 = bool(slm_bf16)
+            log(f"slm: the acoustic stage trains with the term, loss_weight.slm = {float(config.loss_weight.slm):g}, on "
+                f"{'bf16' if slm_bf16 else 'fp32'} operands")
 
     def enter(name):
         st = _Stage(name, ctx)
@@ -439,12 +449,16 @@ def main(argv=None):
                          "validation passes of the acoustic and textual stage also log the slm value; nothing is downloaded")
     ap.add_argument("--slm-train", dest="slm_train", action="store_true",
                     help="with --slm DIR: the acoustic stage trains with the WavLM term, weighted by loss_weight.slm")
+    ap.add_argument("--slm-bf16", dest="slm_bf16", action="store_true",
+                    help="with --slm-train: the training term runs on bf16 operands (bf16 matrix cores, fp32 accumulation); the "
+                         "validation value stays on fp32 operands")
     a = ap.parse_args(argv)
     if a.convert:
         convert(a.config_path, a.model_config_path, a.out, a.checkpoint)
         return
     train(a.config_path, a.model_config_path, a.out, a.stage, a.checkpoint, a.reset_stage, max_steps=a.max_steps,
-          validate_only=a.validate_only, deterministic=a.deterministic, slm_path=a.slm_path, slm_train=a.slm_train)
+          validate_only=a.validate_only, deterministic=a.deterministic, slm_path=a.slm_path, slm_train=a.slm_train,
+          slm_bf16=a.slm_bf16)
 
 
 if __name__ == "__main__":

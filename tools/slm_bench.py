@@ -6,7 +6,13 @@ against is 157.3 TFLOP/s (v_mfma_f32_32x32x2_f32).  python tools/slm_bench.py [B
 
 --grad: the gradient path at the same size instead -- WavLM.forward_keep and WavLM.backward timed apart, the whole
 WavLMLoss.loss_and_grad, the gradient workspace in bytes and the per-family split of one loss_and_grad call.
-python tools/slm_bench.py --grad [B]"""
+python tools/slm_bench.py --grad [B]
+
+--compute fp32|bf16|both (default fp32): the operand mode of the network (slm.py, "Operand mode"); `both` measures the two modes one
+after the other in one process, fp32 first, and states the ratios.
+--step: the c3-gan training step (bench.py's workload: B 32, T 520, bf16 operands, adversarial terms on) with AcousticTrainer driven
+directly, in three settings: without the slm term, with it on fp32 operands, with it on bf16 operands (a full-width key-filled
+WavLMLoss(24000 -> 16000), w_slm 0.2).  python tools/slm_bench.py --step"""
 import json
 import os
 import statistics
@@ -54,13 +60,23 @@ def timed(fn, rounds=ROUNDS, block=BLOCK):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def grad_main(B):
-    """forward-keep, backward, the whole loss_and_grad and its per-family split at the c3 wave size"""
+PEAK_BF16_MFMA = 16 * 157.3e12  # v_mfma_f32_32x32x16_bf16: 16 x the fp32 matrix-core rate per clock
+
+
+def full_width_loss(compute="fp32"):
     with tempfile.TemporaryDirectory() as d:
         from safetensors.torch import save_file
         json.dump({}, open(os.path.join(d, "config.json"), "w"))
         save_file(fill_state_dict(wavlm_manifest(), 23), os.path.join(d, "model.safetensors"))
-        loss = slm.WavLMLoss(d, 24000, 16000).to(DEV)
+        return slm.WavLMLoss(d, 24000, 16000, compute=compute).to(DEV)
+
+
+def grad_main(B, compute="fp32", loss=None):
+    """forward-keep, backward, the whole loss_and_grad and its per-family split at the c3 wave size; returns the medians"""
+    loss = loss or full_width_loss()
+    loss.compute = compute
+    loss.wavlm.set_compute(compute)
+    print(f"---- operand mode {compute} ----")
     g = torch.Generator().manual_seed(3)
     gt = (0.3 * torch.randn(B, N, generator=g)).to(DEV)
     pr = gt + (0.03 * torch.randn(B, N, generator=g)).to(DEV)
@@ -100,19 +116,88 @@ def grad_main(B):
         for r in rows:
             tf = r["flops"] / (r["ms"] * 1e-3) / 1e12 if r["ms"] > 0 else 0.0
             print(f"  {r['name']:44s} {r['launches']:5d} launches {r['ms']:9.3f} ms {100 * r['ms'] / tot:5.1f} %  {tf:6.1f} TFLOP/s")
+        if compute == "bf16":
+            lead = max((r for r in rows if r["flops"] > 0), key=lambda r: r["ms"])
+            tf = lead["flops"] / (lead["ms"] * 1e-3)
+            print(f"leading dense family in bf16 mode: {lead['name']} at {tf / 1e12:.1f} TFLOP/s, {100 * tf / PEAK_BF16_MFMA:.1f} % of the "
+                  f"bf16 matrix-core figure ({PEAK_BF16_MFMA / 1e12:.1f} TFLOP/s)")
+            left = [r["name"] for r in rows if r["name"].startswith("conv1d_mfma_kernel") and r["name"].endswith("false>")]
+            print("dense families left on conv1d_mfma_kernel<...,false> in bf16 mode: " + (", ".join(left) if left else "none"))
+    return dict(forward=plain, forward_keep=fwd, fwd_bwd=fb, loss_and_grad=whole, workspace=ws)
+
+
+def both_modes(B):
+    loss = full_width_loss()
+    res = {c: grad_main(B, c, loss) for c in ("fp32", "bf16")}
+    print("---- fp32 operands against bf16 operands (medians of the blocks above) ----")
+    for k, label in (("forward", "WavLM.forward"), ("forward_keep", "WavLM.forward_keep"), ("fwd_bwd", "forward_keep + backward"),
+                     ("loss_and_grad", "WavLMLoss.loss_and_grad")):
+        a, b = res["fp32"][k], res["bf16"][k]
+        print(f"  {label:28s} fp32 {a[0]:8.2f} ms (min {a[1]:.2f}, max {a[2]:.2f}; spread {a[2] - a[1]:.2f})   bf16 {b[0]:8.2f} ms "
+              f"(min {b[1]:.2f}, max {b[2]:.2f})   ratio {a[0] / b[0]:.2f}x, {a[0] - b[0]:.2f} ms less")
+    print(f"  gradient workspace: fp32 {res['fp32']['workspace'] / 2**30:.2f} GiB, bf16 {res['bf16']['workspace'] / 2**30:.2f} GiB")
+
+
+def step_main():
+    """the c3-gan step with the trainer driven directly: without the term, with it on fp32 operands, with it on bf16 operands"""
+    import bench
+    from stylish_tts_amd.acoustic import AcousticTrainer
+    from stylish_tts_amd.discriminators import ContextFreeDiscriminator, SpecDiscriminator
+    w = bench.WORKLOADS["c3-gan"]
+    inp = bench.make_inputs(w, 1000, DEV)
+    loss = full_width_loss()
+    res = {}
+    for label, kw in (("without the term", {}), ("with slm_train, fp32 operands", dict(slm_train=loss, w_slm=0.2, slm_compute="fp32")),
+                      ("with slm_train, bf16 operands", dict(slm_train=loss, w_slm=0.2, slm_compute="bf16"))):
+        model, style_enc, _ = bench.build_model(DEV)
+        torch.manual_seed(7)
+        mrd = [SpecDiscriminator().to(DEV) for _ in range(3)]
+        trainer = AcousticTrainer(model, style_enc, lr=1e-4, compute=w["compute"], seed=0, mrd=mrd, disc=ContextFreeDiscriminator().to(DEV), **kw)
+        n = [0]
+
+        def step():
+            n[0] += 1
+            trainer.train_batch(audio_gt=inp["audio_gt"], texts=inp["texts"], text_lengths=inp["text_lengths"], pitch=inp["pitch"],
+                                durations=inp["durations"], seed=n[0])
+
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        res[label] = timed(step, rounds=5, block=3)
+        r = res[label]
+        sv = f"  slm value {float(trainer.slm_value):.6f}" if kw else ""
+        print(f"c3-gan step, trainer directly, {label}: median {r[0]:.2f} ms (min {r[1]:.2f}, max {r[2]:.2f}; 5 blocks of 3){sv}")
+        del trainer, model, style_enc, mrd
+        torch.cuda.empty_cache()
+    base, f32, b16 = (res[k] for k in res)
+    print(f"the slm term adds {f32[0] - base[0]:.2f} ms on fp32 operands and {b16[0] - base[0]:.2f} ms on bf16 operands to a c3-gan step of "
+          f"{base[0]:.2f} ms; step ratio fp32 / bf16 {f32[0] / b16[0]:.2f}x ({f32[0] - b16[0]:.2f} ms less; the fp32 blocks' own spread "
+          f"{f32[2] - f32[1]:.2f} ms)")
 
 
 def main():
     assert torch.cuda.is_available(), "needs a HIP device"
-    args = [a for a in sys.argv[1:] if a != "--grad"]
+    argv = sys.argv[1:]
+    compute = "fp32"
+    if "--compute" in argv:
+        i = argv.index("--compute")
+        compute = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+        if compute not in ("fp32", "bf16", "both"):
+            raise SystemExit("--compute fp32|bf16|both")
+    if "--step" in argv:
+        return step_main()
+    args = [a for a in argv if a != "--grad"]
     B = int(args[0]) if args else 32
-    if "--grad" in sys.argv[1:]:
-        return grad_main(B)
+    if "--grad" in argv:
+        return both_modes(B) if compute == "both" else grad_main(B, compute)
+    if compute == "both":
+        raise SystemExit("--compute both goes with --grad")
     with tempfile.TemporaryDirectory() as d:
         from safetensors.torch import save_file
         json.dump({}, open(os.path.join(d, "config.json"), "w"))  # the class defaults
         save_file(fill_state_dict(wavlm_manifest(), 23), os.path.join(d, "model.safetensors"))
-        loss = slm.WavLMLoss(d, 24000, 16000).to(DEV)
+        loss = slm.WavLMLoss(d, 24000, 16000, compute=compute).to(DEV)
     g = torch.Generator().manual_seed(3)
     gt = (0.3 * torch.randn(B, N, generator=g)).to(DEV)
     pr = gt + (0.03 * torch.randn(B, N, generator=g)).to(DEV)
