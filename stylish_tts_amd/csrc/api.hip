@@ -9,11 +9,9 @@
 #include <algorithm>
 #include <functional>
 #include <map>
-#include <mutex>
 #include <string>
-#include <tuple>
 
-#include "model.h"
+#include "run.h"
 
 namespace sty {
 
@@ -828,539 +826,459 @@ struct Builder {
   }
 };
 
-static hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // ---------------------------------------------------------------------------------------------------
-// forward plans
+// forward plans: the blocks and plans of Run (run.h)
 // ---------------------------------------------------------------------------------------------------
-struct Run {
-  sty_model* m;
-  Bump ws;
-  hipStream_t st;
-  int B;
-  float* gb = nullptr;  // style fc outputs
-  int rc = STY_OK;
-
-  // workspace == nullptr: a sizing call (allocations are tracked, nothing is launched)
-  Run(sty_model* model, int batch, void* workspace, size_t ws_bytes, void* stream) : m(model), st(S(stream)), B(batch) {
-    ws.base = (char*)workspace;
-    ws.cap = ws_bytes;
-  }
-  // the end of an entry point: the size a sizing call asked for, or an overflow of the caller's workspace
-  int finish(size_t* need, const void* workspace, size_t ws_bytes) {
-    if (need) *need = align_up(peak > ws.off ? peak : ws.off, 256) + 256;
-    if (workspace && (ws.overflow || peak > ws_bytes)) {
-      set_error("workspace too small: need %zu bytes, have %zu", peak, ws_bytes);
-      return STY_ENOMEM;
-    }
-    return rc;
-  }
-
-  const float* gbp(const AdaFc& a) const { return gb ? gb + a.off * B : nullptr; }
-  void chk(int r) {
-    if (rc == STY_OK && r != STY_OK) rc = r;
-  }
-  bool live() const { return ws.base != nullptr && rc == STY_OK; }
-
-  void conv(const ConvArgs& a0) {
-    ConvArgs a = a0;
-    a.bf16 = m->topts.compute_bf16 | m->wav_bf16;  // the compute mode also applies to the inference plans (wavlm: its own door)
-    if (live()) chk(launch_conv1d(a, st));
-  }
-  ConvArgs base(const PackedConv& w, const float* x, int T, float* y) {
-    ConvArgs a;
-    a.x[0] = x;
-    a.xc[0] = w.Cin;
-    a.nsrc = 1;
-    a.B = B;
-    a.T = T;
-    a.w = w;
-    a.pad = (w.K - 1) / 2;
-    a.y = y;
-    return a;
-  }
-
-  // AdaIN fold of tensor x [B][C][T] -> per-(b,c) affine (a, s)
-  void adain(const float* x, int C, int T, const AdaFc& fc, float* a, float* s, double* part) {
-    if (!live()) return;
-    chk(launch_row_stats(x, B * C, T, part, st));
-    chk(launch_adain_finalize(part, row_stats_nseg(T), gbp(fc), B, C, T, 1e-5f, a, s, st));
-  }
-
-  size_t peak = 0;
-  void note_peak() { peak = ws.off > peak ? ws.off : peak; }
-  struct Scope {  // temporaries taken inside a scope are released (bump pointer rewound) at its end
-    Run& r;
-    size_t off;
-    explicit Scope(Run& run) : r(run), off(run.ws.off) {}
-    ~Scope() {
-      r.note_peak();
-      r.ws.off = off;
-    }
-  };
-
-  // GeneratorConvNeXtBlock: x [B][C][T] -> y.  The fused C == 32 kernel reads a 3-sample halo of x, so it must
-  // run out of place (y != x); the generic path is in place when y == x (its last conv is 1x1).
-  void convnext(const ConvNeXt& c, const float* x, float* y, int T) {
-    const int C = c.C;
-    Scope sc(*this);
-    if (C == 32) {
-      if (live() && x == y) {
-        set_error("internal: fused ConvNeXt32 needs distinct input and output buffers");
-        rc = STY_EINVAL;
-        return;
-      }
-      const int nt = convnext32_ntiles(T);
-      double* part = ws.take<double>((size_t)B * 128 * nt * 2);
-      float* scale = ws.take<float>((size_t)B * 128);
-      if (live()) {
-        Cnx32Args a;
-        a.x = x;
-        a.dw_w = c.dw_w;
-        a.dw_b = c.dw_b;
-        a.gb = gbp(c.norm);
-        a.w1p = c.w1p;
-        a.b1 = c.b1;
-        a.alpha = c.alpha;
-        a.w2a = c.w2a;
-        a.b2eff = c.pw2.bias;
-        a.scale = scale;
-        a.part = part;
-        a.y = y;
-        a.T = T;
-        a.ntiles = nt;
-        a.bf16 = m->topts.compute_bf16;
-        chk(launch_convnext32(a, B, 1, st));
-        chk(launch_grn_finalize(part, nt, c.grn_gamma, B, 128, scale, st));
-        chk(launch_convnext32(a, B, 2, st));
-      }
+// GeneratorConvNeXtBlock: x [B][C][T] -> y.  The fused C == 32 kernel reads a 3-sample halo of x, so it must
+// run out of place (y != x); the generic path is in place when y == x (its last conv is 1x1).
+void Run::convnext(const ConvNeXt& c, const float* x, float* y, int T) {
+  const int C = c.C;
+  Scope sc(*this);
+  if (C == 32) {
+    if (live() && x == y) {
+      set_error("internal: fused ConvNeXt32 needs distinct input and output buffers");
+      rc = STY_EINVAL;
       return;
     }
-    float* u = ws.take<float>((size_t)B * C * T);
-    float* h = ws.take<float>((size_t)B * 4 * C * T);
-    const int nseg = row_stats_nseg(T);
-    double* part = ws.take<double>((size_t)B * 4 * C * nseg * 2);
-    float* scale = ws.take<float>((size_t)B * 4 * C);
+    const int nt = convnext32_ntiles(T);
+    double* part = ws.take<double>((size_t)B * 128 * nt * 2);
+    float* scale = ws.take<float>((size_t)B * 128);
     if (live()) {
-      chk(launch_dwconv_adaln(x, c.dw_w, c.dw_b, B, C, T, 7, 1e-6f, gbp(c.norm), u, st));
-      ConvArgs a = base(c.pw1, u, T, h);
-      a.act = c.alpha ? ACT_SNAKE : ACT_GELU;  // Generator block: snake; AdaptiveConvNeXtBlock: exact GELU
-      a.act_alpha = c.alpha;
+      Cnx32Args a;
+      a.x = x;
+      a.dw_w = c.dw_w;
+      a.dw_b = c.dw_b;
+      a.gb = gbp(c.norm);
+      a.w1p = c.w1p;
+      a.b1 = c.b1;
+      a.alpha = c.alpha;
+      a.w2a = c.w2a;
+      a.b2eff = c.pw2.bias;
+      a.scale = scale;
+      a.part = part;
+      a.y = y;
+      a.T = T;
+      a.ntiles = nt;
+      a.bf16 = m->topts.compute_bf16;
+      chk(launch_convnext32(a, B, 1, st));
+      chk(launch_grn_finalize(part, nt, c.grn_gamma, B, 128, scale, st));
+      chk(launch_convnext32(a, B, 2, st));
+    }
+    return;
+  }
+  float* u = ws.take<float>((size_t)B * C * T);
+  float* h = ws.take<float>((size_t)B * 4 * C * T);
+  const int nseg = row_stats_nseg(T);
+  double* part = ws.take<double>((size_t)B * 4 * C * nseg * 2);
+  float* scale = ws.take<float>((size_t)B * 4 * C);
+  if (live()) {
+    chk(launch_dwconv_adaln(x, c.dw_w, c.dw_b, B, C, T, 7, 1e-6f, gbp(c.norm), u, st));
+    ConvArgs a = base(c.pw1, u, T, h);
+    a.act = c.alpha ? ACT_SNAKE : ACT_GELU;  // Generator block: snake; AdaptiveConvNeXtBlock: exact GELU
+    a.act_alpha = c.alpha;
+    conv(a);
+    chk(launch_row_stats(h, B * 4 * C, T, part, st));
+    chk(launch_grn_finalize(part, nseg, c.grn_gamma, B, 4 * C, scale, st));
+    ConvArgs b2 = base(c.pw2, h, T, y);
+    b2.pro = PRO_SCALE;
+    b2.pa = scale;
+    b2.residual = x;
+    conv(b2);
+  }
+}
+
+// AdaptiveGeneratorBlock in place on x [B][32][T].  When the convs run on the persistent 32-channel kernel, each one
+// leaves the (sum, sum of squares) partials of its OUTPUT behind (ConvArgs::stat_part), so only the first AdaIN of
+// the block needs a statistics pass of its own.
+void Run::resblock(const ResBlock32& r, float* x, int T) {
+  Scope sc_(*this);
+  float* xt = ws.take<float>((size_t)B * 32 * T);
+  const int nseg_row = row_stats_nseg(T), nseg_p = conv32p_stat_nseg(T);
+  const int nseg_max = nseg_row > nseg_p ? nseg_row : nseg_p;
+  double* part_x = ws.take<double>((size_t)B * 32 * nseg_max * 2);
+  double* part_t = ws.take<double>((size_t)B * 32 * nseg_max * 2);
+  float* a = ws.take<float>(B * 32);
+  float* s = ws.take<float>(B * 32);
+  const int dil[3] = {1, 3, 5};
+  bool have_x = false;  // part_x holds the statistics of x (left by the previous iteration's second conv)
+  for (int i = 0; i < 3 && live(); ++i) {
+    if (have_x)
+      chk(launch_adain_finalize(part_x, nseg_p, gbp(r.n1[i]), B, 32, T, 1e-5f, a, s, st));
+    else
+      adain(x, 32, T, r.n1[i], a, s, part_x);
+    ConvArgs c1 = base(r.c1[i], x, T, xt);
+    c1.dil = dil[i];
+    c1.pad = 5 * dil[i];
+    c1.pro = PRO_AFFINE_SNAKE;
+    c1.pa = a;
+    c1.ps = s;
+    c1.palpha = r.a1[i];
+    const bool f1 = plan_route(m, c1).stats();
+    if (f1) c1.stat_part = part_t;
+    conv(c1);
+    if (f1)
+      chk(launch_adain_finalize(part_t, nseg_p, gbp(r.n2[i]), B, 32, T, 1e-5f, a, s, st));
+    else
+      adain(xt, 32, T, r.n2[i], a, s, part_t);
+    ConvArgs c2 = base(r.c2[i], xt, T, x);
+    c2.pro = PRO_AFFINE_SNAKE;
+    c2.pa = a;
+    c2.ps = s;
+    c2.palpha = r.a2[i];
+    c2.residual = x;
+    have_x = plan_route(m, c2).stats() && i + 1 < 3;
+    if (have_x) c2.stat_part = part_x;
+    conv(c2);
+  }
+}
+
+// ConformerBlock on x [B][C][T] -> out (conformer.py:242-250)
+void Run::conformer(const Conformer& c, const float* x, float* out, int C, int T) {
+  Scope sc_(*this);
+  const size_t n = (size_t)B * C * T;
+  float* z = ws.take<float>(n);
+  float* big = ws.take<float>(4 * n);
+  float* xff1 = ws.take<float>(n);
+  float* q = ws.take<float>(2 * n);
+  float* kv = ws.take<float>(4 * n);
+  float* o = ws.take<float>(2 * n);
+  float* x2 = ws.take<float>(n);
+  float* g = ws.take<float>(2 * n);
+  float* d = ws.take<float>(2 * n);
+  float* x3 = ws.take<float>(n);
+  float* x4 = ws.take<float>(n);
+  if (live()) {
+    auto ff = [&](const AdaFc& nrm, const PackedConv& w0, const PackedConv& w3, const float* in, float* res) {
+      layernorm_ada(in, z, C, T, nrm);
+      ConvArgs a = base(w0, z, T, big);
+      a.act = ACT_SWISH;
       conv(a);
-      chk(launch_row_stats(h, B * 4 * C, T, part, st));
-      chk(launch_grn_finalize(part, nseg, c.grn_gamma, B, 4 * C, scale, st));
-      ConvArgs b2 = base(c.pw2, h, T, y);
-      b2.pro = PRO_SCALE;
-      b2.pa = scale;
-      b2.residual = x;
+      ConvArgs b2 = base(w3, big, T, res);
+      b2.out_scale = 0.5f;
+      b2.residual = in;
       conv(b2);
-    }
+    };
+    ff(c.ff1n, c.ff1a, c.ff1b, x, xff1);
+    layernorm_ada(x, z, C, T, c.attn_n);
+    conv(base(c.to_q, z, T, q));
+    conv(base(c.to_kv, z, T, kv));
+    AttnArgs at;
+    const int inner = c.to_q.Cout;  // 512 = 8 x 64
+    at.q = q;
+    at.k = kv;
+    at.v = kv + (size_t)inner * T;
+    at.o = o;
+    at.qbs = (size_t)inner * T;
+    at.kbs = at.vbs = (size_t)2 * inner * T;
+    at.obs = (size_t)inner * T;
+    at.T = T;
+    at.H = 8;
+    at.scale = 1.0f / sqrtf((float)(inner / 8));
+    at.lengths = nullptr;
+    at.bf16 = m->topts.compute_bf16;  // (round 6) bf16 mode: the conformer's attention on the bf16 matrix cores in the inference
+                                      // plan as well (attn16.hip, as the training graph since round 4; c5-bf16: 242 us per forward
+                                      // on the fp32 kernel)
+    chk(launch_attention(at, B, inner / 8, st));
+    ConvArgs ao = base(c.to_out, o, T, x2);
+    ao.residual = xff1;
+    conv(ao);
+    layernorm_ada(x2, z, C, T, c.conv_n);
+    ConvArgs p1 = base(c.pw1, z, T, g);
+    p1.act = ACT_GLU;
+    conv(p1);
+    chk(launch_dwconv_bn_swish(g, c.dw_w, c.dw_b, c.bn_w, c.bn_b, c.bn_rm, c.bn_rv, 1e-5f, B, 2 * C, T, 31, d, st));
+    ConvArgs p2 = base(c.pw2, d, T, x3);
+    p2.residual = x2;
+    conv(p2);
+    ff(c.ff2n, c.ff2a, c.ff2b, x3, x4);
+    layernorm_ada(x4, out, C, T, c.post_n);
   }
+}
 
-  // AdaptiveGeneratorBlock in place on x [B][32][T].  When the convs run on the persistent 32-channel kernel, each one
-  // leaves the (sum, sum of squares) partials of its OUTPUT behind (ConvArgs::stat_part), so only the first AdaIN of
-  // the block needs a statistics pass of its own.
-  void resblock(const ResBlock32& r, float* x, int T) {
-    Scope sc_(*this);
-    float* xt = ws.take<float>((size_t)B * 32 * T);
-    const int nseg_row = row_stats_nseg(T), nseg_p = conv32p_stat_nseg(T);
-    const int nseg_max = nseg_row > nseg_p ? nseg_row : nseg_p;
-    double* part_x = ws.take<double>((size_t)B * 32 * nseg_max * 2);
-    double* part_t = ws.take<double>((size_t)B * 32 * nseg_max * 2);
-    float* a = ws.take<float>(B * 32);
-    float* s = ws.take<float>(B * 32);
-    const int dil[3] = {1, 3, 5};
-    bool have_x = false;  // part_x holds the statistics of x (left by the previous iteration's second conv)
-    for (int i = 0; i < 3 && live(); ++i) {
-      if (have_x)
-        chk(launch_adain_finalize(part_x, nseg_p, gbp(r.n1[i]), B, 32, T, 1e-5f, a, s, st));
-      else
-        adain(x, 32, T, r.n1[i], a, s, part_x);
-      ConvArgs c1 = base(r.c1[i], x, T, xt);
-      c1.dil = dil[i];
-      c1.pad = 5 * dil[i];
-      c1.pro = PRO_AFFINE_SNAKE;
-      c1.pa = a;
-      c1.ps = s;
-      c1.palpha = r.a1[i];
-      const bool f1 = plan_route(m, c1).stats();
-      if (f1) c1.stat_part = part_t;
-      conv(c1);
-      if (f1)
-        chk(launch_adain_finalize(part_t, nseg_p, gbp(r.n2[i]), B, 32, T, 1e-5f, a, s, st));
-      else
-        adain(xt, 32, T, r.n2[i], a, s, part_t);
-      ConvArgs c2 = base(r.c2[i], xt, T, x);
-      c2.pro = PRO_AFFINE_SNAKE;
-      c2.pa = a;
-      c2.ps = s;
-      c2.palpha = r.a2[i];
-      c2.residual = x;
-      have_x = plan_route(m, c2).stats() && i + 1 < 3;
-      if (have_x) c2.stat_part = part_x;
-      conv(c2);
-    }
+// MultiGenerator.forward
+void Run::vocoder(const sty_vocoder_io& io) {
+  const VocoderPlan& v = m->voc;
+  const int T = io.T, Tu = 75 * T, N = 300 * T, C = v.hidden;
+  // ---- harmonic source branch (no grad in the reference) ----
+  float* prior = ws.take<float>((size_t)B * N);
+  float* srcws = ws.take<float>(source_workspace_floats(B, T));
+  float* lap = ws.take<float>((size_t)B * 32 * Tu);
+  float* pp = ws.take<float>((size_t)B * 32 * Tu);
+  float* hs = ws.take<float>((size_t)B * 32 * Tu);
+  float* hp = ws.take<float>((size_t)B * 32 * Tu);
+  const float* prior_used = prior;
+  if (live()) {
+    if (io.prior_override)
+      prior_used = io.prior_override;
+    else
+      chk(launch_source(B, T, io.pitch, io.voiced, io.noise, io.seed, v.lin_w, v.lin_b, prior, srcws, st));
+    chk(launch_stft64(B, N, prior_used, v.stft_fr, v.stft_fi, hs, hp, st));
+    conv(base(v.amp_prior_conv, hs, Tu, lap));
+    conv(base(v.phase_prior_conv, hp, Tu, pp));
   }
-
-  void layernorm_ada(const float* x, float* y, int C, int T, const AdaFc& fc) {
-    if (live()) chk(launch_chan_layernorm(x, y, B, C, T, 1e-5f, 1, nullptr, nullptr, gbp(fc), 0, nullptr, st));
+  resblock(v.amp_prior_block, lap, Tu);
+  resblock(v.phase_prior_block, pp, Tu);
+  if (live()) {
+    tap(io.tap_prior, prior_used, (size_t)B * N);
+    tap(io.tap_har_spec, hs, (size_t)B * 32 * Tu);
+    tap(io.tap_har_phase, hp, (size_t)B * 32 * Tu);
+    tap(io.tap_logamp_prior, lap, (size_t)B * 32 * Tu);
+    tap(io.tap_phase_prior, pp, (size_t)B * 32 * Tu);
   }
-
-  // ConformerBlock on x [B][C][T] -> out (conformer.py:242-250)
-  void conformer(const Conformer& c, const float* x, float* out, int C, int T) {
-    Scope sc_(*this);
-    const size_t n = (size_t)B * C * T;
-    float* z = ws.take<float>(n);
-    float* big = ws.take<float>(4 * n);
-    float* xff1 = ws.take<float>(n);
-    float* q = ws.take<float>(2 * n);
-    float* kv = ws.take<float>(4 * n);
-    float* o = ws.take<float>(2 * n);
-    float* x2 = ws.take<float>(n);
-    float* g = ws.take<float>(2 * n);
-    float* d = ws.take<float>(2 * n);
-    float* x3 = ws.take<float>(n);
-    float* x4 = ws.take<float>(n);
-    if (live()) {
-      auto ff = [&](const AdaFc& nrm, const PackedConv& w0, const PackedConv& w3, const float* in, float* res) {
-        layernorm_ada(in, z, C, T, nrm);
-        ConvArgs a = base(w0, z, T, big);
-        a.act = ACT_SWISH;
-        conv(a);
-        ConvArgs b2 = base(w3, big, T, res);
-        b2.out_scale = 0.5f;
-        b2.residual = in;
-        conv(b2);
-      };
-      ff(c.ff1n, c.ff1a, c.ff1b, x, xff1);
-      layernorm_ada(x, z, C, T, c.attn_n);
-      conv(base(c.to_q, z, T, q));
-      conv(base(c.to_kv, z, T, kv));
-      AttnArgs at;
-      const int inner = c.to_q.Cout;  // 512 = 8 x 64
-      at.q = q;
-      at.k = kv;
-      at.v = kv + (size_t)inner * T;
-      at.o = o;
-      at.qbs = (size_t)inner * T;
-      at.kbs = at.vbs = (size_t)2 * inner * T;
-      at.obs = (size_t)inner * T;
-      at.T = T;
-      at.H = 8;
-      at.scale = 1.0f / sqrtf((float)(inner / 8));
-      at.lengths = nullptr;
-      at.bf16 = m->topts.compute_bf16;  // (round 6) bf16 mode: the conformer's attention on the bf16 matrix cores in the inference
-                                        // plan as well (attn16.hip, as the training graph since round 4; c5-bf16: 242 us per forward
-                                        // on the fp32 kernel)
-      chk(launch_attention(at, B, inner / 8, st));
-      ConvArgs ao = base(c.to_out, o, T, x2);
-      ao.residual = xff1;
-      conv(ao);
-      layernorm_ada(x2, z, C, T, c.conv_n);
-      ConvArgs p1 = base(c.pw1, z, T, g);
-      p1.act = ACT_GLU;
-      conv(p1);
-      chk(launch_dwconv_bn_swish(g, c.dw_w, c.dw_b, c.bn_w, c.bn_b, c.bn_rm, c.bn_rv, 1e-5f, B, 2 * C, T, 31, d, st));
-      ConvArgs p2 = base(c.pw2, d, T, x3);
-      p2.residual = x2;
-      conv(p2);
-      ff(c.ff2n, c.ff2a, c.ff2b, x3, x4);
-      layernorm_ada(x4, out, C, T, c.post_n);
-    }
+  // hs / hp are dead from here on: reuse them
+  // ---- stage A @T ----
+  const size_t mark = ws.off;
+  float* x0 = ws.take<float>((size_t)B * C * T);
+  float* x1 = ws.take<float>((size_t)B * C * T);
+  float* xc = ws.take<float>((size_t)B * C * T);
+  if (live()) {
+    conv(base(v.amp_input_conv, io.mel, T, x0));
+    chk(launch_chan_layernorm(x0, x1, B, C, T, 1e-6f, 0, v.amp_norm_w, v.amp_norm_b, nullptr, 0, nullptr, st));
   }
-
-  // MultiGenerator.forward
-  void vocoder(const sty_vocoder_io& io) {
-    const VocoderPlan& v = m->voc;
-    const int T = io.T, Tu = 75 * T, N = 300 * T, C = v.hidden;
-    // ---- harmonic source branch (no grad in the reference) ----
-    float* prior = ws.take<float>((size_t)B * N);
-    float* srcws = ws.take<float>(source_workspace_floats(B, T));
-    float* lap = ws.take<float>((size_t)B * 32 * Tu);
-    float* pp = ws.take<float>((size_t)B * 32 * Tu);
-    float* hs = ws.take<float>((size_t)B * 32 * Tu);
-    float* hp = ws.take<float>((size_t)B * 32 * Tu);
-    const float* prior_used = prior;
+  conformer(v.conf, x1, xc, C, T);
+  if (live()) tap(io.tap_conformer_out, xc, (size_t)B * C * T);
+  // ---- stage B: ConvNeXt trunk with pixel-shuffle upsampling ----
+  for (const ConvNeXt& c : v.amp_convnext) convnext(c, xc, xc, T);
+  float* cur = xc;
+  int Tc = T, Cc = C;
+  const int rates[3] = {3, 5, 5};
+  float* trunk = nullptr;
+  for (int i = 0; i < 3; ++i) {
+    const int s = rates[i];
+    float* nx = (i == 2) ? hs : ws.take<float>((size_t)B * (Cc / 2) * Tc * s);
     if (live()) {
-      if (io.prior_override)
-        prior_used = io.prior_override;
-      else
-        chk(launch_source(B, T, io.pitch, io.voiced, io.noise, io.seed, v.lin_w, v.lin_b, prior, srcws, st));
-      chk(launch_stft64(B, N, prior_used, v.stft_fr, v.stft_fi, hs, hp, st));
-      conv(base(v.amp_prior_conv, hs, Tu, lap));
-      conv(base(v.phase_prior_conv, hp, Tu, pp));
-    }
-    resblock(v.amp_prior_block, lap, Tu);
-    resblock(v.phase_prior_block, pp, Tu);
-    if (live()) {
-      tap(io.tap_prior, prior_used, (size_t)B * N);
-      tap(io.tap_har_spec, hs, (size_t)B * 32 * Tu);
-      tap(io.tap_har_phase, hp, (size_t)B * 32 * Tu);
-      tap(io.tap_logamp_prior, lap, (size_t)B * 32 * Tu);
-      tap(io.tap_phase_prior, pp, (size_t)B * 32 * Tu);
-    }
-    // hs / hp are dead from here on: reuse them
-    // ---- stage A @T ----
-    const size_t mark = ws.off;
-    float* x0 = ws.take<float>((size_t)B * C * T);
-    float* x1 = ws.take<float>((size_t)B * C * T);
-    float* xc = ws.take<float>((size_t)B * C * T);
-    if (live()) {
-      conv(base(v.amp_input_conv, io.mel, T, x0));
-      chk(launch_chan_layernorm(x0, x1, B, C, T, 1e-6f, 0, v.amp_norm_w, v.amp_norm_b, nullptr, 0, nullptr, st));
-    }
-    conformer(v.conf, x1, xc, C, T);
-    if (live()) tap(io.tap_conformer_out, xc, (size_t)B * C * T);
-    // ---- stage B: ConvNeXt trunk with pixel-shuffle upsampling ----
-    for (const ConvNeXt& c : v.amp_convnext) convnext(c, xc, xc, T);
-    float* cur = xc;
-    int Tc = T, Cc = C;
-    const int rates[3] = {3, 5, 5};
-    float* trunk = nullptr;
-    for (int i = 0; i < 3; ++i) {
-      const int s = rates[i];
-      float* nx = (i == 2) ? hs : ws.take<float>((size_t)B * (Cc / 2) * Tc * s);
-      if (live()) {
-        ConvArgs a = base(v.upconv[i], cur, Tc, nx);
-        a.shuffle = s;
-        conv(a);
-      }
-      Tc *= s;
-      Cc /= 2;
-      if (i == 2) {  // C == 32: fused block, out of place hs -> hp (har_phase is dead by now)
-        convnext(v.upblock[i], nx, hp, Tc);
-        nx = hp;
-      } else {
-        convnext(v.upblock[i], nx, nx, Tc);
-      }
-      cur = nx;
-    }
-    trunk = cur;  // [B][32][Tu] (lives in hp)
-    if (live()) tap(io.tap_trunk, trunk, (size_t)B * 32 * Tu);
-    note_peak();
-    ws.off = mark;
-    // ---- heads @75T ----
-    float* logamp = ws.take<float>((size_t)B * 32 * Tu);
-    float* ph = hs;
-    float* ph_alt = ws.take<float>((size_t)B * 32 * Tu);
-    float* real = ws.take<float>((size_t)B * 32 * Tu);
-    float* imag = ws.take<float>((size_t)B * 32 * Tu);
-    // The final LayerNorms in front of the k = 21 head convs: fused into the tiled kernel's prologue (rounds 1-4) where the
-    // persistent 32-channel kernel does not take the conv; where it does (round 5), a LayerNorm pass + the persistent kernel are
-    // faster than the fused tiled launch (c5-bf16: 121 us against ~35 + 40; the real / imag pair shares one pass)
-    ConvArgs head_probe = base(v.amp_output_conv, trunk, Tu, logamp);
-    const bool head32p = plan_route(m, head_probe).kernel == CONV_32P;
-    float* lnbuf = head32p ? ws.take<float>((size_t)B * 32 * Tu) : nullptr;
-    if (live()) {
-      ConvArgs a = base(v.amp_output_conv, trunk, Tu, logamp);
-      if (head32p) {
-        chk(launch_chan_layernorm(trunk, lnbuf, B, 32, Tu, 1e-6f, 0, v.amp_fln_w, v.amp_fln_b, nullptr, 0, nullptr, st));
-        a.x[0] = lnbuf;
-      } else {
-        a.pro = PRO_LN_AFFINE;
-        a.palpha = v.amp_fln_w;
-        a.pbeta = v.amp_fln_b;
-        a.ln_eps = 1e-6f;
-      }
+      ConvArgs a = base(v.upconv[i], cur, Tc, nx);
+      a.shuffle = s;
       conv(a);
-      tap(io.tap_logamp, logamp, (size_t)B * 32 * Tu);
-      ConvArgs p = base(v.phase_input_conv, trunk, Tu, ph);
-      p.nsrc = 3;
-      p.x[1] = lap;
-      p.x[2] = pp;
-      p.xc[0] = p.xc[1] = p.xc[2] = 32;
-      p.ln_out = 1;
-      p.ln_w = v.phase_norm_w;
-      p.ln_b = v.phase_norm_b;
-      p.ln_eps = 1e-6f;
-      conv(p);
     }
-    for (const ConvNeXt& c : v.phase_convnext) {  // ping-pong: the fused block is out of place
-      convnext(c, ph, ph_alt, Tu);
-      float* t = ph;
-      ph = ph_alt;
-      ph_alt = t;
+    Tc *= s;
+    Cc /= 2;
+    if (i == 2) {  // C == 32: fused block, out of place hs -> hp (har_phase is dead by now)
+      convnext(v.upblock[i], nx, hp, Tc);
+      nx = hp;
+    } else {
+      convnext(v.upblock[i], nx, nx, Tc);
     }
-    if (live()) {
-      ConvArgs r = base(v.real_conv, ph, Tu, real);
-      if (head32p) {
-        chk(launch_chan_layernorm(ph, lnbuf, B, 32, Tu, 1e-6f, 0, v.phase_fln_w, v.phase_fln_b, nullptr, 0, nullptr, st));
-        r.x[0] = lnbuf;
-      } else {
-        r.pro = PRO_LN_AFFINE;
-        r.palpha = v.phase_fln_w;
-        r.pbeta = v.phase_fln_b;
-        r.ln_eps = 1e-6f;
-      }
-      conv(r);
-      r.w = v.imag_conv;
-      r.y = imag;
-      conv(r);
-      chk(launch_istft64(B, Tu, logamp, real, imag, v.stft_br, v.stft_bi, io.audio, st));
-    }
-    note_peak();
+    cur = nx;
   }
+  trunk = cur;  // [B][32][Tu] (lives in hp)
+  if (live()) tap(io.tap_trunk, trunk, (size_t)B * 32 * Tu);
+  note_peak();
+  ws.off = mark;
+  // ---- heads @75T ----
+  float* logamp = ws.take<float>((size_t)B * 32 * Tu);
+  float* ph = hs;
+  float* ph_alt = ws.take<float>((size_t)B * 32 * Tu);
+  float* real = ws.take<float>((size_t)B * 32 * Tu);
+  float* imag = ws.take<float>((size_t)B * 32 * Tu);
+  // The final LayerNorms in front of the k = 21 head convs: fused into the tiled kernel's prologue (rounds 1-4) where the
+  // persistent 32-channel kernel does not take the conv; where it does (round 5), a LayerNorm pass + the persistent kernel are
+  // faster than the fused tiled launch (c5-bf16: 121 us against ~35 + 40; the real / imag pair shares one pass)
+  ConvArgs head_probe = base(v.amp_output_conv, trunk, Tu, logamp);
+  const bool head32p = plan_route(m, head_probe).kernel == CONV_32P;
+  float* lnbuf = head32p ? ws.take<float>((size_t)B * 32 * Tu) : nullptr;
+  if (live()) {
+    ConvArgs a = base(v.amp_output_conv, trunk, Tu, logamp);
+    if (head32p) {
+      chk(launch_chan_layernorm(trunk, lnbuf, B, 32, Tu, 1e-6f, 0, v.amp_fln_w, v.amp_fln_b, nullptr, 0, nullptr, st));
+      a.x[0] = lnbuf;
+    } else {
+      a.pro = PRO_LN_AFFINE;
+      a.palpha = v.amp_fln_w;
+      a.pbeta = v.amp_fln_b;
+      a.ln_eps = 1e-6f;
+    }
+    conv(a);
+    tap(io.tap_logamp, logamp, (size_t)B * 32 * Tu);
+    ConvArgs p = base(v.phase_input_conv, trunk, Tu, ph);
+    p.nsrc = 3;
+    p.x[1] = lap;
+    p.x[2] = pp;
+    p.xc[0] = p.xc[1] = p.xc[2] = 32;
+    p.ln_out = 1;
+    p.ln_w = v.phase_norm_w;
+    p.ln_b = v.phase_norm_b;
+    p.ln_eps = 1e-6f;
+    conv(p);
+  }
+  for (const ConvNeXt& c : v.phase_convnext) {  // ping-pong: the fused block is out of place
+    convnext(c, ph, ph_alt, Tu);
+    float* t = ph;
+    ph = ph_alt;
+    ph_alt = t;
+  }
+  if (live()) {
+    ConvArgs r = base(v.real_conv, ph, Tu, real);
+    if (head32p) {
+      chk(launch_chan_layernorm(ph, lnbuf, B, 32, Tu, 1e-6f, 0, v.phase_fln_w, v.phase_fln_b, nullptr, 0, nullptr, st));
+      r.x[0] = lnbuf;
+    } else {
+      r.pro = PRO_LN_AFFINE;
+      r.palpha = v.phase_fln_w;
+      r.pbeta = v.phase_fln_b;
+      r.ln_eps = 1e-6f;
+    }
+    conv(r);
+    r.w = v.imag_conv;
+    r.y = imag;
+    conv(r);
+    chk(launch_istft64(B, Tu, logamp, real, imag, v.stft_br, v.stft_bi, io.audio, st));
+  }
+  note_peak();
+}
 
-  void tap(float* dst, const float* src, size_t n) {
-    if (dst && src && rc == STY_OK) {
-      hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) rc = hip_fail(e, "tap copy");
+// TextEncoder.forward -> mu [B][inter][L]
+void Run::text_encoder(const int64_t* tokens, const int64_t* lengths, int L, float* mu) {
+  const TextEncPlan& t = m->te;
+  const int H = t.H;
+  Scope sc_(*this);
+  const size_t n = (size_t)B * H * L;
+  float* mask = ws.take<float>((size_t)B * L);
+  float* x = ws.take<float>(n);
+  float* h1 = ws.take<float>(n);
+  float* h2 = ws.take<float>(n);
+  float* q = ws.take<float>(n);
+  float* k = ws.take<float>(n);
+  float* vv = ws.take<float>(n);
+  float* o = ws.take<float>(n);
+  float* f = ws.take<float>((size_t)B * (t.layers.empty() ? H : t.layers[0].f1.Cout) * L);
+  if (live()) {
+    chk(launch_length_mask(lengths, B, L, mask, st));
+    chk(launch_embedding(tokens, t.emb, B, L, H, t.tokens, sqrtf((float)H), x, st));
+    const float* hin = x;
+    for (int i = 0; i < 3; ++i) {
+      ConvArgs a = base(t.pre[i], hin, L, h1);
+      a.pro = PRO_MASK;
+      a.mask = mask;
+      conv(a);
+      chk(launch_chan_layernorm(h1, h2, B, H, L, 1e-4f, 0, t.pre_g[i], t.pre_b[i], nullptr, 1, nullptr, st));
+      hin = h2;
     }
+    // hin holds relu(LN(...)) of layer 3; x = (x + proj(hin)) * mask
+    ConvArgs pj = base(t.proj, hin, L, x);
+    pj.residual = x;
+    pj.out_mask = mask;
+    pj.out_mask_post = 1;
+    conv(pj);
+    for (const TextEncLayer& l : t.layers) {
+      ConvArgs aq = base(l.q, x, L, q);
+      aq.pro = PRO_MASK;
+      aq.mask = mask;
+      conv(aq);
+      aq.w = l.k;
+      aq.y = k;
+      conv(aq);
+      aq.w = l.v;
+      aq.y = vv;
+      conv(aq);
+      chk(launch_rope(q, k, B, 8, H / 8, L, 8, t.theta, st));
+      AttnArgs at;
+      at.q = q;
+      at.k = k;
+      at.v = vv;
+      at.o = o;
+      at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * L;
+      at.T = L;
+      at.H = 8;
+      at.scale = 1.0f / sqrtf((float)(H / 8));
+      at.lengths = lengths;
+      chk(launch_attention(at, B, H / 8, st));
+      // x is masked already (prenet output / previous LN2 output are written masked)
+      ConvArgs ao = base(l.o, o, L, h1);
+      ao.residual = x;
+      conv(ao);
+      chk(launch_chan_layernorm(h1, x, B, H, L, 1e-4f, 0, l.n1g, l.n1b, nullptr, 0, nullptr, st));
+      ConvArgs f1 = base(l.f1, x, L, f);
+      f1.pro = PRO_MASK;
+      f1.mask = mask;
+      f1.act = ACT_RELU;
+      conv(f1);
+      ConvArgs f2 = base(l.f2, f, L, h1);
+      f2.pro = PRO_MASK;
+      f2.mask = mask;
+      f2.out_mask = mask;
+      f2.residual = x;
+      conv(f2);
+      chk(launch_chan_layernorm(h1, x, B, H, L, 1e-4f, 0, l.n2g, l.n2b, nullptr, 0, mask, st));
+    }
+    ConvArgs pm = base(t.proj_m, x, L, mu);
+    pm.out_mask = mask;
+    pm.out_mask_post = 1;
+    conv(pm);
   }
+}
 
-  // TextEncoder.forward -> mu [B][inter][L]
-  void text_encoder(const int64_t* tokens, const int64_t* lengths, int L, float* mu) {
-    const TextEncPlan& t = m->te;
-    const int H = t.H;
-    Scope sc_(*this);
-    const size_t n = (size_t)B * H * L;
-    float* mask = ws.take<float>((size_t)B * L);
-    float* x = ws.take<float>(n);
-    float* h1 = ws.take<float>(n);
-    float* h2 = ws.take<float>(n);
-    float* q = ws.take<float>(n);
-    float* k = ws.take<float>(n);
-    float* vv = ws.take<float>(n);
-    float* o = ws.take<float>(n);
-    float* f = ws.take<float>((size_t)B * (t.layers.empty() ? H : t.layers[0].f1.Cout) * L);
-    if (live()) {
-      chk(launch_length_mask(lengths, B, L, mask, st));
-      chk(launch_embedding(tokens, t.emb, B, L, H, t.tokens, sqrtf((float)H), x, st));
-      const float* hin = x;
-      for (int i = 0; i < 3; ++i) {
-        ConvArgs a = base(t.pre[i], hin, L, h1);
-        a.pro = PRO_MASK;
-        a.mask = mask;
-        conv(a);
-        chk(launch_chan_layernorm(h1, h2, B, H, L, 1e-4f, 0, t.pre_g[i], t.pre_b[i], nullptr, 1, nullptr, st));
-        hin = h2;
-      }
-      // hin holds relu(LN(...)) of layer 3; x = (x + proj(hin)) * mask
-      ConvArgs pj = base(t.proj, hin, L, x);
-      pj.residual = x;
-      pj.out_mask = mask;
-      pj.out_mask_post = 1;
-      conv(pj);
-      for (const TextEncLayer& l : t.layers) {
-        ConvArgs aq = base(l.q, x, L, q);
-        aq.pro = PRO_MASK;
-        aq.mask = mask;
-        conv(aq);
-        aq.w = l.k;
-        aq.y = k;
-        conv(aq);
-        aq.w = l.v;
-        aq.y = vv;
-        conv(aq);
-        chk(launch_rope(q, k, B, 8, H / 8, L, 8, t.theta, st));
-        AttnArgs at;
-        at.q = q;
-        at.k = k;
-        at.v = vv;
-        at.o = o;
-        at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * L;
-        at.T = L;
-        at.H = 8;
-        at.scale = 1.0f / sqrtf((float)(H / 8));
-        at.lengths = lengths;
-        chk(launch_attention(at, B, H / 8, st));
-        // x is masked already (prenet output / previous LN2 output are written masked)
-        ConvArgs ao = base(l.o, o, L, h1);
-        ao.residual = x;
-        conv(ao);
-        chk(launch_chan_layernorm(h1, x, B, H, L, 1e-4f, 0, l.n1g, l.n1b, nullptr, 0, nullptr, st));
-        ConvArgs f1 = base(l.f1, x, L, f);
-        f1.pro = PRO_MASK;
-        f1.mask = mask;
-        f1.act = ACT_RELU;
-        conv(f1);
-        ConvArgs f2 = base(l.f2, f, L, h1);
-        f2.pro = PRO_MASK;
-        f2.mask = mask;
-        f2.out_mask = mask;
-        f2.residual = x;
-        conv(f2);
-        chk(launch_chan_layernorm(h1, x, B, H, L, 1e-4f, 0, l.n2g, l.n2b, nullptr, 0, mask, st));
-      }
-      ConvArgs pm = base(t.proj_m, x, L, mu);
-      pm.out_mask = mask;
-      pm.out_mask_post = 1;
-      conv(pm);
+// AdaptiveDecoderBlock (ada_norm.py:180-192): xcat [B][Cin][T] -> out [B][Cout][T]
+void Run::dec_block(const DecBlock& d, const float* xcat, float* out, int T) {
+  Scope sc_(*this);
+  float* h = ws.take<float>((size_t)B * d.Cout * T);
+  float* sc = ws.take<float>((size_t)B * d.Cout * T);
+  const int cmax = d.Cin > d.Cout ? d.Cin : d.Cout;
+  double* part = ws.take<double>((size_t)B * cmax * row_stats_nseg(T) * 2);
+  float* a = ws.take<float>((size_t)B * cmax);
+  float* s = ws.take<float>((size_t)B * cmax);
+  if (live()) {
+    const float r2 = 0.70710678118654752f;
+    const float* res = xcat;
+    if (d.has_sc) {
+      ConvArgs c = base(d.sc, xcat, T, sc);
+      c.out_scale = r2;
+      conv(c);
+      res = sc;
+    } else {  // identity shortcut (Cin == Cout): (h + x) / sqrt(2)
+      chk(launch_scale_copy(xcat, r2, (size_t)B * d.Cout * T, sc, st));
+      res = sc;
+    }
+    adain(xcat, d.Cin, T, d.n1, a, s, part);
+    ConvArgs c1 = base(d.c1, xcat, T, h);
+    c1.pro = PRO_AFFINE_LRELU;
+    c1.pa = a;
+    c1.ps = s;
+    conv(c1);
+    adain(h, d.Cout, T, d.n2, a, s, part);
+    ConvArgs c2 = base(d.c2, h, T, out);
+    c2.pro = PRO_AFFINE_LRELU;
+    c2.pa = a;
+    c2.ps = s;
+    c2.out_scale = r2;
+    c2.residual = res;
+    conv(c2);
+    if (!d.has_sc && d.Cin != d.Cout) {
+      set_error("decoder block: identity shortcut needs Cin == Cout");
+      rc = STY_EINVAL;
     }
   }
+}
 
-  // AdaptiveDecoderBlock (ada_norm.py:180-192): xcat [B][Cin][T] -> out [B][Cout][T]
-  void dec_block(const DecBlock& d, const float* xcat, float* out, int T) {
-    Scope sc_(*this);
-    float* h = ws.take<float>((size_t)B * d.Cout * T);
-    float* sc = ws.take<float>((size_t)B * d.Cout * T);
-    const int cmax = d.Cin > d.Cout ? d.Cin : d.Cout;
-    double* part = ws.take<double>((size_t)B * cmax * row_stats_nseg(T) * 2);
-    float* a = ws.take<float>((size_t)B * cmax);
-    float* s = ws.take<float>((size_t)B * cmax);
-    if (live()) {
-      const float r2 = 0.70710678118654752f;
-      const float* res = xcat;
-      if (d.has_sc) {
-        ConvArgs c = base(d.sc, xcat, T, sc);
-        c.out_scale = r2;
-        conv(c);
-        res = sc;
-      } else {  // identity shortcut (Cin == Cout): (h + x) / sqrt(2)
-        chk(launch_scale_copy(xcat, r2, (size_t)B * d.Cout * T, sc, st));
-        res = sc;
-      }
-      adain(xcat, d.Cin, T, d.n1, a, s, part);
-      ConvArgs c1 = base(d.c1, xcat, T, h);
-      c1.pro = PRO_AFFINE_LRELU;
-      c1.pa = a;
-      c1.ps = s;
-      conv(c1);
-      adain(h, d.Cout, T, d.n2, a, s, part);
-      ConvArgs c2 = base(d.c2, h, T, out);
-      c2.pro = PRO_AFFINE_LRELU;
-      c2.pa = a;
-      c2.ps = s;
-      c2.out_scale = r2;
-      c2.residual = res;
-      conv(c2);
-      if (!d.has_sc && d.Cin != d.Cout) {
-        set_error("decoder block: identity shortcut needs Cin == Cout");
-        rc = STY_EINVAL;
-      }
-    }
+// Decoder.forward eval mode (decoder.py:77-90): asr [B][128][T] -> mel [B][128][T]
+void Run::decoder(const float* asr, const float* pitch, const float* energy, const float* voiced, int T, float* out) {
+  const DecoderPlan& d = m->dec;
+  Scope sc_(*this);
+  const int din = d.asr_res.Cin, dr = d.asr_res.Cout, dh = d.encode.Cout;
+  float* fnv = ws.take<float>((size_t)B * 3 * T);
+  float* cat = ws.take<float>((size_t)B * (dh + dr + 3) * T);
+  float* x = ws.take<float>((size_t)B * dh * T);
+  float* res = ws.take<float>((size_t)B * dr * T);
+  if (live()) {
+    chk(launch_fnv(pitch, energy, voiced, d.fnv_w, B, T, fnv, st));
+    const float* s1[2] = {asr, fnv};
+    const int c1[2] = {din, 3};
+    chk(launch_concat(s1, c1, 2, B, T, cat, st));
   }
-
-  // Decoder.forward eval mode (decoder.py:77-90): asr [B][128][T] -> mel [B][128][T]
-  void decoder(const float* asr, const float* pitch, const float* energy, const float* voiced, int T, float* out) {
-    const DecoderPlan& d = m->dec;
-    Scope sc_(*this);
-    const int din = d.asr_res.Cin, dr = d.asr_res.Cout, dh = d.encode.Cout;
-    float* fnv = ws.take<float>((size_t)B * 3 * T);
-    float* cat = ws.take<float>((size_t)B * (dh + dr + 3) * T);
-    float* x = ws.take<float>((size_t)B * dh * T);
-    float* res = ws.take<float>((size_t)B * dr * T);
+  dec_block(d.encode, cat, x, T);
+  if (live()) conv(base(d.asr_res, asr, T, res));
+  for (int i = 0; i < 4; ++i) {
     if (live()) {
-      chk(launch_fnv(pitch, energy, voiced, d.fnv_w, B, T, fnv, st));
-      const float* s1[2] = {asr, fnv};
-      const int c1[2] = {din, 3};
-      chk(launch_concat(s1, c1, 2, B, T, cat, st));
+      const float* s2[3] = {x, res, fnv};
+      const int c2[3] = {dh, dr, 3};
+      chk(launch_concat(s2, c2, 3, B, T, cat, st));
     }
-    dec_block(d.encode, cat, x, T);
-    if (live()) conv(base(d.asr_res, asr, T, res));
-    for (int i = 0; i < 4; ++i) {
-      if (live()) {
-        const float* s2[3] = {x, res, fnv};
-        const int c2[3] = {dh, dr, 3};
-        chk(launch_concat(s2, c2, 3, B, T, cat, st));
-      }
-      dec_block(d.decode[i], cat, i == 3 ? out : x, T);
-    }
+    dec_block(d.decode[i], cat, i == 3 ? out : x, T);
   }
-};
+}
 
 // MelStyleEncoder.forward (mel_style_encoder.py:147-152): mel [B][1][n_mels][T] -> style [B][style_dim]
-static void style_run(Run& r, const float* mel, int T, float* style) {
+void style_run(Run& r, const float* mel, int T, float* style) {
   // padded-flat image layout (conv2d.hip): every activation is [B][C][H][W+1] with a zero last column
   const StylePlan& sp = r.m->sty_enc;
   const int B = r.B;
@@ -1458,7 +1376,7 @@ static void style_run(Run& r, const float* mel, int T, float* style) {
   r.note_peak();
 }
 
-static int model_ready(const sty_model* m, const char* kind_a, const char* kind_b = nullptr) {
+int model_ready(const sty_model* m, const char* kind_a, const char* kind_b) {
   if (!m) {
     set_error("null model");
     return STY_EINVAL;
@@ -1473,9 +1391,18 @@ static int model_ready(const sty_model* m, const char* kind_a, const char* kind_
   }
   return STY_OK;
 }
+int entry_ready(const sty_model* m, const char* kind_a, const char* kind_b, bool bad_args, const char* msg) {
+  const int rc = model_ready(m, kind_a, kind_b);
+  if (rc) return rc;
+  if (bad_args) {
+    set_error("%s", msg);
+    return STY_EINVAL;
+  }
+  return STY_OK;
+}
 
 // DurationPredictor.forward (duration_predictor.py:58-87): -> out [B][L][classes]
-static void duration_forward(Run& r, const int64_t* texts, const int64_t* lengths, int L, float* out) {
+void duration_forward(Run& r, const int64_t* texts, const int64_t* lengths, int L, float* out) {
   sty_model* m = r.m;
   const DurationPlan& d = m->dur;
   const int B = r.B, C = m->te.proj_m.Cout;
@@ -1538,7 +1465,7 @@ static void duration_forward(Run& r, const int64_t* texts, const int64_t* length
 }
 
 // PitchEnergyPredictor.forward (pitch_energy_predictor.py:62-82): -> f0 [B][T], energy [B][T]
-static void pitch_energy_forward(Run& r, const int64_t* texts, const int64_t* lengths, const float* alignment,
+void pitch_energy_forward(Run& r, const int64_t* texts, const int64_t* lengths, const float* alignment,
                                  const float* style, int L, int T, float* f0, float* energy) {
   sty_model* m = r.m;
   const PitchEnergyPlan& p = m->pe;
@@ -1622,7 +1549,7 @@ static void pitch_energy_forward(Run& r, const int64_t* texts, const int64_t* le
 // CTCModel.forward in eval mode (text_aligner.py:73-127, 209-274): mel [B][n_mels][T], lengths [B] -> log_probs [B][T][classes].
 // Frames at or beyond a row's length are zeroed in front of each TDNN conv (the conv's mask prologue); what the convs
 // compute on those frames is kept, as the reference keeps it.  fp32 operands throughout (compute_bf16 is refused for the kind).
-static void aligner_forward(Run& r, const float* mel, const int64_t* lengths, int T, float* out) {
+void aligner_forward(Run& r, const float* mel, const int64_t* lengths, int T, float* out) {
   const AlignerPlan& p = r.m->ali;
   const int B = r.B, H = p.hidden, V = p.classes;
   const size_t n = (size_t)B * H * T;
@@ -1665,7 +1592,7 @@ static void aligner_forward(Run& r, const float* mel, const int64_t* lengths, in
 // padded-flat [B][C][H][W + 1] (conv2d.hip).  Level l has H = Tp >> l, W = 128 >> l, C0 << l channels.  cat[l] is the decoder's
 // concat input [B][2 C_l][n_l]: the encoder writes its skip into the second half when it produces it (one launch per
 // utterance: the conv's output has no batch stride), the transposed conv writes the first half.
-static void rmvpe_forward(Run& r, int n, const float* logmel, float* sal) {
+void rmvpe_forward(Run& r, int n, const float* logmel, float* sal) {
   const RmvpePlan& p = r.m->rmv;
   const int B = r.B, L = RMVPE_LEVELS, Tp = 32 * ((n - 1) / 32 + 1);
   auto Hl = [&](int l) { return Tp >> l; };
@@ -1761,422 +1688,7 @@ static void rmvpe_forward(Run& r, int n, const float* logmel, float* sal) {
   if (r.live()) r.chk(launch_rmvpe_salience(logits, B, Tp, n, sal, r.st));
 }
 
-// frames after conv layer i of N16 samples: floor((n - k) / s) + 1; 0 when a layer is left without a frame
-static int wavlm_frames_at(const WavlmPlan& p, int N16, int layer) {
-  long long n = N16;
-  for (int i = 0; i <= layer; ++i) {
-    if (n < p.kern[i]) return 0;
-    n = (n - p.kern[i]) / p.stride[i] + 1;
-  }
-  return (int)n;
-}
-// ---- one strided feature conv of the plan, both directions (wavlm_forward / wavlm_backward and the unit entry
-//      sty_wavlm_strided_conv_fwd_bwd run these) ----
-// bf16 mode: does this conv over T columns run on a family that reads source 0 as its bf16 twin alone (convp16 / convq)?  Asked
-// with a placeholder twin, so that sizing calls and launches decide alike.
-static bool wavlm_twin_route(const Run& r, ConvArgs a, ConvKernel* kernel = nullptr, bool offer_twin = true) {
-  a.bf16 = r.m->wav_bf16;
-  if (a.bf16 && offer_twin) a.x16 = reinterpret_cast<const __bf16*>(sizeof(__bf16));
-  const ConvRoute rt = conv1d_route(a);
-  if (kernel) *kernel = rt.kernel;
-  return a.bf16 && rt.x16_only;
-}
-// Forward: `below` [B][C] rows of xrs floats with Tin frames (layer 0's output with (ga, gs) set: its norm and GELU on the way;
-// gelu_in: a pre-activation) -> y.  fp32 mode, and bf16 mode where no twin family takes the conv: the fp32 view in `stg` and the
-// valid conv over its Tp = Tl + K - 1 columns (rows of Tl frames; keep_pre: the pre-activation, else GELU in the epilogue).  bf16
-// mode otherwise: the view is written once, as the bf16 operand twin, and the conv runs as a SAME-LENGTH conv over the Tp columns
-// (pad 0: the reads past the row's end are the zero padding) -- the twin families take no separate input length -- leaving the
-// pre-activation on rows of Tp floats whose last K - 1 columns are partial sums nobody reads (may_pad says the caller's buffers
-// and readers allow such rows).  Returns y's row stride; *left_pre: y holds pre-activations.
-static int wavlm_strided_fwd(Run& r, const PackedConv& w, const float* below, int xrs, int C, int Tin, int S, int Tl, const float* ga,
-                             const float* gs, int gelu_in, bool keep_pre, bool may_pad, float* stg, float* y, bool* left_pre,
-                             ConvKernel* kernel = nullptr, bool* twin = nullptr) {
-  const int Tp = Tl + w.K - 1;
-  ConvArgs a = r.base(w, stg, Tl, y);
-  a.pad = 0;
-  ConvArgs c = a;
-  c.T = Tp;
-  if ((Tp == Tl || may_pad) && wavlm_twin_route(r, c, kernel)) {
-    r.chk(launch_wavlm_stage_rs(below, ga, gs, r.B, C, Tin, xrs, S, Tp, stg, 1, r.st, gelu_in));
-    c.x16 = reinterpret_cast<const __bf16*>(stg);
-    r.conv(c);
-    *left_pre = true;
-    if (twin) *twin = true;
-    return Tp;
-  }
-  if (twin) *twin = false;
-  if (xrs != Tin)
-    r.chk(launch_wavlm_stage_rs(below, ga, gs, r.B, C, Tin, xrs, S, Tp, stg, 0, r.st, gelu_in));
-  else
-    r.chk(launch_wavlm_stage(below, ga, gs, r.B, C, Tin, S, Tp, stg, r.st, gelu_in));
-  a.Tin = Tp != Tl ? Tp : 0;
-  a.act = keep_pre ? ACT_NONE : ACT_GELU;
-  if (kernel) wavlm_twin_route(r, a, kernel, false);
-  r.conv(a);
-  *left_pre = keep_pre;
-  return Tl;
-}
-// Backward: the transposed conv (full correlation: pad K - 1) from the gradient at the conv's pre-activation to the gradient
-// of its view, dvw [B][S C][Tp].  cur16 set: that gradient comes as its bf16 twin on rows of Tp columns, zero from Tl on, and the
-// conv is a same-length conv over them; else cur is the fp32 tensor on rows of Tl floats.
-static void wavlm_strided_dgrad(Run& r, const PackedConv& wd, int K, const float* cur, const __bf16* cur16, int Tl, float* dvw) {
-  const int Tp = Tl + K - 1;
-  ConvArgs a = r.base(wd, cur, Tp, dvw);
-  a.pad = K - 1;
-  if (cur16)
-    a.x16 = cur16;
-  else
-    a.Tin = Tp != Tl ? Tl : 0;
-  r.conv(a);
-}
-// ... and whether it takes the twin (asked by whoever produces the gradient, ahead of producing it)
-static bool wavlm_dgrad_twin(const Run& r, const PackedConv& wd, int K, int Tl, ConvKernel* kernel = nullptr) {
-  Run& rr = const_cast<Run&>(r);
-  ConvArgs a = rr.base(wd, nullptr, Tl + K - 1, nullptr);
-  a.pad = K - 1;
-  if (wavlm_twin_route(r, a, kernel)) return true;
-  if (kernel) {  // (the route the fp32 tensor takes)
-    a.Tin = K > 1 ? Tl : 0;
-    wavlm_twin_route(r, a, kernel, false);
-  }
-  return false;
-}
-
-// WavLMModel.forward(output_hidden_states=True) in eval mode (modeling_wavlm.py): audio16 [B][N16] -> hidden [layers + 1][B][T][H].
-// Every activation is channel-major [B][C][T]; wavlm.hip says what each of its kernels does.
-// kp (sty_wavlm_fwd_keep): the same launches on the same operands, so the same bits, except that (a) every tensor the backward
-// reads gets a buffer of its own at the front of the workspace, (b) a conv followed by GELU leaves its pre-activation and the
-// GELU runs behind it (wavlm_stage_kernel / wavlm_gelu_kernel: the conv epilogue's expression on the same fp32 value),
-// (c) the attention keeps its row log-sum-exp.
-static void wavlm_forward(Run& r, int N16, const float* audio, float* hidden, WavlmKeep* kp = nullptr) {
-  sty_model* m = r.m;
-  const WavlmPlan& p = m->wav;
-  const int B = r.B, nc = p.n_conv, H = p.hidden, NH = p.heads, DH = H / NH;
-  if (kp) {
-    *kp = WavlmKeep();
-    const size_t bc0 = (size_t)B * p.dim[0], nn = (size_t)B * H * wavlm_frames_at(p, N16, nc - 1);
-    const size_t nh = nn / H * NH, nf = nn / H * p.layers[0].f1.Cout;
-    kp->out0 = r.ws.take<float>(bc0 * wavlm_frames_at(p, N16, 0));
-    kp->ga = r.ws.take<float>(bc0), kp->gs = r.ws.take<float>(bc0), kp->gmean = r.ws.take<float>(bc0), kp->grstd = r.ws.take<float>(bc0);
-    // (bf16 mode: rows of Tp = T + K - 1 columns where the conv ran over its padded view)
-    for (int i = 1; i < nc; ++i)
-      kp->pre[i] = r.ws.take<float>((size_t)B * p.dim[i] * (wavlm_frames_at(p, N16, i) + (m->wav_bf16 ? p.conv[i].K - 1 : 0)));
-    kp->feat = r.ws.take<float>(nn / H * p.dim[nc - 1]);
-    kp->pre_pos = r.ws.take<float>(nn), kp->xa_enc = r.ws.take<float>(nn);
-    kp->tab = r.ws.take<float>((size_t)NH * (2 * (nn / H / B) - 1));
-    for (size_t l = 0; l <= p.layers.size(); ++l) kp->x.push_back(r.ws.take<float>(nn));
-    for (size_t l = 0; l < p.layers.size(); ++l) {
-      WavlmKeepLayer y;
-      y.q = r.ws.take<float>(nn), y.k = r.ws.take<float>(nn), y.v = r.ws.take<float>(nn), y.o = r.ws.take<float>(nn);
-      y.a1 = r.ws.take<float>(nn), y.a2 = r.ws.take<float>(nn);
-      y.lse = r.ws.take<float>(nh), y.gate = r.ws.take<float>(nh);
-      y.pre = r.ws.take<float>(nf);
-      kp->layers.push_back(y);
-    }
-    kp->saved_end = r.ws.off;
-  }
-  int Tl[WAVLM_MAX_CONV], Tp[WAVLM_MAX_CONV] = {0};
-  size_t max_out = 0, max_stage = 0;
-  for (int i = 0; i < nc; ++i) {
-    Tl[i] = wavlm_frames_at(p, N16, i);
-    max_out = std::max(max_out, (size_t)B * p.dim[i] * Tl[i]);
-    if (i) {
-      Tp[i] = Tl[i] + p.conv[i].K - 1;  // columns of the staged view the conv reads
-      max_stage = std::max(max_stage, (size_t)B * p.conv[i].Cin * Tp[i]);
-      if (m->wav_bf16) max_out = std::max(max_out, (size_t)B * p.dim[i] * Tp[i]);
-    }
-  }
-  const int T = Tl[nc - 1], Cl = p.dim[nc - 1];
-  max_stage = std::max(max_stage, (size_t)B * Cl * T);
-  const size_t n = (size_t)B * H * T;
-  float* x = r.ws.take<float>(n);
-  {  // ---- feature encoder and projection ----
-    Run::Scope sc(r);
-    float* out = r.ws.take<float>(max_out);
-    float* stg = r.ws.take<float>(max_stage);
-    const int nt = wavlm_conv0_ntiles(Tl[0]);
-    double* part = r.ws.take<double>((size_t)B * p.dim[0] * nt * 2);
-    float* ga = r.ws.take<float>((size_t)B * p.dim[0]);
-    float* gs = r.ws.take<float>((size_t)B * p.dim[0]);
-    if (kp) ga = kp->ga, gs = kp->gs;
-    if (r.live()) {
-      r.chk(launch_wavlm_conv0(audio, p.conv0_w, B, N16, p.dim[0], p.kern[0], p.stride[0], Tl[0], kp ? kp->out0 : out, part, r.st));
-      r.chk(launch_wavlm_gn_finalize(part, nt, p.gn_w, p.gn_b, B * p.dim[0], p.dim[0], Tl[0], 1e-5f, ga, gs, r.st,
-                                     kp ? kp->gmean : nullptr, kp ? kp->grstd : nullptr));
-    }
-    int xrs = Tl[0];        // row stride of the layer below's output
-    bool pre_below = false;  // ... which holds pre-activations: the GELU runs in the staging pass
-    for (int i = 1; i < nc && r.live(); ++i) {
-      const float* below = !kp ? out : (i == 1 ? kp->out0 : kp->pre[i - 1]);
-      // (the last conv's output goes to an element-wise pass and a LayerNorm over dense rows: no padded rows there)
-      xrs = wavlm_strided_fwd(r, p.conv[i], below, xrs, p.dim[i - 1], Tl[i - 1], p.stride[i], Tl[i], i == 1 ? ga : nullptr, gs,
-                              i > 1 && pre_below, kp != nullptr, i < nc - 1, stg, kp ? kp->pre[i] : out, &pre_below);
-      if (kp) kp->prs[i] = xrs;
-    }
-    if (r.live()) {
-      if (kp)
-        r.chk(launch_wavlm_gelu(kp->pre[nc - 1], nullptr, (size_t)B * Cl * T, kp->feat, r.st));
-      float *ln_in = kp ? kp->feat : out, *ln_out = stg;
-      if (!kp && pre_below) {  // (bf16 mode: the twin families leave the pre-activation; the view in stg has been consumed)
-        r.chk(launch_wavlm_gelu(out, nullptr, (size_t)B * Cl * T, stg, r.st));
-        ln_in = stg, ln_out = out;
-      }
-      r.chk(launch_chan_layernorm(ln_in, ln_out, B, Cl, T, p.ln_eps, 0, p.fp_ln_w, p.fp_ln_b, nullptr, 0, nullptr, r.st));
-      r.conv(r.base(p.proj, ln_out, T, x));
-    }
-  }
-  // ---- encoder ----
-  const int G = p.pos_groups, Cg = H / G, FF = p.layers[0].f1.Cout;
-  float* xa = r.ws.take<float>(n);
-  float* xb = r.ws.take<float>(n);
-  float* q = r.ws.take<float>(n);
-  float* k = r.ws.take<float>(n);
-  float* v = r.ws.take<float>(n);
-  float* o = r.ws.take<float>(n);
-  float* big = r.ws.take<float>((size_t)B * FF * T);
-  float* gate = r.ws.take<float>((size_t)B * NH * T);
-  float* tab = r.ws.take<float>((size_t)NH * (2 * T - 1));
-  if (kp) tab = kp->tab;
-  r.note_peak();
-  if (!r.live()) return;
-  {  // x + GELU(pos_conv(x)) in the group-major layout (q, k as scratch), then the LayerNorm
-    r.chk(launch_wavlm_group_perm(x, B, G, Cg, T, 1, q, r.st));
-    for (int g = 0; g < G && r.live(); ++g) {
-      const size_t off = (size_t)g * B * Cg * T;
-      ConvArgs a = r.base(p.pos[g], q + off, T, (kp ? kp->pre_pos : k) + off);
-      a.pad = p.pos_k / 2;
-      if (!kp) {
-        a.act = ACT_GELU;
-        a.residual = q + off;
-      }
-      r.conv(a);
-    }
-    if (!r.live()) return;
-    if (kp) r.chk(launch_wavlm_gelu(kp->pre_pos, q, n, k, r.st));
-    float* ln_in = kp ? kp->xa_enc : xa;
-    if (kp) x = kp->x[0];
-    r.chk(launch_wavlm_group_perm(k, B, G, Cg, T, 0, ln_in, r.st));
-    r.chk(launch_chan_layernorm(ln_in, x, B, H, T, p.ln_eps, 0, p.enc_ln_w, p.enc_ln_b, nullptr, 0, nullptr, r.st));
-    r.chk(launch_wavlm_transpose_out(x, B, H, T, hidden, r.st));
-  }
-  {  // the position bias table of this frame count, shared by every layer.  The bucket table is one per model: sized for the
-     // largest frame count seen (at least 2 048 frames, 41 s), so a validation split of many lengths allocates once
-    if (T > m->wav_bucket_T) {
-      const int Tm = std::max(T, 2048);
-      std::vector<int32_t> host(2 * Tm - 1);
-      wavlm_rel_buckets(Tm, p.num_buckets, p.max_distance, host.data());
-      int32_t* dev = nullptr;
-      if (hipMalloc((void**)&dev, host.size() * sizeof(int32_t)) != hipSuccess ||
-          hipMemcpy(dev, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {  // (pageable: complete on return)
-        if (dev) (void)hipFree(dev);
-        set_error("wavlm: the bucket table of %d frames could not be placed on the device", Tm);
-        r.rc = STY_EHIP;
-        return;
-      }
-      if (m->wav_bucket_dev) (void)hipFree(m->wav_bucket_dev);  // (hipFree waits for the launches that still read it)
-      m->wav_bucket_dev = dev;
-      m->wav_bucket_T = Tm;
-    }
-    r.chk(launch_wavlm_rel_table(p.rel_embed, m->wav_bucket_dev + (m->wav_bucket_T - T), NH, T, tab, r.st));
-  }
-  for (size_t l = 0; l < p.layers.size() && r.live(); ++l) {
-    const WavlmLayer& y = p.layers[l];
-    float* a2 = xa;
-    if (kp) {  // this layer's kept tensors in the scratch buffers' places; x = its input, xo its output
-      const WavlmKeepLayer& kl = kp->layers[l];
-      q = kl.q, k = kl.k, v = kl.v, o = kl.o, gate = kl.gate, xa = kl.a1, a2 = kl.a2;
-      x = kp->x[l];
-    }
-    float* xo = kp ? kp->x[l + 1] : x;
-    r.chk(launch_wavlm_gate(x, y.gate_w, y.gate_b, y.gate_c, B, NH, DH, T, gate, r.st));
-    r.conv(r.base(y.q, x, T, q));
-    r.conv(r.base(y.k, x, T, k));
-    r.conv(r.base(y.v, x, T, v));
-    if (!r.live()) return;
-    AttnArgs at;
-    at.q = q, at.k = k, at.v = v, at.o = o;
-    at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * T;
-    at.T = T, at.H = NH;
-    at.scale = 1.0f / sqrtf((float)DH);
-    at.lengths = nullptr;
-    at.rel_tab = tab, at.rel_gate = gate;
-    at.bf16 = m->wav_bf16 && DH == 64;  // (head dim 16, the small test config: the fp32 kernels in both modes)
-    if (kp) at.lse = kp->layers[l].lse;
-    r.chk(launch_attention(at, B, DH, r.st));
-    ConvArgs ao = r.base(y.o, o, T, xa);
-    ao.residual = x;
-    r.conv(ao);
-    if (!r.live()) return;
-    r.chk(launch_chan_layernorm(xa, xb, B, H, T, p.ln_eps, 0, y.ln1_w, y.ln1_b, nullptr, 0, nullptr, r.st));
-    ConvArgs f1 = r.base(y.f1, xb, T, kp ? kp->layers[l].pre : big);
-    f1.act = kp ? ACT_NONE : ACT_GELU;
-    r.conv(f1);
-    if (kp && r.live()) r.chk(launch_wavlm_gelu(kp->layers[l].pre, nullptr, (size_t)B * FF * T, big, r.st));
-    ConvArgs f2 = r.base(y.f2, big, T, a2);
-    f2.residual = xb;
-    r.conv(f2);
-    if (!r.live()) return;
-    r.chk(launch_chan_layernorm(a2, xo, B, H, T, p.ln_eps, 0, y.ln2_w, y.ln2_b, nullptr, 0, nullptr, r.st));
-    r.chk(launch_wavlm_transpose_out(xo, B, H, T, hidden + (l + 1) * n, r.st));
-  }
-}
-
-// The backward of wavlm_forward to the wave: d_hidden [layers + 1][B][T][H] -> d_audio [B][N16] (and the optional tap d_enc_in
-// [B][H][T] in front of the positional conv), on the tensors a keep-mode forward left.  Input gradients only (the network is
-// frozen); the steps cite modeling_wavlm.py as the forward does.  Scratch starts behind the kept tensors.
-static void wavlm_backward(Run& r, int N16, const WavlmKeep& kp, const float* d_hidden, float* d_audio, float* d_enc_in) {
-  sty_model* m = r.m;
-  const WavlmPlan& p = m->wav;
-  const int B = r.B, nc = p.n_conv, H = p.hidden, NH = p.heads, DH = H / NH;
-  int Tl[WAVLM_MAX_CONV], Tp[WAVLM_MAX_CONV] = {0};
-  size_t max_out = 0, max_stage = 0;
-  for (int i = 0; i < nc; ++i) {
-    Tl[i] = wavlm_frames_at(p, N16, i);
-    max_out = std::max(max_out, (size_t)B * p.dim[i] * Tl[i]);
-    if (i) {
-      Tp[i] = Tl[i] + p.conv[i].K - 1;
-      max_stage = std::max(max_stage, (size_t)B * p.conv[i].Cin * Tp[i]);
-      if (m->wav_bf16) max_out = std::max(max_out, (size_t)B * p.dim[i] * Tp[i]);  // (padded rows of a gradient twin fit as well)
-    }
-  }
-  const int T = Tl[nc - 1], Cl = p.dim[nc - 1], G = p.pos_groups, Cg = H / G, FF = p.layers[0].f1.Cout;
-  const int L = (int)p.layers.size();
-  const size_t n = (size_t)B * H * T;
-  r.ws.off = kp.saved_end;
-  float* g = r.ws.take<float>(n);   // gradient at the current layer's output
-  float* t1 = r.ws.take<float>(n);
-  float* t2 = r.ws.take<float>(n);
-  float* dq = r.ws.take<float>(n);
-  float* dk = r.ws.take<float>(n);
-  float* dv = r.ws.take<float>(n);
-  float* dbig = r.ws.take<float>((size_t)B * FF * T);
-  float* dpre = r.ws.take<float>((size_t)B * FF * T);
-  float* dgate = r.ws.take<float>((size_t)B * NH * T);
-  float* aws = r.ws.take<float>(attention_bwd_ws_floats(B, NH, T));
-  float* mu = r.ws.take<float>((size_t)B * std::max(T, 64));
-  float* rt = r.ws.take<float>((size_t)B * std::max(T, 64));
-  float* fa = r.ws.take<float>(max_out);
-  float* fb = r.ws.take<float>(max_out);
-  float* dvw = r.ws.take<float>(max_stage);
-  const int gnt = wavlm_gn_bwd_ntiles(Tl[0]);
-  double* gpart = r.ws.take<double>((size_t)B * p.dim[0] * gnt * 2);
-  float* gcoef = r.ws.take<float>((size_t)B * p.dim[0] * 2);
-  r.note_peak();
-  if (!r.live()) return;
-  static const PackedConv none;
-  auto D = [&](const PackedConv& w) -> const PackedConv& {  // the input-gradient weights of a conv of the dgrad table
-    auto it = m->dgrad.find(w.wp);
-    if (it != m->dgrad.end()) return it->second;
-    if (r.rc == STY_OK) {
-      set_error("wavlm_backward: a conv without input-gradient weights (the model was not finalized for the kind)");
-      r.rc = STY_ESTATE;
-    }
-    return none;
-  };
-  auto ln_bwd = [&](const float* x, const float* dy, int C, const float* w, float* dx) {  // input gradient alone
-    r.chk(launch_chan_ln_bwd(x, dy, nullptr, B, C, T, p.ln_eps, 0, w, nullptr, 0, nullptr, dx, 0, mu, rt, nullptr, nullptr, nullptr, r.st));
-  };
-  auto zero = [&](float* x, size_t cnt) {
-    if (r.live() && hipMemsetAsync(x, 0, cnt * sizeof(float), r.st) != hipSuccess) {
-      set_error("wavlm_backward: hipMemsetAsync failed");
-      r.rc = STY_EHIP;
-    }
-  };
-  // (1) cotangent of the last hidden state; every other one is added where its layer's gradient is complete
-  r.chk(launch_wavlm_intake(d_hidden + (size_t)L * n, B, H, T, 0, g, r.st));
-  // (2) encoder layers, post-norm: x_out = LN2(xb + f2(GELU(f1(xb)))), xb = LN1(x + out_proj(attn(x)))
-  for (int l = L - 1; l >= 0 && r.live(); --l) {
-    const WavlmLayer& y = p.layers[l];
-    const WavlmKeepLayer& kl = kp.layers[l];
-    ln_bwd(kl.a2, g, H, y.ln2_w, t1);                      // t1 = d (xb + f2(..))
-    r.conv(r.base(D(y.f2), t1, T, dbig));
-    if (!r.live()) return;
-    r.chk(launch_act_bwd(ACT_GELU, kl.pre, dbig, nullptr, B, FF, T, dpre, 0, nullptr, r.st));
-    ConvArgs f1 = r.base(D(y.f1), dpre, T, t2);
-    f1.residual = t1;
-    r.conv(f1);                                            // t2 = d xb
-    if (!r.live()) return;
-    ln_bwd(kl.a1, t2, H, y.ln1_w, t1);                     // t1 = d (x + out_proj(attn))
-    r.conv(r.base(D(y.o), t1, T, t2));                     // t2 = d attn output
-    zero(dq, n), zero(dk, n), zero(dv, n);                 // (the attention backward accumulates)
-    if (!r.live()) return;
-    // (3) attention with the gated relative position bias: dq, dk, dv and d gate, no [B H][T][T] bias tensor
-    AttnArgs at;
-    at.q = kl.q, at.k = kl.k, at.v = kl.v, at.o = kl.o;
-    at.qbs = at.kbs = at.vbs = at.obs = (size_t)H * T;
-    at.T = T, at.H = NH;
-    at.scale = 1.0f / sqrtf((float)DH);
-    at.lengths = nullptr;
-    at.lse = kl.lse;
-    at.rel_tab = kp.tab, at.rel_gate = kl.gate, at.rel_dgate = dgate;
-    at.bf16 = m->wav_bf16 && DH == 64;
-    r.chk(launch_attention_bwd(at, t2, dq, dk, dv, at.qbs, at.kbs, at.vbs, at.obs, B, DH, aws, r.st));
-    // dx = residual + q / k / v projections' input gradients (+ the gate path, + this layer input's own cotangent)
-    ConvArgs cq = r.base(D(y.q), dq, T, t2);
-    cq.residual = t1;
-    r.conv(cq);
-    ConvArgs ck = r.base(D(y.k), dk, T, t1);
-    ck.residual = t2;
-    r.conv(ck);
-    ConvArgs cv = r.base(D(y.v), dv, T, g);
-    cv.residual = t1;
-    r.conv(cv);
-    if (!r.live()) return;
-    // (4) gate backward into the head slices
-    r.chk(launch_wavlm_gate_bwd(kp.x[l], y.gate_w, y.gate_b, y.gate_c, dgate, B, NH, DH, T, g, r.st));
-    r.chk(launch_wavlm_intake(d_hidden + (size_t)l * n, B, H, T, 1, g, r.st));
-  }
-  if (!r.live()) return;
-  // (5) encoder LayerNorm, then x + GELU(pos_conv(x)): GELU' in front of the grouped dgrad, the residual around it.  The forward
-  // pads k / 2 and never computes the even kernel's last frame, so the flipped taps are padded k / 2 - 1.
-  ln_bwd(kp.xa_enc, g, H, p.enc_ln_w, t1);
-  r.chk(launch_wavlm_group_perm(t1, B, G, Cg, T, 1, t2, r.st));
-  r.chk(launch_act_bwd(ACT_GELU, kp.pre_pos, t2, nullptr, G * B, Cg, T, dq, 0, nullptr, r.st));
-  for (int gi = 0; gi < G && r.live(); ++gi) {
-    const size_t off = (size_t)gi * B * Cg * T;
-    ConvArgs a = r.base(p.pos_d[gi], dq + off, T, dk + off);
-    a.pad = p.pos_k - 1 - p.pos_k / 2;
-    a.residual = t2 + off;
-    r.conv(a);
-  }
-  if (!r.live()) return;
-  r.chk(launch_wavlm_group_perm(dk, B, G, Cg, T, 0, t1, r.st));  // t1 = gradient at the feature projection's output
-  if (d_enc_in && hipMemcpyAsync(d_enc_in, t1, n * sizeof(float), hipMemcpyDeviceToDevice, r.st) != hipSuccess) {
-    set_error("wavlm_backward: the copy of the tap failed");
-    r.rc = STY_EHIP;
-    return;
-  }
-  // (6) feature projection: 1x1 dgrad, LayerNorm, then the GELU' of the last feature conv
-  r.conv(r.base(D(p.proj), t1, T, fa));
-  if (!r.live()) return;
-  ln_bwd(kp.feat, fa, Cl, p.fp_ln_w, fb);
-  r.chk(launch_act_bwd(ACT_GELU, kp.pre[nc - 1], fb, nullptr, B, Cl, T, fa, 0, nullptr, r.st));
-  // (7) strided feature convs: the stride-1 conv over the s-frames-at-a-time view, transposed (full correlation: pad K - 1), then
-  // the un-staging permutation with the GELU' of the layer below; (8) behind layer 0 the GroupNorm backward takes its place
-  float *cur = fa, *other = fb;
-  // bf16 mode: a layer whose transposed conv runs on a twin family gets its gradient from the un-staging above it as the bf16
-  // twin on zero-padded rows (the top layer's comes from the GELU' pass in fp32)
-  bool cur_twin = false;
-  for (int i = nc - 1; i >= 1 && r.live(); --i) {
-    wavlm_strided_dgrad(r, p.conv_d[i], p.conv[i].K, cur, cur_twin ? reinterpret_cast<const __bf16*>(cur) : nullptr, Tl[i], dvw);
-    if (!r.live()) return;
-    if (i > 1 && m->wav_bf16) {
-      cur_twin = wavlm_dgrad_twin(r, p.conv_d[i - 1], p.conv[i - 1].K, Tl[i - 1]);
-      r.chk(launch_wavlm_unstage_rs(dvw, kp.pre[i - 1], B, p.dim[i - 1], Tl[i - 1], kp.prs[i - 1], p.stride[i], Tp[i],
-                                    cur_twin ? Tp[i - 1] : Tl[i - 1], other, cur_twin, r.st));
-    } else if (i > 1)
-      r.chk(launch_wavlm_unstage(dvw, kp.pre[i - 1], B, p.dim[i - 1], Tl[i - 1], p.stride[i], Tp[i], other, r.st));
-    else
-      r.chk(launch_wavlm_gn_bwd(kp.out0, dvw, kp.ga, kp.gs, kp.gmean, kp.grstd, B, p.dim[0], Tl[0], p.stride[1], Tp[1], gpart, gcoef, other,
-                                r.st));
-    std::swap(cur, other);
-  }
-  if (!r.live()) return;
-  // (9) layer 0 transposed: the whole d_audio, the tail no frame reads included (zero)
-  r.chk(launch_wavlm_conv0_bwd(cur, p.conv0_w, B, N16, p.dim[0], p.kern[0], p.stride[0], Tl[0], d_audio, r.st));
-}
-
-static int run_style_fc(Run& r, const float* style) {
+int run_style_fc(Run& r, const float* style) {
   sty_model* m = r.m;
   r.gb = r.ws.take<float>(m->gb_floats_per_batch * r.B);
   if (r.live() && !m->fcs.empty())
@@ -2451,11 +1963,7 @@ int sty_speech_train_workspace_bytes(sty_model* m, int B, int L, int T, size_t* 
     set_error("sty_speech_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  sty_speech_io io;
-  memset(&io, 0, sizeof(io));
-  io.B = B;
-  io.L = L;
-  io.T = T;
+  const sty_speech_io io = speech_io_dims(B, L, T);
   return trainer_speech_forward(m->trainer, &io, nullptr, 0, nullptr, bytes);
 }
 
@@ -2560,10 +2068,7 @@ int sty_vocoder_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes)
     set_error("sty_vocoder_train_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  sty_vocoder_io io;
-  memset(&io, 0, sizeof(io));
-  io.B = B;
-  io.T = T;
+  const sty_vocoder_io io = vocoder_io_dims(B, T);
   return trainer_vocoder_forward(m->trainer, &io, nullptr, 0, nullptr, bytes);
 }
 
@@ -2638,31 +2143,17 @@ static int vocoder_run(sty_model* m, const sty_vocoder_io* io, void* ws, size_t 
 }
 
 int sty_vocoder_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  const int rc = entry_ready(m, "speech_predictor", "vocoder", !bytes || B <= 0 || T <= 1, "sty_vocoder_workspace_bytes: bad argument");
   if (rc) return rc;
-  if (!bytes || B <= 0 || T <= 1) {
-    set_error("sty_vocoder_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
-  sty_vocoder_io io;
-  memset(&io, 0, sizeof(io));
-  io.B = B;
-  io.T = T;
+  const sty_vocoder_io io = vocoder_io_dims(B, T);
   return vocoder_run(const_cast<sty_model*>(m), &io, nullptr, 0, nullptr, bytes);
 }
 
 int sty_vocoder_fwd(sty_model* m, const sty_vocoder_io* io, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
-  if (rc) return rc;
-  if (!io || !workspace || !io->mel || !io->style || !io->audio || io->B <= 0 || io->T <= 1 ||
-      (!io->prior_override && (!io->pitch || !io->voiced))) {
-    set_error("sty_vocoder_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared) {
-    rc = sty_model_prepare(m, stream);
-    if (rc) return rc;
-  }
+  const bool bad = !io || !workspace || !io->mel || !io->style || !io->audio || io->B <= 0 || io->T <= 1 ||
+                   (!io->prior_override && (!io->pitch || !io->voiced));
+  int rc = entry_ready(m, "speech_predictor", "vocoder", bad, "sty_vocoder_fwd: bad argument");
+  if (rc || (rc = ensure_prepared(m, stream))) return rc;
   return vocoder_run(m, io, workspace, ws_bytes, stream, nullptr);
 }
 
@@ -2688,32 +2179,17 @@ static int speech_run(sty_model* m, const sty_speech_io* io, void* ws, size_t ws
 }
 
 int sty_speech_workspace_bytes(const sty_model* m, int B, int L, int T, size_t* bytes) {
-  int rc = model_ready(m, "speech_predictor");
+  const int rc = entry_ready(m, "speech_predictor", nullptr, !bytes || B <= 0 || L <= 0 || T <= 1, "sty_speech_workspace_bytes: bad argument");
   if (rc) return rc;
-  if (!bytes || B <= 0 || L <= 0 || T <= 1) {
-    set_error("sty_speech_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
-  sty_speech_io io;
-  memset(&io, 0, sizeof(io));
-  io.B = B;
-  io.L = L;
-  io.T = T;
+  const sty_speech_io io = speech_io_dims(B, L, T);
   return speech_run(const_cast<sty_model*>(m), &io, nullptr, 0, nullptr, bytes);
 }
 
 int sty_speech_fwd(sty_model* m, const sty_speech_io* io, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor");
-  if (rc) return rc;
-  if (!io || !workspace || !io->texts || !io->text_lengths || !io->alignment || !io->pitch || !io->energy ||
-      !io->voiced || !io->style || !io->denormal_pitch || !io->audio || io->B <= 0 || io->L <= 0 || io->T <= 1) {
-    set_error("sty_speech_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared) {
-    rc = sty_model_prepare(m, stream);
-    if (rc) return rc;
-  }
+  const bool bad = !io || !workspace || !io->texts || !io->text_lengths || !io->alignment || !io->pitch || !io->energy ||
+                   !io->voiced || !io->style || !io->denormal_pitch || !io->audio || io->B <= 0 || io->L <= 0 || io->T <= 1;
+  int rc = entry_ready(m, "speech_predictor", nullptr, bad, "sty_speech_fwd: bad argument");
+  if (rc || (rc = ensure_prepared(m, stream))) return rc;
   return speech_run(m, io, workspace, ws_bytes, stream, nullptr);
 }
 
@@ -2726,23 +2202,15 @@ static int duration_run(sty_model* m, int B, int L, const int64_t* texts, const 
   return r.finish(need, ws, ws_bytes);
 }
 int sty_duration_workspace_bytes(const sty_model* m, int B, int L, size_t* bytes) {
-  int rc = model_ready(m, "duration_predictor");
+  const int rc = entry_ready(m, "duration_predictor", nullptr, !bytes || B <= 0 || L <= 0, "sty_duration_workspace_bytes: bad argument");
   if (rc) return rc;
-  if (!bytes || B <= 0 || L <= 0) {
-    set_error("sty_duration_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
   return duration_run(const_cast<sty_model*>(m), B, L, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, bytes);
 }
 int sty_duration_fwd(sty_model* m, int B, int L, const int64_t* texts, const int64_t* text_lengths, const float* style,
                      float* dur_pred, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "duration_predictor");
-  if (rc) return rc;
-  if (!texts || !text_lengths || !style || !dur_pred || !workspace || B <= 0 || L <= 0) {
-    set_error("sty_duration_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  int rc = entry_ready(m, "duration_predictor", nullptr, !texts || !text_lengths || !style || !dur_pred || !workspace || B <= 0 || L <= 0,
+                       "sty_duration_fwd: bad argument");
+  if (rc || (rc = ensure_prepared(m, stream))) return rc;
   return duration_run(m, B, L, texts, text_lengths, style, dur_pred, workspace, ws_bytes, stream, nullptr);
 }
 // ---- text aligner (inference) ----
@@ -2753,27 +2221,20 @@ static int aligner_run(sty_model* m, int B, int T, const float* mel, const int64
   return r.finish(need, ws, ws_bytes);
 }
 int sty_aligner_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "text_aligner", "text_aligner_train");
+  const int rc = entry_ready(m, "text_aligner", "text_aligner_train", !bytes || B <= 0 || T <= 0, "sty_aligner_workspace_bytes: bad argument");
   if (rc) return rc;
-  if (!bytes || B <= 0 || T <= 0) {
-    set_error("sty_aligner_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
   return aligner_run(const_cast<sty_model*>(m), B, T, nullptr, nullptr, nullptr, nullptr, 0, nullptr, bytes);
 }
 int sty_aligner_fwd(sty_model* m, int B, int T, const float* mel, const int64_t* mel_lengths, float* log_probs,
                     void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "text_aligner", "text_aligner_train");
+  int rc = entry_ready(m, "text_aligner", "text_aligner_train", !mel || !mel_lengths || !log_probs || !workspace || B <= 0 || T <= 0,
+                       "sty_aligner_fwd: bad argument");
   if (rc) return rc;
-  if (!mel || !mel_lengths || !log_probs || !workspace || B <= 0 || T <= 0) {
-    set_error("sty_aligner_fwd: bad argument");
-    return STY_EINVAL;
-  }
   if (m->topts.compute_bf16) {
     set_error("sty_aligner_fwd: compute_bf16 is refused for the text aligner");
     return STY_EINVAL;
   }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  if ((rc = ensure_prepared(m, stream))) return rc;
   return aligner_run(m, B, T, mel, mel_lengths, log_probs, workspace, ws_bytes, stream, nullptr);
 }
 // ---- RMVPE pitch extraction (train/dataprep/rmvpe/inference.py) ----
@@ -2833,7 +2294,7 @@ int sty_rmvpe_fwd(sty_model* m, int B, int n, const float* logmel, float* salien
     set_error("sty_rmvpe_fwd: bad argument");
     return STY_EINVAL;
   }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  if ((rc = ensure_prepared(m, stream))) return rc;
   return rmvpe_run(m, B, n, logmel, salience, workspace, ws_bytes, stream, nullptr);
 }
 int sty_rmvpe_decode(int B, int n, const float* salience, float thred, float* f0, void* stream) {
@@ -2842,355 +2303,6 @@ int sty_rmvpe_decode(int B, int n, const float* salience, float thred, float* f0
     return STY_EINVAL;
   }
   return launch_rmvpe_decode(salience, B * n, thred, f0, S(stream));
-}
-// ---- slm loss value: resampler, WavLM forward, mean |a - b| (train/losses.py:376-394; wavlm.hip) ----
-static int gcd_(int a, int b) { return b ? gcd_(b, a % b) : a; }
-static bool resample_rates_ok(int orig, int nw) { return orig > 0 && nw > 0 && orig / gcd_(orig, nw) <= 1024 && nw / gcd_(orig, nw) <= 1024; }
-int sty_wavlm_set_config(sty_model* m, int n_conv, const int* conv_stride, int max_bucket_distance, float layer_norm_eps) {
-  if (!m || m->kind != "wavlm" || !conv_stride || n_conv < 2 || n_conv > WAVLM_MAX_CONV || max_bucket_distance < 2 || !(layer_norm_eps > 0.f)) {
-    set_error("sty_wavlm_set_config: bad argument (kind 'wavlm', 2 to %d conv layers)", WAVLM_MAX_CONV);
-    return STY_EINVAL;
-  }
-  for (int i = 0; i < n_conv; ++i)
-    if (conv_stride[i] < 1 || conv_stride[i] > 16) {
-      set_error("sty_wavlm_set_config: conv stride %d of layer %d (1 to 16 are built)", conv_stride[i], i);
-      return STY_EINVAL;
-    }
-  WavlmPlan& p = m->wav;
-  p.n_conv = n_conv;
-  for (int i = 0; i < n_conv; ++i) p.stride[i] = conv_stride[i];
-  p.max_distance = max_bucket_distance;
-  p.ln_eps = layer_norm_eps;
-  m->finalized = false;
-  return STY_OK;
-}
-// The kind's own operand mode (sty_model_set_train_opts(compute_bf16) keeps refusing it, as every inference-only kind's does).
-// Nothing is re-packed here: the bf16 fragments of a packed weight are made at its first bf16 launch and live beside the fp32
-// pack for the life of the arena (convp16.hip), so switching back and forth costs nothing after the first call of each mode.
-int sty_wavlm_set_compute(sty_model* m, int bf16) {
-  if (!m) {
-    set_error("sty_wavlm_set_compute: null model");
-    return STY_EINVAL;
-  }
-  if (m->kind != "wavlm") {
-    set_error("sty_wavlm_set_compute: model kind '%s' (the operand mode of kind 'wavlm' alone is set here)", m->kind.c_str());
-    return STY_EINVAL;
-  }
-  if (bf16 != 0 && bf16 != 1) {
-    set_error("sty_wavlm_set_compute: mode %d (0 = fp32 operands, 1 = bf16 operands)", bf16);
-    return STY_EINVAL;
-  }
-  m->wav_bf16 = bf16;
-  return STY_OK;
-}
-int sty_slm_resample_len(int N, int orig, int new_rate) {
-  if (N <= 0 || !resample_rates_ok(orig, new_rate)) return -1;
-  const int g = gcd_(orig, new_rate);
-  return (int)(((long long)N * (new_rate / g) + orig / g - 1) / (orig / g));
-}
-int sty_slm_resample_kernel_host(int orig, int new_rate, float* out) {
-  if (!resample_rates_ok(orig, new_rate)) return -1;
-  const int g = gcd_(orig, new_rate), o = orig / g, n = new_rate / g;
-  if (out) build_resample_kernel(o, n, 6.0, out);
-  return n * (2 * resample_width(o, n, 6.0) + o);
-}
-// the forward (d_accumulate < 0: x = audio [B][N] -> y = out [B][M]) and its adjoint (y = d_out -> x = d_audio, written or added to)
-static int slm_resample_run(const char* who, int B, int N, int orig, int new_rate, const float* src, float* dst, int d_accumulate,
-                            void* stream) {
-  if (!src || !dst || B <= 0 || N <= 0 || !resample_rates_ok(orig, new_rate)) {
-    set_error("%s: bad argument", who);
-    return STY_EINVAL;
-  }
-  const int g = gcd_(orig, new_rate), o = orig / g, n = new_rate / g, width = resample_width(o, n, 6.0);
-  const size_t floats = (size_t)n * (2 * width + o);
-  if (floats * sizeof(float) > 48 * 1024) {
-    set_error("%s: %d -> %d needs a table of %zu taps (more than the kernel keeps)", who, orig, new_rate, floats);
-    return STY_EINVAL;
-  }
-  // device tables by (device, reduced rate pair), built on first use under a lock; a table is cached only once it is filled
-  static std::mutex mu;
-  static std::map<std::tuple<int, int, int>, float*> tables;
-  int device = 0;
-  STY_HIP(hipGetDevice(&device));
-  float* dev = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    float*& slot = tables[std::make_tuple(device, o, n)];
-    if (!slot) {
-      std::vector<float> host(floats);
-      build_resample_kernel(o, n, 6.0, host.data());
-      float* fresh = nullptr;
-      STY_HIP(hipMalloc((void**)&fresh, floats * sizeof(float)));
-      const hipError_t e = hipMemcpy(fresh, host.data(), floats * sizeof(float), hipMemcpyHostToDevice);  // (pageable: complete on return)
-      if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        return hip_fail(e, "hipMemcpy of the resample table");
-      }
-      slot = fresh;
-    }
-    dev = slot;
-  }
-  const int M = sty_slm_resample_len(N, orig, new_rate);
-  if (d_accumulate >= 0) return launch_resample_fir_bwd(src, dev, B, N, M, o, n, width, d_accumulate, dst, S(stream));
-  return launch_resample_fir(src, dev, B, N, M, o, n, width, dst, S(stream));
-}
-int sty_slm_resample_fwd(int B, int N, int orig, int new_rate, const float* audio, float* out, void* stream) {
-  return slm_resample_run("sty_slm_resample_fwd", B, N, orig, new_rate, audio, out, -1, stream);
-}
-int sty_slm_resample_bwd(int B, int N, int orig, int new_rate, const float* d_out, float* d_audio, int accumulate, void* stream) {
-  return slm_resample_run("sty_slm_resample_bwd", B, N, orig, new_rate, d_out, d_audio, accumulate ? 1 : 0, stream);
-}
-int sty_wavlm_frames(const sty_model* m, int N16, int* T) {
-  int rc = model_ready(m, "wavlm");
-  if (rc) return rc;
-  if (!T || N16 <= 0) {
-    set_error("sty_wavlm_frames: bad argument");
-    return STY_EINVAL;
-  }
-  *T = wavlm_frames_at(m->wav, N16, m->wav.n_conv - 1);
-  if (*T < 1) {
-    set_error("wavlm: %d samples leave no frame behind the feature encoder", N16);
-    return STY_ESHAPE;
-  }
-  return STY_OK;
-}
-static int wavlm_run(sty_model* m, int B, int N16, const float* audio, float* hidden, void* ws, size_t ws_bytes, void* stream,
-                     size_t* need) {
-  Run r(m, B, ws, ws_bytes, stream);
-  wavlm_forward(r, N16, audio, hidden);
-  return r.finish(need, ws, ws_bytes);
-}
-int sty_wavlm_workspace_bytes(const sty_model* m, int B, int N16, size_t* bytes) {
-  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
-  if (rc) return rc;
-  if (!bytes || B <= 0) {
-    set_error("sty_wavlm_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
-  return wavlm_run(const_cast<sty_model*>(m), B, N16, nullptr, nullptr, nullptr, 0, nullptr, bytes);
-}
-int sty_wavlm_fwd(sty_model* m, int B, int N16, const float* audio16, float* hidden, void* workspace, size_t ws_bytes, void* stream) {
-  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
-  if (rc) return rc;
-  if (!audio16 || !hidden || !workspace || B <= 0) {
-    set_error("sty_wavlm_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
-  return wavlm_run(m, B, N16, audio16, hidden, workspace, ws_bytes, stream, nullptr);
-}
-// ---- the backward to the wave: forward that keeps, then sty_wavlm_bwd on the same workspace ----
-static int wavlm_grad_need(sty_model* m, int B, int N16, size_t* need) {
-  Run r(m, B, nullptr, 0, nullptr);
-  WavlmKeep kp;
-  wavlm_forward(r, N16, nullptr, nullptr, &kp);
-  wavlm_backward(r, N16, kp, nullptr, nullptr, nullptr);
-  return r.finish(need, nullptr, 0);
-}
-int sty_wavlm_grad_workspace_bytes(const sty_model* m, int B, int N16, size_t* bytes) {
-  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
-  if (rc) return rc;
-  if (!bytes || B <= 0) {
-    set_error("sty_wavlm_grad_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
-  return wavlm_grad_need(const_cast<sty_model*>(m), B, N16, bytes);
-}
-int sty_wavlm_fwd_keep(sty_model* m, int B, int N16, const float* audio16, float* hidden, void* workspace, size_t ws_bytes, void* stream) {
-  int T = 0, rc = sty_wavlm_frames(m, N16, &T);
-  if (rc) return rc;
-  if (!audio16 || !hidden || !workspace || B <= 0) {
-    set_error("sty_wavlm_fwd_keep: bad argument");
-    return STY_EINVAL;
-  }
-  m->wav_keep.valid = false;
-  size_t need = 0;
-  if ((rc = wavlm_grad_need(m, B, N16, &need))) return rc;
-  if (ws_bytes < need) {  // refused on the host: nothing is launched into a workspace that cannot hold the kept tensors
-    set_error("sty_wavlm_fwd_keep: workspace too small: need %zu bytes, have %zu", need, ws_bytes);
-    return STY_ENOMEM;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
-  Run r(m, B, workspace, ws_bytes, stream);
-  wavlm_forward(r, N16, audio16, hidden, &m->wav_keep);
-  rc = r.finish(nullptr, workspace, ws_bytes);
-  if (rc == STY_OK) {
-    m->wav_keep.valid = true;
-    m->wav_keep.B = B, m->wav_keep.N16 = N16, m->wav_keep.ws = workspace;
-    m->wav_keep.bf16 = m->wav_bf16;
-  }
-  return rc;
-}
-int sty_wavlm_bwd(sty_model* m, int B, int N16, const float* d_hidden, float* d_audio16, float* d_enc_in, void* workspace,
-                  size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "wavlm");
-  if (rc) return rc;
-  if (!d_hidden || !d_audio16 || !workspace || B <= 0 || N16 <= 0) {
-    set_error("sty_wavlm_bwd: bad argument");
-    return STY_EINVAL;
-  }
-  WavlmKeep& kp = m->wav_keep;
-  if (!kp.valid) {
-    set_error("sty_wavlm_bwd: no sty_wavlm_fwd_keep call precedes it (a backward consumes its forward's workspace)");
-    return STY_ESTATE;
-  }
-  if (kp.B != B || kp.N16 != N16 || kp.ws != workspace) {
-    set_error("sty_wavlm_bwd: (B, N16) = (%d, %d) on this workspace, but the forward kept (%d, %d)%s", B, N16, kp.B, kp.N16,
-              kp.ws != workspace ? " in another workspace" : "");
-    return STY_ESHAPE;
-  }
-  if (kp.bf16 != m->wav_bf16) {
-    set_error("sty_wavlm_bwd: the model runs %s operands now, but the forward kept in %s mode (sty_wavlm_set_compute between the two)",
-              m->wav_bf16 ? "bf16" : "fp32", kp.bf16 ? "bf16" : "fp32");
-    return STY_ESTATE;
-  }
-  size_t need = 0;
-  if ((rc = wavlm_grad_need(m, B, N16, &need))) return rc;
-  if (ws_bytes < need) {
-    set_error("sty_wavlm_bwd: workspace too small: need %zu bytes, have %zu", need, ws_bytes);
-    return STY_ENOMEM;
-  }
-  kp.valid = false;  // consumed: the scratch of this call overwrites nothing kept, but a second backward is not the contract
-  Run r(m, B, workspace, ws_bytes, stream);
-  wavlm_backward(r, N16, kp, d_hidden, d_audio16, d_enc_in);
-  return r.finish(nullptr, workspace, ws_bytes);
-}
-// ---- one strided feature conv alone, forward and input gradient: the stage + conv / dgrad + un-stage pair of the plan ----
-// x [B][Cin][Nin] is a pre-activation (what the layer below leaves in keep mode): y = conv1d(GELU(x), w, stride s) [B][Cout][T],
-// T = (Nin - k) / s + 1, no activation; dx = GELU'(x) * (the transposed conv of gy) [B][Cin][Nin], zero where no frame reads.
-static int wavlm_strided_unit(int B, int Cin, int Cout, int k, int s, int Nin, const float* x, const float* w, int compute_bf16,
-                              float* y, const float* gy, float* dx, float* view, void* view16, int* routes, void* ws, size_t ws_bytes,
-                              void* stream, size_t* need) {
-  if (B <= 0 || Cin <= 0 || Cout <= 0 || k < 1 || s < 1 || s > 16 || Nin < k || (compute_bf16 != 0 && compute_bf16 != 1)) {
-    set_error("sty_wavlm_strided_conv: bad argument (k >= 1, stride 1 to 16, Nin >= k, compute_bf16 0 or 1)");
-    return STY_EINVAL;
-  }
-  sty_model tmp;
-  tmp.kind = "wavlm";
-  tmp.wav_bf16 = compute_bf16;
-  Run r(&tmp, B, ws, ws_bytes, stream);
-  const int Tl = (Nin - k) / s + 1;
-  PackedConv pc;
-  pc.Cin = s * Cin, pc.Cout = Cout, pc.K = cdiv(k, s);
-  pc.CinP = (int)align_up(pc.Cin, CI_CHUNK), pc.CoutP = (int)align_up(Cout, 32);
-  const int Tp = Tl + pc.K - 1;
-  const size_t wn = (size_t)pc.K * pc.CinP * pc.CoutP, nv = (size_t)B * pc.Cin * Tp, ny = (size_t)B * Cout * Tp;
-  float* wp = r.ws.take<float>(wn);
-  float* wd = r.ws.take<float>(wn);
-  float* stg = r.ws.take<float>(nv);
-  float* ybuf = r.ws.take<float>(ny);
-  float* gpad = r.ws.take<float>(ny);
-  __bf16* g16 = r.ws.take<__bf16>(ny);
-  float* dvw = r.ws.take<float>(nv);
-  r.note_peak();
-  if (!r.live()) return r.finish(need, ws, ws_bytes);
-  pc.wp = wp;
-  PackedConv pd;
-  pd.Cin = pc.Cout, pd.CinP = pc.CoutP, pd.Cout = pc.Cin, pd.CoutP = pc.CinP, pd.K = pc.K, pd.wp = wd;
-  STY_HIP(hipMemsetAsync(wp, 0, wn * sizeof(float), r.st));
-  WavlmPackJob j;
-  j.w = w, j.wp = wp;
-  j.Cout = Cout, j.Cin = Cin, j.K = k, j.s = s, j.CinP = pc.CinP, j.CoutP = pc.CoutP;
-  r.chk(launch_wavlm_pack(j, r.st));
-  r.chk(launch_pack_dgrad(wp, pc.K, pc.CinP, pc.CoutP, wd, r.st));
-  if (!r.live()) return r.rc;
-  ConvKernel kf = CONV_TILED, kd = CONV_TILED;
-  bool left_pre = false, ftwin = false;
-  const int yrs = wavlm_strided_fwd(r, pc, x, Nin, Cin, Nin, s, Tl, nullptr, nullptr, 1, true, true, stg, ybuf, &left_pre, &kf, &ftwin);
-  if (!r.live()) return r.rc;
-  STY_HIP(hipMemcpy2DAsync(y, (size_t)Tl * sizeof(float), ybuf, (size_t)yrs * sizeof(float), (size_t)Tl * sizeof(float), (size_t)B * Cout,
-                           hipMemcpyDeviceToDevice, r.st));
-  if (view16) {
-    if (!ftwin) {
-      set_error("sty_wavlm_strided_conv: the bf16 twin of the view was asked for, but this conv does not run on a twin family");
-      return STY_EINVAL;
-    }
-    STY_HIP(hipMemcpyAsync(view16, stg, nv * sizeof(__bf16), hipMemcpyDeviceToDevice, r.st));
-  }
-  // the gradient as the plan's producers leave it: the twin on zero-padded rows where the transposed conv takes it
-  const bool dtwin = wavlm_dgrad_twin(r, pd, pc.K, Tl, &kd);
-  if (dtwin) {
-    STY_HIP(hipMemsetAsync(gpad, 0, ny * sizeof(float), r.st));
-    STY_HIP(hipMemcpy2DAsync(gpad, (size_t)Tp * sizeof(float), gy, (size_t)Tl * sizeof(float), (size_t)Tl * sizeof(float), (size_t)B * Cout,
-                             hipMemcpyDeviceToDevice, r.st));
-    r.chk(launch_twin_cast(gpad, nullptr, PRO_NONE, B, Cout, Tp, g16, r.st));
-  }
-  wavlm_strided_dgrad(r, pd, pc.K, gy, dtwin ? g16 : nullptr, Tl, dvw);
-  if (!r.live()) return r.rc;
-  if (compute_bf16)
-    r.chk(launch_wavlm_unstage_rs(dvw, x, B, Cin, Nin, Nin, s, Tp, Nin, dx, 0, r.st));
-  else
-    r.chk(launch_wavlm_unstage(dvw, x, B, Cin, Nin, s, Tp, dx, r.st));
-  if (view && r.live()) r.chk(launch_wavlm_stage(x, nullptr, nullptr, B, Cin, Nin, s, Tp, view, r.st, 1));  // (the fp32 mode's view)
-  if (routes) routes[0] = (int)kf, routes[1] = (int)kd, routes[2] = ftwin, routes[3] = dtwin;
-  return r.rc;
-}
-int sty_wavlm_strided_conv_workspace_bytes(int B, int Cin, int Cout, int k, int s, int Nin, size_t* bytes) {
-  if (!bytes) {
-    set_error("sty_wavlm_strided_conv_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
-  return wavlm_strided_unit(B, Cin, Cout, k, s, Nin, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                            nullptr, bytes);
-}
-int sty_wavlm_strided_conv_fwd_bwd(int B, int Cin, int Cout, int k, int s, int Nin, const float* x, const float* w, int compute_bf16,
-                                   float* y, const float* gy, float* dx, float* view, void* view16, int* routes, void* workspace,
-                                   size_t ws_bytes, void* stream) {
-  if (!x || !w || !y || !gy || !dx || !workspace) {
-    set_error("sty_wavlm_strided_conv_fwd_bwd: bad argument");
-    return STY_EINVAL;
-  }
-  size_t need = 0;
-  int rc = sty_wavlm_strided_conv_workspace_bytes(B, Cin, Cout, k, s, Nin, &need);
-  if (rc) return rc;
-  if (ws_bytes < need) {
-    set_error("sty_wavlm_strided_conv_fwd_bwd: workspace too small: need %zu bytes, have %zu", need, ws_bytes);
-    return STY_ENOMEM;
-  }
-  return wavlm_strided_unit(B, Cin, Cout, k, s, Nin, x, w, compute_bf16, y, gy, dx, view, view16, routes, workspace, ws_bytes, stream,
-                            nullptr);
-}
-int sty_wavlm_rel_buckets_host(int T, int num_buckets, int max_distance, int32_t* out) {
-  if (T < 1 || num_buckets < 4 || max_distance < 2 || !out || max_distance <= num_buckets / 4) {
-    set_error("sty_wavlm_rel_buckets_host: bad argument");
-    return STY_EINVAL;
-  }
-  wavlm_rel_buckets(T, num_buckets, max_distance, out);
-  return STY_OK;
-}
-int sty_slm_loss_workspace_bytes(size_t n, size_t* bytes) {
-  if (!bytes || n == 0) {
-    set_error("sty_slm_loss_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
-  *bytes = (size_t)slm_loss_groups(n) * sizeof(double);
-  return STY_OK;
-}
-int sty_slm_loss_fwd(size_t n, const float* a, const float* b, float* loss, void* workspace, size_t ws_bytes, void* stream) {
-  if (!a || !b || !loss || !workspace || n == 0 || ((uintptr_t)workspace & 7)) {
-    set_error("sty_slm_loss_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (ws_bytes < (size_t)slm_loss_groups(n) * sizeof(double)) {
-    set_error("sty_slm_loss_fwd: workspace too small");
-    return STY_ENOMEM;
-  }
-  return launch_slm_loss(n, a, b, loss, (double*)workspace, S(stream));
-}
-int sty_slm_loss_fwd_bwd(size_t n, const float* a, const float* b, float scale, float* loss, float* d_b, void* workspace, size_t ws_bytes,
-                         void* stream) {
-  if (!a || !b || !loss || !d_b || !workspace || n == 0 || ((uintptr_t)workspace & 7)) {
-    set_error("sty_slm_loss_fwd_bwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (ws_bytes < (size_t)slm_loss_groups(n) * sizeof(double)) {
-    set_error("sty_slm_loss_fwd_bwd: workspace too small");
-    return STY_ENOMEM;
-  }
-  // d mean|a - b| / d b = sign(b - a) / n, times scale: one magnitude, formed as torch's division by a host scalar is
-  // (a multiplication by the fp32 reciprocal)
-  const float mag = scale * (1.0f / (float)n);
-  return launch_slm_loss(n, a, b, loss, (double*)workspace, S(stream), mag, d_b);
 }
 // ---- text aligner in the training graph (train_alignment, stage_type.py:268-341): forward, then sty_aligner_bwd ----
 int sty_aligner_train_workspace_bytes(sty_model* m, int B, int T, size_t* bytes) {
@@ -3313,95 +2425,61 @@ int sty_pitch_energy_bwd(sty_model* m, const float* d_pitch, const float* d_ener
   return finish_bwd(m, S(stream));
 }
 int sty_pitch_energy_workspace_bytes(const sty_model* m, int B, int L, int T, size_t* bytes) {
-  int rc = model_ready(m, "pitch_energy_predictor");
+  const int rc = entry_ready(m, "pitch_energy_predictor", nullptr, !bytes || B <= 0 || L <= 0 || T <= 0,
+                             "sty_pitch_energy_workspace_bytes: bad argument");
   if (rc) return rc;
-  if (!bytes || B <= 0 || L <= 0 || T <= 0) {
-    set_error("sty_pitch_energy_workspace_bytes: bad argument");
-    return STY_EINVAL;
-  }
   return pitch_energy_run(const_cast<sty_model*>(m), B, L, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                           nullptr, 0, nullptr, bytes);
 }
 int sty_pitch_energy_fwd(sty_model* m, int B, int L, int T, const int64_t* texts, const int64_t* text_lengths,
                          const float* alignment, const float* style, float* pitch, float* energy, void* workspace,
                          size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "pitch_energy_predictor");
-  if (rc) return rc;
-  if (!texts || !text_lengths || !alignment || !style || !pitch || !energy || !workspace || B <= 0 || L <= 0 ||
-      T <= 0) {
-    set_error("sty_pitch_energy_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  const bool bad = !texts || !text_lengths || !alignment || !style || !pitch || !energy || !workspace || B <= 0 || L <= 0 || T <= 0;
+  int rc = entry_ready(m, "pitch_energy_predictor", nullptr, bad, "sty_pitch_energy_fwd: bad argument");
+  if (rc || (rc = ensure_prepared(m, stream))) return rc;
   return pitch_energy_run(m, B, L, T, texts, text_lengths, alignment, style, pitch, energy, workspace, ws_bytes,
                           stream, nullptr);
 }
 
 // ---- fine-grained entry points ----
+// (defined with the unit backward entries below; no_resblock: the message, with one %s for the prefix, where it names no resblock)
+static int find_block(sty_model* m, const char* kind, const char* prefix, int C, int* k, const void** blk,
+                      const char* no_resblock = "no such resblock (32 channels): %s");
 int sty_convnext_fwd(sty_model* m, const char* prefix, int B, int C, int T, const float* x, const float* style,
                      float* y, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  int rc = entry_ready(m, "speech_predictor", "vocoder", !prefix || !x || !style || !y || !workspace, "sty_convnext_fwd: bad argument");
   if (rc) return rc;
-  if (!prefix || !x || !style || !y || !workspace) {
-    set_error("sty_convnext_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
-  // locate the block by its first requested key
-  const ConvNeXt* blk = nullptr;
-  const std::string want = std::string(prefix) + ".dwconv.weight";
-  auto it = m->params.find(want);
-  if (it == m->params.end()) {
-    set_error("no such block: %s", prefix);
-    return STY_EINVAL;
-  }
-  auto match = [&](const ConvNeXt& c) { return c.dw_w == it->second.p; };
-  for (const ConvNeXt& c : m->voc.amp_convnext)
-    if (match(c)) blk = &c;
-  for (const ConvNeXt& c : m->voc.phase_convnext)
-    if (match(c)) blk = &c;
-  for (int i = 0; i < 3; ++i)
-    if (match(m->voc.upblock[i])) blk = &m->voc.upblock[i];
-  if (!blk || blk->C != C) {
-    set_error("block %s not found or channel mismatch", prefix);
-    return STY_EINVAL;
-  }
+  if ((rc = ensure_prepared(m, stream))) return rc;
+  int k = 0;
+  const void* blk = nullptr;
+  if ((rc = find_block(m, "convnext", prefix, C, &k, &blk))) return rc;
   Run r(m, B, workspace, ws_bytes, stream);
   run_style_fc(r, style);
   if (x == y && C == 32) {
     set_error("sty_convnext_fwd: C == 32 runs out of place, y must differ from x");
     return STY_EINVAL;
   }
-  r.convnext(*blk, x, y, T);
+  r.convnext(*static_cast<const ConvNeXt*>(blk), x, y, T);
   return r.finish(nullptr, workspace, ws_bytes);
 }
 
 int sty_resblock_fwd(sty_model* m, const char* prefix, int B, int T, const float* x, const float* style, float* y,
                      void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "speech_predictor", "vocoder");
+  int rc = entry_ready(m, "speech_predictor", "vocoder", !prefix || !x || !style || !y || !workspace, "sty_resblock_fwd: bad argument");
   if (rc) return rc;
-  if (!prefix || !x || !style || !y || !workspace) {
-    set_error("sty_resblock_fwd: bad argument");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
-  const std::string p(prefix);
-  const ResBlock32* blk = nullptr;
-  if (p.size() >= 15 && p.compare(p.size() - 15, 15, "amp_prior_block") == 0) blk = &m->voc.amp_prior_block;
-  if (p.size() >= 17 && p.compare(p.size() - 17, 17, "phase_prior_block") == 0) blk = &m->voc.phase_prior_block;
-  if (!blk) {
-    set_error("no such resblock: %s", prefix);
-    return STY_EINVAL;
-  }
+  if ((rc = ensure_prepared(m, stream))) return rc;
+  int k = 0;
+  const void* blk = nullptr;
+  if ((rc = find_block(m, "resblock", prefix, 32, &k, &blk, "no such resblock: %s"))) return rc;
   Run r(m, B, workspace, ws_bytes, stream);
   run_style_fc(r, style);
   if (y != x) STY_HIP(hipMemcpyAsync(y, x, (size_t)B * 32 * T * sizeof(float), hipMemcpyDeviceToDevice, r.st));
-  r.resblock(*blk, y, T);
+  r.resblock(*static_cast<const ResBlock32*>(blk), y, T);
   return r.finish(nullptr, workspace, ws_bytes);
 }
 
 // ---- unit backward entry points: one sub-module in the training graph, forward + backward ----
-static int find_block(sty_model* m, const char* kind, const char* prefix, int C, int* k, const void** blk) {
+static int find_block(sty_model* m, const char* kind, const char* prefix, int C, int* k, const void** blk, const char* no_resblock) {
   const std::string p(prefix);
   if (std::string(kind) == "convnext") {
     auto it = m->params.find(p + ".dwconv.weight");
@@ -3430,7 +2508,7 @@ static int find_block(sty_model* m, const char* kind, const char* prefix, int C,
     if (p.size() >= 15 && p.compare(p.size() - 15, 15, "amp_prior_block") == 0) b = &m->voc.amp_prior_block;
     if (p.size() >= 17 && p.compare(p.size() - 17, 17, "phase_prior_block") == 0) b = &m->voc.phase_prior_block;
     if (!b || C != 32) {
-      set_error("no such resblock (32 channels): %s", prefix);
+      set_error(no_resblock, prefix);
       return STY_EINVAL;
     }
     *k = 1;
@@ -3648,44 +2726,30 @@ static int pitch_style_entry(sty_model* m, int B, int T, const float* mel, const
   return r.finish(need, ws, ws_bytes);
 }
 int sty_pitch_style_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "pitch_style_encoder");
+  const int rc = entry_ready(m, "pitch_style_encoder", nullptr, !bytes || B <= 0 || T < 40,
+                             "sty_pitch_style_workspace_bytes: bad argument (T >= 40 frames)");
   if (rc) return rc;
-  if (!bytes || B <= 0 || T < 40) {
-    set_error("sty_pitch_style_workspace_bytes: bad argument (T >= 40 frames)");
-    return STY_EINVAL;
-  }
   return pitch_style_entry(const_cast<sty_model*>(m), B, T, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
                            bytes);
 }
 int sty_pitch_style_fwd(sty_model* m, int B, int T, const float* mel, const float* pitch, const float* energy,
                         float* style, void* workspace, size_t ws_bytes, void* stream) {
-  int rc = model_ready(m, "pitch_style_encoder");
-  if (rc) return rc;
-  if (!mel || !pitch || !energy || !style || !workspace || B <= 0 || T < 40) {
-    set_error("sty_pitch_style_fwd: bad argument (T >= 40 frames)");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  int rc = entry_ready(m, "pitch_style_encoder", nullptr, !mel || !pitch || !energy || !style || !workspace || B <= 0 || T < 40,
+                       "sty_pitch_style_fwd: bad argument (T >= 40 frames)");
+  if (rc || (rc = ensure_prepared(m, stream))) return rc;
   return pitch_style_entry(m, B, T, mel, pitch, energy, style, workspace, ws_bytes, stream, nullptr);
 }
 int sty_style_workspace_bytes(const sty_model* m, int B, int T, size_t* bytes) {
-  int rc = model_ready(m, "mel_style_encoder");
+  const int rc = entry_ready(m, "mel_style_encoder", nullptr, !bytes || B <= 0 || T < 40,
+                             "sty_style_workspace_bytes: bad argument (T >= 40 frames)");
   if (rc) return rc;
-  if (!bytes || B <= 0 || T < 40) {
-    set_error("sty_style_workspace_bytes: bad argument (T >= 40 frames)");
-    return STY_EINVAL;
-  }
   return style_entry(const_cast<sty_model*>(m), B, T, nullptr, nullptr, nullptr, 0, nullptr, bytes);
 }
 int sty_style_fwd(sty_model* m, int B, int T, const float* mel, float* style, void* workspace, size_t ws_bytes,
                   void* stream) {
-  int rc = model_ready(m, "mel_style_encoder");
-  if (rc) return rc;
-  if (!mel || !style || !workspace || B <= 0 || T < 40) {
-    set_error("sty_style_fwd: bad argument (T >= 40 frames)");
-    return STY_EINVAL;
-  }
-  if (!m->prepared && (rc = sty_model_prepare(m, stream))) return rc;
+  int rc = entry_ready(m, "mel_style_encoder", nullptr, !mel || !style || !workspace || B <= 0 || T < 40,
+                       "sty_style_fwd: bad argument (T >= 40 frames)");
+  if (rc || (rc = ensure_prepared(m, stream))) return rc;
   return style_entry(m, B, T, mel, style, workspace, ws_bytes, stream, nullptr);
 }
 // Weight-side half of a style encoder's training forward: the training-mode spectral-norm power iteration (u, v in the
@@ -3774,6 +2838,48 @@ int sty_style_tap(sty_model* m, int index, int grad, float* dst, int* C, int* H,
   }
   return trainer_style_tap(m->trainer, index, grad, dst, C, H, W, S(stream));
 }
+// ---- what the four sty_conv1d_* entries share: a caller's dense conv, packed into the front of the caller's workspace ----
+static PackedConv unit_conv_dims(int Cin, int Cout, int K) {
+  PackedConv pc;
+  pc.Cin = Cin;
+  pc.Cout = Cout;
+  pc.K = K;
+  pc.CinP = (int)align_up(Cin, CI_CHUNK);
+  pc.CoutP = (int)align_up(Cout, 32);  // the model's padding rule (prepare_conv)
+  return pc;
+}
+// floats of the packed weight [K][CinP][CoutP] with its bias row behind it
+static size_t unit_conv_plane(const PackedConv& pc) { return (size_t)pc.K * pc.CinP * pc.CoutP + pc.CoutP; }
+static float* unit_ws_front(void* workspace) { return reinterpret_cast<float*>(align_up(reinterpret_cast<size_t>(workspace), 256)); }
+// w [Cout][Cin][K] (and bias, if any) -> pc.wp and the bias row at the workspace's front; `clear` floats from there are zeroed
+// first (the padding, and whatever else of the caller's lies behind).  bias_row: pc.bias names the row.
+static int unit_conv_pack(PackedConv& pc, const float* w, const float* bias, bool bias_row, void* workspace, size_t clear,
+                          hipStream_t st) {
+  float* wp = unit_ws_front(workspace);
+  float* bp = wp + (size_t)pc.K * pc.CinP * pc.CoutP;
+  STY_HIP(hipMemsetAsync(wp, 0, clear * sizeof(float), st));
+  const int rc = launch_pack_conv(w, nullptr, nullptr, bias, pc.Cout, pc.Cin, pc.K, wp, bp, pc.CinP, pc.CoutP, st);
+  if (rc) return rc;
+  pc.wp = wp;
+  pc.bias = bias_row ? bp : nullptr;
+  return STY_OK;
+}
+// the dense conv with 'same' padding over x [B][Cin][T] -> y
+static ConvArgs unit_conv_args(const PackedConv& w, int B, int T, int dil, const float* x, float* y, int bf16) {
+  const int Cin = w.Cin, K = w.K;
+  ConvArgs a;
+  a.x[0] = x;
+  a.xc[0] = Cin;
+  a.nsrc = 1;
+  a.B = B;
+  a.T = T;
+  a.w = w;
+  a.dil = dil;
+  a.pad = (K - 1) * dil / 2;
+  a.y = y;
+  a.bf16 = bf16;
+  return a;
+}
 // ---- one dense Conv1d ('same' padding) on the MFMA conv kernel: unit parity and kernel tuning ----
 int sty_conv1d_workspace_bytes(int Cout, int Cin, int K, size_t* bytes) {
   if (!bytes || Cout <= 0 || Cin <= 0 || K <= 0) {
@@ -3792,30 +2898,9 @@ int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
     set_error("sty_conv1d_fwd: bad argument, halo > 128 or workspace too small");
     return STY_EINVAL;
   }
-  PackedConv pc;
-  pc.Cin = Cin;
-  pc.Cout = Cout;
-  pc.K = K;
-  pc.CinP = (int)align_up(Cin, CI_CHUNK);
-  pc.CoutP = (int)align_up(Cout, 32);  // the model's padding rule (prepare_conv)
-  float* wp = reinterpret_cast<float*>(align_up(reinterpret_cast<size_t>(workspace), 256));
-  float* bp = wp + (size_t)K * pc.CinP * pc.CoutP;
-  STY_HIP(hipMemsetAsync(wp, 0, ((size_t)K * pc.CinP * pc.CoutP + pc.CoutP) * sizeof(float), S(stream)));
-  rc = launch_pack_conv(w, nullptr, nullptr, bias, Cout, Cin, K, wp, bp, pc.CinP, pc.CoutP, S(stream));
-  if (rc) return rc;
-  pc.wp = wp;
-  pc.bias = bias ? bp : nullptr;
-  ConvArgs a;
-  a.x[0] = x;
-  a.xc[0] = Cin;
-  a.nsrc = 1;
-  a.B = B;
-  a.T = T;
-  a.w = pc;
-  a.dil = dil;
-  a.pad = (K - 1) * dil / 2;
-  a.y = y;
-  a.bf16 = compute_bf16 != 0;
+  PackedConv pc = unit_conv_dims(Cin, Cout, K);
+  if ((rc = unit_conv_pack(pc, w, bias, bias != nullptr, workspace, unit_conv_plane(pc), S(stream)))) return rc;
+  ConvArgs a = unit_conv_args(pc, B, T, dil, x, y, compute_bf16 != 0);
   if (compute_bf16 == 2) {
     // the input as its bf16 operand twin (ConvArgs::x16), made here by the cast pass, and a twin of the OUTPUT written by
     // the conv's output stage (ConvArgs::y16), which is read back and checked against y by ... the caller: the twin
@@ -3833,15 +2918,6 @@ int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   }
   return launch_conv1d(a, S(stream));
 }
-static PackedConv unit_conv_dims(int Cin, int Cout, int K) {
-  PackedConv pc;
-  pc.Cin = Cin;
-  pc.Cout = Cout;
-  pc.K = K;
-  pc.CinP = (int)align_up(Cin, CI_CHUNK);
-  pc.CoutP = (int)align_up(Cout, 32);  // the model's padding rule (prepare_conv)
-  return pc;
-}
 // the same conv with the fused prologue / output stage the text encoder's convs use (fp32 tensors only)
 int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const float* x, const float* w, const float* bias,
                       const float* in_mask, const float* residual, const float* out_mask, int out_mask_post, int relu, float* y,
@@ -3854,30 +2930,9 @@ int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const flo
     set_error("sty_conv1d_fwd_ex: bad argument, halo > 128, a compute mode other than 0 / 1 or workspace too small");
     return STY_EINVAL;
   }
-  PackedConv pc;
-  pc.Cin = Cin;
-  pc.Cout = Cout;
-  pc.K = K;
-  pc.CinP = (int)align_up(Cin, CI_CHUNK);
-  pc.CoutP = (int)align_up(Cout, 32);  // the model's padding rule (prepare_conv)
-  float* wp = reinterpret_cast<float*>(align_up(reinterpret_cast<size_t>(workspace), 256));
-  float* bp = wp + (size_t)K * pc.CinP * pc.CoutP;
-  STY_HIP(hipMemsetAsync(wp, 0, ((size_t)K * pc.CinP * pc.CoutP + pc.CoutP) * sizeof(float), S(stream)));
-  rc = launch_pack_conv(w, nullptr, nullptr, bias, Cout, Cin, K, wp, bp, pc.CinP, pc.CoutP, S(stream));
-  if (rc) return rc;
-  pc.wp = wp;
-  pc.bias = bias ? bp : nullptr;
-  ConvArgs a;
-  a.x[0] = x;
-  a.xc[0] = Cin;
-  a.nsrc = 1;
-  a.B = B;
-  a.T = T;
-  a.w = pc;
-  a.dil = dil;
-  a.pad = (K - 1) * dil / 2;
-  a.y = y;
-  a.bf16 = compute_bf16;
+  PackedConv pc = unit_conv_dims(Cin, Cout, K);
+  if ((rc = unit_conv_pack(pc, w, bias, bias != nullptr, workspace, unit_conv_plane(pc), S(stream)))) return rc;
+  ConvArgs a = unit_conv_args(pc, B, T, dil, x, y, compute_bf16);
   if (in_mask) {
     a.pro = PRO_MASK;
     a.mask = in_mask;
@@ -3901,18 +2956,9 @@ int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int comput
   static float dummy_f[4];
   static double dummy_d[4];
   static __bf16 dummy_h[4];
-  ConvArgs a;
-  a.x[0] = dummy_f;
-  a.xc[0] = Cin;
-  a.nsrc = 1;
-  a.B = B;
-  a.T = T;
-  a.w = unit_conv_dims(Cin, Cout, K);
-  a.w.wp = dummy_f;
-  a.dil = dil;
-  a.pad = (K - 1) * dil / 2;
-  a.y = dummy_f;
-  a.bf16 = compute_bf16 != 0;
+  PackedConv pc = unit_conv_dims(Cin, Cout, K);
+  pc.wp = dummy_f;
+  ConvArgs a = unit_conv_args(pc, B, T, dil, dummy_f, dummy_f, compute_bf16 != 0);
   if (flags & STY_ROUTE_IN_MASK) {
     a.pro = PRO_MASK;
     a.mask = dummy_f;
@@ -3943,8 +2989,7 @@ int sty_conv1d_bwd_workspace_bytes(int B, int Cin, int Cout, int K, int T, size_
     return STY_EINVAL;
   }
   const PackedConv pc = unit_conv_dims(Cin, Cout, K);
-  const size_t plane = (size_t)K * pc.CinP * pc.CoutP + pc.CoutP;
-  *bytes = (3 * plane + wgrad_partial_floats(pc, B, T)) * sizeof(float) + 1024;  // weights, gradient, flipped weights
+  *bytes = (3 * unit_conv_plane(pc) + wgrad_partial_floats(pc, B, T)) * sizeof(float) + 1024;  // weights, gradient, flipped weights
   *bytes += (size_t)B * (Cin + Cout) * T * sizeof(__bf16) + 512;                   // compute_bf16 = 2: the two operand twins
   return STY_OK;
 }
@@ -3961,9 +3006,8 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   hipStream_t st = S(stream);
   PackedConv pc = unit_conv_dims(Cin, Cout, K);
   const size_t plane = (size_t)K * pc.CinP * pc.CoutP;
-  float* wp = reinterpret_cast<float*>(align_up(reinterpret_cast<size_t>(workspace), 256));
-  float* bp = wp + plane;
-  float* gwp = bp + pc.CoutP;  // packed gradient: [K][CinP][CoutP] + bias tail
+  float* wp = unit_ws_front(workspace);
+  float* gwp = wp + unit_conv_plane(pc);  // packed gradient: [K][CinP][CoutP] + bias tail
   float* gbp = gwp + plane;
   PackedConv pd;
   pd.Cin = Cout;
@@ -3973,21 +3017,9 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   pd.CoutP = pc.CinP;
   float* wd = gbp + pc.CoutP;
   float* partial = wd + plane + pc.CoutP;
-  STY_HIP(hipMemsetAsync(wp, 0, (size_t)(partial - wp) * sizeof(float), st));
-  rc = launch_pack_conv(w, nullptr, nullptr, nullptr, Cout, Cin, K, wp, bp, pc.CinP, pc.CoutP, st);
-  if (rc) return rc;
-  pc.wp = wp;
-  pc.bias = dbias ? bp : nullptr;
-  ConvArgs a;
-  a.x[0] = x;
-  a.xc[0] = Cin;
-  a.nsrc = 1;
-  a.B = B;
-  a.T = T;
-  a.w = pc;
-  a.dil = dil;
-  a.pad = (K - 1) * dil / 2;
-  a.bf16 = compute_bf16 != 0;
+  // (the clear takes the gradient and the flipped weights with it: everything in front of the partial planes)
+  if ((rc = unit_conv_pack(pc, w, nullptr, dbias != nullptr, workspace, (size_t)(partial - wp), st))) return rc;
+  ConvArgs a = unit_conv_args(pc, B, T, dil, x, nullptr, compute_bf16 != 0);
   if (compute_bf16 == 3) {  // x is a bf16 TENSOR (two-byte storage, ConvArgs::xh): the weight gradient alone has a form for it here
     if (dx || T % 2) {
       set_error("sty_conv1d_bwd: a two-byte x (compute_bf16 = 3) is for dw / dbias only (dx == NULL), T even");
@@ -4020,17 +3052,8 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
     if (rc) return rc;
     pdm.wp = wd;
     pdm.bias = nullptr;
-    ConvArgs d;
-    d.x[0] = gy;
-    d.xc[0] = Cout;
-    d.nsrc = 1;
-    d.B = B;
-    d.T = T;
-    d.w = pdm;
-    d.dil = dil;
-    d.pad = (K - 1) * dil - a.pad;
-    d.bf16 = a.bf16;
-    d.y = dx;
+    ConvArgs d = unit_conv_args(pdm, B, T, dil, gy, dx, a.bf16);
+    d.pad = (K - 1) * dil - a.pad;  // the other half of an even halo
     d.x16 = a.g16;  // (compute_bf16 = 2) the input-gradient conv reads the gradient's operand twin as well
     rc = launch_conv1d(d, st);
   }

@@ -262,7 +262,7 @@ inline int resample_width(int orig, int nw, double lpw) {
 void build_resample_kernel(int orig, int nw, double lpw, float* out);
 int launch_resample_fir(const float* x, const float* taps, int B, int N, int M, int orig, int nw, int width, float* y, hipStream_t st);
 
-// WavLM = transformers' WavLMModel in eval mode (wavlm.hip has the kernels, api.hip the plan, weights.hip the packs)
+// WavLM = transformers' WavLMModel in eval mode (wavlm.hip has the kernels, plan_wavlm.hip the plan, weights.hip the packs)
 constexpr int WAVLM_MAX_CONV = 8;
 struct WavlmPackJob {  // wp[(kk / s) CinP + (kk % s) Cin + ci][co] = w[co0 + co][ci][kk] * (g ? g[kk] / nrm[kk] : 1); bp[co] = bias[co0 + co]
   const float *w = nullptr, *g = nullptr, *nrm = nullptr, *bias = nullptr;
@@ -338,7 +338,7 @@ int slm_loss_groups(size_t n);
 // d_b (optional): also d_b[i] = mag sign(b[i] - a[i]), 0 at a tie
 int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, double* part, hipStream_t st, float mag = 0.f,
                     float* d_b = nullptr);
-// ---- WavLM backward to the wave (wavlm.hip; api.hip: wavlm_backward) ----
+// ---- WavLM backward to the wave (wavlm.hip; plan_wavlm.hip: wavlm_backward) ----
 int launch_wavlm_gelu(const float* pre, const float* res, size_t n, float* y, hipStream_t st);  // y = res + GELU(pre), res optional
 int launch_wavlm_intake(const float* dh, int B, int C, int T, int accumulate, float* dx, hipStream_t st);  // dx[b][c][t] (+)= dh[b][t][c]
 int launch_wavlm_gate_bwd(const float* x, const float* w, const float* b, const float* c, const float* dgate, int B, int H, int DH,

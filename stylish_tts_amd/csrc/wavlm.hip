@@ -1,6 +1,6 @@
 // WavLM forward for the slm loss value (WavLMLoss, train/losses.py:376-394; transformers' modeling_wavlm.py in eval mode):
 // everything of it that is not a dense conv on launch_conv1d, an attention launch (attn.hip, the gated relative-bias variant)
-// or a channel LayerNorm (norms.hip).  api.hip has the plan (wavlm_forward), weights.hip the packs.
+// or a channel LayerNorm (norms.hip).  plan_wavlm.hip has the plan (wavlm_forward), weights.hip the packs.
 //
 // (1) Feature encoder, layer 0 (Conv1d(1, C, k, stride s), bias-free; k = 10, s = 5 at full size): bandwidth work.
 //     wavlm_conv0_kernel writes the conv's output [B][C][T0] and, from the same registers, the float64 (sum, sum of squares)
@@ -19,7 +19,7 @@
 // (5) wavlm_transpose_out_kernel: [B][C][T] -> the [B][T][C] hidden state the loss reads.
 // (6) slm_loss kernels: mean |a - b| with float64 partials at fixed indices, added in index order (val_loss.hip's discipline);
 //     with d_b set also scale * sign(b - a) / n, the term's cotangent.
-// (7) The backward to the wave (the network is frozen: input gradients only; api.hip has the plan, wavlm_backward): the
+// (7) The backward to the wave (the network is frozen: input gradients only; plan_wavlm.hip has the plan, wavlm_backward): the
 //     cotangent intake, the gate backward, the un-staging of a strided conv's view with the GELU' of the layer below, the
 //     GroupNorm(C, C) backward with float64 tile partials, layer 0 transposed.  The dense steps are launch_conv1d on
 //     input-gradient packs, the attention backward with the gated bias is attn_bwd.hip's, the resampler adjoint rmvpe.hip's.
@@ -359,7 +359,7 @@ int launch_slm_loss(size_t n, const float* a, const float* b, float* loss, doubl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// backward to the wave (api.hip: wavlm_backward).  The network is frozen: input gradients only, no float atomic anywhere --
+// backward to the wave (plan_wavlm.hip: wavlm_backward).  The network is frozen: input gradients only, no float atomic anywhere --
 // every output element has one writer and every sum a fixed order, so the gradient repeats to the bit.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {

@@ -1,5 +1,5 @@
 """The bf16 operand mode of the slm term on the device (sty_wavlm_set_compute; csrc/wavlm.hip, csrc/attn16.hip, the plan in
-csrc/api.hip; stylish_tts_amd/slm.py).  Reads tests/golden only; imports neither transformers nor the reference.
+csrc/plan_wavlm.hip; stylish_tts_amd/slm.py).  Reads tests/golden only; imports neither transformers nor the reference.
 
 Two levels.
 
