@@ -446,12 +446,19 @@ int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float 
 int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const float *x, const float *w, const float *bias,
                       const float *in_mask, const float *residual, const float *out_mask, int out_mask_post, int relu,
                       float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
+/* The generator's pixel-shuffle up-sampling conv (generator.py:731-780): the same conv with the output stored shuffled,
+ * y [B, Cout / shuffle, T * shuffle] with y[b][co / shuffle][t * shuffle + co % shuffle]; Cout % shuffle == 0; compute_bf16 0 / 1. */
+int sty_conv1d_fwd_shuffle(int B, int Cin, int Cout, int K, int dil, int T, int shuffle, const float *x, const float *w,
+                           const float *bias, float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
 /* Which kernel family the dispatch picks for a conv of this shape carrying the operands named in `flags` (host only, nothing is
  * launched): *kernel = position in the dispatch order's list of families (STY_CONV_*), -1 where the conv is refused.
  * STY_ROUTE_FLAT_IMAGE: the conv is a 3-row 2-D conv in flat-image mode (the discriminators' layout): Cin = 3 * the image's
  * channels, T = rows * row pitch (the pitch itself does not enter the choice).                                            */
 enum { STY_ROUTE_IN_MASK = 1, STY_ROUTE_RESIDUAL = 2, STY_ROUTE_OUT_MASK = 4, STY_ROUTE_RELU = 8, STY_ROUTE_TWO_BYTE_X = 16,
-       STY_ROUTE_STATS = 32, STY_ROUTE_Y16 = 64, STY_ROUTE_X16 = 128, STY_ROUTE_FLAT_IMAGE = 256 };
+       STY_ROUTE_STATS = 32, STY_ROUTE_Y16 = 64, STY_ROUTE_X16 = 128, STY_ROUTE_FLAT_IMAGE = 256,
+       /* the output is stored pixel-shuffled / the source is (the input-gradient conv of such a layer): the factor, 2 .. 15, goes
+        * into flags as well, factor << STY_ROUTE_SHUFFLE_SHIFT */
+       STY_ROUTE_SHUFFLE_STORE = 512, STY_ROUTE_SHUFFLE_SOURCE = 1024, STY_ROUTE_SHUFFLE_SHIFT = 16 };
 enum { STY_CONV_STEM2D = 0, STY_CONV_32P, STY_CONV_SC, STY_CONV_K1, STY_CONV_Q, STY_CONV_P16, STY_CONV_TILED };
 int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int compute_bf16, int flags, int *kernel);
 /* Gradients of the same conv on the kernels the training graph uses: dw [Cout,Cin,K] and dbias [Cout] (or NULL) from
@@ -463,6 +470,12 @@ int sty_conv1d_bwd_workspace_bytes(int B, int Cin, int Cout, int K, int T, size_
 int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float *x, const float *w, const float *gy,
                    float *dw, float *dbias, float *dx, void *workspace, size_t ws_bytes, int compute_bf16,
                    void *stream);
+/* The gradients of sty_conv1d_fwd_shuffle from gy [B, Cout / shuffle, T * shuffle], the gradient of the shuffled output, as the
+ * training graph computes them: dw, dbias as above, dx (or NULL) by the input-gradient conv reading the shuffled gradient;
+ * accumulate != 0: dx += (the conv takes dx as its residual operand).  Workspace: sty_conv1d_bwd_workspace_bytes; compute_bf16 0 / 1. */
+int sty_conv1d_bwd_shuffle(int B, int Cin, int Cout, int K, int dil, int T, int shuffle, const float *x, const float *w,
+                           const float *gy, float *dw, float *dbias, float *dx, int accumulate, void *workspace, size_t ws_bytes,
+                           int compute_bf16, void *stream);
 /* The second stage of the two-stage reductions (bias gradient of a dense conv, weight / bias gradient of a depthwise conv)
  * alone, for unit tests: fixed-order float64 sums of nblk partials per output.  dw_form == 0: part [C][nblk] -> db[c] +=;
  * dw_form != 0: part [C][nblk][K+1] -> dw[c][k] += (k < K), db[c] += (k == K).                                      */

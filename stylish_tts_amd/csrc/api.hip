@@ -2918,6 +2918,24 @@ int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   }
   return launch_conv1d(a, S(stream));
 }
+// the generator's up-sampling conv: the output leaves pixel-shuffled, y [B][Cout / shuffle][T shuffle]
+int sty_conv1d_fwd_shuffle(int B, int Cin, int Cout, int K, int dil, int T, int shuffle, const float* x, const float* w,
+                           const float* bias, float* y, void* workspace, size_t ws_bytes, int compute_bf16, void* stream) {
+  size_t need = 0;
+  int rc = sty_conv1d_workspace_bytes(Cout, Cin, K, &need);
+  if (rc) return rc;
+  if (!x || !w || !y || !workspace || B <= 0 || T <= 0 || dil <= 0 || (K - 1) * dil > 128 || ws_bytes < need || shuffle < 1 ||
+      Cout % shuffle || !(compute_bf16 == 0 || compute_bf16 == 1)) {
+    set_error("sty_conv1d_fwd_shuffle: bad argument, halo > 128, Cout no multiple of shuffle, a compute mode other than 0 / 1 or "
+              "workspace too small");
+    return STY_EINVAL;
+  }
+  PackedConv pc = unit_conv_dims(Cin, Cout, K);
+  if ((rc = unit_conv_pack(pc, w, bias, bias != nullptr, workspace, unit_conv_plane(pc), S(stream)))) return rc;
+  ConvArgs a = unit_conv_args(pc, B, T, dil, x, y, compute_bf16);
+  a.shuffle = shuffle;
+  return launch_conv1d(a, S(stream));
+}
 // the same conv with the fused prologue / output stage the text encoder's convs use (fp32 tensors only)
 int sty_conv1d_fwd_ex(int B, int Cin, int Cout, int K, int dil, int T, const float* x, const float* w, const float* bias,
                       const float* in_mask, const float* residual, const float* out_mask, int out_mask_post, int relu, float* y,
@@ -2979,6 +2997,14 @@ int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int comput
     a.hpad = 1;
     a.Cin2d = Cin / 3;
   }
+  const int sf = (flags >> STY_ROUTE_SHUFFLE_SHIFT) & 15;  // the factor of a shuffled store / source
+  if ((flags & (STY_ROUTE_SHUFFLE_STORE | STY_ROUTE_SHUFFLE_SOURCE)) && sf < 2) {
+    set_error("sty_conv1d_route: a shuffled store / source needs its factor (2 .. 15) in bits %d .. %d of flags",
+              STY_ROUTE_SHUFFLE_SHIFT, STY_ROUTE_SHUFFLE_SHIFT + 3);
+    return STY_EINVAL;
+  }
+  if (flags & STY_ROUTE_SHUFFLE_STORE) a.shuffle = sf;
+  if (flags & STY_ROUTE_SHUFFLE_SOURCE) a.in_shuffle = sf;
   const ConvRoute r = conv1d_route(a);
   *kernel = r.refusal == CONV_OK ? (int)r.kernel : -1;
   return STY_OK;
@@ -2993,9 +3019,11 @@ int sty_conv1d_bwd_workspace_bytes(int B, int Cin, int Cout, int K, int T, size_
   *bytes += (size_t)B * (Cin + Cout) * T * sizeof(__bf16) + 512;                   // compute_bf16 = 2: the two operand twins
   return STY_OK;
 }
-int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float* x, const float* w, const float* gy,
-                   float* dw, float* dbias, float* dx, void* workspace, size_t ws_bytes, int compute_bf16,
-                   void* stream) {
+// shuffle > 1: gy is the gradient of the pixel-shuffled output, [B][Cout / shuffle][T shuffle]; accumulate: dx += (the input-
+// gradient conv takes dx as its residual, as conv_bwd does with a gradient buffer that already holds a term)
+static int unit_conv_bwd(int B, int Cin, int Cout, int K, int dil, int T, int shuffle, const float* x, const float* w,
+                         const float* gy, float* dw, float* dbias, float* dx, int accumulate, void* workspace, size_t ws_bytes,
+                         int compute_bf16, void* stream) {
   size_t need = 0;
   int rc = sty_conv1d_bwd_workspace_bytes(B, Cin, Cout, K, T, &need);
   if (rc) return rc;
@@ -3020,6 +3048,7 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   // (the clear takes the gradient and the flipped weights with it: everything in front of the partial planes)
   if ((rc = unit_conv_pack(pc, w, nullptr, dbias != nullptr, workspace, (size_t)(partial - wp), st))) return rc;
   ConvArgs a = unit_conv_args(pc, B, T, dil, x, nullptr, compute_bf16 != 0);
+  a.shuffle = shuffle;
   if (compute_bf16 == 3) {  // x is a bf16 TENSOR (two-byte storage, ConvArgs::xh): the weight gradient alone has a form for it here
     if (dx || T % 2) {
       set_error("sty_conv1d_bwd: a two-byte x (compute_bf16 = 3) is for dw / dbias only (dx == NULL), T even");
@@ -3055,9 +3084,26 @@ int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
     ConvArgs d = unit_conv_args(pdm, B, T, dil, gy, dx, a.bf16);
     d.pad = (K - 1) * dil - a.pad;  // the other half of an even halo
     d.x16 = a.g16;  // (compute_bf16 = 2) the input-gradient conv reads the gradient's operand twin as well
+    d.in_shuffle = shuffle > 1 ? shuffle : 0;
+    d.residual = accumulate ? dx : nullptr;
     rc = launch_conv1d(d, st);
   }
   return rc;
+}
+int sty_conv1d_bwd(int B, int Cin, int Cout, int K, int dil, int T, const float* x, const float* w, const float* gy,
+                   float* dw, float* dbias, float* dx, void* workspace, size_t ws_bytes, int compute_bf16,
+                   void* stream) {
+  return unit_conv_bwd(B, Cin, Cout, K, dil, T, 1, x, w, gy, dw, dbias, dx, 0, workspace, ws_bytes, compute_bf16, stream);
+}
+int sty_conv1d_bwd_shuffle(int B, int Cin, int Cout, int K, int dil, int T, int shuffle, const float* x, const float* w,
+                           const float* gy, float* dw, float* dbias, float* dx, int accumulate, void* workspace, size_t ws_bytes,
+                           int compute_bf16, void* stream) {
+  if (shuffle < 1 || Cout <= 0 || Cout % shuffle || !(compute_bf16 == 0 || compute_bf16 == 1) || (accumulate && !dx)) {
+    set_error("sty_conv1d_bwd_shuffle: Cout no multiple of shuffle, a compute mode other than 0 / 1, or accumulate without dx");
+    return STY_EINVAL;
+  }
+  return unit_conv_bwd(B, Cin, Cout, K, dil, T, shuffle, x, w, gy, dw, dbias, dx, accumulate, workspace, ws_bytes, compute_bf16,
+                       stream);
 }
 int sty_partial_sum(int dw_form, const float* part, int C, int K, int nblk, float* dw, float* db, void* stream) {
   if (!part || !db || C <= 0 || nblk <= 0 || (dw_form && (!dw || K <= 0))) {

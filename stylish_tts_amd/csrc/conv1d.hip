@@ -412,9 +412,11 @@ static int launch_tiled(const ConvArgs& a, hipStream_t st) {
   // Tile choice: the biggest output tile that still gives the chip >= ~2 workgroups per CU; the 256-channel stage
   // runs at T <= 800 frames, where 128x128 tiles would launch ~100 workgroups on 256 CUs.
   const long tiles128 = (long)cdiv(a.T, 128) * (a.w.CoutP / 128) * a.B;
-  // (round 5, bf16 mode: 256 -- what is left on this kernel there are a dozen launches of 300-600 tiles, the pixel-shuffle
-  //  up-convs and their input gradients, and they run faster on the larger tiles: c3 45.48 -> 45.19 ms, c5-bf16 4.42 -> 4.35;
-  //  fp32 (c2): neutral in the step, +0.5 ms in the serial step: stays at 512.  profiles/r05_ab_env.txt block 20)
+  // (round 5, bf16 mode: 256 -- measured when a dozen launches of 300-600 tiles were left on this kernel there, the pixel-shuffle
+  //  up-convs and their input gradients, which ran faster on the larger tiles: c3 45.48 -> 45.19 ms, c5-bf16 4.42 -> 4.35;
+  //  fp32 (c2): neutral in the step, +0.5 ms in the serial step: stays at 512.  profiles/r05_ab_env.txt block 20.  Those
+  //  launches have since left for convp16_up_kernel (convp16.hip); in the bf16 mode the figure now decides for the decoder's two
+  //  K = 7 convs, the K = 21 conv and the launches below the other families' tile thresholds, and was not re-tuned for them.)
   const long t128_min = a.bf16 ? 256 : 512;
   const long t64_min = a.bf16 ? 256 : 512;
   constexpr long t32_min = 512;

@@ -136,9 +136,14 @@ struct QConst {
   int va[NFRAG];     // vector offset of this wave's fragment loads (lane * 16, or out of range for fragments beyond K 2 CO32)
   int fa[NFRAG];     // byte offset of the fragment relative to QPos::abase
   int adst[NFRAG];   // LDS bf16x8 index of the fragment in an A buffer (-1: none)
+  int srcp;          // pixel-shuffle forms: ceil(2^16 / s), so that (i * srcp) >> 16 == i / s for i < 2^16 / s
 };
 
-template <int PRO, bool FLAT, int NFRAG, bool X16 = false>
+// SHUF (the up-sampling convs, K <= QU_MAXK): 0 plain; QS_STORE: the output leaves pixel-shuffled, y[b][co / s][t s + co % s]
+// (ConvArgs::shuffle); QS_SOURCE: source 0 is stored that way (ConvArgs::in_shuffle, the input-gradient conv of such a layer)
+constexpr int QS_STORE = 1, QS_SOURCE = 2;
+
+template <int PRO, bool FLAT, int NFRAG, bool X16 = false, int SHUF = 0>
 __device__ __forceinline__ void q_issue(const ConvArgs& a, const QPos& p, const QConst<NFRAG>& k, int lane, QSet<NFRAG>& R) {
   const int T = a.T;
   const __amdgpu_buffer_rsrc_t rs = p.rs;
@@ -148,7 +153,19 @@ __device__ __forceinline__ void q_issue(const ConvArgs& a, const QPos& p, const 
   // (a dead column group -- the third one of a K = 1 conv -- loads from outside the descriptor.  No branch around the
   // loads: every path through a chunk step must issue the SAME number of vector-memory instructions, or the compiler's
   // s_waitcnt for the other register set, whose loads are one step younger, degrades to vmcnt(0) -- see the step loop.)
-  if constexpr (X16) {
+  if constexpr (SHUF == QS_SOURCE) {
+    // channel c of the un-shuffled view, sample t, lives at row c / s, column t s + c % s of the [C / s][T s] slab: the lanes of
+    // a load are s floats apart, and the s channels of a group, which one wave loads back to back, fill the lines between
+    // them.  A position left or right of the row lands in a neighbouring row or outside the slab: dropped by R.in.
+    const int s = a.in_shuffle;
+    const int vs = k.vcol + (p.t0 - a.pad) * 4 * s;  // (vcol = 4 s jcol here)
+    const int c0 = p.chunk * 32 + k.rg8;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int c = c0 + r, cq = (c * k.srcp) >> 16, cr = c - cq * s;
+      R.bv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vs + (cq * T * s + cr) * 4, 0, 0));
+    }
+  } else if constexpr (X16) {
     // the operand twin: the same eight rows, two bytes each, already what the MFMA multiplies (prologue applied, rounded
     // by the tensor's producer); eight 16-bit loads, paired into four dwords -- no conversion, no prologue in q_commit
 #pragma unroll
@@ -324,11 +341,64 @@ __device__ __forceinline__ void q_drain(const ConvArgs& a, const float* ost, con
   }
 }
 
-template <int MTW, int PRO, int RELU, bool FLAT, bool X16 = false>
-__global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles) {
+// ---- producer: drain the output stage into a pixel-shuffled tensor (QS_STORE) ----
+// y[b][co / s][t s + co % s], bias and out_scale only (what convp16_eligible admits with a shuffle).  The s stage rows of an
+// output row R interleave into (tile columns) s CONSECUTIVE floats of it, so the tile leaves as 16-byte stores of contiguous
+// memory: a lane takes four consecutive floats of (R, segment of 256 floats) and gathers them from the stage.  (T % 4 == 0: a
+// row's share of a tile is a whole number of such quads and starts on a 16-byte boundary.)  A group of s rows that the 64-row
+// tile edge cuts is written by both tiles, each its own rows, one dword at a time.
+template <int MTW>
+__device__ __forceinline__ void q_drain_shuffle(const ConvArgs& a, const float* ost, const float* bias_lds, QTile tl, int pw,
+                                                int lane, int part, int nparts, int srcp) {
+  const int T = a.T, Cout = a.w.Cout, s = a.shuffle;
+  constexpr int ROWS = 64 * MTW;
+  const int co_lo = tl.cot * ROWS, co_hi = co_lo + ROWS < Cout ? co_lo + ROWS : Cout;
+  if (co_lo >= co_hi) return;
+  const int ncol = T - tl.t0 < Q_TT ? T - tl.t0 : Q_TT;
+  const int n = ncol * s;                 // floats of one output row that this tile holds
+  const int nseg = (n + 255) >> 8;        // (s <= 8: at most 4)
+  const int segrcp = nseg == 1 ? 65536 : nseg == 2 ? 32768 : nseg == 3 ? 21846 : 16384;
+  const int R0 = (co_lo * srcp) >> 16, R1 = ((co_hi - 1) * srcp) >> 16;
+  const int units = (R1 - R0 + 1) * nseg;
+  const __amdgpu_buffer_rsrc_t yrs =
+      __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)tl.b * Cout * T, 0, Cout * T * 4, 0x00020000);
+  const float sc = a.out_scale;
+#pragma unroll 1
+  for (int u = pw + Q_NP * part; u < units; u += Q_NP * nparts) {
+    const int ri = (u * segrcp) >> 16, seg = u - ri * nseg;
+    const int R = R0 + ri;
+    const int f = seg * 256 + 4 * lane;
+    if (f >= n) continue;
+    const bool full = R * s >= co_lo && R * s + s <= co_hi;
+    float v[4];
+    bool own[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int col = ((f + e) * srcp) >> 16;  // (f + e < 1 024)
+      const int co = R * s + (f + e) - col * s;
+      own[e] = co >= co_lo && co < co_hi;
+      const int cl = own[e] ? co : co_lo;      // (a row of the neighbouring tile: not read)
+      v[e] = (ost[(cl - co_lo) * Q_TT + col] + bias_lds[cl]) * sc;
+    }
+    const int off = (R * T * s + tl.t0 * s + f) * 4;
+    if (full) {
+      const float4 o4 = make_float4(v[0], v[1], v[2], v[3]);
+      __builtin_amdgcn_raw_buffer_store_b128(
+          __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o4), yrs, off, 0, 0);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (own[e]) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[e]), yrs, off + 4 * e, 0, 0);
+    }
+  }
+}
+
+// The kernel's body.  NFRAG: A fragments per producer wave and chunk, K 2 CO32 <= 12 NFRAG (2 for convp16_kernel, K <= 5 or a
+// 128-row tile at K <= 3; 4 for the K <= 11 up-sampling convs on 64-row tiles).  SHUF: see q_issue.
+template <int MTW, int PRO, int RELU, bool FLAT, bool X16, int NFRAG, int SHUF>
+__device__ __forceinline__ void q_body(const ConvArgs& a, int tiles_per_row, int ncot, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int CO32 = 2 * MTW;
-  constexpr int NFRAG = 2;  // A fragments per producer wave and chunk: K 2 CO32 <= 24 over 12 waves
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -378,8 +448,20 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
     kc.jcol = lane + 64 * q;
     kc.jlive = kc.jcol < LWt;
     kc.qlive = q < Q_TT / 64 || 64 * q < LWt;
-    kc.vcol = kc.qlive ? kc.jcol * (X16 ? 2 : 4) : 0x7FFFFF00;
+    kc.vcol = kc.qlive ? kc.jcol * (X16 ? 2 : 4) * (SHUF == QS_SOURCE ? a.in_shuffle : 1) : 0x7FFFFF00;
     kc.bdst = kc.jcol * Q_PITCH + 8 * rg;
+    kc.srcp = 0;
+    if constexpr (SHUF != 0) {  // (the one division of these forms, once per wave)
+      const int s_ = SHUF == QS_STORE ? a.shuffle : a.in_shuffle;
+      kc.srcp = (65536 + s_ - 1) / s_;
+    }
+#define STY_Q_DRAIN(part, nparts)                                                                     \
+  {                                                                                                   \
+    if constexpr (SHUF == QS_STORE)                                                                   \
+      q_drain_shuffle<MTW>(a, ost, bias_lds, prev_tl, pw, lane, part, nparts, kc.srcp);               \
+    else                                                                                              \
+      q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, part, nparts);                          \
+  }
 #pragma unroll
     for (int i = 0; i < NFRAG; ++i) {
       const int f = pw + Q_NP * i;
@@ -404,7 +486,7 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
     }
     int ncommit = 0;  // chunk step number of the next commit
 #define STY_Q_ISSUE(R)                                                          \
-  if (pi.n < nchunks) q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R);       \
+  if (pi.n < nchunks) q_issue<PRO, FLAT, NFRAG, X16, SHUF>(a, pi, kc, lane, R);       \
   q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);
 #define STY_Q_STEP(R) /* commit chunk `ncommit` from its register set, then request the chunk two ahead into the same set */ \
   {                                                                                                             \
@@ -414,13 +496,13 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
   }
     const bool steady = nsteps > 4;  // the unconditional loop below runs (and then so does this prologue: see there)
     if (steady) {
-      q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R0);
+      q_issue<PRO, FLAT, NFRAG, X16, SHUF>(a, pi, kc, lane, R0);
       q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);
-      q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R1);
+      q_issue<PRO, FLAT, NFRAG, X16, SHUF>(a, pi, kc, lane, R1);
       q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);
       q_commit<PRO, NFRAG, X16>(kc, R0, bring, aring, lane);
       ++ncommit;
-      q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R0);
+      q_issue<PRO, FLAT, NFRAG, X16, SHUF>(a, pi, kc, lane, R0);
       q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);
     } else {
       STY_Q_ISSUE(R0)
@@ -443,7 +525,7 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
     __syncthreads();
 #define STY_Q_BODY(R)                                                                                  \
   {                                                                                                    \
-    if (ti > 0 && c < ndr) q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, c, ndr); \
+    if (ti > 0 && c < ndr) STY_Q_DRAIN(c, ndr) \
     if (ncommit < nchunks) STY_Q_STEP(R)                                                               \
     STY_Q_NEXT                                                                                         \
   }
@@ -454,10 +536,10 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
     // issued ONE step earlier, a full memory round trip (1-2 us) per 0.3 us of MFMAs.
 #define STY_Q_FAST(R)                                                                                  \
   {                                                                                                    \
-    if (ti > 0 && c < ndr) q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, c, ndr); \
+    if (ti > 0 && c < ndr) STY_Q_DRAIN(c, ndr) \
     q_commit<PRO, NFRAG, X16>(kc, R, bring + (ncommit & 1) * bsz, aring + (ncommit & 1) * asz, lane);  \
     ++ncommit;                                                                                         \
-    q_issue<PRO, FLAT, NFRAG, X16>(a, pi, kc, lane, R);                                                     \
+    q_issue<PRO, FLAT, NFRAG, X16, SHUF>(a, pi, kc, lane, R);                                                     \
     q_pos_next<FLAT, X16>(a, pi, nch, tiles_per_row, ncot, rg, CO32, astep, tstride);                       \
     STY_Q_NEXT                                                                                         \
   }
@@ -476,7 +558,8 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
 #undef STY_Q_FAST
 #undef STY_Q_NEXT
 #undef STY_Q_BODY
-    q_drain<MTW, RELU>(a, ost, bias_lds, prev_tl, pw, lane, 0, 1);  // the last tile
+    STY_Q_DRAIN(0, 1)  // the last tile
+#undef STY_Q_DRAIN
 #undef STY_Q_STEP
 #undef STY_Q_ISSUE
     return;
@@ -553,6 +636,20 @@ __global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int t
     __syncthreads();
   }
 #undef STY_SGB
+}
+
+template <int MTW, int PRO, int RELU, bool FLAT, bool X16 = false>
+__global__ __launch_bounds__(Q_THREADS, 4) void convp16_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles) {
+  q_body<MTW, PRO, RELU, FLAT, X16, 2, 0>(a, tiles_per_row, ncot, ntiles);
+}
+
+// The generator's pixel-shuffle up-sampling convs (K = 11, generator.py:731-780) and their input-gradient convs: 64-row tiles,
+// so that a chunk's 2 K A fragments per 32-row block fit the ring twice (K = 11: 2 x 44 KB beside 22 KB of input tiles and
+// the 32 KB output stage), four fragment loads per producer wave and chunk.  fp32 source, no prologue, no activation.
+constexpr int QU_MAXK = 11;
+template <int SHUF>
+__global__ __launch_bounds__(Q_THREADS, 4) void convp16_up_kernel(ConvArgs a, int tiles_per_row, int ncot, int ntiles) {
+  q_body<1, PRO_NONE, 0, false, false, 4, SHUF>(a, tiles_per_row, ncot, ntiles);
 }
 
 // fp32 packed weights [K][CinP][CoutP] -> bf16 A fragments in the order q_issue_a reads them
@@ -764,8 +861,32 @@ static size_t q_lds_bytes(const ConvArgs& a) {
          (size_t)a.w.CoutP * 4;  // B ring, A ring, output stage, bias
 }
 
+// The up-sampling form (convp16_up_kernel): a K = 6 .. 11 conv whose output leaves pixel-shuffled, or whose source is stored that
+// way; exactly the operands of the generator's up-convs and their input-gradient convs (train.hip, conv_bwd): fp32 tensors, bias,
+// out_scale, and the gradient buffer as residual on the input-gradient side.  Everything else stays where it was.
+static bool q_up_form(const ConvArgs& a) { return a.shuffle != 1 || a.in_shuffle > 1; }
+static bool q_up_eligible(const ConvArgs& a) {
+  if (getenv("STY_NO_CONVP16_UP")) return false;  // (read per call) restores the tiled kernel for these launches
+  const bool store = a.shuffle != 1;
+  const int s = store ? a.shuffle : a.in_shuffle;
+  if (store && a.in_shuffle > 1) return false;
+  if (s < 2 || s > 8 || a.w.K <= Q_MAXK || a.w.K > QU_MAXK || a.dil != 1) return false;
+  if (a.w.CinP < 2 * CI_CHUNK || a.nsrc != 1 || a.flatW || a.Tin || a.ln_out || a.pro != PRO_NONE || a.act != ACT_NONE ||
+      a.mask || a.out_mask || a.x16 || a.y16 || a.y_split || a.up_g || a.xh || a.yh || a.rh || a.stat_part)
+    return false;
+  // shuffled store: whole groups of s couts, quads of the shuffled row (q_drain_shuffle), nothing added to it
+  if (store && (a.w.Cout % s || a.T % 4 || a.residual)) return false;
+  if (!store && a.w.Cin % s) return false;
+  if ((long)a.w.Cin * a.T >= (1l << 28) || (long)a.w.Cout * a.T >= (1l << 28)) return false;  // 31-bit byte offsets in a slab
+  if (q_lds_bytes(a) > 160 * 1024) return false;
+  const char* mt = getenv("STY_CONVP16_UP_MIN_TILES");  // read per call: the unit tests lower it for small shapes
+  const int min_tiles = mt ? atoi(mt) : 48;              // (convp16_kernel's figure; the model's launches have 300-1 000 tiles)
+  return (long)cdiv(a.T, Q_TT) * a.B * cdiv(a.w.CoutP, 64) >= min_tiles;
+}
+
 bool convp16_eligible(const ConvArgs& a) {
   if (!a.bf16 || getenv("STY_NO_CONVP16")) return false;  // (read per call: the A/B parity test toggles it)
+  if (q_up_form(a)) return q_up_eligible(a);
   if (a.w.CinP < 2 * CI_CHUNK || a.nsrc != 1 || a.in_shuffle > 1 || a.shuffle != 1 || a.ln_out || a.Tin ||
       !(a.act == ACT_NONE || a.act == ACT_RELU || (a.act == ACT_LRELU01 && a.pro == PRO_NONE && a.T % 4 == 0)) ||
       a.w.K > Q_MAXK)
@@ -836,10 +957,42 @@ static int launch_q_pro(const ConvArgs& a, hipStream_t st) {
 
 int convp16_frags(const ConvArgs& a, hipStream_t st, const void** out) { return q_frags(a, st, out); }  // (convk1.hip)
 
+template <int SHUF>
+static int launch_q_up(const ConvArgs& a, hipStream_t st) {
+  const size_t lds = q_lds_bytes(a);
+  static bool raised = false;
+  if (!raised) {
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&convp16_up_kernel<SHUF>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024));
+    raised = true;
+  }
+  const int tiles_per_row = cdiv(a.T, Q_TT), ncot = cdiv(a.w.CoutP, 64);
+  const int ntiles = tiles_per_row * a.B * ncot;
+  const int cus = num_cus();
+  const int grid = ntiles < cus ? ntiles : cus;
+  const double outs = (double)a.B * a.w.Cout * a.T;
+  const double flops = 2.0 * a.w.Cin * a.w.K * outs;
+  const double bytes = 4.0 * ((double)a.B * a.w.Cin * a.T + outs * (a.residual ? 2.0 : 1.0) + (double)a.w.Cout * a.w.Cin * a.w.K);
+  char detail[40];
+  snprintf(detail, sizeof(detail), "ci%d co%d k%d T%d W%d", a.w.Cin, a.w.Cout, a.w.K, a.T, a.flatW);
+  ProfScope prof(SHUF == QS_STORE ? "convp16_up_kernel<store>" : "convp16_up_kernel<source>", flops, bytes, st, detail);
+  hipLaunchKernelGGL((convp16_up_kernel<SHUF>), dim3(grid), dim3(Q_THREADS), lds, st, a, tiles_per_row, ncot, ntiles);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
 int launch_convp16(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
   int rc = q_frags(a0, st, &a.w.wf);
   if (rc) return rc;
+  if (q_up_form(a)) {
+    static_assert(4 * QU_MAXK <= 4 * Q_NP, "2 K fragments per 32-row block, two blocks, over Q_NP producer waves x NFRAG = 4");
+    if (a.w.K > QU_MAXK) {
+      set_error("convp16: K = %d up-sampling conv does not fit the fragment ring", a.w.K);
+      return STY_EINVAL;
+    }
+    return a.shuffle != 1 ? launch_q_up<QS_STORE>(a, st) : launch_q_up<QS_SOURCE>(a, st);
+  }
   if (a.x16 && a.act != ACT_LRELU01) {
     // source 0 comes as its bf16 operand twin: the prologue (LeakyReLU / the [B][T] mask) is already in it
     a.pro = PRO_NONE;

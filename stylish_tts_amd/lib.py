@@ -135,6 +135,8 @@ SYMBOLS = {
     "sty_conv1d_workspace_bytes": (C.c_int, [_I, _I, _I, _SZP]),
     "sty_conv1d_fwd": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
     "sty_conv1d_fwd_ex": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, C.c_size_t, _I, _P]),
+    "sty_conv1d_fwd_shuffle": (C.c_int, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
+    "sty_conv1d_bwd_shuffle": (C.c_int, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, C.c_size_t, _I, _P]),
     "sty_conv1d_route": (C.c_int, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     "sty_conv1d_bwd_workspace_bytes": (C.c_int, [_I, _I, _I, _I, _I, _SZP]),
     "sty_conv1d_bwd": (C.c_int, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _P]),
