@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstylish_hip.so")
-SOURCES = ["api.hip", "plan_wavlm.hip", "conv1d.hip", "convnext.hip", "norms.hip", "attn.hip", "source.hip", "misc.hip", "conv2d.hip",
+SOURCES = ["host_state.hip", "builder.hip", "plan_speech.hip", "plan_predictors.hip", "plan_wavlm.hip", "entry_train.hip", "entry_unit.hip","conv1d.hip", "convnext.hip", "norms.hip", "attn.hip", "source.hip", "misc.hip", "conv2d.hip",
            "frontend.hip", "bwd.hip", "wgrad.hip", "attn_bwd.hip", "train.hip", "optim.hip", "convnext_bwd.hip", "predictors.hip", "conv32p.hip", "convp16.hip", "wgradb.hip", "disc.hip", "cfdisc.hip", "convk1.hip", "convsc.hip", "attn16.hip", "convq.hip", "comm.hip", "convnext16.hip", "voicepack.hip", "align.hip", "ctc.hip", "weights.hip", "rmvpe.hip", "val_loss.hip", "wavlm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-file additions.  convnext16.hip (the bf16-mode instantiations of csrc/convnext_kernel.h, which says what was measured): the SLP

@@ -207,7 +207,7 @@ int launch_log_softmax_rows(const float* x, int B, int V, int T, float* out, hip
 int launch_fill_f32(float* x, int n, float v, hipStream_t st);
 
 // RMVPE = E2E0(n_blocks, 1, (2, 2), 5, inter_layers, 1, en_out_channels) in eval mode (train/dataprep/rmvpe/model.py:49-86,
-// deepunet.py, seq.py); rmvpe.hip has the kernels, api.hip the plan
+// deepunet.py, seq.py); rmvpe.hip has the kernels, plan_predictors.hip the plan
 constexpr int RMVPE_MELS = 128, RMVPE_CLASSES = 360, RMVPE_HOP = 200, RMVPE_LEVELS = 5;
 constexpr float RMVPE_LOG_CLAMP = -11.5129254649702f;  // log(1e-5)
 struct RmvpePackJob {  // one conv whose BatchNorm (if any) is folded while it is packed (rmvpe_pack_conv_kernel)

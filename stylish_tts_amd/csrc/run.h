@@ -1,6 +1,7 @@
 // The inference side as the entry-point files share it: Run (one call's workspace, stream and status, with the block and
 // plan methods), the readiness checks in front of an entry, and the per-model forward functions.  Bodies longer than a few
-// lines live in one .hip each: plan_wavlm.hip has the WavLM graph, api.hip everything else.
+// lines live in one .hip each: plan_speech.hip has the speech predictor and the vocoder, plan_predictors.hip the style
+// encoders, the second-stage predictors, the aligner and RMVPE, plan_wavlm.hip the WavLM graph, builder.hip the readiness checks.
 #pragma once
 #include <string.h>
 
@@ -89,7 +90,7 @@ struct Run {
     }
   }
 
-  // ---- blocks and plans (api.hip) ----
+  // ---- blocks and plans (plan_speech.hip) ----
   void convnext(const ConvNeXt& c, const float* x, float* y, int T);
   void resblock(const ResBlock32& r, float* x, int T);
   void conformer(const Conformer& c, const float* x, float* out, int C, int T);
@@ -99,7 +100,7 @@ struct Run {
   void decoder(const float* asr, const float* pitch, const float* energy, const float* voiced, int T, float* out);
 };
 
-// ---- in front of an entry point ----
+// ---- in front of an entry point (builder.hip) ----
 // the model exists, is of the kind (either kind) and finalized
 int model_ready(const sty_model* m, const char* kind_a, const char* kind_b = nullptr);
 // ... and the entry's own argument check passed (bad_args: its outcome, msg: what sty_last_error then says), in that order
@@ -124,8 +125,11 @@ inline sty_vocoder_io vocoder_io_dims(int B, int T) {
 }
 
 // ---- the forward functions ----
-int run_style_fc(Run& r, const float* style);                                // api.hip
-void style_run(Run& r, const float* mel, int T, float* style);
+int run_style_fc(Run& r, const float* style);  // plan_speech.hip
+// the vocoder block a state_dict prefix names, *k = 0: a ConvNeXt, 1: a ResBlock32 (no_resblock: the message, with one %s for the prefix)
+int find_block(sty_model* m, const char* kind, const char* prefix, int C, int* k, const void** blk,
+               const char* no_resblock = "no such resblock (32 channels): %s");
+void style_run(Run& r, const float* mel, int T, float* style);  // plan_predictors.hip
 void duration_forward(Run& r, const int64_t* texts, const int64_t* lengths, int L, float* out);
 void pitch_energy_forward(Run& r, const int64_t* texts, const int64_t* lengths, const float* alignment, const float* style,
                           int L, int T, float* f0, float* energy);

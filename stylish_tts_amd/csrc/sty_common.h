@@ -34,7 +34,7 @@ inline const void* kernel_handle(R (*f)(A...)) {  // a kernel's name decays to t
     (kernelName)<<<(numBlocks), (numThreads), (memPerBlock), (streamId)>>>(__VA_ARGS__);           \
   } while (0)
 
-// in-situ timing of kernel families (api.hip); no-ops unless sty_prof_enable(1)
+// in-situ timing of kernel families (host_state.hip); no-ops unless sty_prof_enable(1)
 struct ProfScope {
   int slot = -1;
   hipStream_t st;

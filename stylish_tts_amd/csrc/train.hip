@@ -1,7 +1,7 @@
 // Training-mode graphs (SpeechPredictor: text encoder -> expand -> decoder -> vocoder; MelStyleEncoder; vocoder alone;
 // the predictors and the aligner) recorded on the tape of tape.h.
 //
-// The forward here is the UNFUSED-epilogue form of the inference plan in api.hip: convs keep their fused input
+// The forward here is the UNFUSED-epilogue form of the inference plan in plan_speech.hip: convs keep their fused input
 // prologues (AdaIN+Snake, GRN scale, ...) but activations / LayerNorms that the backward needs the inputs of are
 // separate ops, nothing is computed in place, and no workspace is recycled, so that every backward step finds its
 // operands.  Each forward op pushes one closure; backward runs them in reverse (Tape::run_tape).  This file holds the ops
@@ -780,7 +780,7 @@ struct Trainer : Tape {
   }
 
   // AdaptiveGeneratorBlock (ada_norm.py:109-120).  Convs that run on the persistent 32-channel kernel leave the
-  // statistics of their output behind for the next AdaIN (see Run::resblock in api.hip).
+  // statistics of their output behind for the next AdaIN (see Run::resblock in plan_speech.hip).
   // A conv over THREE concatenated 32-channel sources with a 32-channel output (phase_input_conv, generator.py:760-768: k = 21
   // over [trunk | logamp prior | phase prior]) on the persistent kernel, bf16 mode: three accumulating launches forward -- one per
   // source, each with the source's 32 x 32 block of every tap (ConvArgs::w_row / w_tap), the second and third through the

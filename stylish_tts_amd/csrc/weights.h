@@ -1,5 +1,5 @@
 // The weight side of a model (weights.hip): bound parameters -> prepared (packed) weights before a forward, packed gradients ->
-// the caller's gradient buffers after a backward.  The Builder (api.hip) describes the work as a list of PackJob; five device
+// the caller's gradient buffers after a backward.  The Builder (builder.hip) describes the work as a list of PackJob; five device
 // tables, one typed record each, let every step cover all layers of a model in one launch.  See DESIGN.md section 4.
 #pragma once
 #include <vector>

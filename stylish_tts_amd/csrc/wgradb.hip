@@ -28,7 +28,6 @@ constexpr int WB_MODE = 1;    // wgradb_kernel, wgradb16_kernel
 constexpr int WP32_MODE = 2;  // wgradp32_kernel: 144 (1) / 141 (2) / 142 us (0) alone on the chip; 68 / 65 / 119 MB fetched on the block workload
 constexpr int CNX_MODE = 2;   // wgrad_cnx_kernel: 143 (1) / 128 (2) / 132 us (0); 134 / 101 / 144 MB
 constexpr int WB_PITCH = 136;  // bf16 elements between LDS rows
-constexpr int WB_TW_MASKED = 64;
 constexpr int WB_OOB = 0x7fffff00;
 
 // (bit-casting the builtin's result to an ext_vector_type and indexing it made hipcc emit ONE buffer_load_dword and

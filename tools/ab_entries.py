@@ -9,7 +9,9 @@ every (entry, arguments) whose record differs and exits non-zero if there is one
 
 Host half: the model-free sizing and table entries, sty_conv1d_route over all flag bits, sty_model_create with good and bad
 kinds, and every model-bound entry on a created but un-finalized model of every kind (and on a null model).
-Device half: workspace bytes of the model-bound sizing entries, inference and training, default and deterministic mode.
+Device half: workspace bytes of the model-bound sizing entries, inference and training, default and deterministic mode; every
+training entry in front of the same finalized models (its own kind and the others, training enabled or not) with null and zero
+arguments, and each *_fwd_train with too small a workspace in deterministic mode.
 """
 import argparse
 import ctypes as C
@@ -138,8 +140,74 @@ def host_half(L, lib):
     return r.rows
 
 
+TRAIN_ENTRY = re.compile(r"^sty_\w+(_train_workspace_bytes|_fwd_train|_prepare_train|_bwd|_bwd_pe)$|^sty_block_fwd_bwd$")
+
+
+def train_checks(L, r, tag, handle, buf):
+    """Every training entry in front of a finalized model, of its kind or of another, with training enabled or not: null
+    arguments, then zero dimensions over non-null pointers.  Nothing may reach the device with made-up buffers, so the stream
+    stays null, a zeroed io struct stands for an io, and a *_bwd gets null gradients only.  A *_prepare_train of the model's
+    kind has no argument to refuse: with training enabled it runs for real."""
+    for name in sorted(n for n in L.SYMBOLS if TRAIN_ENTRY.match(n) and MODEL_BOUND.match(n)):
+        argtypes = L.SYMBOLS[name][1]
+        io = (C.c_char * 1024)()
+        for nulls in (True, False):
+            if not nulls and (name.endswith(("_bwd", "_bwd_pe", "_prepare_train"))):
+                continue
+            args, shown = [handle], []
+            for i, t in enumerate(argtypes[1:], 1):
+                stream = t is C.c_void_p and i == len(argtypes) - 1 and not name.endswith("_workspace_bytes")
+                if t is C.c_int:
+                    v = 40 if nulls else 0
+                elif t in (C.c_size_t, C.c_uint, C.c_uint64):
+                    v = 4096
+                elif t is C.c_float:
+                    v = 0.25
+                elif nulls or stream:
+                    v = None
+                elif t is C.c_char_p:
+                    v = b"generator.amp_prior_block"
+                elif t is C.c_void_p:
+                    v = buf
+                else:  # an io struct, all null, or the size_t a sizing entry writes
+                    v = C.cast(io, t)
+                args.append(v)
+                shown.append(v if t in (C.c_int, C.c_float) else ("NULL" if v is None else "p"))
+            r.call(name, tag + shown, args)
+
+
+def small_workspace(L, r, tag, name, handle, ints, buf):
+    """a *_fwd_train with every buffer in place and 256 bytes of workspace, in deterministic mode: refused with the bytes the
+    mode needs before anything is launched"""
+    args, ints = [handle], list(ints)
+    argtypes = L.SYMBOLS[name][1]
+    keep = []
+    for i, t in enumerate(argtypes[1:], 1):
+        if t is C.c_int:
+            args.append(ints.pop(0))
+        elif t is C.c_size_t:
+            args.append(256)
+        elif t is C.c_uint:
+            args.append(0)
+        elif t is C.c_float:
+            args.append(0.1)
+        elif t is C.c_void_p:
+            args.append(None if i == len(argtypes) - 1 else buf)
+        else:  # the io struct: its dimensions, and every input and output on the buffer (taps and the style stream stay null)
+            io = t._type_()
+            for f, ft in io._fields_:
+                if f in "BLT":
+                    setattr(io, f, ints.pop(0))
+                elif ft is C.c_void_p and not f.startswith("tap_") and f != "style_stream":
+                    setattr(io, f, buf)
+            keep.append(io)
+            args.append(C.byref(io))
+    r.call(name, tag + ["256 bytes"], args)
+
+
 def device_half(L, lib):
-    """workspace bytes of the model-bound sizing entries on finalized models with synthetic weights"""
+    """workspace bytes of the model-bound sizing entries on finalized models with synthetic weights, and the checks in front of
+    the training entries on the same models"""
     import torch
     import stylish_tts_amd as S
     from stylish_tts_amd import manifest as M
@@ -159,6 +227,8 @@ def device_half(L, lib):
         return m
 
     n_ = C.c_size_t(0)
+    zeros = torch.zeros(1 << 20, device=dev)
+    buf = zeros.data_ptr()
     for det in (0, 1):
         L.set_deterministic(det)
         for train in (False, True):
@@ -178,6 +248,11 @@ def device_half(L, lib):
                         v = [kind, prefix, B, Cc, 75 * T]
                         r.call("sty_block_train_workspace_bytes", ["SpeechPredictor", "det" if det else "default", kind.decode(), B, Cc, 75 * T],
                                [m._handle] + v + [C.byref(n_)], lambda: n_.value)
+                tag = [cls.__name__, "det" if det else "default", "train" if train else "inference"]
+                if det and train:
+                    for stem, sig in entries:
+                        small_workspace(L, r, tag, stem + "_fwd_train", m._handle, [dict(B=3, L=24, T=80)[c] for c in sig], buf)
+                train_checks(L, r, tag, m._handle, buf)
                 del m
             torch.manual_seed(1234)
             a = TrainableTextAligner(80, 178, hidden_dim=80).to(dev)
@@ -187,6 +262,10 @@ def device_half(L, lib):
             for B, T, _ in shapes:
                 r.call("sty_aligner" + sfx, ["TrainableTextAligner", "det" if det else "default", B, T], [a._handle, B, T, C.byref(n_)],
                        lambda: n_.value)
+            tag = ["TrainableTextAligner", "det" if det else "default", "train" if train else "inference"]
+            if det and train:
+                small_workspace(L, r, tag, "sty_aligner_fwd_train", a._handle, [3, 80], buf)
+            train_checks(L, r, tag, a._handle, buf)
             del a
     L.set_deterministic(0)
     return r.rows
