@@ -342,6 +342,16 @@ typedef struct {
                           the speech predictor's Decoder builds its blocks with the default 0 (decoder.py:19-35).    */
 } sty_train_opts;
 int sty_model_set_train_opts(sty_model *m, const sty_train_opts *opts);
+/* fp32 split mode (bf16x3) of the inference entries, kind "speech_predictor" only (every other kind: STY_EINVAL, the kind named
+ * in the error text): the 32 -> 32 channel convs the persistent kernel takes (the vocoder's AdaptiveGeneratorBlocks and prior /
+ * output convs) split each fp32 operand into three bf16 pieces and multiply six pairs of pieces on the bf16 matrix cores, with
+ * fp32 accumulation -- fp32 accuracy (the parity gates of the fp32 mode hold) on the bf16 matrix cores.  Every other conv keeps its
+ * fp32 route.  Exclusive with the bf16 compute mode, never silently: refused (STY_EINVAL) while compute_bf16 is set, and
+ * sty_model_set_train_opts(compute_bf16 = 1) is refused while the split is on.  Switching it on un-finalizes the model when the
+ * weights' fragment triples still have to be packed (call sty_model_finalize again, as after sty_model_enable_training);
+ * switching it off again needs nothing.  Read by sty_vocoder_fwd, sty_speech_fwd and sty_resblock_fwd; the training graph
+ * (*_fwd_train, *_bwd) does not read it.                                                                                  */
+int sty_model_set_fp32_split(sty_model *m, int on);
 
 /* Data-parallel overlap: a callback the backward entry points invoke ON THE CALLING THREAD as soon as
  * a segment of the bound parameter gradients is final on `stream` (every later kernel of the same backward leaves it
@@ -438,6 +448,14 @@ int sty_pitch_style_fwd_train(sty_model *m, int B, int T, const float *mel, cons
  * conv / Linear of the path runs on; for unit parity tests and kernel tuning.  x [B,Cin,T], w [Cout,Cin,K],
  * bias [Cout] or NULL -> y [B,Cout,T].  (K-1)*dil <= 128.                                                     */
 int sty_conv1d_workspace_bytes(int Cout, int Cin, int K, size_t *bytes);
+/* compute_bf16 of sty_conv1d_fwd: 0 = fp32 operands; 1 = bf16 operands; 2 = bf16 operand twins (the input's twin made here, the
+ * output's written behind the workspace); 3 is taken by sty_conv1d_bwd (x is a two-byte tensor) and means bf16 operands here;
+ * 4 = the fp32 split mode (bf16x3: every fp32 operand as three bf16 pieces, six products per k-step on the bf16 matrix cores,
+ * fp32 accuracy) where the conv is eligible for it (a 32 -> 32 channel conv on the persistent kernel) and the fp32 route
+ * elsewhere; the fragment triples are packed into the workspace, which sty_conv1d_workspace_bytes sizes for them.
+ * sty_conv1d_route with 4 answers STY_CONV_32P for an eligible shape and what 0 answers for every other.  sty_conv1d_fwd and
+ * sty_conv1d_route alone know mode 4: sty_conv1d_fwd_ex and sty_conv1d_fwd_shuffle take 0 or 1 and refuse everything else,
+ * sty_conv1d_bwd treats every other nonzero value as bf16.                                                                  */
 int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float *x, const float *w, const float *bias,
                    float *y, void *workspace, size_t ws_bytes, int compute_bf16, void *stream);
 /* The same conv with the fused prologue and output stage of the text encoder's convs: x * in_mask[b,t] in front (in_mask [B,T] or

@@ -54,9 +54,15 @@ struct Builder {
     float* bp = m->ab.take<float>(pc.CoutP);
     pc.wp = wp;
     pc.bias = (bias || bias_override_src) ? bp : nullptr;
+    float* w3 = nullptr;
+    if (m->fp32_split && pc.CinP == CI_CHUNK && pc.CoutP == 32 && !glu) {  // the split mode's fragment triples (conv32p.hip)
+      w3 = m->ab.take<float>(split3_bytes(pc.K) / sizeof(float));
+      pc.w3 = w3;
+    }
     if (!dry)
       m->jobs.push_back(PackJob::conv(glu ? PK_CONV_GLU : (wn ? PK_CONV_WN : PK_CONV), pc, wn ? nullptr : w->p,
                                       g ? g->p : nullptr, wn ? w->p : nullptr, b, wp, bp));
+    if (!dry && w3) m->jobs.push_back(PackJob::split3(pc, w3));
     if (m->train_enabled || m->kind == "wavlm") {  // (wavlm: frozen, but its input-gradient chain is built)
       if (glu) {  // the training graph runs GLU as a separate op: it needs the plain channel order
         PackedConv pl = pc;
@@ -870,6 +876,7 @@ int sty_model_finalize(sty_model* m) {
   }
   m->finalized = true;
   m->prepared = false;
+  m->split_packed = m->fp32_split != 0;
   return STY_OK;
 }
 
@@ -904,7 +911,29 @@ int sty_model_set_train_opts(sty_model* m, const sty_train_opts* o) {
     set_error("sty_model_set_train_opts(compute_bf16): model kind 'text_aligner_train' runs fp32 operands");
     return STY_EINVAL;
   }
+  if (o->compute_bf16 && m->fp32_split) {
+    set_error("sty_model_set_train_opts(compute_bf16): the model runs the fp32 split mode (sty_model_set_fp32_split); switch it off first");
+    return STY_EINVAL;
+  }
   m->topts = *o;
+  return STY_OK;
+}
+
+int sty_model_set_fp32_split(sty_model* m, int on) {
+  if (!m) {
+    set_error("sty_model_set_fp32_split: null model");
+    return STY_EINVAL;
+  }
+  if (m->kind != "speech_predictor") {
+    set_error("sty_model_set_fp32_split: model kind '%s' has no split mode (speech_predictor alone)", m->kind.c_str());
+    return STY_EINVAL;
+  }
+  if (on && m->topts.compute_bf16) {
+    set_error("sty_model_set_fp32_split: the model runs the bf16 compute mode (sty_model_set_train_opts); switch it off first");
+    return STY_EINVAL;
+  }
+  m->fp32_split = on ? 1 : 0;
+  if (on && !m->split_packed) m->finalized = false;  // the fragment triples are laid out and packed by the next finalize
   return STY_OK;
 }
 

@@ -454,12 +454,13 @@ static int launch_tiled(const ConvArgs& a, hipStream_t st) {
 // family reads its switches and thresholds in its predicate).  conv1d_route is their only caller and the only statement of the order.
 bool stem2d_eligible(const ConvArgs& a);   // conv2d.hip
 bool conv32p_eligible(const ConvArgs& a);  // conv32p.hip
+bool conv32p_split_eligible(const ConvArgs& a);  // ... and whether a conv it takes runs in the split (bf16x3) form
 bool convsc_eligible(const ConvArgs& a);   // convsc.hip
 bool convk1_eligible(const ConvArgs& a);   // convk1.hip
 bool convp16_eligible(const ConvArgs& a);  // convp16.hip
 bool convq_eligible(const ConvArgs& a);    // convq.hip
 int launch_stem2d(const ConvArgs& a, hipStream_t st);
-int launch_conv32p(const ConvArgs& a, hipStream_t st);
+int launch_conv32p(const ConvArgs& a, bool split, hipStream_t st);
 int launch_convsc(const ConvArgs& a, hipStream_t st);
 int launch_convk1(const ConvArgs& a, hipStream_t st);
 int launch_convq(const ConvArgs& a, hipStream_t st);
@@ -469,8 +470,10 @@ ConvRoute conv1d_route(const ConvArgs& a) {
   ConvRoute r;
   if (stem2d_eligible(a))
     r.kernel = CONV_STEM2D;
-  else if (conv32p_eligible(a))
+  else if (conv32p_eligible(a)) {
     r.kernel = CONV_32P;
+    r.split = conv32p_split_eligible(a);
+  }
   else if (a.xh || a.yh || a.rh)  // (the persistent 32-channel kernel alone has the two-byte stages and the statistics)
     r.refusal = CONV_NO_TWO_BYTE;
   else if (a.stat_part)
@@ -524,7 +527,7 @@ int launch_conv1d(const ConvArgs& a, hipStream_t st) {
   int rc = STY_OK;
   switch (r.kernel) {
     case CONV_STEM2D: rc = launch_stem2d(a, st); break;
-    case CONV_32P: rc = launch_conv32p(a, st); break;
+    case CONV_32P: rc = launch_conv32p(a, r.split, st); break;
     case CONV_SC: rc = launch_convsc(a, st); break;
     case CONV_K1: rc = launch_convk1(a, st); break;
     case CONV_Q: rc = launch_convq(a, st); break;

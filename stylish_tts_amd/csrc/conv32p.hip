@@ -558,7 +558,256 @@ __global__ __launch_bounds__(64 * (4 + p_npw<BF>()), 1) void conv32p_kernel(Conv
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Split mode (bf16x3): fp32 accuracy on the bf16 matrix pipe.  gfx950 has no xf32 and v_mfma_f32_32x32x2_f32 runs at the vector
+// rate (64 cycles for k = 2); v_mfma_f32_32x32x16_bf16 takes 32 cycles for k = 16.  Every fp32 operand is split into three bf16
+// pieces h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) (h + m + l == x exactly) and a k-step multiplies six pairs of pieces
+// (weight piece, input piece): (h,h) (h,m) (m,h) (h,l) (m,m) (l,h) -- every term down to 2^-16 relative is kept, the three terms
+// of order 2^-24 are dropped: 6 x 32 = 192 matrix cycles per 16 channels where the fp32 mode spends 8 x 64 = 512.
+//
+// Same roles as conv32p_kernel, same 256-column tile (so p_res_load / p_drain, the output stages and the stat_part layout are
+// shared unchanged), eight waves: four consumers, four producers of eight rows each (the fp32 mode's shape: 256 registers a
+// wave, which the consumers' two operand sets and four accumulators and the producers' register-held tile both need).
+//   LDS   three planes [LW][32 ch] bf16 at the bf16 mode's 80-byte pitch: 3 x LW x 80 B = 73 440 B at K = 11, dilation 5
+//         (LW = 306), 91 920 B at the largest halo the kernel takes (LW = 383); two output stages [32][256] fp32 = 65 536 B.
+//         138 976 B at K = 11 / dilation 5, 157 456 B at most, of 163 840.  TWO sets of planes do not fit beside the output
+//         stages (2 x 73 440 + 65 536 = 212 416), so the input tile is single-buffered in LDS and double-buffered in REGISTERS:
+//         a tile is 32 x LW <= 12 256 values = 48 per producer lane.  While the consumers work on tile i the producers load
+//         tile i + 1, drain tile i - 1, run the prologue and the split and hold the 3 x 48 bf16 pieces (72 registers); behind
+//         the barrier that ends the consumers' tile they write them (18 ds_write_b128 per lane, ~600 cycles for the CU against
+//         ~8 400 matrix cycles per tile at K = 11) and a second barrier releases the consumers.  Two barriers per tile.
+//   weights  bf16 A-fragment triples [K][2 k-steps][3 pieces][64 lanes] x 16 B = K x 6 KB in global memory (66 KB at K = 11,
+//         126 KB at K = 21: not in LDS), made once by launch_pack_split3; the consumers stream them one k-step ahead through
+//         a buffer descriptor, three 16-byte loads per step, L2 hits after the first tile.
+//   consumer  per k-step (16 channels) and wave: 3 A loads, 6 ds_read_b128 (three planes x two 32-column fragments), 12 MFMAs;
+//         the operands of step s + 1 are requested while step s issues, one LDS read per two MFMAs.  The (h,h) products go into
+//         the accumulators that start at the bias, the five correction products into a second pair that is added once at the
+//         end: the main sum then rounds as often as the bf16 mode's, K x 2 times, and the corrections (<= 2^-8 of it) lose nothing.
+//   prologue  the fp32 mode's pro_apply (accurate sine for Snake): the hardware sine belongs to the bf16 mode's definition.
+// PRO_NONE and PRO_AFFINE_SNAKE, fp32 tensors, dense [K][32][32] weights only (conv32p_split_eligible).
+constexpr int S_NPW = 4, S_RPW = 8;  // producer waves, rows of each
+
+// the raw values of tile `tl`: lane -> column lane + 64 q of the wave's eight rows (requests only; nothing waits here)
+__device__ __forceinline__ void s_tile_load(const ConvArgs& a, PTile tl, int LW, int pw, int lane, float (&vv)[P_MAXQ][S_RPW]) {
+  const int T = a.T, Cin = a.w.Cin;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.x[0] + (size_t)tl.b * Cin * T), 0, Cin * T * 4, 0x00020000);
+  const int voff = (tl.t0 - a.pad + lane) * 4;
+#pragma unroll
+  for (int q = 0; q < P_MAXQ; ++q) {
+    if (!(q < P_TT / 64 || 64 * q < LW)) continue;
+#pragma unroll
+    for (int r = 0; r < S_RPW; ++r) {
+      // The whole byte offset in the VGPR, opaque to the compiler: inside the tile loop it otherwise keeps the CURRENT tile's
+      // offset in the register and reaches the next tile through the instruction's immediate (+1024 + 256 q), and where the
+      // next tile starts a new batch row the register is then negative for a column that is inside the row (columns 0-7 of
+      // such a tile came out wrong).  The unit shapes with more tiles than workgroups in tests/test_fp32_split_gpu.py
+      // (96 and 160 batch rows of five tiles) are the guard for this.
+      int off = voff + 256 * q + (S_RPW * pw + r) * T * 4;
+      asm("" : "+v"(off));
+      vv[q][r] = buf_load(rs, off);
+    }
+  }
+}
+// prologue, zero padding (after it), and the three-way split: pk[p][q] = piece p of the wave's eight rows of column lane + 64 q
+template <int PRO>
+__device__ __forceinline__ void s_tile_split(const ConvArgs& a, PTile tl, int LW, int pw, int lane, const float (&vv)[P_MAXQ][S_RPW],
+                                             uint4 (&pk)[3][P_MAXQ]) {
+  const int T = a.T, Cin = a.w.Cin;
+  float pa[S_RPW], ps[S_RPW], al[S_RPW], ral[S_RPW];
+#pragma unroll
+  for (int r = 0; r < S_RPW; ++r)
+    p_row_params<PRO>(a, tl.b, S_RPW * pw + r, S_RPW * pw + r < Cin, pa[r], ps[r], al[r], ral[r]);
+#pragma unroll
+  for (int q = 0; q < P_MAXQ; ++q) {
+    if (!(q < P_TT / 64 || 64 * q < LW)) continue;
+    const int t = tl.t0 - a.pad + lane + 64 * q;
+    const bool tin = t >= 0 && t < T;
+    unsigned w[3][S_RPW / 2];
+#pragma unroll
+    for (int r = 0; r < S_RPW; r += 2) {  // two rows at a time: every difference below is exact in fp32
+      const float v0 = (S_RPW * pw + r < Cin && tin) ? pro_apply<PRO>(vv[q][r], pa[r], ps[r], al[r], ral[r], 1.f) : 0.f;
+      const float v1 =
+          (S_RPW * pw + r + 1 < Cin && tin) ? pro_apply<PRO>(vv[q][r + 1], pa[r + 1], ps[r + 1], al[r + 1], ral[r + 1], 1.f) : 0.f;
+      const unsigned h = sty_pack2_bf16(v0, v1);
+      const float a0 = v0 - sty_bf_lo(h), a1 = v1 - sty_bf_hi(h);
+      const unsigned m = sty_pack2_bf16(a0, a1);
+      w[0][r / 2] = h;
+      w[1][r / 2] = m;
+      w[2][r / 2] = sty_pack2_bf16(a0 - sty_bf_lo(m), a1 - sty_bf_hi(m));
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) pk[p][q] = make_uint4(w[p][0], w[p][1], w[p][2], w[p][3]);
+  }
+}
+__device__ __forceinline__ void s_tile_write(__bf16* xin, int LW, int pw, int lane, const uint4 (&pk)[3][P_MAXQ]) {
+#pragma unroll
+  for (int q = 0; q < P_MAXQ; ++q) {
+    const int j = lane + 64 * q;
+    if (j >= LW) continue;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+      *reinterpret_cast<uint4*>(xin + ((size_t)p * LW + j) * P_PITCH + S_RPW * pw) = pk[p][q];
+  }
+}
+
+template <int PRO>
+__global__ __launch_bounds__(64 * (4 + S_NPW), 1) void conv32p_split_kernel(ConvArgs a, int tiles_per_row, int ntiles) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool consumer = wave < 4;
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int K = a.w.K;
+  const int LW = P_TT + (K - 1) * a.dil;
+  const int planesz = LW * P_PITCH;                  // halfs of one plane
+  __bf16* xin = reinterpret_cast<__bf16*>(lds);      // three planes [LW][P_PITCH]
+  float* ost = lds + (3 * planesz) / 2;              // two output stages [32][256] fp32
+
+  const int per = ntiles / (int)gridDim.x, rem = ntiles % (int)gridDim.x;
+  const int first = (int)blockIdx.x * per + ((int)blockIdx.x < rem ? (int)blockIdx.x : rem);
+  const int count = per + ((int)blockIdx.x < rem ? 1 : 0);
+  if (count == 0) return;
+
+  const __amdgpu_buffer_rsrc_t wrs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w.w3), 0, K * 2 * 3 * 64 * 16, 0x00020000);
+  const bool want_res = a.residual != nullptr;
+  // The two roles run loops of their own with the same barrier count, 1 + 2 per tile: a wave meets every barrier of the workgroup
+  // in one role's code (the branch is wave-uniform), and neither role's registers are live across the other's code.
+  if (!consumer) {
+    const int pw = wave - 4;
+    float vv[P_MAXQ][S_RPW];
+    uint4 pk[3][P_MAXQ];  // the pieces of the next tile, held over the barrier
+    const PTile t0 = p_tile(first, tiles_per_row);
+    s_tile_load(a, t0, LW, pw, lane, vv);
+    s_tile_split<PRO>(a, t0, LW, pw, lane, vv, pk);
+    s_tile_write(xin, LW, pw, lane, pk);
+    __syncthreads();
+    for (int i = 0; i < count; ++i) {
+      // residual of tile i - 1, loads of tile i + 1, drain of tile i - 1, prologue + split; the LDS write behind the barrier
+      const int tile = first + i;
+      const bool have_prev = i > 0, have_next = i + 1 < count;
+      PDrain<S_RPW> d;
+      const PTile prev = p_tile(tile - 1, tiles_per_row), next = p_tile(tile + 1, tiles_per_row);
+      if (have_prev) p_res_load(a, prev, pw, lane, want_res, d);
+      if (have_next) s_tile_load(a, next, LW, pw, lane, vv);
+      if (have_prev) p_drain(a, ost + ((i - 1) & 1) * P_OUT, prev, pw, lane, d, tiles_per_row);
+      if (have_next) s_tile_split<PRO>(a, next, LW, pw, lane, vv, pk);
+      __syncthreads();  // the consumers have read the planes of tile i for the last time and left its output stage
+      if (have_next) s_tile_write(xin, LW, pw, lane, pk);
+      __syncthreads();  // the planes of tile i + 1 are in LDS
+    }
+    const PTile last = p_tile(first + count - 1, tiles_per_row);
+    PDrain<S_RPW> d;
+    p_res_load(a, last, pw, lane, want_res, d);
+    p_drain(a, ost + ((count - 1) & 1) * P_OUT, last, pw, lane, d, tiles_per_row);
+    return;
+  }
+  const int tw = wave * (32 * P_NT);
+  float bias_r[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) bias_r[r] = a.w.bias ? a.w.bias[(r & 3) + 8 * (r >> 2) + 4 * hi] : 0.f;
+  __syncthreads();
+#define STY_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
+  for (int i = 0; i < count; ++i) {
+    {
+      // ---- consumer: LDS -> MFMA -> LDS, one k-step (16 channels of a tap) per pipeline stage ----
+      f32x16 acc[P_NT], accc[P_NT];
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int n = 0; n < P_NT; ++n) acc[n][r] = bias_r[r], accc[n][r] = 0.f;
+      bf16x8 awA[3], bxA[3][P_NT], awB[3], bxB[3][P_NT];
+#define STY_LD3(AW, BX, k, s)                                                                                    \
+  {                                                                                                              \
+    const __bf16* col = xin + (size_t)(tw + l31 + (k) * a.dil) * P_PITCH + 8 * hi + 16 * (s);                    \
+    _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                                              \
+      AW[p] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane * 16,                   \
+                                                                                (((k) * 2 + (s)) * 3 + p) * 1024, 0)); \
+      _Pragma("unroll") for (int n = 0; n < P_NT; ++n) BX[p][n] =                                                \
+          *reinterpret_cast<const bf16x8*>(col + (size_t)p * planesz + (size_t)n * 32 * P_PITCH);                \
+    }                                                                                                            \
+  }
+#define STY_MF(W, X, ACC) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W, X, ACC, 0, 0, 0)
+  // (smallest corrections first; neighbours in the issue order never share an accumulator)
+#define STY_MM3(AW, BX)                                                                  \
+  _Pragma("unroll") for (int n = 0; n < P_NT; ++n) STY_MF(AW[0], BX[0][n], acc[n]);      \
+  _Pragma("unroll") for (int n = 0; n < P_NT; ++n) STY_MF(AW[0], BX[2][n], accc[n]);     \
+  _Pragma("unroll") for (int n = 0; n < P_NT; ++n) STY_MF(AW[2], BX[0][n], accc[n]);     \
+  _Pragma("unroll") for (int n = 0; n < P_NT; ++n) STY_MF(AW[1], BX[1][n], accc[n]);     \
+  _Pragma("unroll") for (int n = 0; n < P_NT; ++n) STY_MF(AW[0], BX[1][n], accc[n]);     \
+  _Pragma("unroll") for (int n = 0; n < P_NT; ++n) STY_MF(AW[1], BX[0][n], accc[n]);
+#define STY_SCHED3                                 \
+  _Pragma("unroll") for (int g = 0; g < 6; ++g) {  \
+    STY_SGB(0x008, 1);                             \
+    STY_SGB(0x100, 1);                             \
+    STY_SGB(0x008, 1);                             \
+    if (g < 3) STY_SGB(0x020, 1);                  \
+  }                                                \
+  __builtin_amdgcn_sched_barrier(0);
+      STY_LD3(awA, bxA, 0, 0)
+      __builtin_amdgcn_sched_barrier(0);
+      int k = 0;
+      for (; k + 1 < K; ++k) {  // two k-steps (one tap) per trip: the two operand sets alternate without register copies
+        STY_LD3(awB, bxB, k, 1)
+        STY_MM3(awA, bxA)
+        STY_SCHED3
+        STY_LD3(awA, bxA, k + 1, 0)
+        STY_MM3(awB, bxB)
+        STY_SCHED3
+      }
+      STY_LD3(awB, bxB, k, 1)  // the last tap
+      STY_MM3(awA, bxA)
+      STY_SCHED3
+      STY_MM3(awB, bxB)
+#undef STY_SCHED3
+#undef STY_MM3
+#undef STY_MF
+#undef STY_LD3
+      float* ob = ost + (i & 1) * P_OUT + tw + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+#pragma unroll
+        for (int n = 0; n < P_NT; ++n) ob[row * P_TT + n * 32] = (acc[n][r] + accc[n][r]) * a.out_scale;
+      }
+    }
+    __syncthreads();  // (the producers write the planes of tile i + 1 between the two)
+    __syncthreads();
+  }
+#undef STY_SGB
+}
+
 int conv32p_stat_nseg(int T) { return cdiv(T, P_TT); }
+
+static size_t s_lds_bytes(const ConvArgs& a) {
+  const int LW = P_TT + (a.w.K - 1) * a.dil;
+  return (size_t)3 * LW * P_PITCH * 2 + (size_t)2 * P_OUT * 4;
+}
+
+template <int PRO>
+static int launch_s(const ConvArgs& a, hipStream_t st) {
+  const size_t lds = s_lds_bytes(a);
+  static bool raised = false;
+  if (!raised) {
+    STY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv32p_split_kernel<PRO>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    raised = true;
+  }
+  const int tiles_per_row = cdiv(a.T, P_TT);
+  const int ntiles = tiles_per_row * a.B;
+  const int grid = ntiles < num_cus() ? ntiles : num_cus();
+  const double outs = (double)a.B * a.w.Cout * a.T;
+  const double flops = 2.0 * a.w.Cin * a.w.K * outs;
+  const double bytes = 4.0 * a.B * a.w.Cin * a.T + 4.0 * outs + (a.residual ? 4.0 * outs : 0.0) + (double)split3_bytes(a.w.K);
+  char detail[40];
+  snprintf(detail, sizeof(detail), "ci%d co%d k%d d%d T%d", a.w.Cin, a.w.Cout, a.w.K, a.dil, a.T);
+  ProfScope prof("conv32p_kernel<split>", flops, bytes, st, detail);
+  hipLaunchKernelGGL((conv32p_split_kernel<PRO>), dim3(grid), dim3(64 * (4 + S_NPW)), lds, st, a, tiles_per_row, ntiles);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
 
 static size_t p_lds_bytes(const ConvArgs& a) {
   const int LW = P_TT + (a.w.K - 1) * a.dil + (a.bf16 && a.xh ? (a.pad & 1) : 0);
@@ -610,7 +859,19 @@ bool conv32p_eligible(const ConvArgs& a) {
   return (long)cdiv(a.T, P_TT) * a.B >= min_tiles;
 }
 
-int launch_conv32p(const ConvArgs& a, hipStream_t st) {
+// Whether a conv the kernel takes runs in its split form (conv1d_route asks, once per conv): asked for, never with the bf16
+// mode, weights packed as triples, one of the two prologues the vocoder's 32-channel layers use, fp32 tensors, dense weights.
+// Asked only of a conv that has passed conv32p_eligible (same tile, so STY_CONV32P_MIN_TILES counts the same 256-column tiles,
+// and the fp32 form's LDS bound covers this one's halo); where this says no the conv keeps the fp32 form of the kernel.
+bool conv32p_split_eligible(const ConvArgs& a) {
+  if (!a.split || a.bf16 || !a.w.w3) return false;
+  if (!(a.pro == PRO_NONE || a.pro == PRO_AFFINE_SNAKE)) return false;
+  if (a.xh || a.yh || a.rh || a.w_row || a.w_tap) return false;
+  return s_lds_bytes(a) <= 160 * 1024;
+}
+
+int launch_conv32p(const ConvArgs& a, bool split, hipStream_t st) {
+  if (split) return a.pro == PRO_AFFINE_SNAKE ? launch_s<PRO_AFFINE_SNAKE>(a, st) : launch_s<PRO_NONE>(a, st);
 #define STY_P_GO(PRO) return a.bf16 ? launch_p<true, PRO>(a, st) : launch_p<false, PRO>(a, st)
   switch (a.pro) {
     case PRO_AFFINE_SNAKE: STY_P_GO(PRO_AFFINE_SNAKE);

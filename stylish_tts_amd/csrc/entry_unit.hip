@@ -193,13 +193,19 @@ static ConvArgs unit_conv_args(const PackedConv& w, int B, int T, int dil, const
   a.bf16 = bf16;
   return a;
 }
+// the packed weight's share of the workspace, and behind it (compute mode 4) the split mode's fragment triples of a conv with
+// one 32-channel chunk each way
+static size_t unit_conv_base_bytes(int Cout, int Cin, int K) {
+  return ((size_t)K * align_up(Cin, CI_CHUNK) * align_up(Cout, 128) + align_up(Cout, 128)) * sizeof(float) + 512;
+}
+static bool unit_conv_splittable(int Cout, int Cin) { return Cin <= CI_CHUNK && Cout <= 32; }
 // ---- one dense Conv1d ('same' padding) on the MFMA conv kernel: unit parity and kernel tuning ----
 int sty_conv1d_workspace_bytes(int Cout, int Cin, int K, size_t* bytes) {
   if (!bytes || Cout <= 0 || Cin <= 0 || K <= 0) {
     set_error("sty_conv1d_workspace_bytes: bad argument");
     return STY_EINVAL;
   }
-  *bytes = ((size_t)K * align_up(Cin, CI_CHUNK) * align_up(Cout, 128) + align_up(Cout, 128)) * sizeof(float) + 512;
+  *bytes = unit_conv_base_bytes(Cout, Cin, K) + (unit_conv_splittable(Cout, Cin) ? split3_bytes(K) + 256 : 0);
   return STY_OK;
 }
 int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float* x, const float* w, const float* bias,
@@ -213,7 +219,14 @@ int sty_conv1d_fwd(int B, int Cin, int Cout, int K, int dil, int T, const float*
   }
   PackedConv pc = unit_conv_dims(Cin, Cout, K);
   if ((rc = unit_conv_pack(pc, w, bias, bias != nullptr, workspace, unit_conv_plane(pc), S(stream)))) return rc;
-  ConvArgs a = unit_conv_args(pc, B, T, dil, x, y, compute_bf16 != 0);
+  if (compute_bf16 == 4 && unit_conv_splittable(Cout, Cin)) {  // the split mode's fragment triples, behind the packed weight
+    void* w3 = reinterpret_cast<void*>(
+        align_up(reinterpret_cast<size_t>(static_cast<char*>(workspace) + unit_conv_base_bytes(Cout, Cin, K)), 256));
+    if ((rc = launch_pack_split3(pc.wp, K, w3, S(stream)))) return rc;
+    pc.w3 = w3;
+  }
+  ConvArgs a = unit_conv_args(pc, B, T, dil, x, y, compute_bf16 != 0 && compute_bf16 != 4);
+  a.split = compute_bf16 == 4;
   if (compute_bf16 == 2) {
     // the input as its bf16 operand twin (ConvArgs::x16), made here by the cast pass, and a twin of the OUTPUT written by
     // the conv's output stage (ConvArgs::y16), which is read back and checked against y by ... the caller: the twin
@@ -289,7 +302,9 @@ int sty_conv1d_route(int B, int Cin, int Cout, int K, int dil, int T, int comput
   static __bf16 dummy_h[4];
   PackedConv pc = unit_conv_dims(Cin, Cout, K);
   pc.wp = dummy_f;
-  ConvArgs a = unit_conv_args(pc, B, T, dil, dummy_f, dummy_f, compute_bf16 != 0);
+  if (compute_bf16 == 4 && unit_conv_splittable(Cout, Cin)) pc.w3 = dummy_f;
+  ConvArgs a = unit_conv_args(pc, B, T, dil, dummy_f, dummy_f, compute_bf16 != 0 && compute_bf16 != 4);
+  a.split = compute_bf16 == 4;
   if (flags & STY_ROUTE_IN_MASK) {
     a.pro = PRO_MASK;
     a.mask = dummy_f;

@@ -403,6 +403,10 @@ struct sty_model {
   sty::RmvpePlan rmv;
   sty::WavlmPlan wav;
   sty::WavlmKeep wav_keep;
+  // sty_model_set_fp32_split (kind speech_predictor): the inference entries run the 32-channel convs conv32p takes in its split
+  // form; split_packed: the arena of the last finalize holds the fragment triples (PackedConv::w3) of those convs
+  int fp32_split = 0;
+  bool split_packed = false;
   int wav_bf16 = 0;  // sty_wavlm_set_compute: the dense contractions of the kind on the bf16 matrix cores (0 for every other kind)
   // device bucket table of the distances -(wav_bucket_T - 1) .. wav_bucket_T - 1: a bucket depends on the distance alone, so one
   // table sized for the largest frame count seen serves every smaller one at an offset

@@ -46,6 +46,7 @@ struct Run {
   void conv(const ConvArgs& a0) {
     ConvArgs a = a0;
     a.bf16 = m->topts.compute_bf16 | m->wav_bf16;  // the compute mode also applies to the inference plans (wavlm: its own door)
+    a.split = m->fp32_split && !a.bf16;             // sty_model_set_fp32_split: the inference plans alone read it
     if (live()) chk(launch_conv1d(a, st));
   }
   ConvArgs base(const PackedConv& w, const float* x, int T, float* y) {

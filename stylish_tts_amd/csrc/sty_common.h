@@ -151,7 +151,11 @@ struct PackedConv {
   const float* bias = nullptr;  // [CoutP] (zero padded) or nullptr
   int Cin = 0, Cout = 0, K = 1, CinP = 0, CoutP = 0;
   const void* wf = nullptr;     // convp16 only, filled by its launcher: the same weights as bf16 MFMA A fragments
+  const void* w3 = nullptr;     // conv32p split mode (CinP = CoutP = 32): the weights as bf16 A-fragment triples (h, m, l),
+                                // [K][2 k-steps][3 pieces][64 lanes] x 16 B, made by launch_pack_split3 (weights.hip)
 };
+
+inline size_t split3_bytes(int K) { return (size_t)K * 2 * 3 * 64 * 16; }  // of PackedConv::w3
 
 constexpr int CI_CHUNK = 32;  // channels staged in LDS per reduction chunk
 
@@ -185,6 +189,8 @@ struct ConvArgs {
   int flatW = 0;
   int ksplit_max = 4;     // most wave groups the in-workgroup split-K may use (the front end's DFT GEMMs keep 2)
   int bf16 = 0;           // 1: GEMM operands rounded to bf16 (v_mfma_f32_32x32x16_bf16), fp32 accumulation and storage
+  int split = 0;          // 1 (never with bf16): fp32 operands as three bf16 pieces each, six products per k-step on the bf16
+                          // matrix cores (bf16x3); honoured by conv32p_kernel where conv1d_route(a).split says so, else ignored
   int in_shuffle = 0;     // > 1: source 0 is stored pixel-shuffled [B][C/s][T*s] (backward of a shuffled store)
   PackedConv w;
   int pro = PRO_NONE;
@@ -275,6 +281,7 @@ struct ConvRoute {
   ConvKernel kernel = CONV_TILED;
   ConvRefusal refusal = CONV_OK;
   bool x16_only = false;  // reads source 0 as its bf16 twin a.x16 alone (the fp32 tensor a.x[0] then has no reader in the launch)
+  bool split = false;     // CONV_32P only: the launch takes the split (bf16x3) form of the kernel (ConvArgs::split)
   bool up_stage = false;  // has the up-sample + gate output stage (ConvArgs::up_g; asked with or without the up_* operands set)
   // writes the a.y16 twin from its own output stage (behind every other kernel launch_conv1d runs the cast pass)
   bool writes_y16() const { return kernel == CONV_STEM2D || kernel == CONV_Q || kernel == CONV_P16; }

@@ -11,7 +11,7 @@ struct sty_model;
 namespace sty {
 
 // ---- host side: what the Builder emits, one entry per prepared tensor ----
-enum PackKind { PK_CONV, PK_CONV_WN, PK_CONV_GLU, PK_W2A, PK_CONV2D_SN, PK_DW2D_SN, PK_DGRAD, PK_DGRAD2D };
+enum PackKind { PK_CONV, PK_CONV_WN, PK_CONV_GLU, PK_W2A, PK_CONV2D_SN, PK_DW2D_SN, PK_DGRAD, PK_DGRAD2D, PK_SPLIT3 };
 struct PackJob {
   PackKind kind;
   const float *w = nullptr, *g = nullptr, *v = nullptr, *bias = nullptr, *extra = nullptr;
@@ -33,6 +33,12 @@ struct PackJob {
   static PackJob dgrad(const PackedConv& fwd, float* wd) {
     PackJob j;
     j.kind = PK_DGRAD, j.w = fwd.wp, j.K = fwd.K, j.CinP = fwd.CinP, j.CoutP = fwd.CoutP, j.wp = wd;
+    return j;
+  }
+  // bf16 A-fragment triples of the packed 32 x 32 conv `pc` -> w3 (the split mode of conv32p.hip)
+  static PackJob split3(const PackedConv& pc, float* w3) {
+    PackJob j;
+    j.kind = PK_SPLIT3, j.w = pc.wp, j.K = pc.K, j.CinP = pc.CinP, j.CoutP = pc.CoutP, j.wp = w3;
     return j;
   }
   // ... of a 2-D conv packed as `fwd` (reduction index (kh, ci), K = KW) -> wd
@@ -76,6 +82,12 @@ struct DgradPackJob {  // packed weights wp -> input-gradient weights wd
   int K = 1, CinP = 0, CoutP = 0;                    // of the forward conv (K = KW in 2-D)
   int two_d = 0;                                     // flat 2-D layout: rows (kh', co), columns ci, taps flipped both ways
   int KH = 1, Cin = 0, Cout = 0, CinPd = 0, CoutPd = 0;  // two_d only: the layer's dims and the padded extents of wd
+  int blk0 = 0;
+};
+struct SplitPackJob {  // packed weights wp [K][32][32] -> w3: the three bf16 pieces of every weight as MFMA A fragments
+  const float* wp = nullptr;
+  void* w3 = nullptr;  // [K][2 k-steps][3 pieces][64 lanes] x 16 B (split3_bytes)
+  int K = 1;
   int blk0 = 0;
 };
 struct GradUnpackJob {  // packed gradient gwp (+ packed bias gradient gbp) -> dW, or (dg, dv) of weight norm, and db; all +=
@@ -139,10 +151,11 @@ struct JobTable {
     blocks.free();
   }
 };
-// the five tables of a model, built from its PackJob list on first use after a finalize (weights_build_tables)
+// the tables of a model, built from its PackJob list on first use after a finalize (weights_build_tables)
 struct WeightTables {
   JobTable<ConvPackJob> pack;
   JobTable<DgradPackJob> dgrad;
+  JobTable<SplitPackJob> split3;  // (only while sty_model_set_fp32_split is on at the finalize)
   JobTable<GradUnpackJob> unpack;
   JobTable<SnPrepJob> sn_prep;
   BlockList sn_wtu;  // sn_prep's second grid: the W^T u blocks of the power iteration
@@ -150,7 +163,7 @@ struct WeightTables {
   int seg_blk_split = 0;  // `unpack` blocks [0, seg_blk_split) belong to gradient segment 1 (sty_model::seg_job_split)
   bool ready = false;
   void free() {
-    pack.free(), dgrad.free(), unpack.free(), sn_prep.free(), sn_wtu.free(), sn_unpack.free();
+    pack.free(), dgrad.free(), split3.free(), unpack.free(), sn_prep.free(), sn_wtu.free(), sn_unpack.free();
     ready = false;
   }
 };
@@ -167,6 +180,7 @@ int weights_unpack(sty_model* m, hipStream_t st, int seg = -1);
 // one launch per table
 int launch_conv_pack_table(const JobTable<ConvPackJob>& t, hipStream_t st);
 int launch_dgrad_pack_table(const JobTable<DgradPackJob>& t, hipStream_t st);
+int launch_split3_pack_table(const JobTable<SplitPackJob>& t, hipStream_t st);
 int launch_grad_unpack_table(const JobTable<GradUnpackJob>& t, int blk_base, int nblocks, hipStream_t st);  // a block sub-range
 int launch_sn_unpack_table(const JobTable<SnUnpackJob>& t, hipStream_t st);
 // conv2d.hip: spectral-norm weight preparation of EVERY spectral-norm layer of a model in a few launches (power_iter: the
@@ -178,6 +192,7 @@ int sn_wtu_blocks(int n);  // W^T u blocks of a layer with n weights per output 
 int launch_pack_conv(const float* w, const float* g, const float* v, const float* bias, int Cout, int Cin, int K,
                      float* wp, float* bp, int CinP, int CoutP, hipStream_t st);
 int launch_pack_dgrad(const float* wp, int K, int CinP, int CoutP, float* wd, hipStream_t st);
+int launch_pack_split3(const float* wp, int K, void* w3, hipStream_t st);  // wp [K][32][32] -> split3_bytes(K) at w3
 int launch_pack_dgrad2d(const float* wp, int KW, int KH, int Cin, int Cout, int CinP, int CoutP, int CinPd, int CoutPd,
                         float* wd, hipStream_t st);
 int launch_unpack_grad(const float* gwp, const float* g, const float* v, int Cout, int Cin, int K, int CinP, int CoutP,

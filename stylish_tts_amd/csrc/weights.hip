@@ -132,6 +132,48 @@ int launch_dgrad_pack_table(const JobTable<DgradPackJob>& t, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Split-mode fragments of a packed 32 x 32 conv (conv32p.hip, conv32p_split_kernel): every weight as three bf16 pieces
+// h = bf16(w), m = bf16(w - h), l = bf16(w - h - m), each piece in the lane order of v_mfma_f32_32x32x16_bf16's A operand: lane
+// (co = l31, k-block = hi) of k-step s holds the input channels 16 s + 8 hi .. + 7.  One block per tap, one thread per
+// (k-step, lane).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pack_split3_body(const SplitPackJob& j, int k) {
+  const int s = threadIdx.x >> 6, ln = threadIdx.x & 63;
+  const int co = ln & 31, ci0 = 16 * s + 8 * (ln >> 5);
+  float h[8], m[8], l[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float w = j.wp[((size_t)k * 32 + ci0 + e) * 32 + co];
+    h[e] = sty_round_bf16(w);
+    m[e] = sty_round_bf16(w - h[e]);
+    l[e] = (w - h[e]) - m[e];
+  }
+  bf16x8* out = static_cast<bf16x8*>(j.w3) + ((size_t)(k * 2 + s) * 3) * 64 + ln;
+  out[0] = sty_pack_bf16(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
+  out[64] = sty_pack_bf16(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
+  out[128] = sty_pack_bf16(l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7]);
+}
+__global__ __launch_bounds__(128) void pack_split3_kernel(SplitPackJob j) { pack_split3_body(j, blockIdx.x); }
+__global__ __launch_bounds__(128) void pack_split3_multi_kernel(const SplitPackJob* __restrict__ jobs,
+                                                                const int* __restrict__ job_of_block) {
+  const SplitPackJob j = jobs[job_of_block[blockIdx.x]];
+  pack_split3_body(j, blockIdx.x - j.blk0);
+}
+int launch_pack_split3(const float* wp, int K, void* w3, hipStream_t st) {
+  SplitPackJob j;
+  j.wp = wp, j.w3 = w3, j.K = K;
+  hipLaunchKernelGGL(pack_split3_kernel, dim3(K), dim3(128), 0, st, j);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+int launch_split3_pack_table(const JobTable<SplitPackJob>& t, hipStream_t st) {
+  if (t.blocks.n <= 0) return STY_OK;
+  hipLaunchKernelGGL(pack_split3_multi_kernel, dim3(t.blocks.n), dim3(128), 0, st, t.jobs, t.blocks.dev);
+  STY_LAUNCH_CHECK();
+  return STY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Packed gradient -> parameter gradients (+=); one block per output channel co.
 //   plain:        dW[co][ci][k] += gwp[k][ci][co]
 //   weight_norm:  w = g v/|v|:  dg[co] += <gw, v>/|v|,  dv += g/|v| (gw - v <gw, v>/|v|^2)
@@ -318,6 +360,7 @@ struct HostTable {
 int weights_build_tables(sty_model* m) {
   HostTable<ConvPackJob> pack;
   HostTable<DgradPackJob> dgrad;
+  HostTable<SplitPackJob> split3;
   HostTable<GradUnpackJob> unpack;
   HostTable<SnPrepJob> sn_prep;
   HostTable<SnUnpackJob> sn_unpack;
@@ -354,6 +397,10 @@ int weights_build_tables(sty_model* m) {
     } else if (j.kind == PK_DGRAD) {
       const DgradPackJob a = dgrad_job(j.w, j.K, j.CinP, j.CoutP, j.wp);
       dgrad.add(a, dgrad_job_blocks(a));
+    } else if (j.kind == PK_SPLIT3) {  // (source: the conv pack, launched before this table)
+      SplitPackJob a;
+      a.wp = j.w, a.w3 = j.wp, a.K = j.K;
+      split3.add(a, j.K);
     } else if (j.kind == PK_DGRAD2D) {  // (source: the spectral-norm pack, launched before this table)
       const DgradPackJob a = dgrad2d_job(j.w, j.K, j.KH, j.Cin, j.Cout, j.CinP, j.CoutP,
                                          (int)align_up(j.KH * j.Cout, CI_CHUNK), (int)align_up(j.Cin, 32), j.wp);
@@ -381,6 +428,7 @@ int weights_build_tables(sty_model* m) {
   int rc;
   if ((rc = wt.pack.upload(pack.jobs, pack.job_of_block))) return rc;
   if ((rc = wt.dgrad.upload(dgrad.jobs, dgrad.job_of_block))) return rc;
+  if ((rc = wt.split3.upload(split3.jobs, split3.job_of_block))) return rc;
   if ((rc = wt.unpack.upload(unpack.jobs, unpack.job_of_block))) return rc;
   if ((rc = wt.sn_prep.upload(sn_prep.jobs, sn_prep.job_of_block))) return rc;
   if ((rc = wt.sn_wtu.upload(sn_wtu))) return rc;
@@ -478,6 +526,7 @@ int weights_prepare(sty_model* m, hipStream_t st) {
   // weights are made from these packed weights.
   if ((r = launch_sn_prep_table(m->wt.sn_prep, m->wt.sn_wtu, false, true, st)) != STY_OK) return r;
   if ((r = launch_dgrad_pack_table(m->wt.dgrad, st)) != STY_OK) return r;
+  if ((r = launch_split3_pack_table(m->wt.split3, st)) != STY_OK) return r;  // (the split mode's fragments, from the conv packs)
   if (m->kind == "speech_predictor") {
     const DecoderPlan& d = m->dec;
     if ((r = launch_prep_fnv(d.f0_g, d.f0_v, d.f0_b, d.n_g, d.n_v, d.n_b, d.v_g, d.v_v, d.v_b, d.fnv_w, st)) != STY_OK) return r;

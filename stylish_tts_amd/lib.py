@@ -111,6 +111,7 @@ SYMBOLS = {
     "sty_model_enable_training": (C.c_int, [_P]),
     "sty_model_bind_grad": (C.c_int, [_P, C.c_char_p, _P]),
     "sty_model_set_train_opts": (C.c_int, [_P, C.POINTER(TrainOpts)]),
+    "sty_model_set_fp32_split": (C.c_int, [_P, _I]),
     "sty_vocoder_train_workspace_bytes": (C.c_int, [_P, _I, _I, _SZP]),
     "sty_vocoder_fwd_train": (C.c_int, [_P, C.POINTER(VocoderIO), _P, C.c_size_t, _P]),
     "sty_vocoder_bwd": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -77,6 +77,7 @@ def _init_value(key, shape):
 
 class _HipModule(torch.nn.Module):
     KIND = None
+    _fp32_split = False  # SpeechPredictor.set_fp32_split
 
     def _build(self, manifest, stft_buffers=None):
         for key, shape in manifest.items():
@@ -164,6 +165,8 @@ class _HipModule(torch.nn.Module):
             h = C.c_void_p()
             L.check(lib.sty_model_create(self.KIND.encode(), C.byref(h)))
             self._handle = h
+            if self._fp32_split:  # (before the finalize below: it lays out the fragment triples)
+                L.check(lib.sty_model_set_fp32_split(h, 1))
         gptrs = {}
         if getattr(self, "_train", False):
             # gradient buffers are owned by the shell and persistent: after torch's zero_grad(set_to_none=True) the
@@ -357,6 +360,22 @@ class SpeechPredictor(_HipModule):
         cfg = dict(DEFAULT_CFG) if model_config is None else _cfg_from_model_config(model_config)
         self.cfg = cfg
         self._build(speech_predictor_manifest(cfg), _stft_buffers())
+
+    def set_fp32_split(self, on=True):
+        """fp32 split mode (bf16x3) of the inference forwards (sty_model_set_fp32_split): the vocoder's 32 -> 32 channel convs
+        on the persistent kernel multiply every fp32 operand as three bf16 pieces on the bf16 matrix cores -- fp32 accuracy,
+        the fp32 parity gates hold.  Exclusive with set_train_opts(compute_bf16=True); the training graph does not read it."""
+        on = bool(on)
+        if self.KIND != "speech_predictor":
+            raise L.StyError(f"{type(self).__name__}: model kind '{self.KIND}' has no fp32 split mode")
+        if self._handle is not None:
+            L.check(L.load().sty_model_set_fp32_split(self._handle, int(on)))
+            if on and not self._fp32_split:
+                # the fragment triples of the weights are laid out by a finalize: the next _ensure binds and finalizes again
+                self._bound = None
+                self.__dict__.pop("_fast_sig", None)
+        self._fp32_split = on
+        return self
 
     def forward(self, texts, text_lengths, alignment, pitch, energy, voiced, style, denormal_pitch, *, noise=None,
                 seed=0, prior_override=None, taps=None):

@@ -3,6 +3,7 @@ reference's tts/cli.py:32-96 `speak_document` runs the exported ONNX file under 
 stylish_tts_amd.ExportModel on the models of a checkpoint).
 
     python -m stylish_tts_amd.speak CHECKPOINT VOICEPACK INFILE OUTFILE --model-config MODEL.yml [--reference-index]
+                                    [--compute {fp32,bf16,bf16x3}]
 
 INFILE holds one `phonemes|plain text` line per utterance (tts/cli.py:62-66; phoneme input only, as the reference).  Per
 line: TextCleaner -> the pack's row for that token count (voicepack.style_index; --reference-index: row 511 for every
@@ -10,6 +11,11 @@ line, which is what tts/cli.py:78 computes) -> ExportModel.forward with seed = t
 (loudness.normalize) -> * 32768 -> int16.  The reference's `.astype(np.int16)` WRAPS a sample beyond full scale to the
 other sign; here such a sample SATURATES.  The utterances are concatenated into one 24 kHz PCM16 wav (stdlib `wave`).  An
 utterance shorter than one 0.4 s loudness block is written un-normalised, with a logged warning (pyloudnorm raises there).
+
+--compute: fp32 (default) multiplies fp32 operands; bf16 rounds the operands of the dense convs / Linears of the three models
+to bf16 (set_train_opts(compute_bf16=True): fastest, outside the fp32 parity gates); bf16x3 keeps fp32 accuracy and runs the
+speech predictor's 32-channel vocoder convs on the bf16 matrix cores with every operand split into three bf16 pieces
+(SpeechPredictor.set_fp32_split).
 """
 import wave
 
@@ -20,6 +26,7 @@ from . import lib as L
 from .config import check_supported
 
 TARGET_LUFS = -25.0  # tts/cli.py:87
+COMPUTE_MODES = ("fp32", "bf16", "bf16x3")
 SPEAK_KEYS = ("speech_predictor", "pitch_energy_predictor", "duration_predictor")
 
 
@@ -37,18 +44,26 @@ class Speaker:
     """The three inference models of a checkpoint directory in ExportModel + the static voicepack split 64 / 64 / 64
     (tts/cli.py:49-51)."""
 
-    def __init__(self, checkpoint, model_config_path, voicepack_path, device=None):
+    def __init__(self, checkpoint, model_config_path, voicepack_path, device=None, compute="fp32"):
         import stylish_tts_amd as S
         from . import stage_io as IO
         from .data import TextCleaner
         from .train import get_model_config
         from .voicepack import _model_registry, _need_device, read_voicepack
+        if compute not in COMPUTE_MODES:
+            raise L.StyError(f"speak: compute mode {compute!r} is none of {', '.join(COMPUTE_MODES)}")
+        self.compute = compute
         mc = self.model_config = check_supported(get_model_config(model_config_path))
         pack = read_voicepack(voicepack_path)  # (refuses a dynamic pack and a file without a voicepack key)
         self.device = _need_device("speak", device)
         ctx = _model_registry(mc, self.device)
         models = {k: ctx.model(k) for k in SPEAK_KEYS}
         IO.load_checkpoint(checkpoint, models)
+        if compute == "bf16":
+            for m in models.values():
+                m.set_train_opts(compute_bf16=True)
+        elif compute == "bf16x3":  # the speech predictor alone has the split mode; the other two models stay fp32
+            models["speech_predictor"].set_fp32_split(True)
         self.model = S.ExportModel(class_count=mc.duration_predictor.duration_classes,
                                    max_dur=mc.duration_predictor.max_duration, coarse_multiplier=mc.coarse_multiplier,
                                    **models).eval()
@@ -119,8 +134,12 @@ def main(argv=None):
     ap.add_argument("--model-config", dest="model_config_path", default="")
     ap.add_argument("--reference-index", dest="reference_index", action="store_true",
                     help="row 511 of the voicepack for every line, as the reference's speak computes it")
+    ap.add_argument("--compute", choices=COMPUTE_MODES, default="fp32",
+                    help="operand mode: fp32; bf16 (rounded operands, all three models); bf16x3 (fp32 accuracy on the bf16 "
+                         "matrix cores for the speech predictor's 32-channel vocoder convs)")
     a = ap.parse_args(argv)
-    speak_document(a.infile, a.outfile, Speaker(a.checkpoint, a.model_config_path, a.voicepack),
+    _log(f"compute mode {a.compute}")
+    speak_document(a.infile, a.outfile, Speaker(a.checkpoint, a.model_config_path, a.voicepack, compute=a.compute),
                    reference_index=a.reference_index)
 
 
